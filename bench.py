@@ -2,7 +2,7 @@
 """bench.py — Mray/s of the MI355X path-tracing hot path on BASELINE.json configs[1]
 (input/hdr.json, 1280x720, 256 spp, 8 bounces; the venus mesh is the generated 524 288-triangle stand-in).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 One step = one full frame: every rank renders ITS share of the frame (N = 1: the whole frame as one region;
@@ -10,8 +10,14 @@ N > 1: every N-th 4-row strip, which balances the ranks where dealing out tiles 
 all 256 passes in one dispatch of the persistent kernel, then the float framebuffers are summed onto rank 0 with one
 RCCL reduce (non-owned pixels are exactly 0, so the sum is a gather). The frame is a fixed job, so N > 1 is STRONG scaling.
 value = rays (getClosestIsect calls, primary + secondary, counted by the kernel) of all ranks / wall time.
+ms_per_step = wall time of the K timed steps / K.
 
-Extra objects on the JSON line (N = 1 only for cpu_baseline):
+A plain run sets up, warms up, times the K steps and prints the headline line. --dump-outputs DIR also writes what the
+last timed step computed (dump_outputs: the frame rank 0 holds, float32, and the step's ray / path counts, float64) as
+DIR/<name>.npy. Everything else the line can carry takes runs of its own and is measured only with --full:
+  counting pass, roofline, scaling_cfg4 / scaling_soup10m, cpu_baseline + parity, dropin / dropin_iterative, other_workloads.
+
+Extra objects on the JSON line with --full (N = 1 only for cpu_baseline):
   roofline     HBM roofline of k_pathtrace: algorithmic bytes per launch (DESIGN.md §"Algorithmic bytes")
                / average launch duration measured with HIP events on the launch stream, vs 8 TB/s.
   cpu_baseline the reference's own pthread renderer (oracle/_ref/c-ray-ref, built from the unmodified
@@ -41,6 +47,8 @@ WORKLOADS["soup10m"] = {"scene": None, "blob": "soup_10m", "width": 2560, "heigh
                         "what": "synthetic 10 M-triangle soup {W}x{H}, {SPP} spp, {B} bounces (BASELINE.json configs[4] at its real size; the 1.04 GB scene is built on this box by "
                                 "tools/make_soup_blob.py: gen_soup's triangles as the reference's loader reads them + the GPU BVH builder, the reference's tree)"}
 WORKLOAD = WORKLOADS["cfg2"]
+ENV_STANDIN_NOTE = ("; environment map: a generated stand-in of the HDR's size (tools/cfg2_blob.py — no reference tree to flatten hdr.json from): "
+                    "the same paths and rays, other radiance")
 # what `other_workloads` measures beside the headline: (workload, spp of the timed dispatch = BASELINE's own, spp of the counting dispatch, spp of a short dispatch kept for
 # continuity with rounds 1-4). Round 6: configs[3] is timed ONCE at its own 2048 passes too (24 s of one GPU; the seed of a (pixel, pass) depends on the
 # sample count, sampler.c:42, and so does the path mix) — its counters come from a 256-pass counting dispatch (bytes per ray carried over: stated in the object), and the
@@ -53,6 +61,10 @@ def workload_blob(key, built_dir):
     """Path of a workload's scene blob; the 10 M soup is built here on first use (tools/make_soup_blob.py, kept in the temp directory)."""
     wl = WORKLOADS[key]
     path = os.path.join(built_dir, wl["blob"] + ".blob")
+    if key == "cfg2" and not os.path.exists(path):          # no flattened blob here: the one build() made with a generated environment map (tools/cfg2_blob.py)
+        from __graft_entry__ import CFG2_STANDIN
+        if os.path.exists(os.path.join(built_dir, CFG2_STANDIN + ".blob")):
+            return os.path.join(built_dir, CFG2_STANDIN + ".blob")
     if os.path.exists(path) or not wl.get("triangles"):
         return path
     import tempfile
@@ -561,6 +573,27 @@ def cpu_baseline(oracle_py, blob_path, w, h, bounces, budget_s=12.0, frames=None
             "sample": f"oracle/libcray_oracle.so (OpenMP, {cores} threads): {w}x{h}, {spp} spp (of {WORKLOAD['samples']}), {bounces} bounces, {port_s:.2f} s" + note}
 
 
+DUMP_LIMIT_BYTES = 60_000_000          # all files of --dump-outputs stay below 64 MB
+
+
+def dump_outputs(out_dir, frame, rays_per_step, paths_per_step, seed=0):
+    """What the timed path computed in its last step, as DIR/<name>.npy: `frame` = the float32 framebuffer [H, W, 3] rank 0 holds (the frame a caller of
+    FrameRenderer.render + reduce receives) and `counters` = float64 [rays, paths] of one step. A frame above DUMP_LIMIT_BYTES is written as a fixed, seeded
+    sample of its pixels instead: `frame_sample` [n, 3] and `frame_sample_pixels` (float64 row-major pixel indices)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "frame.npy"), frame)
+    else:
+        flat = frame.reshape(-1, frame.shape[-1])
+        n = DUMP_LIMIT_BYTES // (flat.shape[1] * 4 + 8)
+        pix = np.sort(np.random.default_rng(seed).choice(flat.shape[0], size=n, replace=False))
+        np.save(os.path.join(out_dir, "frame_sample.npy"), flat[pix])
+        np.save(os.path.join(out_dir, "frame_sample_pixels.npy"), pix.astype(np.float64))
+    np.save(os.path.join(out_dir, "counters.npy"), np.array([rays_per_step, paths_per_step], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -569,6 +602,11 @@ def main():
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="cfg2",
                     help="cfg2 (default, the headline: BASELINE.json configs[1]); cfg4 = configs[3], the scene the 1/2/4/8-GPU curve is quoted on; "
                          "soup10m = configs[4] at its real size (the scene is built on this box on first use)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (the frame, its ray / path counts) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: counting pass + roofline, the scaling objects, the CPU baseline + parity, "
+                         "the drop-in program, the other BASELINE workloads (--no-cpu, --no-dropin and --no-others leave parts of it out)")
     ap.add_argument("--samples", type=int, default=0, help=argparse.SUPPRESS)   # dev only: fewer passes than the config names
     ap.add_argument("--no-cpu", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-dropin", action="store_true", help=argparse.SUPPRESS)
@@ -631,12 +669,14 @@ def main():
         else:
             fr.reduce(dist)
 
-    # counting pass (outside the timed region): every crh_counters field for the roofline's algorithmic bytes
-    ctx.set_option(abi.OPT_COUNTER_LEVEL, 2)
-    ctx.reset_counters()
-    step()
-    barrier()
-    full = ctx.counters()
+    full = None
+    if a.full:
+        # counting pass (outside the timed region): every crh_counters field for the roofline's algorithmic bytes
+        ctx.set_option(abi.OPT_COUNTER_LEVEL, 2)
+        ctx.reset_counters()
+        step()
+        barrier()
+        full = ctx.counters()
 
     ctx.set_option(abi.OPT_COUNTER_LEVEL, 1)          # timed runs keep only the ray / path counters
     for _ in range(a.warmup):
@@ -661,11 +701,28 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.SUM)
         elapsed, gather_ms, kernel_ms_max = float(tmax[0]), float(tmax[3]), float(tmax[4])
     total_rays, total_paths = float(tt[1]), float(tt[2])
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, fr.fb.cpu().numpy(), total_rays / a.steps, total_paths / a.steps)
 
     out = None
     if rank == 0:
         ms_per_step = elapsed / a.steps * 1e3
         value = total_rays / elapsed / 1e6
+        out = {
+            "metric": "Mray/s (primary+secondary)", "value": round(value, 2), "unit": "Mray/s", "n_gpus": world,
+            "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
+            "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": WORKLOAD["what"].format(W=W, H=H, SPP=SPP, B=B) + (ENV_STANDIN_NOTE if blob.endswith("_envstandin.blob") else ""),
+                       "rays_per_step": int(total_rays / a.steps), "paths_per_step": int(total_paths / a.steps),
+                       "parallelism": ("1 rank: the whole frame in one dispatch" if world == 1 else
+                                       f"4-row strips interleaved over {world} ranks; rank 0 gathers the owned strips (1/{world} of the float framebuffer per rank, "
+                                       "RCCL send / receive over xGMI; render.py: StripGather — bit-identical to the one-reduce form)"),
+                       "baseline_config": {"cfg2": "configs[1] (the 1-GPU headline; at N > 1 a STRONG-scaling run of the same 68 ms frame)", "cfg3": "configs[2]",
+                                           "cfg4": "configs[3] (the scene BASELINE.json quotes the 1/2/4/8-GPU curve on: --workload cfg4)",
+                                           "soup": "configs[4] at 1 M triangles", "soup10m": "configs[4]"}.get(a.workload)},
+            "gather_ms": round(gather_ms, 3) if world > 1 else None, "kernel_ms_max_over_ranks": round(kernel_ms_max, 3),
+        }
+    if rank == 0 and a.full:
         avg_kernel_ms = kernel_total_ms / max(launches, 1)
         alg = algorithmic_bytes(full)
         alg_no_state = algorithmic_bytes(full, path_state=False)
@@ -676,19 +733,7 @@ def main():
         sat = ((valu or {}).get("calibration") or {}).get("of_saturated_rate")
         frac_state = achieved / HBM_PEAK_GBS
         achieved_scene = alg_no_state / (avg_kernel_ms * 1e-3) / 1e9
-        out = {
-            "metric": "Mray/s (primary+secondary)", "value": round(value, 2), "unit": "Mray/s", "n_gpus": world,
-            "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": WORKLOAD["what"].format(W=W, H=H, SPP=SPP, B=B),
-                       "rays_per_step": int(total_rays / a.steps), "paths_per_step": int(total_paths / a.steps),
-                       "parallelism": ("1 rank: the whole frame in one dispatch" if world == 1 else
-                                       f"4-row strips interleaved over {world} ranks; rank 0 gathers the owned strips (1/{world} of the float framebuffer per rank, "
-                                       "RCCL send / receive over xGMI; render.py: StripGather — bit-identical to the one-reduce form)"),
-                       "baseline_config": {"cfg2": "configs[1] (the 1-GPU headline; at N > 1 a STRONG-scaling run of the same 68 ms frame)", "cfg3": "configs[2]",
-                                           "cfg4": "configs[3] (the scene BASELINE.json quotes the 1/2/4/8-GPU curve on: --workload cfg4)",
-                                           "soup": "configs[4] at 1 M triangles", "soup10m": "configs[4]"}.get(a.workload)},
-            "gather_ms": round(gather_ms, 3) if world > 1 else None, "kernel_ms_max_over_ranks": round(kernel_ms_max, 3),
+        out.update({
             # `bound` is set from the evidence: the PMC run of THIS device code (profiles/, fingerprint-gated) shows the vector ALU issuing most of the time
             # -> "valu-issue"; without such a run the label is the metric's nominal one, "hbm", and the note says that nothing measured backs it
             # `bound` is set from the evidence, CALIBRATED since round 5: the vector pipe's formula is held against its reading at known saturation (profiles/calibration.json)
@@ -718,13 +763,13 @@ def main():
                          # the one number that says how far the kernel is from the machine: the share of the vector pipe's saturated issue rate it uses
                          # x the share of a wave's 64 lanes that are active in what it issues
                          "lane_fraction": round(sat * valu["lane_utilisation"], 4) if sat and (valu or {}).get("lane_utilisation") else None},
-        }
+        })
         if world > 1:
             # the headline FIRST: the scaling objects below are the first time RCCL's grouped send / receive meets the 1 GB soup on N real GPUs — whatever
             # happens there, this line is out. The complete line follows when they have run
             print(json.dumps({**out, "provisional": "headline only: the complete line (scaling_cfg4, scaling_soup10m) follows"}), flush=True)
     scaling = {}
-    if a.workload == "cfg2" and SPP == WORKLOAD["samples"] and not a.no_others:
+    if a.full and a.workload == "cfg2" and SPP == WORKLOAD["samples"] and not a.no_others:
         for key in ("cfg4", "soup10m"):
             try:
                 scaling[key] = scaling_workload(key, api, render, torch, dist, BUILT, local_rank, rank, world)
@@ -733,7 +778,7 @@ def main():
     if rank == 0:
         for key, obj in scaling.items():
             out["scaling_" + key] = obj
-        if world == 1 and not a.no_cpu:
+        if world == 1 and a.full and not a.no_cpu:
             sys.path.insert(0, os.path.join(REPO, "oracle"))
             import oracle_py
             frames = {}
@@ -754,7 +799,7 @@ def main():
                         out["parity"]["reference_strict_vs_default_flags"] = parity_columns(frames["strict"], frames["default"])
                 except Exception as e:
                     out["parity"] = {"failed": f"{type(e).__name__}: {e}"[:200]}
-        if world == 1 and not a.no_dropin and SPP == WORKLOAD["samples"] and a.workload == "cfg2":
+        if world == 1 and a.full and not a.no_dropin and SPP == WORKLOAD["samples"] and a.workload == "cfg2":
             try:
                 fr.close()                 # the drop-in is its own process with its own context
             except Exception:
@@ -763,7 +808,7 @@ def main():
             out["dropin_iterative"] = dropin_iterative(WORKLOAD)
             if isinstance(out["dropin"].get("render_phase_ms"), (int, float)):
                 out["dropin"]["vs_bench_ms_per_step"] = round(out["dropin"]["render_phase_ms"] / ms_per_step, 3)
-        if world == 1 and not a.no_others and a.workload == "cfg2" and SPP == WORKLOAD["samples"]:
+        if world == 1 and a.full and not a.no_others and a.workload == "cfg2" and SPP == WORKLOAD["samples"]:
             out["other_workloads"] = measure_other_workloads(api, abi, BUILT)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -70,3 +70,53 @@ def test_committed_traffic_records_carry_what_the_line_needs(bench):
         assert t["source_md5"] and t["write_bytes"] > 0 and t["fetch_bytes_raw"] > 0
     if not seen:
         pytest.skip("no round-5 traffic record yet")
+
+
+def test_dump_outputs_writes_the_frame_or_a_fixed_sample_within_the_budget(bench, tmp_path, monkeypatch):
+    """--dump-outputs DIR: the last step's frame (float32) and its ray / path counts (float64) as .npy; a frame above the budget becomes a seeded sample of its
+    pixels, the same one on every run, and all files together stay below 64 MB."""
+    import numpy as np
+    assert bench.DUMP_LIMIT_BYTES < 64e6
+    frame = np.random.default_rng(3).random((72, 128, 3), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "small"), frame, 1234.0, 56.0)
+    assert sorted(os.listdir(tmp_path / "small")) == ["counters.npy", "frame.npy"]
+    got = np.load(tmp_path / "small" / "frame.npy")
+    assert got.dtype == np.float32 and (got == frame).all()
+    assert np.load(tmp_path / "small" / "counters.npy").tolist() == [1234.0, 56.0]
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", frame.nbytes // 4)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), frame, 1.0, 2.0)
+    assert sorted(os.listdir(tmp_path / "a")) == ["counters.npy", "frame_sample.npy", "frame_sample_pixels.npy"]
+    pix, sample = np.load(tmp_path / "a" / "frame_sample_pixels.npy"), np.load(tmp_path / "a" / "frame_sample.npy")
+    assert pix.dtype == np.float64 and sample.dtype == np.float32 and sample.nbytes + pix.nbytes <= bench.DUMP_LIMIT_BYTES
+    assert (sample == frame.reshape(-1, 3)[pix.astype(np.int64)]).all()
+    assert (np.load(tmp_path / "b" / "frame_sample_pixels.npy") == pix).all()
+
+
+def test_bench_scene_rebuilds_without_the_reference(oracle, tmp_path):
+    """tools/cfg2_blob.py: bench.py's scene from the committed skeleton, the generated statue and the restated BVH builder. With the reference's
+    environment map it is byte for byte the blob the reference's loader + the flattener write (where that blob is built); with the generated map it
+    differs from it in the map's texels only, and hashes to the md5 recorded in the skeleton."""
+    import hashlib
+    import sys
+    import numpy as np
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    import cfg2_blob
+    out = str(tmp_path / "cfg2_hdr_envstandin.blob")
+    cfg2_blob.rebuild(out)
+    data = open(out, "rb").read()
+    meta, _ = cfg2_blob.load_skeleton()
+    assert len(data) == 70030944 and hashlib.md5(data).hexdigest() == meta["md5_standin"]
+    off, w, h = cfg2_blob.env_map_range(bytearray(data))
+    sky = np.frombuffer(data, np.float32, count=w * h * 3, offset=off)
+    assert (w, h) == (1024, 512) and np.isfinite(sky).all() and sky.min() > 0
+    flattened = os.path.join(REPO, "scenes", "_built", "cfg2_hdr.blob")
+    if not os.path.exists(flattened):
+        return
+    real = open(flattened, "rb").read()
+    assert hashlib.md5(real).hexdigest() == meta["md5_flattened"]
+    env = np.frombuffer(real, np.float32, count=w * h * 3, offset=off).reshape(h, w, 3)
+    _, skeleton = cfg2_blob.load_skeleton()
+    assert bytes(cfg2_blob.fill(skeleton, meta, env)) == real
+    differ = np.nonzero(np.frombuffer(data, np.uint8) != np.frombuffer(real, np.uint8))[0]
+    assert differ.min() >= off and differ.max() < off + w * h * 12

@@ -8,7 +8,7 @@ cd "$(dirname "$0")/.." || exit 1
 O=gpurun_out/evidence_$TAG
 mkdir -p $O
 timeout 900 python -m pytest tests -m gpu -q -rfE --tb=short > $O/pytest_gpu.log 2>&1; echo "pytest rc $?"; tail -2 $O/pytest_gpu.log
-timeout 900 python bench.py --steps 10 --warmup 2 > $O/bench_1gpu.log 2>&1; echo "bench rc $?"
+timeout 900 python bench.py --full --steps 10 --warmup 2 > $O/bench_1gpu.log 2>&1; echo "bench rc $?"
 timeout 400 tools/profile_round.sh $TAG cfg2 > $O/profile_cfg2.log 2>&1
 B=scenes/_built
 timeout 600 python tools/run_config.py --blob $B/cfg2_hdr.blob --width 1280 --height 720 --spp 256 --bounces 8 --parity-spp 256 --tag cfg2_hdr_full > $O/cfg2_hdr_full_parity.json 2> $O/cfg2.err
@@ -29,5 +29,5 @@ timeout 300 python tools/probe_step_clocks.py > $O/probe_step_clocks.log 2>&1
 timeout 300 python tools/bvh_bench.py --blob $B/soup_1m.blob --tag soup_1m > $O/bvh_build_soup_1m.json 2>&1
 timeout 300 python tools/bvh_bench.py --blob $B/cfg2_hdr.blob --tag cfg2_hdr > $O/bvh_build_cfg2_hdr.json 2>&1
 timeout 300 python tools/probe_share8.py > $O/probe_share8.log 2>&1
-CRH_FORCE_PROGRAMS=1 timeout 200 python bench.py --steps 3 --no-cpu --no-dropin > $O/bench_forced_rare_features_variant.log 2>&1
+CRH_FORCE_PROGRAMS=1 timeout 200 python bench.py --full --steps 3 --no-cpu --no-dropin > $O/bench_forced_rare_features_variant.log 2>&1
 for f in $O/*.json; do echo "$f: $(head -c 300 $f)"; done
