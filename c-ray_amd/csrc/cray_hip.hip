@@ -269,7 +269,8 @@ struct SchedWg { int wNode, wTri, wCtrl, swapMin, fillTo, runNum, triInRun, ctrl
 
 /* Per-wave PATH TABLE in global memory: a path lives in one 128-B record (one cache line, one lane reads or writes it
  * with a few 16-B accesses) from its camera ray to its last bounce; what moves between the work stacks is its one-byte
- * slot id (LDS). Record = 8 x f4: {o, depth} {d, item} {weight, rng.lo} {radiance, rng.hi} {t, u, v, slot} {inst, -, -, -} - - */
+ * slot id (LDS). Record = 8 x f4: {o, depth} {d, item} {weight, rng.lo} {radiance, rng.hi} {t, u, v, slot} {inst, -, -, -} - -
+ * (k_pathtrace_roll without node programs or volumes splits the same words into three arrays: PathTab below) */
 #define CRH_PATHS 256u        /* slots per wave = the most paths a wave keeps in flight */
 #define CRH_PATH_F4 8u
 #define CRH_WAVE_QUEUE_FLOATS (CRH_PATHS * CRH_PATH_F4 * 4u)
@@ -304,6 +305,34 @@ template <int SAMP> struct TablePort {
 	__device__ __forceinline__ void save(int i, uint32_t v) { ((uint32_t *)(q + 6))[i] = v; }
 	__device__ __forceinline__ uint32_t load(int i) { return ((const uint32_t *)(q + 6))[i]; }
 };
+
+/* Where k_pathtrace_roll keeps a path's words. LEAN (the instantiations without node programs or volumes, whose walk never touches
+ * TablePort::save / load): the same words, bit for bit, in three arrays inside the wave's table instead of one 128-B record per path, so that a
+ * path occupies 84 B of L2 instead of a 128-B line of which 44 B were never used:
+ *   rec(id)  64 B  {o, depth} {d, item} {weight, rng.lo} {radiance, rng.hi}   (half a 128-B line; TablePort::draw finds the sampler where it was)
+ *   hit(id)  16 B  {t, u, v, slot}        at f4 CRH_PATHS * 4 + id
+ *   inst(id)  4 B  instance of a hit      at f4 CRH_PATHS * 5 + id / 4
+ * (CRH_PATHS * 84 B of the wave's CRH_PATHS * 128 B.) Otherwise the 128-B record above. CRH_PATH_LEAN=0 builds every instantiation with the
+ * 128-B record (the A/B reference: tests/test_path_record_layout.py). */
+#ifndef CRH_PATH_LEAN
+#define CRH_PATH_LEAN 1
+#endif
+template <bool LEAN> struct PathTab {
+	f4 *base;
+	/* (the arrays' starts are added to the lane's byte offset, not to the wave's base: the compiler would otherwise keep two more 64-bit bases in SGPRs across the
+	 * whole machine — 11 more spilled SGPRs in the bench instantiation) */
+	__device__ __forceinline__ static uint32_t vgprConst(uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+		__asm__ volatile("" : "+v"(v));
+#endif
+		return v;
+	}
+	__device__ __forceinline__ f4 *at(uint32_t bytes) const { return (f4 *)((char *)base + bytes); }
+	__device__ __forceinline__ f4 *rec(uint32_t id) const { return base + id * (LEAN ? 4u : CRH_PATH_F4); }
+	__device__ __forceinline__ f4 *hit(uint32_t id) const { return LEAN ? at(vgprConst(CRH_PATHS * 64u) + id * 16u) : base + id * CRH_PATH_F4 + 4u; }
+	__device__ __forceinline__ float *inst(uint32_t id) const { return LEAN ? (float *)at(vgprConst(CRH_PATHS * 80u) + id * 4u) : (float *)(base + id * CRH_PATH_F4 + 5u); }
+};
+static_assert(CRH_PATHS * (4u + 1u) * 4u + CRH_PATHS <= CRH_WAVE_QUEUE_FLOATS, "the lean arrays fit in the wave's table");
 
 /* rank of this lane among the set bits of a ballot mask below it */
 __device__ __forceinline__ uint32_t laneRank(unsigned long long m) {

@@ -93,7 +93,7 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 	float *const myStage = stage + (size_t)__builtin_amdgcn_readfirstlane(wave) * (size_t)NS * slabFloats;
 	const int passEnd = P.first_pass + P.pass_count;
 	const uint32_t trisOff = (uint32_t)((const char *)S.tris - (const char *)S.nodes);          /* (one allocation: crh_scene_upload) */
-	f4 *const ptab = (f4 *)(queues + (size_t)__builtin_amdgcn_readfirstlane(wave) * CRH_WAVE_QUEUE_FLOATS);
+	const PathTab<CRH_PATH_LEAN && !PROG> tab{(f4 *)(queues + (size_t)__builtin_amdgcn_readfirstlane(wave) * CRH_WAVE_QUEUE_FLOATS)};          /* (the path's words: PathTab) */
 	/* the counting kernel's wave-level numbers (steps, lanes served, clocks per step kind: indices 8.. of the counter block) go straight to this wave's own words behind
 	 * the global counters — one fire-and-forget atomic by lane 0 per event, no contention — instead of through two dozen registers per lane that are summed at the end:
 	 * those registers were 70 spilled VGPRs, and the counting kernel's step clocks were not the timed kernel's */
@@ -172,10 +172,9 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 		const unsigned long long hm = __ballot(finHit), mm = __ballot(finMiss);
 		uint32_t cls = 0;
 		if (fin) {
-			f4 *q = ptab + myPath * CRH_PATH_F4;
-			q[4] = f4{w.hit.t, w.hit.u, w.hit.v, asF32((uint32_t)w.hit.slot)};
+			*tab.hit(myPath) = f4{w.hit.t, w.hit.u, w.hit.v, asF32((uint32_t)w.hit.slot)};
 			if (finHit) {
-				q[5].x = asF32((uint32_t)w.hit.inst);
+				*tab.inst(myPath) = asF32((uint32_t)w.hit.inst);
 				if (sorted) cls = (uint32_t)((volatile __attribute__((address_space(3))) uint8_t *)s_cls)[w.hit.inst];
 				hits[(uint32_t)hq + laneRank(hm)] = (uint16_t)(myPath | (cls << 8));
 			} else {
@@ -216,9 +215,9 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 		if (idle && (int)er < take) {
 			myPath = ids[CRH_IDS_RAYS + (uint32_t)(rq - take) + er];
 #endif
-			const f4 *q = ptab + myPath * CRH_PATH_F4;
+			const f4 *q = tab.rec(myPath);
 			const f4 q0 = q[0], q1 = q[1];
-			{ TablePort<SAMP> port2{ptab + myPath * CRH_PATH_F4}; walkBegin(S, w, stk, v3{q0.x, q0.y, q0.z}, v3{q1.x, q1.y, q1.z}, cnt, port2, (uint32_t)K.rayFlags); }
+			{ TablePort<SAMP> port2{tab.rec(myPath)}; walkBegin(S, w, stk, v3{q0.x, q0.y, q0.z}, v3{q1.x, q1.y, q1.z}, cnt, port2, (uint32_t)K.rayFlags); }
 			if constexpr (LEVEL >= 2) {
 				if (dumpRays && dumpCount + er < dumpCap) { float *o = dumpRays + (size_t)(dumpCount + er) * 6u; o[0] = q0.x; o[1] = q0.y; o[2] = q0.z; o[3] = q1.x; o[4] = q1.y; o[5] = q1.z; }
 			}
@@ -255,7 +254,7 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 		}
 #endif
 		const uint32_t ph = w.phase;
-		TablePort<SAMP> port{ptab + myPath * CRH_PATH_F4};
+		TablePort<SAMP> port{tab.rec(myPath)};
 		const int nN = __popcll(__ballot(ph == PH_NODE)), nT = __popcll(__ballot(ph == PH_TRI)), nC = __popcll(__ballot(ph == PH_CTRL || ph == PH_NODE_SLOW));
 		const int nF = __popcll(__ballot(ph == PH_SHADE));
 		const int nE = 64 - nN - nT - nC - nF;
@@ -342,7 +341,7 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 						if (nFi + nEi >= K.swapInRun && (nFi > 0 || rqRun > 0) && hqRun < 64 && mqRun < 64) {
 							if constexpr (LEVEL >= 2) { if (lane == 0) { CRH_WCTR(21, 1); CRH_WCTR(23, nFi + min(nEi + nFi, rqRun)); } }
 							retireRefill(rqRun, hqRun, mqRun);
-							port = TablePort<SAMP>{ptab + myPath * CRH_PATH_F4};
+							port = TablePort<SAMP>{tab.rec(myPath)};
 						}
 					}
 					now = __popcll(__ballot(w.phase == PH_NODE));
@@ -448,7 +447,7 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 					v3 ro, rd;
 					PathRecT<RngT<SAMP>> r;
 					beginPath(S, P, x, y, pass, ro, rd, r, cnt);
-					putPathRay(ptab + id * CRH_PATH_F4, ro, rd, r, item | ((uint32_t)g << CRH_ROLL_SLOT_SHIFT));
+					putPathRay(tab.rec(id), ro, rd, r, item | ((uint32_t)g << CRH_ROLL_SLOT_SHIFT));
 					ids[CRH_IDS_RAYS + (uint32_t)raysQ + rk] = (uint8_t)id;
 				}
 				if (lane == 0) {
@@ -465,7 +464,7 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 				int mySlot = -1;
 				if ((int)lane < n) {
 					const uint32_t id = ids[CRH_ROLL_IDS_MISSES + (uint32_t)(missQn - n) + lane];
-					const f4 *q = ptab + id * CRH_PATH_F4;
+					const f4 *q = tab.rec(id);
 					const f4 q1 = q[1], q2 = q[2], q3 = q[3];
 					v3 ro{0.0f, 0.0f, 0.0f}, rd{q1.x, q1.y, q1.z};
 					PathRecT<RngT<SAMP>> r;
@@ -475,7 +474,7 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 					const uint32_t item = asU32(q1.w);
 					mySlot = (int)(item >> CRH_ROLL_SLOT_SHIFT);
 					TravHit h;
-					h.t = q[4].x; h.u = h.v = 0.0f; h.slot = -1; h.inst = -1;
+					h.t = tab.hit(id)->x; h.u = h.v = 0.0f; h.slot = -1; h.inst = -1;
 					(void)shadeCore(S, P, ro, rd, h, r, cnt, stk);
 					float *so = sampleSlot(mySlot, item & CRH_ROLL_ITEM_MASK); so[0] = r.fr; so[1] = r.fg; so[2] = r.fb;
 					ids[CRH_IDS_FREE_END - 1u - (uint32_t)freeQ - lane] = (uint8_t)id;
@@ -568,8 +567,8 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 				uint32_t id = 0;
 				if ((int)lane < n) {
 					id = (uint32_t)hits[(uint32_t)(hitsQ - n) + lane] & 255u;
-					f4 *q = ptab + id * CRH_PATH_F4;
-					const f4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4];
+					f4 *q = tab.rec(id);
+					const f4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = *tab.hit(id);
 					v3 ro{q0.x, q0.y, q0.z}, rd{q1.x, q1.y, q1.z};
 					PathRecT<RngT<SAMP>> r;
 					r.wr = q2.x; r.wg = q2.y; r.wb = q2.z;
@@ -579,7 +578,7 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 					const uint32_t item = asU32(q1.w);
 					TravHit h;
 					h.t = q4.x; h.u = q4.y; h.v = q4.z;
-					h.slot = (int32_t)asU32(q4.w); h.inst = (int32_t)asU32(q[5].x);
+					h.slot = (int32_t)asU32(q4.w); h.inst = (int32_t)asU32(*tab.inst(id));
 					__builtin_assume(h.inst >= 0);
 					cont = shadeCore(S, P, ro, rd, h, r, cnt, stk);
 					done = !cont;
