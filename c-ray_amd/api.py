@@ -68,6 +68,12 @@ def library():
         "crh_framebuffer_strips_to_srgb8": (C.c_int, [ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
         "crh_render_region": (C.c_int, [ctx, C.POINTER(abi.RenderParams), C.c_void_p]),
         "crh_render_tiles": (C.c_int, [ctx, C.POINTER(abi.RenderParams), C.POINTER(abi.Tile), C.c_uint32, C.c_void_p]),
+        "crh_aov_alloc": (C.c_int, [ctx, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+        "crh_aov_free": (C.c_int, [ctx, C.c_void_p]),
+        "crh_aov_clear": (C.c_int, [ctx, C.c_void_p, C.c_int, C.c_int]),
+        "crh_aov_download": (C.c_int, [ctx, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+        "crh_render_aov": (C.c_int, [ctx, C.POINTER(abi.RenderParams), C.POINTER(abi.Tile), C.c_uint32, C.c_void_p]),
+        "crh_aov_kernel_time_ms": (C.c_int, [ctx, C.POINTER(C.c_float)]),
         "crh_synchronize": (C.c_int, [ctx]),
         "crh_frames_reduce": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
         "crh_frames_gather": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -185,12 +191,16 @@ class Context:
         _check(self.L.crh_context_create(int(device), C.c_void_p(stream) if stream else None, C.byref(self.h)),
                "crh_context_create")
         self._owned_fbs = []
+        self._owned_aovs = []
 
     def close(self):
         if self.h:
             for fb in self._owned_fbs:
                 self.L.crh_framebuffer_free(self.h, fb)
             self._owned_fbs = []
+            for buf in self._owned_aovs:
+                self.L.crh_aov_free(self.h, buf)
+            self._owned_aovs = []
             self.L.crh_context_destroy(self.h)
             self.h = C.c_void_p()
 
@@ -258,6 +268,39 @@ class Context:
                              samples - first_pass if pass_count is None else pass_count, samples, bounces)
         arr = (abi.Tile * len(tiles))(*[abi.Tile(*t) for t in tiles])
         _check(self.L.crh_render_tiles(self.h, C.byref(p), arr, len(tiles), fb), "crh_render_tiles")
+
+    # ---- AOV buffers: albedo, normal, depth, coverage of every camera ray's first hit (include/cray_hip.h: crh_render_aov) ----
+    def aov_buffer(self, width, height):
+        """A zeroed device buffer of abi.AOV_CHANNELS floats per pixel, owned by the context."""
+        p = C.c_void_p()
+        _check(self.L.crh_aov_alloc(self.h, width, height, C.byref(p)), "crh_aov_alloc")
+        self._owned_aovs.append(p)
+        return p
+
+    def clear_aov(self, buf, width, height):
+        _check(self.L.crh_aov_clear(self.h, buf, width, height), "crh_aov_clear")
+
+    def render_aov(self, buf, width, height, samples, tiles=None, region=None, first_pass=0, pass_count=None):
+        """Fold passes [first_pass, first_pass + pass_count) of `samples` into `buf`: the pixels of `tiles` (a list of x0, y0, x1, y1), or of `region`, or the whole image."""
+        x0, y0, x1, y1 = region if region else (0, 0, width, height)
+        p = abi.RenderParams(x0, y0, x1, y1, width, height, first_pass, samples - first_pass if pass_count is None else pass_count, samples, 0)
+        if tiles is None:
+            _check(self.L.crh_render_aov(self.h, C.byref(p), None, 0, buf), "crh_render_aov")
+        elif len(tiles):          # (an empty list is no work; to the C entry a count of 0 means "the region of params")
+            arr = (abi.Tile * len(tiles))(*[abi.Tile(*t) for t in tiles])
+            _check(self.L.crh_render_aov(self.h, C.byref(p), arr, len(tiles), buf), "crh_render_aov")
+
+    def download_aov(self, buf, width, height):
+        """float32 [height, width, 8]: albedo r g b, normal x y z, depth, coverage (row 0 = the top of the image, like download())."""
+        out = np.empty((height, width, abi.AOV_CHANNELS), dtype=np.float32)
+        _check(self.L.crh_aov_download(self.h, buf, width, height, out.ctypes.data), "crh_aov_download")
+        return out
+
+    def aov_kernel_time_ms(self):
+        """Milliseconds of the most recent render_aov's kernel (waits for it)."""
+        ms = C.c_float(0.0)
+        _check(self.L.crh_aov_kernel_time_ms(self.h, C.byref(ms)), "crh_aov_kernel_time_ms")
+        return float(ms.value)
 
     def synchronize(self):
         _check(self.L.crh_synchronize(self.h), "crh_synchronize")

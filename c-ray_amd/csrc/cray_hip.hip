@@ -420,6 +420,7 @@ __global__ __launch_bounds__(CRH_BLOCK) void k_trace_rays(const DScene Sarg, con
 
 #include "pathtrace_stream.h"        /* k_stream_walk / k_stream_shade / k_stream_fold: the streaming form (CRH_KERNEL_STREAM, round 6) */
 #include "walk_probe.h"              /* k_walk_probe: the walk of k_pathtrace_roll on its own, on the path tracer's own rays (round 6: a measurement entry, crh_debug_walk_probe) */
+#include "aov.h"                     /* k_aov: albedo, normal, depth and coverage of every camera ray's first hit (crh_render_aov) */
 
 /* bounces <= 0: pathTrace() returns black (pathtrace.c:36); only the running mean moves (renderer.c:288-291) */
 __global__ void k_fold_black(const crh_render_params P, const crh_tile *tiles, uint32_t ntiles, float *fb, unsigned long long *counters) {
@@ -591,6 +592,15 @@ struct crh_ctx {
 	float lastMs = 0.0f;
 	double totalMs = 0.0;
 	uint64_t launches = 0;
+	/* crh_render_aov (aov.h): state of its own — an AOV dispatch leaves the render path's counters, times and kernel name as they were. The dispatch's tile list and unit
+	 * starts go through one pinned host buffer and its device twin; the work counter is reset behind the kernel */
+	uint32_t aovDepth = 0;                   /* CompiledScene::max_albedo_depth of the resident scene */
+	uint32_t *dAovCounter = nullptr;
+	void *dAovTiles = nullptr, *hAovTiles = nullptr;
+	size_t aovTileCap = 0;
+	hipEvent_t aovDone = nullptr, aovEvA = nullptr, aovEvB = nullptr;
+	bool aovInFlight = false, aovTimed = false;
+	float aovLastMs = 0.0f;
 };
 #define CRH_WORK_SLOTS 64
 static_assert(sizeof(((crh_ctx *)nullptr)->tileSlots) / sizeof(crh_ctx::TileSlot) == CRH_WORK_SLOTS, "one tile slot per work counter");
@@ -887,6 +897,12 @@ int crh_context_destroy(crh_ctx *c) {
 	if (c->dDefer) (void)hipFree(c->dDefer);
 	if (c->dQueues) (void)hipFree(c->dQueues);
 	if (c->dOvf) (void)hipFree(c->dOvf);
+	if (c->dAovCounter) (void)hipFree(c->dAovCounter);
+	if (c->dAovTiles) (void)hipFree(c->dAovTiles);
+	if (c->hAovTiles) (void)hipHostFree(c->hAovTiles);
+	if (c->aovDone) (void)hipEventDestroy(c->aovDone);
+	if (c->aovEvA) (void)hipEventDestroy(c->aovEvA);
+	if (c->aovEvB) (void)hipEventDestroy(c->aovEvB);
 	if (c->hErr) (void)hipHostFree(c->hErr);
 	if (c->pinned) (void)hipHostFree(c->pinned);
 	releaseJanitor(c, true);
@@ -1078,6 +1094,7 @@ static int uploadCompiled(crh_ctx *c, const CompiledScene &cs, const int32_t *pr
 		fprintf(stderr, "libcray_hip: CRH_WALK_WIDE4 was asked for, but this scene has no 4-ary copy (%s): the binary walk renders it\n", cs.wide_refused.c_str());
 	c->hasPrograms = cs.prog.size() > 1 || cs.has_volumes || getenv("CRH_FORCE_PROGRAMS") != nullptr;    /* the rare-features kernel variant */
 	c->hasVolumes = cs.has_volumes;
+	c->aovDepth = cs.max_albedo_depth;
 	c->haveScene = true;
 	/* The scene is resident, and the device has nothing left to do, when this function returns: a blocking device-to-host copy on the NULL stream ends the
 	 * set-up. Measured in round 3 (CRH_TRACE_SYNC): without it the first dispatch's kernel starts 7-25 ms after its launch — behind work the runtime
@@ -1823,6 +1840,152 @@ int crh_render_region(crh_ctx *c, const crh_render_params *P, float *dev_fb) {
 	if (!P) return fail(CRH_ERR_INVALID, "crh_render_region: params is NULL");
 	const crh_tile t{P->x0, P->y0, P->x1, P->y1};
 	return crh_render_tiles(c, P, &t, 1, dev_fb);
+}
+
+/* ---- AOV buffers: albedo, normal, depth, coverage of the first hit (aov.h) ----------------------- */
+int crh_aov_alloc(crh_ctx *c, int width, int height, float **dev_out) {
+	if (!c || !dev_out || width <= 0 || height <= 0) return fail(CRH_ERR_INVALID, "crh_aov_alloc: bad argument");
+	int rc = setDevice(c);
+	if (rc) return rc;
+	void *p = nullptr;
+	const size_t bytes = (size_t)width * height * CRH_AOV_CHANNELS * sizeof(float);
+	HIP_TRY(hipMalloc(&p, bytes));
+	HIP_TRY(hipMemsetAsync(p, 0, bytes, c->stream));
+	*dev_out = (float *)p;
+	return CRH_OK;
+}
+
+int crh_aov_free(crh_ctx *c, float *dev_aov) {
+	if (!c) return fail(CRH_ERR_INVALID, "crh_aov_free: ctx is NULL");
+	int rc = setDevice(c);
+	if (rc) return rc;
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	if (dev_aov) HIP_TRY(hipFree(dev_aov));
+	return CRH_OK;
+}
+
+int crh_aov_clear(crh_ctx *c, float *dev_aov, int width, int height) {
+	if (!c || !dev_aov || width <= 0 || height <= 0) return fail(CRH_ERR_INVALID, "crh_aov_clear: bad argument");
+	int rc = setDevice(c);
+	if (rc) return rc;
+	HIP_TRY(hipMemsetAsync(dev_aov, 0, (size_t)width * height * CRH_AOV_CHANNELS * sizeof(float), c->stream));
+	return CRH_OK;
+}
+
+int crh_aov_download(crh_ctx *c, const float *dev_aov, int width, int height, float *host_whc8) {
+	if (!c || !dev_aov || !host_whc8 || width <= 0 || height <= 0) return fail(CRH_ERR_INVALID, "crh_aov_download: bad argument");
+	int rc = setDevice(c);
+	if (rc) return rc;
+	HIP_TRY(hipMemcpyAsync(host_whc8, dev_aov, (size_t)width * height * CRH_AOV_CHANNELS * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	c->aovInFlight = false;
+	return CRH_OK;
+}
+
+int crh_render_aov(crh_ctx *c, const crh_render_params *P, const crh_tile *tiles, uint32_t tile_count, float *dev_aov) {
+	if (!c || !P || !dev_aov || (!tiles && tile_count)) return fail(CRH_ERR_INVALID, "crh_render_aov: NULL argument");
+	if (!c->haveScene) return fail(CRH_ERR_INVALID, "crh_render_aov: no scene uploaded");
+	if (P->image_width <= 0 || P->image_height <= 0 || P->pass_count < 0 || P->first_pass < 0 || P->max_passes < P->first_pass + P->pass_count)
+		return fail(CRH_ERR_INVALID, "crh_render_aov: bad render parameters");
+	const crh_tile whole{P->x0, P->y0, P->x1, P->y1};
+	if (!tiles || !tile_count) { tiles = &whole; tile_count = 1; }
+	for (uint32_t i = 0; i < tile_count; ++i) {
+		const crh_tile &t = tiles[i];
+		if (t.x0 < 0 || t.y0 < 0 || t.x1 > P->image_width || t.y1 > P->image_height) return fail(CRH_ERR_INVALID, "crh_render_aov: rectangle " + std::to_string(i) + " lies outside the image");
+	}
+	if (c->aovDepth > CRH_AOV_STACK)
+		return fail(CRH_ERR_UNSUPPORTED, "crh_render_aov: a material nests mix / add nodes " + std::to_string(c->aovDepth) + " deep (the albedo evaluator holds " + std::to_string(CRH_AOV_STACK) + " frames)");
+	if (P->pass_count == 0) return CRH_OK;
+	/* units of `group` consecutive pixels of a tile (aov.h) */
+	const uint32_t group = 64u / (uint32_t)std::min(P->pass_count, 64);
+	std::vector<crh_tile> work;
+	std::vector<uint32_t> start;
+	uint64_t allGroups = 0;
+	for (uint32_t i = 0; i < tile_count; ++i) {
+		const crh_tile &t = tiles[i];
+		if (t.x1 <= t.x0 || t.y1 <= t.y0) continue;
+		work.push_back(t);
+		allGroups += ((uint64_t)(t.x1 - t.x0) * (uint64_t)(t.y1 - t.y0) + group - 1u) / group;
+	}
+	if (allGroups == 0) return CRH_OK;
+	if (allGroups >= (1ull << 31)) return fail(CRH_ERR_INVALID, "crh_render_aov: too many pixels in one dispatch");
+	/* a unit = `groups` consecutive groups of a tile: about eight units per wave of a full grid (every pull is an atomic on one counter), 64 groups at the most;
+	 * CRH_AOV_UNIT_GROUPS=<n> (dev / tests) fixes it */
+	const uint64_t fullWaves = (uint64_t)c->cuCount * CRH_AOV_BLOCKS_PER_CU * (CRH_BLOCK / 64);
+	uint32_t groups = (uint32_t)std::min<uint64_t>(64u, std::max<uint64_t>(1u, allGroups / (fullWaves * 8u)));
+	if (const char *env = getenv("CRH_AOV_UNIT_GROUPS")) { if (atoi(env) >= 1 && atoi(env) <= 4096) groups = (uint32_t)atoi(env); }
+	uint64_t total = 0;
+	for (const crh_tile &t : work) {
+		start.push_back((uint32_t)total);
+		const uint64_t tileGroups = ((uint64_t)(t.x1 - t.x0) * (uint64_t)(t.y1 - t.y0) + group - 1u) / group;
+		total += (tileGroups + groups - 1u) / groups;
+	}
+	start.push_back((uint32_t)total);
+	int rc = setDevice(c);
+	if (rc) return rc;
+	const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)c->cuCount * CRH_AOV_BLOCKS_PER_CU, (total + CRH_BLOCK / 64 - 1) / (CRH_BLOCK / 64));          /* (as many workgroups as a CU holds: aov.h) */
+	{
+		const size_t need = (size_t)grid * (CRH_BLOCK / 64) * CRH_OVF_WORDS_PER_WAVE;          /* the render kernels' overflow columns: the same stream, one dispatch at a time */
+		if (need > c->ovfWords) {
+			HIP_TRY(hipStreamSynchronize(c->stream));
+			if (c->dOvf) HIP_TRY(hipFree(c->dOvf));
+			c->dOvf = nullptr; c->ovfWords = 0;
+			HIP_TRY(hipMalloc((void **)&c->dOvf, need * sizeof(uint32_t)));
+			c->ovfWords = need;
+		}
+	}
+	if (!c->dAovCounter) {
+		HIP_TRY(hipMalloc((void **)&c->dAovCounter, sizeof(uint32_t)));
+		HIP_TRY(hipMemsetAsync(c->dAovCounter, 0, sizeof(uint32_t), c->stream));
+		HIP_TRY(hipEventCreateWithFlags(&c->aovDone, hipEventDisableTiming));
+		HIP_TRY(hipEventCreate(&c->aovEvA));
+		HIP_TRY(hipEventCreate(&c->aovEvB));
+	}
+	if (c->aovInFlight) { HIP_TRY(hipEventSynchronize(c->aovDone)); c->aovInFlight = false; }          /* the dispatch before this one has read the list */
+	const size_t tileBytes = work.size() * sizeof(crh_tile), startBytes = start.size() * sizeof(uint32_t);
+	if (tileBytes + startBytes > c->aovTileCap) {
+		if (c->dAovTiles) HIP_TRY(hipFree(c->dAovTiles));
+		if (c->hAovTiles) HIP_TRY(hipHostFree(c->hAovTiles));
+		c->dAovTiles = c->hAovTiles = nullptr; c->aovTileCap = 0;
+		const size_t cap = std::max<size_t>(4096, 2 * (tileBytes + startBytes));
+		HIP_TRY(hipMalloc(&c->dAovTiles, cap));
+		HIP_TRY(hipHostMalloc(&c->hAovTiles, cap, hipHostMallocDefault));
+		c->aovTileCap = cap;
+	}
+	memcpy(c->hAovTiles, work.data(), tileBytes);
+	memcpy((char *)c->hAovTiles + tileBytes, start.data(), startBytes);
+	HIP_TRY(hipMemcpyAsync(c->dAovTiles, c->hAovTiles, tileBytes + startBytes, hipMemcpyHostToDevice, c->stream));
+	AovUnits U;
+	U.tiles = (const crh_tile *)c->dAovTiles;
+	U.start = (const uint32_t *)((const char *)c->dAovTiles + tileBytes);
+	U.ntiles = (uint32_t)work.size(); U.total = (uint32_t)total; U.counter = c->dAovCounter; U.group = group; U.groups = groups;
+	const uint32_t rayFlags = (uint32_t)c->sched.rayFlags;
+	HIP_TRY(hipEventRecord(c->aovEvA, c->stream));
+#define CRH_LAUNCH_AOV(SAMP, RARE) hipLaunchKernelGGL((k_aov<SAMP, RARE>), dim3(grid), dim3(CRH_BLOCK), 0, c->stream, c->d, *P, U, dev_aov, rayFlags, c->dOvf)
+	if (c->sampler == CRH_SAMPLER_HALTON) { if (c->hasPrograms) CRH_LAUNCH_AOV(1, true); else CRH_LAUNCH_AOV(1, false); }
+	else { if (c->hasPrograms) CRH_LAUNCH_AOV(0, true); else CRH_LAUNCH_AOV(0, false); }
+#undef CRH_LAUNCH_AOV
+	const hipError_t e = hipGetLastError();
+	HIP_TRY(hipEventRecord(c->aovEvB, c->stream));
+	HIP_TRY(hipMemsetAsync(c->dAovCounter, 0, sizeof(uint32_t), c->stream));          /* ready for the next dispatch */
+	HIP_TRY(hipEventRecord(c->aovDone, c->stream));
+	c->aovInFlight = true; c->aovTimed = true;
+	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string("k_aov launch: ") + hipGetErrorString(e));
+	return CRH_OK;
+}
+
+/* Duration of the most recent crh_render_aov's kernel (HIP events on the context's stream; waits for it); 0 before the first one. */
+int crh_aov_kernel_time_ms(crh_ctx *c, float *last_ms) {
+	if (!c || !last_ms) return fail(CRH_ERR_INVALID, "crh_aov_kernel_time_ms: NULL argument");
+	int rc = setDevice(c);
+	if (rc) return rc;
+	if (c->aovTimed) {
+		HIP_TRY(hipEventSynchronize(c->aovEvB));
+		HIP_TRY(hipEventElapsedTime(&c->aovLastMs, c->aovEvA, c->aovEvB));
+		c->aovTimed = false;
+	}
+	*last_ms = c->aovLastMs;
+	return CRH_OK;
 }
 
 /* ---- RCCL (loaded lazily: single-GPU users never need it) ---------------------------------------- */

@@ -72,6 +72,7 @@ struct Compiler {
 	CompiledScene &out;
 	std::map<uint32_t, uint32_t> oprMemo;
 	std::vector<uint8_t> needUv;          /* per bsdf gnode: its graph reads the hit's uv */
+	std::vector<uint32_t> albedoDepth;    /* per bsdf gnode: mix / add nodes nested on the deepest way down from it (a plastic node passes its diffuse layer's on) */
 	std::function<void()> texelsReady;
 	double tRelayoutPar = 0, tRelayoutDepth = 0, tTriLoop = 0, tResize = 0;          /* CRH_TRACE_UPLOAD: where "BLAS + prepared triangles" goes */
 	static double nowMs() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -350,6 +351,7 @@ struct Compiler {
 		out.bsdfs.assign(N ? N : 1, DBsdf{0, CRH_NONE, CRH_NONE, CRH_NONE});
 		std::vector<uint32_t> addDepth(N, 0);
 		needUv.assign(N, 0);
+		albedoDepth.assign(N, 0);
 		auto oprUv = [](uint32_t opr) { const uint32_t k = opr >> 29; return opr != CRH_NONE && (k == CRH_OPR_IMAGE || k == CRH_OPR_IMAGE_ALPHA || k == CRH_OPR_PROGRAM); };
 		for (uint32_t g = 0; g < N; ++g) {
 			const crh_gnode &n = s->gnodes[g];
@@ -362,13 +364,13 @@ struct Compiler {
 				case CRH_BSDF_GLASS: d.a = operand(n.a, g, COLOR); d.b = operand(n.b, g, VALUE); d.c = operand(n.c, g, VALUE); break;
 				case CRH_BSDF_PLASTIC:
 					d.a = operand(n.a, g, COLOR); d.b = operand(n.b, g, COLOR); d.c = bsdfChild(n.c, g);
-					addDepth[g] = addDepth[n.c]; break;
+					addDepth[g] = addDepth[n.c]; albedoDepth[g] = albedoDepth[n.c]; break;
 				case CRH_BSDF_MIX:
 					d.a = bsdfChild(n.a, g); d.b = bsdfChild(n.b, g); d.c = operand(n.c, g, VALUE);
-					addDepth[g] = std::max(addDepth[n.a], addDepth[n.b]); break;
+					addDepth[g] = std::max(addDepth[n.a], addDepth[n.b]); albedoDepth[g] = 1 + std::max(albedoDepth[n.a], albedoDepth[n.b]); break;
 				case CRH_BSDF_ADD:
 					d.a = bsdfChild(n.a, g); d.b = bsdfChild(n.b, g);
-					addDepth[g] = 1 + std::max(addDepth[n.a], addDepth[n.b]); break;
+					addDepth[g] = 1 + std::max(addDepth[n.a], addDepth[n.b]); albedoDepth[g] = 1 + std::max(albedoDepth[n.a], albedoDepth[n.b]); break;
 				case CRH_BSDF_EMISSION: d.a = operand(n.a, g, COLOR); d.b = operand(n.b, g, VALUE); break;
 				case CRH_BSDF_BACKGROUND: d.a = operand(n.a, g, COLOR); d.b = operand(n.b, g, VALUE); d.c = operand(n.c, g, VALUE); break;
 				default: break;
@@ -461,6 +463,7 @@ struct Compiler {
 			const uint32_t b = s->materials[m].bsdf;
 			CHECK(b < s->gnode_count && isBsdfKind(s->gnodes[b].kind) && s->gnodes[b].kind != CRH_BSDF_BACKGROUND, CRH_ERR_INVALID, "material %llu has no surface bsdf", (unsigned long long)m);
 			out.materials[m].pad[0] = needUv[b];
+			out.max_albedo_depth = std::max(out.max_albedo_depth, albedoDepth[b]);
 		}
 
 		const double tBlas0 = nowMs();

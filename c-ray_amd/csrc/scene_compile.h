@@ -94,6 +94,7 @@ struct CompiledScene {
 	uint32_t tlas_first = 0;    /* device index of TLAS node 1 (the TLAS nodes are contiguous: node i at tlas_first - 1 + i) */
 	uint32_t max_stack = 0;     /* worst-case traversal stack entries (TLAS depth + saved TLAS state + deepest BLAS) */
 	uint32_t max_add_depth = 0;
+	uint32_t max_albedo_depth = 0;   /* deepest nesting of mix / add nodes under a material's root: the frames crh_render_aov's albedo evaluator opens (aov.h: CRH_AOV_STACK) */
 	/* CRH_OPT_WALK = CRH_WALK_WIDE4 (round 5, an OPTION: the binary walk over `nodes` stays the contract): a derived 4-ary copy of every BVH with at least one inner
 	 * node, collapsed from the reference's binary tree (the inner child with the largest surface is replaced by its two children until four children stand; the boxes are
 	 * the binary nodes' own bits). A wide node = 4 x 32 B: {minx, maxx, miny, maxy} {minz, maxz, ref, 0}; ref = CRH_NONE for an unused slot (its box is never hit), the

@@ -32,7 +32,9 @@
  * does renderFrame() end with logr(error, ...).
  *
  * Environment: CRAY_HIP_DEVICES=<n> caps the number of GPUs used; CRH_DROPIN_PASSES=<n> (dev / tests) fixes the passes per dispatch; CRH_DUMP_F32=<path> dumps the float buffer; CRH_DUMP_STATS=<path>
- * writes where the frame's time went; CRH_FRAMES=reduce: see above.
+ * writes where the frame's time went; CRH_FRAMES=reduce: see above. CRAY_HIP_AOV=<n> (user-facing, like CRAY_HIP_WALK): after the frame, GPU 0 renders the guide buffers
+ * a denoiser or a compositor asks for — albedo, normal, depth of every camera ray's first hit, n passes of them (crh_render_aov) — and writes them beside the frame
+ * through the reference's own encoders (writeAovs below); CRH_DUMP_AOV_F32=<path> dumps their floats.
  * No GPU => logr(error, ...) (which exits, src/utils/logging.c:69-73): there is no CPU fallback in this file.
  */
 #include <stdlib.h>
@@ -57,6 +59,7 @@
 #include "utils/platform/thread.h"
 #include "utils/platform/mutex.h"
 #include "utils/args.h"
+#include "utils/encoders/encoder.h"
 
 #include "cray_hip.h"
 #include "flatten.h"
@@ -163,6 +166,10 @@ static int frameWalk(void) {
 
 static crh_ctx *makeContext(int device) {
 	crh_ctx *c = NULL;
+	if (crh_abi_version() != CRH_ABI_VERSION) {          /* this file is built with the header of the library it expects */
+		logr(warning, "c-ray-hip: libcray_hip has ABI version %i, this program was built for %i\n", crh_abi_version(), CRH_ABI_VERSION);
+		return NULL;
+	}
 	/* counter level 1: this host reports rays only (the detailed counters cost ~20 % of the kernel's time) */
 	if (crh_context_create(device, NULL, &c) != CRH_OK) return NULL;
 	if (crh_set_option(c, CRH_OPT_COUNTER_LEVEL, 1) != CRH_OK || crh_set_option(c, CRH_OPT_WALK, frameWalk()) != CRH_OK ||
@@ -551,6 +558,59 @@ static int assembleOnHost(struct renderer *r, struct gpuWorker *workers, int gpu
 	return 0;
 }
 
+/* CRAY_HIP_AOV=<n>: min(n, sampleCount) passes of the first-hit buffers of the whole image, on GPU 0 (primary rays only: nothing to gather), written as 8-bit
+ * images <imgFileName>_albedo, _normal (0.5 n + 0.5) and _depth (divided by the frame's largest depth) beside the frame, by the reference's own newImageFile /
+ * writeImage; CRH_DUMP_AOV_F32=<path> dumps the raw [H, W, 8] floats the way CRH_DUMP_F32 dumps the frame. The scene is still resident in ctx. */
+static void writeAovs(struct renderer *r, crh_ctx *ctx, int W, int H) {
+	const char *e = getenv("CRAY_HIP_AOV");
+	int n = e ? atoi(e) : 0;
+	if (n <= 0 || !ctx) return;
+	if (n > r->prefs.sampleCount) n = r->prefs.sampleCount;
+	const size_t pixels = (size_t)W * (size_t)H;
+	float *host = malloc(pixels * CRH_AOV_CHANNELS * sizeof(float));
+	float *dev = NULL;
+	crh_render_params p;
+	memset(&p, 0, sizeof(p));
+	p.x1 = W; p.y1 = H; p.image_width = W; p.image_height = H; p.pass_count = n; p.max_passes = r->prefs.sampleCount;
+	if (!host || crh_aov_alloc(ctx, W, H, &dev) != CRH_OK || crh_render_aov(ctx, &p, NULL, 0, dev) != CRH_OK || crh_aov_download(ctx, dev, W, H, host) != CRH_OK) {
+		logr(warning, "c-ray-hip: the AOV buffers could not be rendered: %s\n", host ? crh_last_error() : "out of memory");
+		if (dev) crh_aov_free(ctx, dev);
+		free(host);
+		return;
+	}
+	crh_aov_free(ctx, dev);
+	const char *dump = getenv("CRH_DUMP_AOV_F32");
+	if (dump) {
+		FILE *f = fopen(dump, "wb");
+		if (f) { fwrite(host, sizeof(float), pixels * CRH_AOV_CHANNELS, f); fclose(f); }
+	}
+	float maxDepth = 0.0f;
+	for (size_t i = 0; i < pixels; ++i) if (host[i * CRH_AOV_CHANNELS + 6] > maxDepth) maxDepth = host[i * CRH_AOV_CHANNELS + 6];
+	static const char *const suffix[3] = {"_albedo", "_normal", "_depth"};
+	const char *base = r->prefs.imgFileName ? r->prefs.imgFileName : "rendered";
+	for (int k = 0; k < 3; ++k) {
+		struct texture *t = newTexture(char_p, (size_t)W, (size_t)H, 3);
+		for (size_t i = 0; i < pixels; ++i) {          /* (the buffer's pixel order is the frame's: texture.c:24-28) */
+			const float *a = host + i * CRH_AOV_CHANNELS;
+			for (int c = 0; c < 3; ++c) {
+				float v = k == 0 ? a[c] : k == 1 ? 0.5f * a[3 + c] + 0.5f : (maxDepth > 0.0f ? a[6] / maxDepth : 0.0f);
+				v = v > 0.0f ? (v < 1.0f ? v : 1.0f) : 0.0f;          /* (NaN -> 0) */
+				t->data.byte_p[i * 3 + (size_t)c] = (unsigned char)(v * 255.0f);
+			}
+		}
+		char *name = malloc(strlen(base) + strlen(suffix[k]) + 1);
+		if (name) {
+			strcpy(name, base); strcat(name, suffix[k]);
+			struct imageFile *file = newImageFile(t, r->prefs.imgFilePath ? r->prefs.imgFilePath : "", name, r->prefs.imgCount, r->prefs.imgType);
+			writeImage(file);
+			destroyImageFile(file);          /* (the texture goes with it) */
+			free(name);
+		} else destroyTexture(t);
+	}
+	logr(info, "%i AOV pass%s written (albedo, normal, depth).\n", n, n == 1 ? "" : "es");
+	free(host);
+}
+
 struct texture *renderFrame(struct renderer *r) {
 	const int W = (int)r->prefs.imageWidth, H = (int)r->prefs.imageHeight;
 	struct timeval frame;
@@ -709,6 +769,7 @@ struct texture *renderFrame(struct renderer *r) {
 		if (f) { fwrite(buf->data.float_p, sizeof(float), (size_t)W * H * 3, f); fclose(f); }
 	}
 	logr(info, "%llu rays traced on %i GPU%s.\n", (unsigned long long)rays, gpus, PLURAL(gpus));
+	if (!workers[0].failed && !r->state.renderAborted) writeAovs(r, workers[0].ctx, W, H);
 
 	for (int g = 0; g < gpus; ++g) {
 		if (workers[g].ctx && workers[g].fb) crh_framebuffer_free(workers[g].ctx, workers[g].fb);

@@ -35,8 +35,9 @@ extern "C" {
  * 3 (round 5): crh_scene_compile / crh_scene_upload_compiled / crh_compiled_scene_free (one layout compile for the contexts of a multi-GPU frame) and CRH_OPT_WALK exist.
  * (round 6 adds values, not entry points — CRH_KERNEL_STREAM for CRH_OPT_KERNEL, CRH_OPT_STREAM_COHORTS, and the debug entries crh_debug_ray_dump* / crh_debug_walk_probe* of the
  * walk-only probe —: a version-3 host is unaffected, the version stays 3.)
+ * 4: the AOV entry points — crh_aov_alloc / crh_aov_free / crh_aov_clear / crh_aov_download / crh_render_aov / crh_aov_kernel_time_ms — exist.
  * A host checks crh_abi_version() == CRH_ABI_VERSION. */
-#define CRH_ABI_VERSION 3
+#define CRH_ABI_VERSION 4
 /* layout version of crh_scene_desc and of the scene blobs (crh_blob_save / crh_blob_load): the records have not changed since round 1 */
 #define CRH_SCENE_VERSION 1
 
@@ -405,6 +406,37 @@ int crh_render_region(crh_ctx *ctx, const crh_render_params *params, float *dev_
  * one launch per tile. Tiles must not overlap. */
 typedef struct crh_tile { int32_t x0, y0, x1, y1; } crh_tile;
 int crh_render_tiles(crh_ctx *ctx, const crh_render_params *params, const crh_tile *tiles, uint32_t tile_count, float *dev_fb);
+
+/* AOV buffers — what a denoiser or a compositor asks of a path tracer besides the frame: albedo, normal, depth and coverage of every camera ray's FIRST hit.
+ * An AOV buffer is a device float buffer of CRH_AOV_CHANNELS floats per pixel in the frame buffer's pixel order, index (x + (H-1-y)*W) * 8:
+ *   0..2 albedo r g b | 3..5 normal x y z | 6 depth | 7 coverage
+ * For every pixel of the dispatch and every pass in [first_pass, first_pass + pass_count): the ray is exactly the one crh_render_region starts for that (x, y, pass) —
+ * initSampler(pass, max_passes, y * image_width + x), then getCameraRay, with the sampler CRH_OPT_SAMPLER names —, the hit is getClosestIsect's over the reference's
+ * binary trees (whatever CRH_OPT_WALK says; degenerate slabs as CRH_OPT_RENDER_SLABS says; in a scene with volumes the walk draws from this path's sampler in the
+ * render's order, so the first hit is the render's first hit). A miss's sample is eight zeros. A hit's: coverage 1, depth = the record's distance, normal = the
+ * record's normal exactly as crh_hit.normal reports it (world space, not turned towards the viewer, a sphere's not renormalised), and the albedo — a pure function of
+ * the hit, no sampler draws, on the material's bsdf root; C = the colour operand, V = the value operand evaluated at the hit:
+ *   diffuse, metal, glass, transparent, isotropic: C(a) | emission: C(a) * V(b) | plastic: the albedo of its diffuse layer c
+ *   mix: (1 - V(c)) * albedo(a) + V(c) * albedo(b) (cmix, color.h:46) | add: albedo(a) + albedo(b)
+ * A scattering event inside a volume: coverage 1, its distance, normal (0, 0, 0) (the reference's is a placeholder), the albedo of the volume's material.
+ * Every channel is folded into the buffer with the running mean of renderer.c:288-291, in pass order with completedSamples = pass + 1: a buffer filled by several
+ * dispatches over consecutive pass ranges equals one dispatch over all of them bit for bit, and the result does not depend on the tile list.
+ * The albedo is evaluated with CRH_AOV_ALBEDO_DEPTH frames: a scene in which a material nests mix / add nodes deeper (decided once, at upload; rendering is
+ * unaffected) makes crh_render_aov return CRH_ERR_UNSUPPORTED. An AOV dispatch leaves crh_counters, crh_kernel_time_ms and crh_last_kernel_name as they were;
+ * params->bounces is ignored. CRH_ERR_INVALID: a NULL argument, no scene, a rectangle outside the image. A dispatch with no work (pass_count == 0, empty
+ * rectangles) is CRH_OK and writes nothing. */
+#define CRH_AOV_CHANNELS 8
+#define CRH_AOV_ALBEDO_DEPTH 8
+int crh_aov_alloc(crh_ctx *ctx, int width, int height, float **dev_out);      /* zeroed */
+int crh_aov_free(crh_ctx *ctx, float *dev_aov);
+int crh_aov_clear(crh_ctx *ctx, float *dev_aov, int width, int height);
+int crh_aov_download(crh_ctx *ctx, const float *dev_aov, int width, int height, float *host_whc8);      /* synchronises the stream */
+/* tiles == NULL / tile_count == 0: the region x0..y1 of params; otherwise the rectangles of the list (x0..y1 of params are ignored; they must not overlap).
+ * Asynchronous on the context's stream; dev_aov may be a caller-owned device pointer (a torch tensor). */
+int crh_render_aov(crh_ctx *ctx, const crh_render_params *params, const crh_tile *tiles, uint32_t tile_count, float *dev_aov);
+/* Duration in milliseconds of the most recent crh_render_aov's kernel (waits for it); 0 before the first one. */
+int crh_aov_kernel_time_ms(crh_ctx *ctx, float *last_ms);
+
 /* Multi-GPU inside one process (the C host, c-ray_amd/host/renderer_hip.c: one crh_ctx + one dispatch thread per
  * GPU): sum the n per-GPU float framebuffers onto ctxs[0]'s with ONE RCCL reduce over xGMI (ncclReduce, float,
  * sum, root 0; communicators from ncclCommInitAll). Tiles are disjoint and non-owned pixels are 0, so the sum is

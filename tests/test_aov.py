@@ -1,0 +1,404 @@
+"""First-hit guide buffers (crh_render_aov, c-ray_amd/csrc/aov.h): albedo, normal, depth and coverage of every camera ray's first hit,
+folded per pixel with the frame's running mean — what a denoiser or a compositor asks of a path tracer besides the frame.
+
+The GPU tier holds the buffers to the oracle and to the reference's own renders bit for bit: the geometry channels against
+oracle.camera_ray -> oracle.trace_rays, the albedo against the golden frame where the frame IS the albedo (diffuse materials under a white
+background) and against a restatement of the albedo rule on constant graphs, the coverage against the oracle's render of a scene in which
+every surface emits white under a black sky (volumes and both samplers included), and every decomposition of a dispatch against one
+dispatch. The CPU tier runs this file's GPU tests on the kernel emulation (tests/emu: the same kernel source on a HIP shim)."""
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import resize_camera
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EMU_DIR = os.path.join(REPO, "tests", "emu")
+NONE = 0xFFFFFFFF
+# enum crh_node_kind (include/cray_hip.h)
+DIFFUSE, METAL, GLASS, PLASTIC, MIX, ADD, TRANSPARENT, EMISSION, ISOTROPIC = range(1, 10)
+COLOR_CONSTANT, VALUE_CONSTANT = 32, 64
+KIND_NAMES = {DIFFUSE: "diffuse", METAL: "metal", GLASS: "glass", PLASTIC: "plastic", MIX: "mix", ADD: "add", TRANSPARENT: "transparent",
+              EMISSION: "emission", ISOTROPIC: "isotropic"}
+
+
+@pytest.fixture(scope="module")
+def ctx(pkg):
+    if pkg.api.device_count() < 1:
+        pytest.fail("GPU tier needs a HIP device; libcray_hip has no CPU fallback")
+    c = pkg.api.Context(0)
+    yield c
+    c.close()
+
+
+def fold(mean, sample, completed):
+    """renderer.c:288-291 in float32, the operations in the reference's order."""
+    n1, t = np.float32(completed - 1), np.float32(1.0) / np.float32(completed)
+    return ((mean * n1) + sample) * t
+
+
+def first_hits(oracle, oscene, w, h, passes, max_passes, region=None):
+    """oracle.camera_ray -> oracle.trace_rays for every pixel of the region and every pass: hits[pass][row, col] (stored rows run top-down)."""
+    x0, y0, x1, y1 = region or (0, 0, w, h)
+    rays = np.zeros((len(passes), y1 - y0, x1 - x0, 6), np.float32)
+    for k, p in enumerate(passes):
+        for y in range(y0, y1):
+            for x in range(x0, x1):
+                rays[k, y1 - 1 - y, x - x0] = oracle.camera_ray(oscene, x, y, p, max_passes)
+    return oracle.trace_rays(oscene, rays.reshape(-1, 6)).reshape(len(passes), y1 - y0, x1 - x0)
+
+
+def geometry_expected(hits, passes):
+    """Channels 3..7 of the samples (a miss: zeros; a hit: the record's normal and distance, coverage 1), folded in pass order."""
+    mean = np.zeros(hits.shape[1:] + (5,), np.float32)
+    for k, p in enumerate(passes):
+        hit = hits[k]["inst"] >= 0
+        s = np.zeros_like(mean)
+        s[..., 0:3] = np.where(hit[..., None], hits[k]["normal"], np.float32(0))
+        s[..., 3] = np.where(hit, hits[k]["distance"], np.float32(0))
+        s[..., 4] = hit.astype(np.float32)
+        mean = fold(mean, s, p + 1)
+    return mean
+
+
+def gpu_aov(pkg, ctx, blob, w, h, samples, resize=False, **kw):
+    scene = pkg.api.Scene(blob)
+    if resize:
+        resize_camera(scene, w, h)
+    ctx.upload(scene)
+    buf = ctx.aov_buffer(w, h)
+    ctx.render_aov(buf, w, h, samples, **kw)
+    return ctx.download_aov(buf, w, h)
+
+
+GEOMETRY_CASES = [("nodezoo_display", 320, 192, 3, False), ("uvsphere", 160, 100, 2, False), ("cfg1_scene", 160, 100, 2, True)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,w,h,passes,resize", GEOMETRY_CASES)
+def test_geometry_channels_equal_the_oracles_first_hits(name, w, h, passes, resize, pkg, ctx, oracle, golden_blob):
+    """Normal, depth and coverage of `passes` passes of `passes`: the oracle's camera rays through the oracle's getClosestIsect, folded in numpy."""
+    blob = golden_blob(name)
+    oscene = oracle.OracleScene(blob)
+    if resize:
+        resize_camera(oscene, w, h)
+    hits = first_hits(oracle, oscene, w, h, range(passes), passes)
+    want = geometry_expected(hits, range(passes))
+    got = gpu_aov(pkg, ctx, blob, w, h, passes, resize=resize)
+    miss0 = float((hits[0]["inst"] < 0).mean())
+    print(f"{name}: {miss0:.3f} of the pass-0 rays miss")
+    assert miss0 < 0.99 and (name != "nodezoo_display" or 0.17 < miss0 < 0.18), "the fixture shows hits (nodezoo_display: 17.5 % misses)"
+    assert np.array_equal(got[..., 3:8].view(np.uint32), want.view(np.uint32)), f"{name}: {(got[..., 3:8].view(np.uint32) != want.view(np.uint32)).sum()} floats differ"
+
+
+@pytest.mark.gpu
+def test_albedo_equals_the_references_render_on_diffuse_materials(pkg, ctx, oracle, golden_blob, golden_ref):
+    """nodezoo_display, 1 pass of 1: where the first hit lands on a material whose root is a diffuse bsdf and which does not emit, and the path's second ray
+    reached the white background (the golden pixel is not black), the reference's pixel IS the albedo: image, checker, blackbody, combineRGB, vecToColor graphs."""
+    from test_nodes import check_known_answers
+    w, h = 320, 192
+    blob = golden_blob("nodezoo_display")
+    oscene = oracle.OracleScene(blob)
+    hits = first_hits(oracle, oscene, w, h, [0], 1)[0]
+    d = oscene.desc
+    diffuse = np.array([d.gnodes[d.materials[m].bsdf].kind == DIFFUSE and not any(d.materials[m].emission[c] != 0.0 for c in range(3))
+                        for m in range(d.material_count)])
+    golden = golden_ref("nodezoo_display")
+    hit = hits["inst"] >= 0
+    mat = np.where(hit, hits["material"], 0)
+    sel = hit & diffuse[mat] & (golden != 0).any(axis=2)
+    print(f"{int(sel.sum())} pixels over {len(np.unique(mat[sel]))} materials")
+    assert sel.sum() >= 8000 and len(np.unique(mat[sel])) >= 40
+    got = gpu_aov(pkg, ctx, blob, w, h, 1)
+    assert np.array_equal(got[..., 0:3][sel].view(np.uint32), golden[sel].view(np.uint32)), f"{(got[..., 0:3][sel] != golden[sel]).any(axis=1).sum()} pixels differ"
+    check_known_answers(np.ascontiguousarray(got[..., 0:3]))
+
+
+def constant_albedo(g, i, kinds):
+    """The albedo rule (include/cray_hip.h) on a graph in which every colour and value operand the rule reads is a constant node: float32[3], or None."""
+    def color(j):
+        return np.float32(list(g[j].f[0:3])) if j != NONE and g[j].kind == COLOR_CONSTANT else None
+
+    def value(j):
+        return np.float32(g[j].f[0]) if j != NONE and g[j].kind == VALUE_CONSTANT else None
+    n = g[i]
+    kinds.add(n.kind)
+    if n.kind in (DIFFUSE, METAL, GLASS, TRANSPARENT, ISOTROPIC):
+        return color(n.a)
+    if n.kind == EMISSION:
+        c, v = color(n.a), value(n.b)
+        return None if c is None or v is None else c * v
+    if n.kind == PLASTIC:
+        return constant_albedo(g, n.c, kinds)
+    if n.kind in (MIX, ADD):
+        a, b = constant_albedo(g, n.a, kinds), constant_albedo(g, n.b, kinds)
+        if a is None or b is None:
+            return None
+        if n.kind == ADD:
+            return a + b
+        v = value(n.c)
+        return None if v is None else (np.float32(1.0) - v) * a + v * b
+    return None
+
+
+@pytest.mark.gpu
+def test_albedo_rules_on_constant_graphs(pkg, ctx, oracle, golden_blob):
+    """nodezoo, 1 pass of 1: the materials whose graphs hold constants only, against the rule restated in numpy float32."""
+    w, h = 320, 192
+    blob = golden_blob("nodezoo")
+    oscene = oracle.OracleScene(blob)
+    hits = first_hits(oracle, oscene, w, h, [0], 1)[0]
+    d = oscene.desc
+    want = np.zeros((h, w, 3), np.float32)
+    sel = np.zeros((h, w), bool)
+    kinds, materials = set(), 0
+    for m in np.unique(hits["material"][hits["inst"] >= 0]):
+        k = set()
+        a = constant_albedo(d.gnodes, d.materials[int(m)].bsdf, k)
+        if a is None:
+            continue
+        here = (hits["inst"] >= 0) & (hits["material"] == m)
+        want[here] = a
+        sel |= here
+        kinds |= k
+        materials += 1
+    print(f"{materials} materials, {int(sel.sum())} pixels, kinds {sorted(KIND_NAMES[k] for k in kinds)}")
+    assert kinds == {DIFFUSE, METAL, GLASS, PLASTIC, MIX, ADD, EMISSION, ISOTROPIC}, sorted(KIND_NAMES[k] for k in kinds)
+    assert sel.sum() >= 2500 and materials >= 10
+    got = gpu_aov(pkg, ctx, blob, w, h, 1)
+    assert np.array_equal(got[..., 0:3][sel].view(np.uint32), want[sel].view(np.uint32)), f"{(got[..., 0:3][sel] != want[sel]).any(axis=1).sum()} pixels differ"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("halton", [False, True], ids=["random", "halton"])
+@pytest.mark.parametrize("name,w,h,passes", [("volumes", 240, 160, 8), ("glowmetal", 160, 100, 4)])
+def test_coverage_equals_the_oracles_render_of_white_emitters(name, w, h, passes, halton, pkg, ctx, oracle, golden_blob):
+    """In the oracle's copy of the scene every material emits (1, 1, 1) and the sky is black: one bounce of its render is the coverage, with the
+    walk's own sampler draws inside the volumes. The GPU side uploads the unmodified blob."""
+    blob = golden_blob(name)
+    oscene = oracle.OracleScene(blob)
+    d = oscene.desc
+    for m in range(d.material_count):
+        for c in range(3):
+            d.materials[m].emission[c] = 1.0
+    sky = d.gnodes[d.gnodes[d.background].a]
+    sky.kind = COLOR_CONSTANT
+    for c in range(4):
+        sky.f[c] = 0.0
+    want = oracle.render(oscene, w, h, passes, 1, halton=halton, threads=1)[0][..., 0]
+    ctx.set_option(pkg.abi.OPT_SAMPLER, pkg.abi.SAMPLER_HALTON if halton else pkg.abi.SAMPLER_RANDOM)
+    try:
+        got = gpu_aov(pkg, ctx, blob, w, h, passes)[..., 7]
+    finally:
+        ctx.set_option(pkg.abi.OPT_SAMPLER, pkg.abi.SAMPLER_RANDOM)
+    partial = int(((want > 0) & (want < 1)).sum())
+    print(f"{name} {'halton' if halton else 'random'}: {partial} partial pixels")
+    assert partial >= 100
+    assert np.array_equal(got.view(np.uint32), np.ascontiguousarray(want).view(np.uint32)), f"{(got != want).sum()} pixels differ"
+
+
+def ragged_tiles(w, h):
+    """Rectangles that cover the frame: columns of widths 1, 7, 13, 67, ... cut into rows of heights 3, 37, rest."""
+    tiles, x, k = [], 0, 0
+    while x < w:
+        x1 = min(w, x + (1, 7, 13, 67)[k % 4])
+        for y0, y1 in ((0, 3), (3, 40), (40, h)):
+            tiles.append((x, y0, x1, y1))
+        x, k = x1, k + 1
+    return tiles
+
+
+class DeviceArray:
+    """A caller-owned AOV buffer filled by the caller (crh_render_aov takes any device pointer): a torch tensor on the GPU; under the kernel
+    emulation, whose device memory is the host heap, a numpy array."""
+
+    def __init__(self, pkg, values):
+        self.emulated = hasattr(pkg.api.library(), "crh_emu_stats")
+        if self.emulated:
+            self.a = np.ascontiguousarray(values, np.float32).copy()
+            self.ptr = self.a.ctypes.data
+        else:
+            import torch
+            self.a = torch.from_numpy(np.ascontiguousarray(values, np.float32)).to("cuda:0")
+            torch.cuda.synchronize()
+            self.ptr = self.a.data_ptr()
+
+    def read(self, ctx):
+        ctx.synchronize()
+        return self.a.copy() if self.emulated else self.a.cpu().numpy()
+
+
+@pytest.mark.gpu
+def test_dispatch_decompositions_give_the_same_buffer(pkg, ctx, oracle, golden_blob):
+    w, h, n = 160, 100, 5
+    blob = golden_blob("glowmetal")
+    base = gpu_aov(pkg, ctx, blob, w, h, n)
+    assert (base[..., 7] > 0).any() and (base[..., 7] < 1).any()
+    # ragged rectangles x consecutive pass ranges
+    buf = ctx.aov_buffer(w, h)
+    tiles = ragged_tiles(w, h)
+    assert sum((t[2] - t[0]) * (t[3] - t[1]) for t in tiles) == w * h
+    for first, count in ((0, 1), (1, 3), (4, 1)):
+        ctx.render_aov(buf, w, h, n, tiles=tiles, first_pass=first, pass_count=count)
+    got = ctx.download_aov(buf, w, h)
+    assert np.array_equal(got.view(np.uint32), base.view(np.uint32)), f"{(got.view(np.uint32) != base.view(np.uint32)).sum()} floats differ"
+    # work units of seven pixel groups (the library sizes them by the dispatch: a frame this small gets units of one group on a full-size GPU)
+    buf = ctx.aov_buffer(w, h)
+    os.environ["CRH_AOV_UNIT_GROUPS"] = "7"
+    try:
+        ctx.render_aov(buf, w, h, n, tiles=tiles)
+    finally:
+        del os.environ["CRH_AOV_UNIT_GROUPS"]
+    got = ctx.download_aov(buf, w, h)
+    assert np.array_equal(got.view(np.uint32), base.view(np.uint32)), f"{(got.view(np.uint32) != base.view(np.uint32)).sum()} floats differ"
+    # a sub-rectangle: every other pixel of a caller-owned buffer keeps its sentinel
+    region = (23, 11, 90, 58)
+    x0, y0, x1, y1 = region
+    sentinel = np.arange(w * h * 8, dtype=np.float32).reshape(h, w, 8) + np.float32(0.5)
+    mine = np.s_[h - y1:h - y0, x0:x1]
+    start = sentinel.copy()
+    start[mine] = 0.0
+    dev = DeviceArray(pkg, start)
+    ctx.render_aov(dev.ptr, w, h, n, region=region)
+    got = dev.read(ctx)
+    assert np.array_equal(got[mine].view(np.uint32), base[mine].view(np.uint32))
+    got[mine] = sentinel[mine]
+    assert np.array_equal(got, sentinel), "pixels outside the rectangle were written"
+    # 70 passes of 70 on 9 x 5 pixels: two pass chunks, the second one of a count that is no power of two
+    region = (70, 40, 79, 45)
+    x0, y0, x1, y1 = region
+    oscene = oracle.OracleScene(blob)
+    want = geometry_expected(first_hits(oracle, oscene, w, h, range(70), 70, region=region), range(70))
+    buf = ctx.aov_buffer(w, h)
+    ctx.render_aov(buf, w, h, 70, region=region)
+    got = ctx.download_aov(buf, w, h)
+    mine = np.s_[h - y1:h - y0, x0:x1]
+    assert (want[..., 4] > 0).any()
+    assert np.array_equal(got[mine][..., 3:8].view(np.uint32), want.view(np.uint32))
+    got[mine] = 0.0
+    assert not got.any()
+    # a single pixel
+    x, y = 75, 42
+    buf = ctx.aov_buffer(w, h)
+    ctx.render_aov(buf, w, h, n, region=(x, y, x + 1, y + 1))
+    got = ctx.download_aov(buf, w, h)
+    assert np.array_equal(got[h - 1 - y, x].view(np.uint32), base[h - 1 - y, x].view(np.uint32)) and got[h - 1 - y, x, 7] > 0
+    got[h - 1 - y, x] = 0.0
+    assert not got.any()
+
+
+@pytest.mark.gpu
+def test_entry_point_behaviour(pkg, oracle, golden_blob):
+    import ctypes as C
+    api, abi = pkg.api, pkg.abi
+    L = api.library()
+    if api.device_count() < 1:
+        pytest.fail("GPU tier needs a HIP device; libcray_hip has no CPU fallback")
+    w, h = 160, 100
+    c = api.Context(0)
+    try:
+        buf = c.aov_buffer(w, h)
+        p = abi.RenderParams(0, 0, w, h, w, h, 0, 2, 2, 0)
+        assert L.crh_render_aov(c.h, C.byref(p), None, 0, buf) == abi.ERR_INVALID          # no scene
+        c.upload(api.Scene(golden_blob("glowmetal")))
+        out = C.c_void_p()
+        assert L.crh_aov_alloc(None, w, h, C.byref(out)) == abi.ERR_INVALID
+        assert L.crh_aov_alloc(c.h, w, h, None) == abi.ERR_INVALID
+        assert L.crh_aov_alloc(c.h, 0, h, C.byref(out)) == abi.ERR_INVALID
+        assert L.crh_aov_free(None, None) == abi.ERR_INVALID
+        assert L.crh_aov_clear(c.h, None, w, h) == abi.ERR_INVALID
+        assert L.crh_aov_download(c.h, buf, w, h, None) == abi.ERR_INVALID
+        assert L.crh_aov_download(c.h, None, w, h, None) == abi.ERR_INVALID
+        assert L.crh_aov_kernel_time_ms(c.h, None) == abi.ERR_INVALID
+        assert L.crh_render_aov(None, C.byref(p), None, 0, buf) == abi.ERR_INVALID
+        assert L.crh_render_aov(c.h, None, None, 0, buf) == abi.ERR_INVALID
+        assert L.crh_render_aov(c.h, C.byref(p), None, 0, None) == abi.ERR_INVALID
+        assert L.crh_render_aov(c.h, C.byref(p), None, 3, buf) == abi.ERR_INVALID           # a count without a list
+        for bad in ((0, 0, w + 1, h), (-1, 0, w, h), (0, 0, w, h + 1), (0, -2, w, h)):
+            with pytest.raises(api.CrhError) as e:
+                c.render_aov(buf, w, h, 2, region=bad)
+            assert e.value.code == abi.ERR_INVALID
+            with pytest.raises(api.CrhError) as e:
+                c.render_aov(buf, w, h, 2, tiles=[(0, 0, 4, 4), bad])
+            assert e.value.code == abi.ERR_INVALID
+        with pytest.raises(api.CrhError) as e:
+            c.render_aov(buf, w, h, 2, first_pass=1, pass_count=2)                         # passes beyond max_passes
+        assert e.value.code == abi.ERR_INVALID
+        assert c.aov_kernel_time_ms() == 0.0
+        # dispatches without work: CRH_OK, nothing written
+        c.render_aov(buf, w, h, 2, pass_count=0)
+        c.render_aov(buf, w, h, 2, region=(5, 5, 5, 9))
+        c.render_aov(buf, w, h, 2, tiles=[])
+        c.render_aov(buf, w, h, 2, tiles=[(3, 3, 3, 3), (9, 4, 12, 4)])
+        assert not c.download_aov(buf, w, h).any()
+        # the render path's counters, time and kernel name are the render's after an AOV dispatch
+        fb = c.framebuffer(w, h)
+        c.reset_counters()
+        c.render_region(fb, w, h, 2, 3)
+        before = (c.counters(), c.kernel_time_ms(), c.last_kernel_name())
+        c.render_aov(buf, w, h, 2)
+        img = c.download_aov(buf, w, h)
+        assert (c.counters(), c.kernel_time_ms(), c.last_kernel_name()) == before
+        assert img[..., 7].any() and c.aov_kernel_time_ms() > 0.0
+        c.clear_aov(buf, w, h)
+        assert not c.download_aov(buf, w, h).any()
+    finally:
+        c.close()
+
+
+@pytest.mark.gpu
+def test_dropin_program_writes_the_buffers(pkg, ctx, manifest, golden_blob, tmp_path):
+    """c-ray-hip with CRAY_HIP_AOV=2: the dump equals Context.render_aov's two passes, three images stand beside the frame; unset, nothing more is written."""
+    import json
+    from test_gpu_parity import dropin_env
+    exe = os.path.join(REPO, "c-ray_amd", "_lib", "c-ray-hip")
+    overlay = os.path.join(REPO, "oracle", "_ref", "input")
+    if not (os.path.exists(exe) and os.path.exists(os.path.join(overlay, "scene.json"))):
+        pytest.skip("c-ray-hip or the asset overlay is not built (needs /root/reference at build time)")
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    import refrun
+    m = manifest["cfg1_scene"]
+    w, h, s, b = m["width"], m["height"], m["samples"], m["bounces"]
+    scene = refrun.rewrite_scene("scene.json", w, h, s, b, out_dir=str(tmp_path))
+    dump, frame = str(tmp_path / "aov.f32"), str(tmp_path / "frame.f32")
+    env = dict(os.environ, CRH_DUMP_F32=frame, CRAY_HIP_DEVICES="1", **dropin_env())
+    env.pop("CRAY_HIP_AOV", None)
+    proc = subprocess.run([exe], input=json.dumps(scene).encode(), cwd=overlay, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+    assert proc.returncode == 0, proc.stdout.decode(errors="replace")[-2000:]
+    plain = sorted(f for f in os.listdir(tmp_path) if f.endswith(".bmp"))
+    assert len(plain) == 1, plain
+    proc = subprocess.run([exe], input=json.dumps(scene).encode(), cwd=overlay, env=dict(env, CRAY_HIP_AOV="2", CRH_DUMP_AOV_F32=dump), stdout=subprocess.PIPE,
+                          stderr=subprocess.STDOUT, timeout=600)
+    assert proc.returncode == 0, proc.stdout.decode(errors="replace")[-2000:]
+    got = np.fromfile(dump, dtype=np.float32).reshape(h, w, 8)
+    want = gpu_aov(pkg, ctx, golden_blob("cfg1_scene"), w, h, s, pass_count=2)
+    assert want[..., 7].any()
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    files = sorted(f for f in os.listdir(tmp_path) if f.endswith(".bmp"))
+    stem = plain[0][:-len("_0000.bmp")]
+    assert files == sorted(plain + [f"{stem}_{k}_0000.bmp" for k in ("albedo", "normal", "depth")]), files
+    for f in files:
+        data = open(tmp_path / f, "rb").read()
+        assert data[:2] == b"BM" and int.from_bytes(data[18:22], "little") == w and abs(int.from_bytes(data[22:26], "little", signed=True)) == h, f
+
+
+def test_aov_kernel_on_the_emulation():
+    """CPU tier: this file's GPU tests run by a child pytest against the kernel emulation (tests/emu/libcray_hip_emu.so: k_aov and crh_render_aov compiled
+    unmodified on the HIP-on-CPU shim) — every one of them runs and passes there, none skipped (the drop-in test where the drop-in program is built)."""
+    from conftest import locked_make
+    locked_make(["make", "-s", "-C", EMU_DIR, "libcray_hip_emu.so"])
+    dropin = os.path.exists(os.path.join(REPO, "c-ray_amd", "_lib", "c-ray-hip")) and os.path.exists(os.path.join(REPO, "oracle", "_ref", "input", "scene.json")) \
+        and os.path.isdir(os.path.join(EMU_DIR, "_dropin_libs"))
+    env = dict(os.environ, CRH_LIB=os.path.join(EMU_DIR, "libcray_hip_emu.so"), CRH_ALLOW_EMULATION="1", CRH_DROPIN_LIBDIR=os.path.join(EMU_DIR, "_dropin_libs"),
+               HIPEMU_CUS="2", HIPEMU_THREADS="3")
+    cmd = [sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider"] + ([] if dropin else ["-k", "not dropin"])
+    r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=1700)
+    tail = (r.stdout + r.stderr)[-4000:]
+    assert r.returncode == 0, tail
+    m = re.search(r"(\d+) passed", r.stdout)
+    assert m and int(m.group(1)) == (12 if dropin else 11), tail
+    assert "skipped" not in r.stdout.strip().splitlines()[-1], tail
