@@ -292,6 +292,15 @@ __device__ __forceinline__ void putPathRay(f4 *q, const v3 &o, const v3 &d, cons
 	q[3] = f4{r.fr, r.fg, r.fb, asF32((uint32_t)(r.rng.state >> 32))};
 }
 
+/* the same words into registers (PathTab::storeRec4 writes them) */
+template <class PR>
+__device__ __forceinline__ void packPathRay(f4 &q0, f4 &q1, f4 &q2, f4 &q3, const v3 &o, const v3 &d, const PR &r, uint32_t item) {
+	q0 = f4{o.x, o.y, o.z, asF32((uint32_t)r.depth)};
+	q1 = f4{d.x, d.y, d.z, asF32(item)};
+	q2 = f4{r.wr, r.wg, r.wb, asF32((uint32_t)r.rng.state)};
+	q3 = f4{r.fr, r.fg, r.fb, asF32((uint32_t)(r.rng.state >> 32))};
+}
+
 /* What a walk may ask of its path (pt_device.h: volumes): the sampler lives in words 2.w / 3.w of the path's record, words 6..7 are free */
 template <int SAMP> struct TablePort {
 	f4 *q;
@@ -317,8 +326,60 @@ template <int SAMP> struct TablePort {
 #ifndef CRH_PATH_LEAN
 #define CRH_PATH_LEAN 1
 #endif
+/* Round 8 (profiles/r08_record_coop.log), the lean instantiations' SHADE, GEN and MISS steps only — with all three at 0 the kernels' machine code is the parent's.
+ * Each was measured alone and in combination on hdr.json (bench.py, three interleaved runs each); the defaults are what paid:
+ *   CRH_REC_COOP_STORE  1: SHADE and GEN write the four 64-B records of a quad's lanes together, one aligned 64-B line per store instruction (PathTab::storeRec4):
+ *                       +1.3 % alone — a record is one L2 write request instead of four
+ *   CRH_MISS_SKIP_HIT   1: a walk that ended in a miss leaves no hit part: ST_MISS read only its .x, for ShadeRec::distance, which only a node program
+ *                       (CRH_VALUE_RAYLENGTH, pt_device.h: runProgram) ever reads — and the lean instantiations have none: +1.2 % alone, +2.9 % with the stores
+ *   CRH_REC_COOP_LOAD   0: 1 = SHADE and MISS read the records the same way (PathTab::loadRec4), 2 = MISS alone. -1.2 % in SHADE (16 instead of 12 spilled VGPRs, and
+ *                       the exchange sits in front of the step's longest dependency chain), +-0 in MISS alone, and -0.2 % on top of the other two: off */
+#ifndef CRH_REC_COOP_LOAD
+#define CRH_REC_COOP_LOAD 0
+#endif
+#ifndef CRH_REC_COOP_STORE
+#define CRH_REC_COOP_STORE 1
+#endif
+#ifndef CRH_MISS_SKIP_HIT
+#define CRH_MISS_SKIP_HIT 1
+#endif
+/* the value of quad lane K (quad_perm:[K,K,K,K]) / of the lane whose index differs in bit 0 ([1,0,3,2]) or in bit 1 ([2,3,0,1]) */
+template <int K> __device__ __forceinline__ uint32_t quadLane(uint32_t v) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, K * 0x55, 0xF, 0xF, true); }
+__device__ __forceinline__ float quadXor1(float v) { return asF32((uint32_t)__builtin_amdgcn_mov_dpp((int)asU32(v), 0xB1, 0xF, 0xF, true)); }
+__device__ __forceinline__ float quadXor2(float v) { return asF32((uint32_t)__builtin_amdgcn_mov_dpp((int)asU32(v), 0x4E, 0xF, 0xF, true)); }
+/* One exchange of the quad's 4 x 4 transpose, in place: the lanes with `hi` (their bit of the stage set) give a and take the partner's b into it, the others give
+ * b and take the partner's a. Both moves are unconditional and the selects follow them: no branch, and every lane of the wave takes part. */
+__device__ __forceinline__ void quadSwap(bool hi, float &a, float &b, float pa, float pb) { a = hi ? pb : a; b = hi ? b : pa; }
+#define CRH_QUAD_SWAP4(X, hi, A, B) do { const f4 pa_ = f4{X(A.x), X(A.y), X(A.z), X(A.w)}, pb_ = f4{X(B.x), X(B.y), X(B.z), X(B.w)}; \
+	quadSwap(hi, A.x, B.x, pa_.x, pb_.x); quadSwap(hi, A.y, B.y, pa_.y, pb_.y); quadSwap(hi, A.z, B.z, pa_.z, pb_.z); quadSwap(hi, A.w, B.w, pa_.w, pb_.w); } while (0)
+/* In: lane j of a quad holds quarter j of the records of the quad's lanes 0..3 in a0..a3 — or its own record's quarters 0..3. Out: the other (the transpose is its own inverse). */
+__device__ __forceinline__ void quadTranspose(f4 &a0, f4 &a1, f4 &a2, f4 &a3) {
+	const bool b0 = (threadIdx.x & 1u) != 0u, b1 = (threadIdx.x & 2u) != 0u;
+	CRH_QUAD_SWAP4(quadXor1, b0, a0, a1); CRH_QUAD_SWAP4(quadXor1, b0, a2, a3);
+	CRH_QUAD_SWAP4(quadXor2, b1, a0, a2); CRH_QUAD_SWAP4(quadXor2, b1, a1, a3);
+}
+
 template <bool LEAN> struct PathTab {
 	f4 *base;
+	/* Quad-cooperative access to rec(id), LEAN only; the WHOLE WAVE calls (the exchange reads every lane of a quad). A lane without a record passes have = false: it
+	 * addresses the wave's slot 0 — never anything outside the wave's table — whose line it reads and ignores, and writes nothing. A quad's load or store k covers the
+	 * aligned 64-B line of quad lane k's record: one L1 look-up / one L2 write request instead of four. */
+	__device__ __forceinline__ void loadRec4(uint32_t id, bool have, f4 &q0, f4 &q1, f4 &q2, f4 &q3) const {
+		const uint32_t off = have ? id * 64u : 0u, sub = (threadIdx.x & 3u) * 16u;
+		q0 = *at(quadLane<0>(off) + sub); q1 = *at(quadLane<1>(off) + sub); q2 = *at(quadLane<2>(off) + sub); q3 = *at(quadLane<3>(off) + sub);
+		quadTranspose(q0, q1, q2, q3);
+	}
+	/* q0..q3 in putPathRay's word order; they are the transposed values afterwards. Store k runs in the quads whose lane k is active: a whole line of a live record, or nothing */
+	__device__ __forceinline__ void storeRec4(uint32_t id, bool active, f4 &q0, f4 &q1, f4 &q2, f4 &q3) const {
+		const uint32_t off = active ? id * 64u : 0u, on = active ? 1u : 0u, sub = (threadIdx.x & 3u) * 16u;
+		quadTranspose(q0, q1, q2, q3);
+		const uint32_t o0 = quadLane<0>(off), o1 = quadLane<1>(off), o2 = quadLane<2>(off), o3 = quadLane<3>(off);
+		const bool w0 = quadLane<0>(on) != 0u, w1 = quadLane<1>(on) != 0u, w2 = quadLane<2>(on) != 0u, w3 = quadLane<3>(on) != 0u;
+		if (w0) *at(o0 + sub) = q0;
+		if (w1) *at(o1 + sub) = q1;
+		if (w2) *at(o2 + sub) = q2;
+		if (w3) *at(o3 + sub) = q3;
+	}
 	/* (the arrays' starts are added to the lane's byte offset, not to the wave's base: the compiler would otherwise keep two more 64-bit bases in SGPRs across the
 	 * whole machine — 11 more spilled SGPRs in the bench instantiation) */
 	__device__ __forceinline__ static uint32_t vgprConst(uint32_t v) {
@@ -333,6 +394,7 @@ template <bool LEAN> struct PathTab {
 	__device__ __forceinline__ float *inst(uint32_t id) const { return LEAN ? (float *)at(vgprConst(CRH_PATHS * 80u) + id * 4u) : (float *)(base + id * CRH_PATH_F4 + 5u); }
 };
 static_assert(CRH_PATHS * (4u + 1u) * 4u + CRH_PATHS <= CRH_WAVE_QUEUE_FLOATS, "the lean arrays fit in the wave's table");
+static_assert((CRH_WAVE_QUEUE_FLOATS * sizeof(float)) % 64u == 0, "a wave's table starts on a 64-B line when the allocation does, and a lean rec(id) (64 B) is one aligned line: loadRec4 / storeRec4");
 
 /* rank of this lane among the set bits of a ballot mask below it */
 __device__ __forceinline__ uint32_t laneRank(unsigned long long m) {
@@ -771,6 +833,7 @@ static int preloadKernel(crh_ctx *c, bool again = false) {
 		if (c->dQueues) HIP_TRY(hipFree(c->dQueues));
 		c->dQueues = nullptr; c->queueFloats = 0;
 		HIP_TRY(hipMalloc((void **)&c->dQueues, waves * CRH_WAVE_QUEUE_FLOATS * sizeof(float)));
+		if (((uintptr_t)c->dQueues & 63u) != 0u) return fail(CRH_ERR_HIP, "path table: the allocation is not 64-byte aligned (PathTab::loadRec4 / storeRec4 move aligned 64-B lines)");
 		c->queueFloats = waves * CRH_WAVE_QUEUE_FLOATS;
 	}
 	const size_t slabs = rollForm(c) ? CRH_ROLL_SLOTS : 1u;        /* one sample slab per open job */
@@ -1746,6 +1809,7 @@ int crh_render_tiles(crh_ctx *c, const crh_render_params *P, const crh_tile *til
 			if (c->dQueues) HIP_TRY(hipFree(c->dQueues));
 			c->dQueues = nullptr; c->queueFloats = 0;
 			HIP_TRY(hipMalloc((void **)&c->dQueues, need * sizeof(float)));
+			if (((uintptr_t)c->dQueues & 63u) != 0u) return fail(CRH_ERR_HIP, "path table: the allocation is not 64-byte aligned (PathTab::loadRec4 / storeRec4 move aligned 64-B lines)");
 			c->queueFloats = need;
 		}
 	}

@@ -93,7 +93,10 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 	float *const myStage = stage + (size_t)__builtin_amdgcn_readfirstlane(wave) * (size_t)NS * slabFloats;
 	const int passEnd = P.first_pass + P.pass_count;
 	const uint32_t trisOff = (uint32_t)((const char *)S.tris - (const char *)S.nodes);          /* (one allocation: crh_scene_upload) */
-	const PathTab<CRH_PATH_LEAN && !PROG> tab{(f4 *)(queues + (size_t)__builtin_amdgcn_readfirstlane(wave) * CRH_WAVE_QUEUE_FLOATS)};          /* (the path's words: PathTab) */
+	constexpr bool LEANTAB = CRH_PATH_LEAN && !PROG;
+	/* round 8 (PathTab::loadRec4 / storeRec4; the lean instantiations only): SHADE, GEN and MISS move a path's 64-B record quad-cooperatively, and a finished miss leaves no hit part */
+	constexpr bool COOP_LOAD = LEANTAB && CRH_REC_COOP_LOAD == 1, COOP_LOAD_MISS = LEANTAB && CRH_REC_COOP_LOAD >= 1 /* (2: ST_MISS alone) */, COOP_STORE = LEANTAB && CRH_REC_COOP_STORE, MISS_SKIP_HIT = LEANTAB && CRH_MISS_SKIP_HIT;
+	const PathTab<LEANTAB> tab{(f4 *)(queues + (size_t)__builtin_amdgcn_readfirstlane(wave) * CRH_WAVE_QUEUE_FLOATS)};          /* (the path's words: PathTab) */
 	/* the counting kernel's wave-level numbers (steps, lanes served, clocks per step kind: indices 8.. of the counter block) go straight to this wave's own words behind
 	 * the global counters — one fire-and-forget atomic by lane 0 per event, no contention — instead of through two dozen registers per lane that are summed at the end:
 	 * those registers were 70 spilled VGPRs, and the counting kernel's step clocks were not the timed kernel's */
@@ -172,7 +175,7 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 		const unsigned long long hm = __ballot(finHit), mm = __ballot(finMiss);
 		uint32_t cls = 0;
 		if (fin) {
-			*tab.hit(myPath) = f4{w.hit.t, w.hit.u, w.hit.v, asF32((uint32_t)w.hit.slot)};
+			if (!MISS_SKIP_HIT || finHit) *tab.hit(myPath) = f4{w.hit.t, w.hit.u, w.hit.v, asF32((uint32_t)w.hit.slot)};
 			if (finHit) {
 				*tab.inst(myPath) = asF32((uint32_t)w.hit.inst);
 				if (sorted) cls = (uint32_t)((volatile __attribute__((address_space(3))) uint8_t *)s_cls)[w.hit.inst];
@@ -441,6 +444,20 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 				const bool valid = item < genItems && decodeItem(J, item, x, y, pass);         /* (the ballot below: every lane has read the job's words) */
 				const unsigned long long vm = __ballot(valid);
 				const int n = (int)__popcll(vm);
+				if constexpr (COOP_STORE) {
+					f4 q0 = f4{0.0f, 0.0f, 0.0f, 0.0f}, q1 = q0, q2 = q0, q3 = q0;
+					uint32_t id = 0;
+					if (valid) {
+						const uint32_t rk = laneRank(vm);
+						id = ids[CRH_IDS_FREE_END - (uint32_t)freeQ + rk];
+						v3 ro, rd;
+						PathRecT<RngT<SAMP>> r;
+						beginPath(S, P, x, y, pass, ro, rd, r, cnt);
+						packPathRay(q0, q1, q2, q3, ro, rd, r, item | ((uint32_t)g << CRH_ROLL_SLOT_SHIFT));
+						ids[CRH_IDS_RAYS + (uint32_t)raysQ + rk] = (uint8_t)id;
+					}
+					tab.storeRec4(id, valid, q0, q1, q2, q3);
+				} else
 				if (valid) {
 					const uint32_t rk = laneRank(vm);
 					const uint32_t id = ids[CRH_IDS_FREE_END - (uint32_t)freeQ + rk];
@@ -462,10 +479,15 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 			case ST_MISS: {
 				const int n = min(missQn, 64);
 				int mySlot = -1;
-				if ((int)lane < n) {
-					const uint32_t id = ids[CRH_ROLL_IDS_MISSES + (uint32_t)(missQn - n) + lane];
-					const f4 *q = tab.rec(id);
-					const f4 q1 = q[1], q2 = q[2], q3 = q[3];
+				const bool have = (int)lane < n;
+				uint32_t id = 0;
+				f4 q0, q1, q2, q3;
+				if constexpr (COOP_LOAD_MISS) {
+					if (have) id = ids[CRH_ROLL_IDS_MISSES + (uint32_t)(missQn - n) + lane];
+					tab.loadRec4(id, have, q0, q1, q2, q3);          /* (q0 is not needed: its selects fall away) */
+				}
+				if (have) {
+					if constexpr (!COOP_LOAD_MISS) { id = ids[CRH_ROLL_IDS_MISSES + (uint32_t)(missQn - n) + lane]; const f4 *q = tab.rec(id); q1 = q[1]; q2 = q[2]; q3 = q[3]; }
 					v3 ro{0.0f, 0.0f, 0.0f}, rd{q1.x, q1.y, q1.z};
 					PathRecT<RngT<SAMP>> r;
 					r.wr = q2.x; r.wg = q2.y; r.wb = q2.z;
@@ -474,7 +496,7 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 					const uint32_t item = asU32(q1.w);
 					mySlot = (int)(item >> CRH_ROLL_SLOT_SHIFT);
 					TravHit h;
-					h.t = tab.hit(id)->x; h.u = h.v = 0.0f; h.slot = -1; h.inst = -1;
+					h.t = MISS_SKIP_HIT ? 0.0f : tab.hit(id)->x; h.u = h.v = 0.0f; h.slot = -1; h.inst = -1;          /* (ShadeRec::distance of a miss: read by node programs only) */
 					(void)shadeCore(S, P, ro, rd, h, r, cnt, stk);
 					float *so = sampleSlot(mySlot, item & CRH_ROLL_ITEM_MASK); so[0] = r.fr; so[1] = r.fg; so[2] = r.fb;
 					ids[CRH_IDS_FREE_END - 1u - (uint32_t)freeQ - lane] = (uint8_t)id;
@@ -565,10 +587,17 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 				bool cont = false, done = false;
 				int mySlot = -1;
 				uint32_t id = 0;
-				if ((int)lane < n) {
-					id = (uint32_t)hits[(uint32_t)(hitsQ - n) + lane] & 255u;
+				const bool have = (int)lane < n;
+				f4 q0, q1, q2, q3;          /* (defined on every path that reads them: loaded by the whole wave, or zero outside the batch, where storeRec4 moves but never stores them) */
+				if constexpr (COOP_LOAD) {
+					if (have) id = (uint32_t)hits[(uint32_t)(hitsQ - n) + lane] & 255u;
+					tab.loadRec4(id, have, q0, q1, q2, q3);
+				} else if constexpr (COOP_STORE) q0 = q1 = q2 = q3 = f4{0.0f, 0.0f, 0.0f, 0.0f};
+				if (have) {
+					if constexpr (!COOP_LOAD) id = (uint32_t)hits[(uint32_t)(hitsQ - n) + lane] & 255u;
 					f4 *q = tab.rec(id);
-					const f4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = *tab.hit(id);
+					if constexpr (!COOP_LOAD) { q0 = q[0]; q1 = q[1]; q2 = q[2]; q3 = q[3]; }
+					const f4 q4 = *tab.hit(id);
 					v3 ro{q0.x, q0.y, q0.z}, rd{q1.x, q1.y, q1.z};
 					PathRecT<RngT<SAMP>> r;
 					r.wr = q2.x; r.wg = q2.y; r.wb = q2.z;
@@ -582,12 +611,14 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 					__builtin_assume(h.inst >= 0);
 					cont = shadeCore(S, P, ro, rd, h, r, cnt, stk);
 					done = !cont;
-					if (cont) putPathRay(q, ro, rd, r, item);
-					else {
+					if constexpr (COOP_STORE) packPathRay(q0, q1, q2, q3, ro, rd, r, item);          /* (of an ending path too: words nobody stores, and no select) */
+					else if (cont) putPathRay(q, ro, rd, r, item);
+					if (!cont) {
 						mySlot = (int)(item >> CRH_ROLL_SLOT_SHIFT);
 						float *so = sampleSlot(mySlot, item & CRH_ROLL_ITEM_MASK); so[0] = r.fr; so[1] = r.fg; so[2] = r.fb;
 					}
 				}
+				if constexpr (COOP_STORE) tab.storeRec4(id, cont, q0, q1, q2, q3);
 				const unsigned long long cm = __ballot(cont), dm = __ballot(done);
 				int fin[NS];
 #pragma unroll
