@@ -74,6 +74,10 @@ def library():
         "crh_aov_download": (C.c_int, [ctx, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
         "crh_render_aov": (C.c_int, [ctx, C.POINTER(abi.RenderParams), C.POINTER(abi.Tile), C.c_uint32, C.c_void_p]),
         "crh_aov_kernel_time_ms": (C.c_int, [ctx, C.POINTER(C.c_float)]),
+        "crh_denoise_params_default": (None, [C.POINTER(abi.DenoiseParams)]),
+        "crh_denoise": (C.c_int, [ctx, C.POINTER(abi.DenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+        "crh_denoise_time_ms": (C.c_int, [ctx, C.POINTER(C.c_float)]),
+        "crh_debug_denoise_launch_ms": (C.c_int, [ctx, C.POINTER(C.c_float), C.c_uint32]),
         "crh_synchronize": (C.c_int, [ctx]),
         "crh_frames_reduce": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
         "crh_frames_gather": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -301,6 +305,33 @@ class Context:
         ms = C.c_float(0.0)
         _check(self.L.crh_aov_kernel_time_ms(self.h, C.byref(ms)), "crh_aov_kernel_time_ms")
         return float(ms.value)
+
+    # ---- the guided a-trous denoiser (include/cray_hip.h: crh_denoise) ----
+    def denoise(self, fb, aov, width, height, out=None, **params):
+        """Filter the float RGB frame `fb` guided by the AOV buffer `aov` into `out` (None: in place). Device pointers, the context's or the caller's;
+        params: iterations, sigma_normal, sigma_depth, sigma_color (crh_denoise_params_default otherwise). Asynchronous on the context's stream."""
+        p = abi.DenoiseParams()
+        self.L.crh_denoise_params_default(C.byref(p))
+        p.width, p.height = width, height
+        for k, v in params.items():
+            if k not in ("iterations", "sigma_normal", "sigma_depth", "sigma_color"):
+                raise TypeError(f"denoise() got an unexpected parameter {k!r}")
+            setattr(p, k, v)
+        _check(self.L.crh_denoise(self.h, C.byref(p), fb, aov, fb if out is None else out), "crh_denoise")
+
+    def denoise_time_ms(self):
+        """Milliseconds of the most recent denoise(), summed over its launches (waits for it); 0.0 before the first one."""
+        ms = C.c_float(0.0)
+        _check(self.L.crh_denoise_time_ms(self.h, C.byref(ms)), "crh_denoise_time_ms")
+        return float(ms.value)
+
+    def denoise_launch_ms(self):
+        """... launch by launch: [prepare, iteration 0, iteration 1, ...] (crh_debug_denoise_launch_ms)."""
+        ms = (C.c_float * 16)()
+        n = self.L.crh_debug_denoise_launch_ms(self.h, ms, 16)
+        if n < 0:
+            _check(n, "crh_debug_denoise_launch_ms")
+        return [float(ms[i]) for i in range(n)]
 
     def synchronize(self):
         _check(self.L.crh_synchronize(self.h), "crh_synchronize")

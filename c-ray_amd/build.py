@@ -13,6 +13,8 @@ and three that matter for speed (-O2 rather than -O3: +0.4..1.7 %, two rounds in
                                                  bench kernel), and on gfx950 those are far slower than the two plain instructions they replace (measured in
                                                  round 3: six v_pk_fma_f32 in the node step cost 19-30 %): without them +4..5.6 % on every workload, 29
                                                  instead of 38 spilled VGPRs (profiles/r03h_ab_noslp.log); per-component IEEE results are the same
+and one for the link: -Wl,-s leaves the local symbol table out (51 KB of a library whose exported names are all in .dynsym; the kernels' own symbol tables, inside
+the code objects, are untouched) — tests/test_abi.py holds the library under 3 MiB, and the denoise kernels would have taken it 16 KB over.
 The library has no CPU path: without a HIP device every entry point returns CRH_ERR_NO_DEVICE.
 """
 import os
@@ -64,7 +66,7 @@ def build(force=False, verbose=True, extra=()):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-Wall", "-I" + os.path.join(REPO, "include"),
                                "-I" + CSRC, "-c", src, "-o", obj])
         objs.append(obj)
-    cmd = [HIPCC] + FLAGS + list(extra) + ["-x", "hip"] + SOURCES + ["-x", "none"] + objs + ["-shared", "-ldl", "-o", LIB + ".tmp"]
+    cmd = [HIPCC] + FLAGS + list(extra) + ["-x", "hip"] + SOURCES + ["-x", "none"] + objs + ["-shared", "-Wl,-s", "-ldl", "-o", LIB + ".tmp"]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)

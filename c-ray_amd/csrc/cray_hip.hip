@@ -26,6 +26,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <condition_variable>
@@ -483,6 +484,7 @@ __global__ __launch_bounds__(CRH_BLOCK) void k_trace_rays(const DScene Sarg, con
 #include "pathtrace_stream.h"        /* k_stream_walk / k_stream_shade / k_stream_fold: the streaming form (CRH_KERNEL_STREAM, round 6) */
 #include "walk_probe.h"              /* k_walk_probe: the walk of k_pathtrace_roll on its own, on the path tracer's own rays (round 6: a measurement entry, crh_debug_walk_probe) */
 #include "aov.h"                     /* k_aov: albedo, normal, depth and coverage of every camera ray's first hit (crh_render_aov) */
+#include "denoise.h"                 /* k_denoise_prepare / k_denoise_iter: the guided a-trous filter that consumes them (crh_denoise) */
 
 /* bounces <= 0: pathTrace() returns black (pathtrace.c:36); only the running mean moves (renderer.c:288-291) */
 __global__ void k_fold_black(const crh_render_params P, const crh_tile *tiles, uint32_t ntiles, float *fb, unsigned long long *counters) {
@@ -663,6 +665,14 @@ struct crh_ctx {
 	hipEvent_t aovDone = nullptr, aovEvA = nullptr, aovEvB = nullptr;
 	bool aovInFlight = false, aovTimed = false;
 	float aovLastMs = 0.0f;
+	/* crh_denoise (denoise.h): three planes of 16-byte records (C ping, C pong, G) sized lazily for the largest frame so far, and one event around every launch */
+	f4 *dDenoise = nullptr;
+	size_t denoisePixels = 0;
+	hipEvent_t denoiseEv[CRH_DN_MAX_ITERATIONS + 2] = {};
+	uint32_t denoiseLaunches = 0;            /* of the most recent crh_denoise */
+	bool denoiseTimed = false;
+	float denoiseLaunchMs[CRH_DN_MAX_ITERATIONS + 1] = {};
+	float denoiseLastMs = 0.0f;
 };
 #define CRH_WORK_SLOTS 64
 static_assert(sizeof(((crh_ctx *)nullptr)->tileSlots) / sizeof(crh_ctx::TileSlot) == CRH_WORK_SLOTS, "one tile slot per work counter");
@@ -966,6 +976,8 @@ int crh_context_destroy(crh_ctx *c) {
 	if (c->aovDone) (void)hipEventDestroy(c->aovDone);
 	if (c->aovEvA) (void)hipEventDestroy(c->aovEvA);
 	if (c->aovEvB) (void)hipEventDestroy(c->aovEvB);
+	if (c->dDenoise) (void)hipFree(c->dDenoise);
+	for (hipEvent_t e : c->denoiseEv) if (e) (void)hipEventDestroy(e);
 	if (c->hErr) (void)hipHostFree(c->hErr);
 	if (c->pinned) (void)hipHostFree(c->pinned);
 	releaseJanitor(c, true);
@@ -2050,6 +2062,109 @@ int crh_aov_kernel_time_ms(crh_ctx *c, float *last_ms) {
 	}
 	*last_ms = c->aovLastMs;
 	return CRH_OK;
+}
+
+/* ---- the guided a-trous denoiser (denoise.h) ------------------------------------------------------ */
+void crh_denoise_params_default(crh_denoise_params *p) {
+	if (!p) return;
+	p->width = 0; p->height = 0; p->iterations = 5;
+	p->sigma_normal = 1.0f; p->sigma_depth = 0.05f; p->sigma_color = 1.0f;
+}
+
+/* The form of iteration i (denoise.h: 'd' direct, 't' dense tile, 'l' sub-lattice tile). Measured on a 1280 x 720 frame, the direct gather is the fastest at every
+ * step (profiles/denoise_rate.log: 65-68 us a step against 71-84 dense and 73-93 sub-lattice — five correctly rounded divisions a tap keep the VALU busier than
+ * the taps keep the caches). CRH_DENOISE_FORM=<one letter per iteration> (dev / tests) overrides it where this build holds the form for the step: the dense tiles of
+ * the steps 2, 4 and 8 are compiled only with -DCRH_DENOISE_ALL_FORMS (the A/B variant library) or -DCRH_WITH_ALT_KERNELS (the emulation tier). */
+static char dnDefaultForm(int) { return 'd'; }
+
+int crh_denoise(crh_ctx *c, const crh_denoise_params *P, const float *dev_fb, const float *dev_aov, float *dev_out) {
+	if (!c || !P || !dev_fb || !dev_aov || !dev_out) return fail(CRH_ERR_INVALID, "crh_denoise: NULL argument");
+	if (P->width <= 0 || P->height <= 0 || P->iterations < 0 || P->iterations > CRH_DN_MAX_ITERATIONS)
+		return fail(CRH_ERR_INVALID, "crh_denoise: bad size or iteration count (0.." + std::to_string(CRH_DN_MAX_ITERATIONS) + ")");
+	for (float s : {P->sigma_normal, P->sigma_depth, P->sigma_color})
+		if (!(s > 0.0f) || !std::isfinite(s)) return fail(CRH_ERR_INVALID, "crh_denoise: a sigma is not a positive finite number");
+	if ((const float *)dev_out == dev_aov) return fail(CRH_ERR_INVALID, "crh_denoise: the output aliases the guide buffers");
+	int rc = setDevice(c);
+	if (rc) return rc;
+	const size_t pixels = (size_t)P->width * (size_t)P->height;
+	if (pixels > c->denoisePixels) {
+		HIP_TRY(hipStreamSynchronize(c->stream));
+		if (c->dDenoise) HIP_TRY(hipFree(c->dDenoise));
+		c->dDenoise = nullptr; c->denoisePixels = 0;
+		HIP_TRY(hipMalloc((void **)&c->dDenoise, pixels * 3 * sizeof(f4)));
+		c->denoisePixels = pixels;
+	}
+	if (!c->denoiseEv[0]) for (hipEvent_t &e : c->denoiseEv) HIP_TRY(hipEventCreate(&e));
+	f4 *const G = c->dDenoise, *Cin = c->dDenoise + pixels, *Cout = c->dDenoise + 2 * pixels;
+	const int N = P->iterations;
+	const char *forms = getenv("CRH_DENOISE_FORM");
+	const size_t nforms = forms ? strlen(forms) : 0;
+	c->denoiseTimed = false;
+	HIP_TRY(hipEventRecord(c->denoiseEv[0], c->stream));
+	hipLaunchKernelGGL(k_denoise_prepare, dim3((uint32_t)((pixels + CRH_BLOCK - 1) / CRH_BLOCK)), dim3(CRH_BLOCK), 0, c->stream, dev_fb, dev_aov, Cin, G, N == 0 ? dev_out : (float *)nullptr, (uint64_t)pixels);
+	hipError_t e = hipGetLastError();
+	HIP_TRY(hipEventRecord(c->denoiseEv[1], c->stream));
+	for (int i = 0; i < N && e == hipSuccess; ++i) {
+		DnParams D;
+		D.W = P->width; D.H = P->height; D.step = 1 << i; D.stride = 1;
+		D.sigmaNormal = P->sigma_normal; D.sigmaDepth = P->sigma_depth; D.sigmaColor = P->sigma_color * ldexpf(1.0f, -i);
+		char form = dnDefaultForm(i);
+		if ((size_t)i < nforms && (forms[i] == 'd' || forms[i] == 'l' || (forms[i] == 't' && D.step <= CRH_DN_DENSE_MAX_STEP))) form = forms[i];
+		if (form == 'l') D.stride = D.step;
+		const uint32_t s = (uint32_t)D.stride;          /* per residue: the tiles of an image of ceil(W / s) x ceil(H / s) pixels */
+		const uint32_t lw = ((uint32_t)P->width + s - 1) / s, lh = ((uint32_t)P->height + s - 1) / s;
+		const dim3 grid(s * ((lw + CRH_DN_TW - 1) / CRH_DN_TW), s * ((lh + CRH_DN_TH - 1) / CRH_DN_TH));
+		float *const out = i == N - 1 ? dev_out : nullptr;
+#define CRH_LAUNCH_DN(LS) hipLaunchKernelGGL((k_denoise_iter<LS>), grid, dim3(CRH_BLOCK), 0, c->stream, (const f4 *)Cin, (const f4 *)G, Cout, dev_aov, out, D)
+		if (form == 'd') CRH_LAUNCH_DN(0);
+		else if (form == 'l' || D.step == 1) CRH_LAUNCH_DN(1);
+#ifdef CRH_DENOISE_ALL_FORMS
+		else if (D.step == 2) CRH_LAUNCH_DN(2);
+		else if (D.step == 4) CRH_LAUNCH_DN(4);
+		else CRH_LAUNCH_DN(8);
+#endif
+#undef CRH_LAUNCH_DN
+		e = hipGetLastError();
+		HIP_TRY(hipEventRecord(c->denoiseEv[2 + i], c->stream));
+		std::swap(Cin, Cout);
+	}
+	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string("k_denoise launch: ") + hipGetErrorString(e));
+	c->denoiseLaunches = (uint32_t)N + 1u;
+	c->denoiseTimed = true;
+	return CRH_OK;
+}
+
+static int dnFetchTimes(crh_ctx *c) {
+	if (!c->denoiseTimed) return CRH_OK;
+	HIP_TRY(hipEventSynchronize(c->denoiseEv[c->denoiseLaunches]));
+	float sum = 0.0f;
+	for (uint32_t i = 0; i < c->denoiseLaunches; ++i) {
+		HIP_TRY(hipEventElapsedTime(&c->denoiseLaunchMs[i], c->denoiseEv[i], c->denoiseEv[i + 1]));
+		sum += c->denoiseLaunchMs[i];
+	}
+	c->denoiseLastMs = sum;
+	c->denoiseTimed = false;
+	return CRH_OK;
+}
+
+/* The launches of the most recent crh_denoise, summed (HIP events on the context's stream around each of them; waits for the last); 0 before the first call. */
+int crh_denoise_time_ms(crh_ctx *c, float *last_ms) {
+	if (!c || !last_ms) return fail(CRH_ERR_INVALID, "crh_denoise_time_ms: NULL argument");
+	int rc = setDevice(c);
+	if (rc) return rc;
+	if ((rc = dnFetchTimes(c))) return rc;
+	*last_ms = c->denoiseLastMs;
+	return CRH_OK;
+}
+
+/* ... and one by one: prepare, then the iterations. Returns how many there were (at most `cap` are written), or an error. */
+int crh_debug_denoise_launch_ms(crh_ctx *c, float *ms, uint32_t cap) {
+	if (!c || (!ms && cap)) return fail(CRH_ERR_INVALID, "crh_debug_denoise_launch_ms: NULL argument");
+	int rc = setDevice(c);
+	if (rc) return rc;
+	if ((rc = dnFetchTimes(c))) return rc;
+	for (uint32_t i = 0; i < c->denoiseLaunches && i < cap; ++i) ms[i] = c->denoiseLaunchMs[i];
+	return (int)c->denoiseLaunches;
 }
 
 /* ---- RCCL (loaded lazily: single-GPU users never need it) ---------------------------------------- */

@@ -34,7 +34,9 @@
  * Environment: CRAY_HIP_DEVICES=<n> caps the number of GPUs used; CRH_DROPIN_PASSES=<n> (dev / tests) fixes the passes per dispatch; CRH_DUMP_F32=<path> dumps the float buffer; CRH_DUMP_STATS=<path>
  * writes where the frame's time went; CRH_FRAMES=reduce: see above. CRAY_HIP_AOV=<n> (user-facing, like CRAY_HIP_WALK): after the frame, GPU 0 renders the guide buffers
  * a denoiser or a compositor asks for — albedo, normal, depth of every camera ray's first hit, n passes of them (crh_render_aov) — and writes them beside the frame
- * through the reference's own encoders (writeAovs below); CRH_DUMP_AOV_F32=<path> dumps their floats.
+ * through the reference's own encoders (writeAovs below); CRH_DUMP_AOV_F32=<path> dumps their floats. CRAY_HIP_DENOISE=<iterations> (user-facing): GPU 0 renders the guides,
+ * filters the frame with them (crh_denoise) into a buffer of its own and writes <imgFileName>_denoised beside the frame (writeDenoised below); CRH_DUMP_DENOISED_F32=<path>
+ * dumps its floats. The frame, its image and the returned texture are untouched.
  * No GPU => logr(error, ...) (which exits, src/utils/logging.c:69-73): there is no CPU fallback in this file.
  */
 #include <stdlib.h>
@@ -611,6 +613,52 @@ static void writeAovs(struct renderer *r, crh_ctx *ctx, int W, int H) {
 	free(host);
 }
 
+/* CRAY_HIP_DENOISE=<iterations, 1..8>: the frame on GPU 0, filtered by crh_denoise into a second buffer with guides rendered here — CRAY_HIP_AOV's n passes if that
+ * is set, min(16, sampleCount) otherwise —, written as <imgFileName>_denoised beside the frame (8-bit exactly as the frame's: crh_framebuffer_to_srgb8, then the
+ * reference's newImageFile / writeImage); CRH_DUMP_DENOISED_F32=<path> dumps the [H, W, 3] floats. Unset: nothing is allocated, nothing is written. */
+static void writeDenoised(struct renderer *r, crh_ctx *ctx, const float *fb, int W, int H) {
+	const char *e = getenv("CRAY_HIP_DENOISE");
+	const int iterations = e ? atoi(e) : 0;
+	if (iterations <= 0 || !ctx || !fb) return;
+	const char *a = getenv("CRAY_HIP_AOV");
+	int n = a ? atoi(a) : 0;
+	if (n <= 0) n = 16;
+	if (n > r->prefs.sampleCount) n = r->prefs.sampleCount;
+	const size_t pixels = (size_t)W * (size_t)H;
+	float *aov = NULL, *out = NULL;
+	float *host = malloc(pixels * 3 * sizeof(float));
+	struct texture *t = newTexture(char_p, (size_t)W, (size_t)H, 3);
+	crh_render_params p;
+	memset(&p, 0, sizeof(p));
+	p.x1 = W; p.y1 = H; p.image_width = W; p.image_height = H; p.pass_count = n; p.max_passes = r->prefs.sampleCount;
+	crh_denoise_params d;
+	crh_denoise_params_default(&d);
+	d.width = W; d.height = H; d.iterations = iterations;
+	float ms = 0.0f;
+	const bool ok = host && crh_aov_alloc(ctx, W, H, &aov) == CRH_OK && crh_framebuffer_alloc(ctx, W, H, &out) == CRH_OK && crh_render_aov(ctx, &p, NULL, 0, aov) == CRH_OK
+		&& crh_denoise(ctx, &d, fb, aov, out) == CRH_OK && crh_denoise_time_ms(ctx, &ms) == CRH_OK && crh_framebuffer_to_srgb8(ctx, out, W, H, t->data.byte_p) == CRH_OK
+		&& crh_framebuffer_download(ctx, out, W, H, host) == CRH_OK;
+	if (!ok) logr(warning, "c-ray-hip: the frame could not be denoised: %s\n", host ? crh_last_error() : "out of memory");
+	if (aov) crh_aov_free(ctx, aov);
+	if (out) crh_framebuffer_free(ctx, out);
+	const char *base = r->prefs.imgFileName ? r->prefs.imgFileName : "rendered";
+	char *name = ok ? malloc(strlen(base) + strlen("_denoised") + 1) : NULL;
+	if (name) {
+		const char *dump = getenv("CRH_DUMP_DENOISED_F32");
+		if (dump) {
+			FILE *f = fopen(dump, "wb");
+			if (f) { fwrite(host, sizeof(float), pixels * 3, f); fclose(f); }
+		}
+		strcpy(name, base); strcat(name, "_denoised");
+		struct imageFile *file = newImageFile(t, r->prefs.imgFilePath ? r->prefs.imgFilePath : "", name, r->prefs.imgCount, r->prefs.imgType);
+		writeImage(file);
+		destroyImageFile(file);          /* (the texture goes with it) */
+		free(name);
+		logr(info, "Denoised frame written (%i iteration%s, %i guide pass%s, %.3f ms).\n", iterations, iterations == 1 ? "" : "s", n, n == 1 ? "" : "es", (double)ms);
+	} else destroyTexture(t);
+	free(host);
+}
+
 struct texture *renderFrame(struct renderer *r) {
 	const int W = (int)r->prefs.imageWidth, H = (int)r->prefs.imageHeight;
 	struct timeval frame;
@@ -770,6 +818,7 @@ struct texture *renderFrame(struct renderer *r) {
 	}
 	logr(info, "%llu rays traced on %i GPU%s.\n", (unsigned long long)rays, gpus, PLURAL(gpus));
 	if (!workers[0].failed && !r->state.renderAborted) writeAovs(r, workers[0].ctx, W, H);
+	if (!failed && !r->state.renderAborted) writeDenoised(r, workers[0].ctx, workers[0].fb, W, H);          /* (a frame assembled on the host is not on GPU 0) */
 
 	for (int g = 0; g < gpus; ++g) {
 		if (workers[g].ctx && workers[g].fb) crh_framebuffer_free(workers[g].ctx, workers[g].fb);

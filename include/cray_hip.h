@@ -36,8 +36,9 @@ extern "C" {
  * (round 6 adds values, not entry points — CRH_KERNEL_STREAM for CRH_OPT_KERNEL, CRH_OPT_STREAM_COHORTS, and the debug entries crh_debug_ray_dump* / crh_debug_walk_probe* of the
  * walk-only probe —: a version-3 host is unaffected, the version stays 3.)
  * 4: the AOV entry points — crh_aov_alloc / crh_aov_free / crh_aov_clear / crh_aov_download / crh_render_aov / crh_aov_kernel_time_ms — exist.
+ * 5: the denoiser — crh_denoise_params / crh_denoise_params_default / crh_denoise / crh_denoise_time_ms (and crh_debug_denoise_launch_ms) — exists.
  * A host checks crh_abi_version() == CRH_ABI_VERSION. */
-#define CRH_ABI_VERSION 4
+#define CRH_ABI_VERSION 5
 /* layout version of crh_scene_desc and of the scene blobs (crh_blob_save / crh_blob_load): the records have not changed since round 1 */
 #define CRH_SCENE_VERSION 1
 
@@ -436,6 +437,38 @@ int crh_aov_download(crh_ctx *ctx, const float *dev_aov, int width, int height, 
 int crh_render_aov(crh_ctx *ctx, const crh_render_params *params, const crh_tile *tiles, uint32_t tile_count, float *dev_aov);
 /* Duration in milliseconds of the most recent crh_render_aov's kernel (waits for it); 0 before the first one. */
 int crh_aov_kernel_time_ms(crh_ctx *ctx, float *last_ms);
+
+/* The consumer of those buffers: an edge-avoiding a-trous wavelet filter on the albedo-demodulated frame, guided by normal and depth. No scene is needed.
+ *   dev_fb   float RGB [H, W, 3]           dev_aov   [H, W, 8] as above           dev_out   float RGB [H, W, 3]; may be dev_fb, must not be dev_aov
+ * all in the frame buffer's stored order (row 0 = the top of the image), caller-owned device pointers welcome. The arithmetic is part of the interface: only
+ * correctly rounded float32 + - * / sqrt, comparisons and |x|, in this order (max(a, b) = a > b ? a : b), so a restatement in any IEEE float32 gives the same bits.
+ *   ea = 2^-8, ez = 1e-6f, el = 1e-4f; lum(r, g, b) = ((0.2126f r) + (0.7152f g)) + (0.0722f b); k = {3/8, 1/4, 1/16} by |offset|
+ * Prepare, per pixel: a_c = max(albedo_c + (1 - coverage), ea) (a miss counts as albedo 1); c_c = fb_c if it is finite and > 0, else 0; I_c = c_c / a_c; L = lum(I);
+ *   nn = (nx nx + ny ny) + nz nz; n^ = nn > 0 ? n / sqrt(nn) : 0; z = coverage > 0 ? depth / coverage : 0. Records C = {I_r, I_g, I_b, L}, G = {n^x, n^y, n^z, z}.
+ * Iteration i = 0 .. iterations - 1 (s = 2^i, sc = sigma_color * 2^-i), per pixel p: sum = 0, wsum = 0; for dy = -2 .. 2 (stored rows), for dx = -2 .. 2,
+ *   q = p + s (dx, dy), skipped when outside the image:
+ *     h = k[|dx|] k[|dy|]; D = n^p - n^q; d2 = (Dx Dx + Dy Dy) + Dz Dz; t = max(1 - sigma_normal d2, 0); t2 = t t; wn = t2 t2
+ *     r = (|zp - zq| / (max(zp, zq) + ez)) / sigma_depth; wz = 1 / (1 + r r)
+ *     e = (Lp - Lq) / (sc ((Lp + Lq) + el)); wc = 1 / (1 + e e)
+ *     w = ((h wn) wz) wc; sum_c = sum_c + w C_q,c; wsum = wsum + w
+ *   I'_c = sum_c / wsum; the next record is {I', lum(I')}; G never changes.
+ * Finish: out_c = I_c a_c.
+ * Asynchronous on the context's stream; the records live in scratch of the context, sized on first use for the largest frame so far and freed with it.
+ * CRH_ERR_INVALID: a NULL argument, a size <= 0, iterations outside 0..8, a sigma that is not a positive finite number, dev_out == dev_aov. Like an AOV
+ * dispatch, a denoise leaves crh_counters, crh_kernel_time_ms and crh_last_kernel_name as they were. */
+typedef struct crh_denoise_params {
+	int32_t width, height;
+	int32_t iterations;          /* 0..8; default 5 */
+	float sigma_normal;          /* default 1 */
+	float sigma_depth;           /* default 0.05 */
+	float sigma_color;           /* default 1 */
+} crh_denoise_params;
+void crh_denoise_params_default(crh_denoise_params *params);          /* the defaults; width and height 0 */
+int crh_denoise(crh_ctx *ctx, const crh_denoise_params *params, const float *dev_fb, const float *dev_aov, float *dev_out);
+/* Milliseconds of the most recent crh_denoise: the sum over its launches, each between two events of the library's own (waits for the last); 0 before the first call. */
+int crh_denoise_time_ms(crh_ctx *ctx, float *last_ms);
+/* ... one by one (dev): ms[0] the prepare launch, ms[1 + i] iteration i; returns the number of launches (at most cap are written) or an error code. */
+int crh_debug_denoise_launch_ms(crh_ctx *ctx, float *ms, uint32_t cap);
 
 /* Multi-GPU inside one process (the C host, c-ray_amd/host/renderer_hip.c: one crh_ctx + one dispatch thread per
  * GPU): sum the n per-GPU float framebuffers onto ctxs[0]'s with ONE RCCL reduce over xGMI (ncclReduce, float,
