@@ -223,9 +223,11 @@ CRH_DEV float SRGBToLinear(float c) {                                           
 	if (c <= 0.04045f) return c / 12.92f;
 	return em::powf_(((c + 0.055f) / 1.055f), 2.4f);
 }
-/* color.h:37-40: 0.587 is a double constant, so the sum is carried in double */
+/* color.h:42-45: 0.587 and 0.114 are double constants (only 0.299f carries the suffix), so two products and the sum are carried in double. The squares are
+ * powf(x, 2) in the source, which the reference's compiler evaluates as x * x (gcc folds a constant exponent of 2 at every optimisation level) — and glibc's
+ * powf(x, 2.0f) is NOT x * x rounded once: 761 of a million random x in [0, 1) differ by an ulp. The reference binary is the contract, so: x * x. */
 CRH_DEV float grayscaleOf(rgba c) {
-	return sqrtf((float)(0.299f * em::powf_(c.r, 2.0f) + 0.587 * (double)em::powf_(c.g, 2.0f) + (double)(0.114f * em::powf_(c.b, 2.0f))));
+	return sqrtf((float)(0.299f * (c.r * c.r) + 0.587 * (double)(c.g * c.g) + 0.114 * (double)(c.b * c.b)));
 }
 /* color.c:27-70 */
 CRH_DEV rgba colorForKelvin(float kelvin) {

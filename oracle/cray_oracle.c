@@ -90,9 +90,10 @@ static inline float SRGBToLinear(float c) {                                     
 	return powf(((c + 0.055f) / 1.055f), 2.4f);
 }
 static inline color colorFromSRGB(color c) { return (color){SRGBToLinear(c.r), SRGBToLinear(c.g), SRGBToLinear(c.b), c.a}; } /* color.h:76 */
-/* color.h:37-40 — note the double constant 0.587 (no f suffix): the sum is carried in double. */
+/* color.h:42-45 — note the double constants 0.587 and 0.114 (no f suffix; only 0.299f has one): two products and the sum are carried in double. */
 static inline float grayscaleOf(color c) {
-	return sqrtf(0.299f * powf(c.r, 2) + 0.587 * powf(c.g, 2) + 0.114f * powf(c.b, 2));
+	/* (powf(x, 2) is x * x in the reference binary: gcc folds the constant exponent; written out so that no compiler of the oracle decides otherwise) */
+	return sqrtf(0.299f * (c.r * c.r) + 0.587 * (c.g * c.g) + 0.114 * (c.b * c.b));
 }
 /* color.c:27-70 */
 static color colorForKelvin(float kelvin) {

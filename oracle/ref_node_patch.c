@@ -13,6 +13,8 @@
  *                           the known-answer spheres 0..37 keep their plain material (multi-bounce frames stay in [0, ~3]).
  *   CRH_NODE_PATCH=volumes  sphere / mesh instances flagged in the scene become newSphereVolume / newMeshVolume instances
  *                           with an isotropic medium (instance.c:62-92, 187-216); the TLAS is rebuilt.
+ *   CRH_NODE_PATCH=whitesky the background becomes constant white and nothing else changes (the JSON loader's own backgrounds are a gradient
+ *                           or an image): under it a diffuse first hit whose second ray escapes IS the albedo (tools/gen_golden.py: texwrap).
  *
  * Called between crLoadSceneFromBuf() and the render / flatten step (oracle/ref_main.c, tools/flatten_main.c).
  */
@@ -186,5 +188,6 @@ void crh_apply_node_patch(struct renderer *r) {
 	W = r->scene;
 	if (!strcmp(p, "zoo")) patchZoo(r);
 	else if (!strcmp(p, "volumes")) patchVolumes(r);
+	else if (!strcmp(p, "whitesky")) W->background = newBackground(W, newConstantTexture(W, (struct color){1.0f, 1.0f, 1.0f, 1.0f}), NULL, NULL);
 	else { fprintf(stderr, "unknown CRH_NODE_PATCH=%s\n", p); exit(3); }
 }

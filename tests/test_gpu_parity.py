@@ -16,7 +16,7 @@ import pytest
 from conftest import BIG_CASES, built_blob, camera_rays, image_stats, kernel_forms, resize_camera
 
 pytestmark = pytest.mark.gpu
-CASES = ["cfg1_scene", "alphanode", "fence", "glowmetal", "refraction", "uvsphere"]
+CASES = ["cfg1_scene", "alphanode", "fence", "glowmetal", "refraction", "uvsphere", "texwrap"]
 
 
 @pytest.fixture(scope="module")

@@ -6,7 +6,7 @@ import pytest
 
 from conftest import BIG_CASES, built_blob, resize_camera
 
-CASES = ["cfg1_scene", "alphanode", "fence", "glowmetal", "refraction", "uvsphere"]
+CASES = ["cfg1_scene", "alphanode", "fence", "glowmetal", "refraction", "uvsphere", "texwrap"]
 
 
 @pytest.mark.parametrize("name", CASES)

@@ -148,6 +148,54 @@ def ensure_soup(n):
     return js
 
 
+def write_png(path, pixels):
+    """An 8-bit RGB / RGBA PNG from uint8 [H, W, 3 or 4] (filter type 0 on every row)."""
+    import struct
+    import zlib
+    h, w, c = pixels.shape
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+    raw = b"".join(b"\0" + np.ascontiguousarray(pixels[y]).tobytes() for y in range(h))
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, {3: 2, 4: 6}[c], 0, 0, 0))
+                + chunk(b"IDAT", zlib.compress(raw, 9)) + chunk(b"IEND", b""))
+
+
+# texture-coordinate ranges of the texwrap fixture's quads (tools/gen_golden.py: write_texwrap_scene): uv' = scale * uv + offset per axis
+TEXWRAP_QUADS = {
+    "identity": ((1.0, 1.0), (0.0, 0.0)),
+    "tiling": ((5.3, 5.3), (-2.6, -2.6)),                                        # tiles, and negative coordinates
+    "band7x6": ((3.0 / 7, 3.0 / 6), (-1.5 / 7, -1.5 / 6)),                       # uv * size - 0.5 spans (-2, 1) on the 7 x 6 texture
+    "far": ((1e5, 1e5), (0.0, 0.0)),
+}
+
+
+def write_texwrap_assets():
+    """texwrap/: one quad per texture-coordinate range (the plane of shapes/gridplane.obj, one unit half-width), a 7 x 6 RGBA and a 16 x 16 RGB PNG of
+    fixed-seed random bytes (both sizes no powers of two resp. one; columns 0..4 of the 16 x 16 one grey, 5..9 with r = g, the rest free)."""
+    out = os.path.join(OVERLAY, "texwrap")
+    os.makedirs(out, exist_ok=True)
+    rng = np.random.default_rng(7061616)
+    a = rng.integers(0, 256, (6, 7, 4), dtype=np.uint8)
+    a[0, 0], a[5, 6] = 0, 255
+    write_png(os.path.join(out, "rgba7x6.png"), a)
+    b = rng.integers(0, 256, (16, 16, 3), dtype=np.uint8)
+    b[:, 0:5, 1] = b[:, 0:5, 0]
+    b[:, 0:5, 2] = b[:, 0:5, 0]
+    b[:, 5:10, 1] = b[:, 5:10, 0]
+    b[0, 15], b[15, 15] = 0, 255
+    write_png(os.path.join(out, "rgb16.png"), b)
+    with open(os.path.join(out, "quad.mtl"), "w") as f:
+        f.write("newmtl quad\nKd 0.8 0.8 0.8\nKe 0 0 0\nNi 1.45\nd 1.0\nillum 2\n")
+    for name, ((su, sv), (ou, ov)) in TEXWRAP_QUADS.items():
+        with open(os.path.join(out, f"quad_{name}.obj"), "w") as f:
+            f.write("mtllib quad.mtl\no quad\nv -1 0 1\nv 1 0 1\nv -1 0 -1\nv 1 0 -1\n")
+            for u, v in ((1, 0), (0, 1), (0, 0), (1, 1)):
+                f.write("vt %.9g %.9g\n" % (su * u + ou, sv * v + ov))
+            f.write("vn 0 1 0\nusemtl quad\ns off\nf 2/1/1 3/2/1 1/3/1\nf 2/1/1 4/4/1 3/2/1\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--soup", type=int, action="append", default=[], help="also write soup_<N>.obj/.json")
@@ -161,6 +209,7 @@ def main():
     if not os.path.exists(venus):
         n = write_statue(venus)
         print(f"gen_assets: wrote stand-in venusscaled.obj ({n} triangles)")
+    write_texwrap_assets()
     for n in a.soup:
         print("gen_assets:", ensure_soup(n))
     return 0

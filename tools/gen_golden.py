@@ -51,6 +51,10 @@ PATCHED_CASES = {
     # participating media. Sphere volumes (radius marked ...7) and a cube-shaped mesh volume with solid objects inside and
     # behind them, in front of the HDR environment (instance.c:62-92, 187-216; isotropic.c:40-47)
     "volumes": ("volumes.json", {"CRH_NODE_PATCH": "volumes", "CRH_VOLUME_MESHES": "0", "CRH_VOLUME_DENSITY": "9"}, 240, 160, 8, 12),
+    # texture coordinates no other fixture has — tiling and negative, the (int) truncation band, far from the origin — on two small textures (7 x 6: no powers
+    # of two), filtered and nearest, with and without the sRGB transform, and a mix whose factor is grayscale(image); constant white sky
+    "texwrap": ("texwrap.json", {"CRH_NODE_PATCH": "whitesky"}, 160, 100, 4, 4),
+    "texwrap_display": ("texwrap.json", {"CRH_NODE_PATCH": "whitesky"}, 160, 100, 1, 2),    # first hit x white background: the albedo
 }
 ZOO_COLS, ZOO_ROWS, ZOO_PITCH, ZOO_RADIUS = 10, 6, 0.1, 0.042
 
@@ -103,6 +107,45 @@ def write_nodezoo_scene():
              "scene": {"ambientColor": {"offset": 0, "down": {"r": 1.0, "g": 1.0, "b": 1.0}, "up": {"r": 0.5, "g": 0.7, "b": 1.0}},
                        "primitives": prims, "meshes": meshes}}
     with open(os.path.join(refrun.INPUT_DIR, "nodezoo.json"), "w") as f:
+        json.dump(scene, f, indent=1)
+
+
+def write_texwrap_scene():
+    """Ten quads facing the camera (tools/gen_assets.py: write_texwrap_assets), in two rows of five. Image options as the JSON loader maps them
+    (sceneloader.c:788-803): "transform" false drops the sRGB transform, "lerp" true selects the bilinear fetch; a nearest fetch is used only where
+    the coordinates are not negative (the reference's (size_t) of a negative float is undefined)."""
+    a, b = "texwrap/rgba7x6.png", "texwrap/rgb16.png"
+
+    def image(path, lerp, transform):
+        return {"path": path, "lerp": lerp, "transform": transform}
+    quads = [
+        ("identity", {"type": "diffuse", "color": image(a, True, True)}),
+        ("identity", {"type": "diffuse", "color": image(b, False, True)}),
+        ("tiling", {"type": "diffuse", "color": image(a, True, False)}),
+        ("tiling", {"type": "diffuse", "color": image(b, True, True)}),
+        ("band7x6", {"type": "diffuse", "color": image(a, True, False)}),
+        ("far", {"type": "diffuse", "color": image(b, True, False)}),
+        ("identity", {"type": "diffuse", "color": image(a, False, False)}),
+        ("tiling", {"type": "mix", "A": {"type": "diffuse", "color": [0.8, 0.2, 0.2]}, "B": {"type": "diffuse", "color": image(a, True, True)},
+                    "factor": image(b, True, True)}),          # a value operand that is an image: grayscale(image) (sceneloader.c:770)
+        # ... as an emission's strength it scales the frame itself (a mix factor only picks a branch): colorToGrayscale's double constants, color.h:42-45
+        ("identity", {"type": "emissive", "color": [0.9, 0.7, 0.5], "strength": image(b, True, False)}),
+        ("tiling", {"type": "emissive", "color": image(a, True, True), "strength": image(b, True, True)}),
+    ]
+    meshes = []
+    for i, (coords, material) in enumerate(quads):
+        x, y = (i % 5 - 2) * 0.29, (0.5 - i // 5) * 0.3
+        meshes.append({"fileName": f"texwrap/quad_{coords}.obj", "bsdf": "lambertian", "material": material,
+                       "instances": [{"transforms": [{"type": "scaleUniform", "scale": 0.13}, {"type": "rotateX", "degrees": -90},
+                                                     {"type": "translate", "x": x, "y": y, "z": 0.0}]}]})
+    scene = {"version": 1.0,
+             "renderer": {"threads": 0, "samples": 4, "bounces": 4, "antialiasing": True, "tileWidth": 32, "tileHeight": 32, "tileOrder": "fromMiddle",
+                          "outputFilePath": "/tmp/", "outputFileName": "texwrap", "fileType": "bmp", "count": 0, "width": 160, "height": 100},
+             "display": {"isFullscreen": False, "isBorderless": False, "windowScale": 1.0},
+             "camera": {"FOV": 28.0, "focalDistance": 3.0, "fstops": 0, "transforms": [{"type": "translate", "x": 0, "y": 0, "z": -3.0}]},
+             "scene": {"ambientColor": {"offset": 0, "down": {"r": 1.0, "g": 1.0, "b": 1.0}, "up": {"r": 1.0, "g": 1.0, "b": 1.0}},          # (the patch makes it constant)
+                       "primitives": [], "meshes": meshes}}
+    with open(os.path.join(refrun.INPUT_DIR, "texwrap.json"), "w") as f:
         json.dump(scene, f, indent=1)
 
 
@@ -193,6 +236,8 @@ def main():
             write_nodezoo_scene()
         if scene == "volumes.json":
             write_volumes_scene()
+        if scene == "texwrap.json":
+            write_texwrap_scene()
         entry = {"scene": scene, "patch": env, "width": w, "height": h, "samples": spp, "bounces": bounces,
                  "ref_flavour": "c-ray-ref-strict + oracle/ref_node_patch.c"}
         if (scene, str(env)) not in blobs_done:
