@@ -122,6 +122,11 @@ class DenoiseParams(C.Structure):
                 ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("sigma_color", C.c_float)]
 
 
+class DenoiseVarianceParams(C.Structure):
+    """crh_denoise_variance_params (crh_denoise_variance_params_default fills the defaults and the variance scale)."""
+    _fields_ = DenoiseParams._fields_ + [("variance_scale", C.c_float)]
+
+
 # numpy dtype of crh_hit for bulk comparisons
 HIT_DTYPE = [("inst", "<i4"), ("poly", "<i4"), ("distance", "<f4"), ("uv", "<f4", (2,)), ("point", "<f4", (3,)),
              ("normal", "<f4", (3,)), ("node_tests", "<u4"), ("tri_tests", "<u4"), ("material", "<u4")]
@@ -137,6 +142,7 @@ EXPORTED_SYMBOLS = [
     "crh_scene_compile", "crh_scene_upload_compiled", "crh_compiled_scene_free", "crh_debug_upload_counts",
     "crh_aov_alloc", "crh_aov_free", "crh_aov_clear", "crh_aov_download", "crh_render_aov", "crh_aov_kernel_time_ms",
     "crh_denoise_params_default", "crh_denoise", "crh_denoise_time_ms", "crh_debug_denoise_launch_ms",
+    "crh_denoise_variance_params_default", "crh_denoise_variance", "crh_framebuffer_copy",
     "crh_debug_ray_dump", "crh_debug_ray_dump_counts", "crh_debug_ray_dump_fetch", "crh_debug_walk_probe", "crh_debug_walk_probe_fetch", "crh_debug_walk_probe_compare",
 ]
 MATH_FUNCTIONS = ("sinf", "cosf", "sincosf_sin", "sincosf_cos", "logf", "log10f", "atanf", "acosf", "asinf", "tanf", "powf", "atan2f")   # enum crh_math_function

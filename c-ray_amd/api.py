@@ -78,6 +78,9 @@ def library():
         "crh_denoise": (C.c_int, [ctx, C.POINTER(abi.DenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p]),
         "crh_denoise_time_ms": (C.c_int, [ctx, C.POINTER(C.c_float)]),
         "crh_debug_denoise_launch_ms": (C.c_int, [ctx, C.POINTER(C.c_float), C.c_uint32]),
+        "crh_denoise_variance_params_default": (None, [C.POINTER(abi.DenoiseVarianceParams), C.c_int, C.c_int]),
+        "crh_denoise_variance": (C.c_int, [ctx, C.POINTER(abi.DenoiseVarianceParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "crh_framebuffer_copy": (C.c_int, [ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
         "crh_synchronize": (C.c_int, [ctx]),
         "crh_frames_reduce": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
         "crh_frames_gather": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -319,14 +322,30 @@ class Context:
             setattr(p, k, v)
         _check(self.L.crh_denoise(self.h, C.byref(p), fb, aov, fb if out is None else out), "crh_denoise")
 
+    def denoise_variance(self, fb, half, aov, width, height, half_passes, passes, out=None, **params):
+        """denoise() with the colour weight in units of each pixel's standard deviation (crh_denoise_variance): `half` is the frame after the first `half_passes`
+        of its `passes` passes (copy_framebuffer between two dispatches). params: iterations, sigma_normal, sigma_depth, sigma_color, variance_scale."""
+        p = abi.DenoiseVarianceParams()
+        self.L.crh_denoise_variance_params_default(C.byref(p), half_passes, passes)
+        p.width, p.height = width, height
+        for k, v in params.items():
+            if k not in ("iterations", "sigma_normal", "sigma_depth", "sigma_color", "variance_scale"):
+                raise TypeError(f"denoise_variance() got an unexpected parameter {k!r}")
+            setattr(p, k, v)
+        _check(self.L.crh_denoise_variance(self.h, C.byref(p), fb, half, aov, fb if out is None else out), "crh_denoise_variance")
+
+    def copy_framebuffer(self, src, dst, width, height):
+        """dst = src on the device, in stream order (crh_framebuffer_copy)."""
+        _check(self.L.crh_framebuffer_copy(self.h, src, dst, width, height), "crh_framebuffer_copy")
+
     def denoise_time_ms(self):
-        """Milliseconds of the most recent denoise(), summed over its launches (waits for it); 0.0 before the first one."""
+        """Milliseconds of the most recent denoise() or denoise_variance(), summed over its launches (waits for it); 0.0 before the first one."""
         ms = C.c_float(0.0)
         _check(self.L.crh_denoise_time_ms(self.h, C.byref(ms)), "crh_denoise_time_ms")
         return float(ms.value)
 
     def denoise_launch_ms(self):
-        """... launch by launch: [prepare, iteration 0, iteration 1, ...] (crh_debug_denoise_launch_ms)."""
+        """... launch by launch: [prepare, iteration 0, iteration 1, ...]; after denoise_variance() [prepare, prefilter, iteration 0, ...] (crh_debug_denoise_launch_ms)."""
         ms = (C.c_float * 16)()
         n = self.L.crh_debug_denoise_launch_ms(self.h, ms, 16)
         if n < 0:

@@ -665,13 +665,14 @@ struct crh_ctx {
 	hipEvent_t aovDone = nullptr, aovEvA = nullptr, aovEvB = nullptr;
 	bool aovInFlight = false, aovTimed = false;
 	float aovLastMs = 0.0f;
-	/* crh_denoise (denoise.h): three planes of 16-byte records (C ping, C pong, G) sized lazily for the largest frame so far, and one event around every launch */
+	/* crh_denoise / crh_denoise_variance (denoise.h): three planes of 16-byte records (C ping, C pong, G) — and, for the variance kind, a plane of floats behind
+	 * them — sized lazily for the largest call so far, and one event around every launch (prepare, the variance prefilter, the iterations) */
 	f4 *dDenoise = nullptr;
-	size_t denoisePixels = 0;
-	hipEvent_t denoiseEv[CRH_DN_MAX_ITERATIONS + 2] = {};
-	uint32_t denoiseLaunches = 0;            /* of the most recent crh_denoise */
+	size_t denoiseBytes = 0;
+	hipEvent_t denoiseEv[CRH_DN_MAX_ITERATIONS + 3] = {};
+	uint32_t denoiseLaunches = 0;            /* of the most recent denoise of either kind */
 	bool denoiseTimed = false;
-	float denoiseLaunchMs[CRH_DN_MAX_ITERATIONS + 1] = {};
+	float denoiseLaunchMs[CRH_DN_MAX_ITERATIONS + 2] = {};
 	float denoiseLastMs = 0.0f;
 };
 #define CRH_WORK_SLOTS 64
@@ -1334,6 +1335,15 @@ int crh_framebuffer_clear(crh_ctx *c, float *dev_fb, int width, int height) {
 	int rc = setDevice(c);
 	if (rc) return rc;
 	HIP_TRY(hipMemsetAsync(dev_fb, 0, (size_t)width * height * 3 * sizeof(float), c->stream));
+	return CRH_OK;
+}
+
+/* device to device, in stream order: how a caller keeps the frame of the first h passes (crh_denoise_variance) */
+int crh_framebuffer_copy(crh_ctx *c, const float *dev_src, float *dev_dst, int width, int height) {
+	if (!c || !dev_src || !dev_dst || width <= 0 || height <= 0) return fail(CRH_ERR_INVALID, "crh_framebuffer_copy: bad argument");
+	int rc = setDevice(c);
+	if (rc) return rc;
+	if (dev_src != dev_dst) HIP_TRY(hipMemcpyAsync(dev_dst, dev_src, (size_t)width * height * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
 	return CRH_OK;
 }
 
@@ -2077,6 +2087,19 @@ void crh_denoise_params_default(crh_denoise_params *p) {
  * the steps 2, 4 and 8 are compiled only with -DCRH_DENOISE_ALL_FORMS (the A/B variant library) or -DCRH_WITH_ALT_KERNELS (the emulation tier). */
 static char dnDefaultForm(int) { return 'd'; }
 
+/* the context's scratch, at least `bytes` large, and the events */
+static int dnScratch(crh_ctx *c, size_t bytes) {
+	if (bytes > c->denoiseBytes) {
+		HIP_TRY(hipStreamSynchronize(c->stream));
+		if (c->dDenoise) HIP_TRY(hipFree(c->dDenoise));
+		c->dDenoise = nullptr; c->denoiseBytes = 0;
+		HIP_TRY(hipMalloc((void **)&c->dDenoise, bytes));
+		c->denoiseBytes = bytes;
+	}
+	if (!c->denoiseEv[0]) for (hipEvent_t &e : c->denoiseEv) HIP_TRY(hipEventCreate(&e));
+	return CRH_OK;
+}
+
 int crh_denoise(crh_ctx *c, const crh_denoise_params *P, const float *dev_fb, const float *dev_aov, float *dev_out) {
 	if (!c || !P || !dev_fb || !dev_aov || !dev_out) return fail(CRH_ERR_INVALID, "crh_denoise: NULL argument");
 	if (P->width <= 0 || P->height <= 0 || P->iterations < 0 || P->iterations > CRH_DN_MAX_ITERATIONS)
@@ -2087,14 +2110,7 @@ int crh_denoise(crh_ctx *c, const crh_denoise_params *P, const float *dev_fb, co
 	int rc = setDevice(c);
 	if (rc) return rc;
 	const size_t pixels = (size_t)P->width * (size_t)P->height;
-	if (pixels > c->denoisePixels) {
-		HIP_TRY(hipStreamSynchronize(c->stream));
-		if (c->dDenoise) HIP_TRY(hipFree(c->dDenoise));
-		c->dDenoise = nullptr; c->denoisePixels = 0;
-		HIP_TRY(hipMalloc((void **)&c->dDenoise, pixels * 3 * sizeof(f4)));
-		c->denoisePixels = pixels;
-	}
-	if (!c->denoiseEv[0]) for (hipEvent_t &e : c->denoiseEv) HIP_TRY(hipEventCreate(&e));
+	if ((rc = dnScratch(c, pixels * 3 * sizeof(f4)))) return rc;
 	f4 *const G = c->dDenoise, *Cin = c->dDenoise + pixels, *Cout = c->dDenoise + 2 * pixels;
 	const int N = P->iterations;
 	const char *forms = getenv("CRH_DENOISE_FORM");
@@ -2130,6 +2146,57 @@ int crh_denoise(crh_ctx *c, const crh_denoise_params *P, const float *dev_fb, co
 	}
 	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string("k_denoise launch: ") + hipGetErrorString(e));
 	c->denoiseLaunches = (uint32_t)N + 1u;
+	c->denoiseTimed = true;
+	return CRH_OK;
+}
+
+/* ---- ... guided by the variance a half-sample frame buffer gives (denoise.h: k_denoise_prepare_v, k_denoise_variance, k_denoise_iter_v) ---- */
+void crh_denoise_variance_params_default(crh_denoise_variance_params *p, int half_passes, int passes) {
+	if (!p) return;
+	p->width = 0; p->height = 0; p->iterations = 5;
+	p->sigma_normal = 1.0f; p->sigma_depth = 0.05f; p->sigma_color = 3.0f;
+	p->variance_scale = (half_passes >= 1 && half_passes < passes) ? (float)half_passes / (float)(passes - half_passes) : 0.0f;
+}
+
+int crh_denoise_variance(crh_ctx *c, const crh_denoise_variance_params *P, const float *dev_fb, const float *dev_half, const float *dev_aov, float *dev_out) {
+	if (!c || !P || !dev_fb || !dev_half || !dev_aov || !dev_out) return fail(CRH_ERR_INVALID, "crh_denoise_variance: NULL argument");
+	if (P->width <= 0 || P->height <= 0 || P->iterations < 0 || P->iterations > CRH_DN_MAX_ITERATIONS)
+		return fail(CRH_ERR_INVALID, "crh_denoise_variance: bad size or iteration count (0.." + std::to_string(CRH_DN_MAX_ITERATIONS) + ")");
+	for (float s : {P->sigma_normal, P->sigma_depth, P->sigma_color, P->variance_scale})
+		if (!(s > 0.0f) || !std::isfinite(s)) return fail(CRH_ERR_INVALID, "crh_denoise_variance: a sigma or the variance scale is not a positive finite number");
+	if ((const float *)dev_out == dev_aov || (const float *)dev_out == dev_half) return fail(CRH_ERR_INVALID, "crh_denoise_variance: the output aliases the guide buffers or the half-sample frame");
+	int rc = setDevice(c);
+	if (rc) return rc;
+	const size_t pixels = (size_t)P->width * (size_t)P->height;
+	if ((rc = dnScratch(c, pixels * (3 * sizeof(f4) + sizeof(float))))) return rc;
+	f4 *const G = c->dDenoise, *Cin = c->dDenoise + pixels, *Cout = c->dDenoise + 2 * pixels;
+	float *const Vraw = (float *)(c->dDenoise + 3 * pixels);
+	const int N = P->iterations;
+	DnParams D;
+	D.W = P->width; D.H = P->height; D.step = 1; D.stride = 1;
+	D.sigmaNormal = P->sigma_normal; D.sigmaDepth = P->sigma_depth; D.sigmaColor = P->sigma_color;
+	const dim3 grid(((uint32_t)P->width + CRH_DN_TW - 1) / CRH_DN_TW, ((uint32_t)P->height + CRH_DN_TH - 1) / CRH_DN_TH);
+	uint32_t launches = 0;
+	c->denoiseTimed = false;
+	HIP_TRY(hipEventRecord(c->denoiseEv[0], c->stream));
+	hipLaunchKernelGGL(k_denoise_prepare_v, dim3((uint32_t)((pixels + CRH_BLOCK - 1) / CRH_BLOCK)), dim3(CRH_BLOCK), 0, c->stream, dev_fb, dev_half, dev_aov, Cin, G, Vraw,
+	                   N == 0 ? dev_out : (float *)nullptr, P->variance_scale, (uint64_t)pixels);
+	hipError_t e = hipGetLastError();
+	HIP_TRY(hipEventRecord(c->denoiseEv[++launches], c->stream));
+	if (N > 0 && e == hipSuccess) {
+		hipLaunchKernelGGL(k_denoise_variance, grid, dim3(CRH_BLOCK), 0, c->stream, (const float *)Vraw, (const f4 *)G, Cin, D);
+		e = hipGetLastError();
+		HIP_TRY(hipEventRecord(c->denoiseEv[++launches], c->stream));
+	}
+	for (int i = 0; i < N && e == hipSuccess; ++i) {
+		D.step = 1 << i;
+		hipLaunchKernelGGL(k_denoise_iter_v, grid, dim3(CRH_BLOCK), 0, c->stream, (const f4 *)Cin, (const f4 *)G, Cout, dev_aov, i == N - 1 ? dev_out : (float *)nullptr, D);
+		e = hipGetLastError();
+		HIP_TRY(hipEventRecord(c->denoiseEv[++launches], c->stream));
+		std::swap(Cin, Cout);
+	}
+	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string("k_denoise launch: ") + hipGetErrorString(e));
+	c->denoiseLaunches = launches;
 	c->denoiseTimed = true;
 	return CRH_OK;
 }

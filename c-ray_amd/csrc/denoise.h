@@ -24,6 +24,12 @@
  * two 16-byte reads that the caches serve — so the kernel is bound by arithmetic, and staging buys nothing to pay for its barrier; the sub-lattice's strided
  * global reads cost more the larger the step. The product library keeps the LS = 1 tile besides (the GPU tier of the tests runs it); the dense tiles of the
  * steps 2, 4, 8 are built only for the A/B (-DCRH_DENOISE_ALL_FORMS) and the emulation tier. No packed-float instructions, no MFMA, no scratch; 30-42 VGPRs.
+ *
+ * The variance-guided filter (crh_denoise_variance; k_denoise_prepare_v / k_denoise_variance / k_denoise_iter_v at the end of this file) stops at luminance edges
+ * in units of the pixel's own standard deviation instead of a fixed relative difference. The variance comes from a second frame buffer, the mean of the first h
+ * of the n passes: Var(frame) ~ h / (n - h) (L(half) - L(frame))^2, one degree of freedom a pixel, which a guide-weighted 5 x 5 mean (k_denoise_variance) makes
+ * usable; every iteration carries it along (V' = sum w^2 V / (sum w)^2). Its record is C = {irradiance r g b, variance}: a tap stays at two 16-byte reads and the
+ * luminance is recomputed from the record (the same function of the same bits). Direct gather only (a tap is bound by its five divisions, as above); the per-pixel sqrt is outside the loop.
  */
 #pragma once
 
@@ -151,4 +157,111 @@ __global__ __launch_bounds__(CRH_BLOCK) void k_denoise_iter(const f4 *Cin, const
 		dnAlbedo(((const f4 *)aovArg)[2 * p], ((const f4 *)aovArg)[2 * p + 1], ar, ag, ab);
 		out[3 * p] = ir * ar; out[3 * p + 1] = ig * ag; out[3 * p + 2] = ib * ab;
 	} else Cout[p] = f4{ir, ig, ib, dnLum(ir, ig, ib)};
+}
+
+/* ---- the variance-guided filter (crh_denoise_variance) ---------------------------------------------------------------------------------------------
+ * Prepare: the records C = {I_r, I_g, I_b, 0} and G as above, and the raw variance of every pixel in a plane of its own (the prefilter cannot run in place):
+ * scale (L(half) - L(frame))^2, NaN and anything above 2^100 -> 2^100 (a zero weight times an infinite variance would be a NaN). out != null: as above. */
+#define CRH_DN_VARIANCE_MAX 0x1p100f
+
+__device__ __forceinline__ float dnGuard(float v) { return (v > 0.0f && v < __builtin_inff()) ? v : 0.0f; }          /* NaN, inf, negative -> 0 */
+
+__global__ __launch_bounds__(CRH_BLOCK) void k_denoise_prepare_v(const float *fb, const float *half, const float *aovArg, f4 *C, f4 *G, float *Vraw, float *out, float scale, uint64_t pixels) {
+	const uint64_t i = (uint64_t)blockIdx.x * CRH_BLOCK + threadIdx.x;
+	if (i >= pixels) return;
+	const f4 a0 = ((const f4 *)aovArg)[2 * i], a1 = ((const f4 *)aovArg)[2 * i + 1];
+	float ar, ag, ab;
+	dnAlbedo(a0, a1, ar, ag, ab);
+	const float ir = dnGuard(fb[3 * i]) / ar, ig = dnGuard(fb[3 * i + 1]) / ag, ib = dnGuard(fb[3 * i + 2]) / ab;
+	if (out) { out[3 * i] = ir * ar; out[3 * i + 1] = ig * ag; out[3 * i + 2] = ib * ab; return; }
+	const float hr = dnGuard(half[3 * i]) / ar, hg = dnGuard(half[3 * i + 1]) / ag, hb = dnGuard(half[3 * i + 2]) / ab;
+	const float d = dnLum(hr, hg, hb) - dnLum(ir, ig, ib);
+	const float v = scale * (d * d);
+	const float nx = a0.w, ny = a1.x, nz = a1.y;
+	const float nn = (nx * nx + ny * ny) + nz * nz;
+	f4 g = f4{0.0f, 0.0f, 0.0f, 0.0f};
+	if (nn > 0.0f) { const float len = sqrtf(nn); g.x = nx / len; g.y = ny / len; g.z = nz / len; }
+	if (a1.w > 0.0f) g.w = a1.z / a1.w;
+	C[i] = f4{ir, ig, ib, 0.0f};
+	G[i] = g;
+	Vraw[i] = v < CRH_DN_VARIANCE_MAX ? v : CRH_DN_VARIANCE_MAX;
+}
+
+/* wn and wz of dnTap: how well q's normal and depth agree with p's */
+__device__ __forceinline__ void dnGuideWeights(const f4 Gp, const f4 Gq, const DnParams &P, float &wn, float &wz) {
+	const float dx = Gp.x - Gq.x, dy = Gp.y - Gq.y, dz = Gp.z - Gq.z;
+	const float d2 = (dx * dx + dy * dy) + dz * dz;
+	const float t = dnMax(1.0f - P.sigmaNormal * d2, 0.0f);
+	const float t2 = t * t;
+	wn = t2 * t2;
+	const float r = (fabsf(Gp.w - Gq.w) / (dnMax(Gp.w, Gq.w) + CRH_DN_EPS_DEPTH)) / P.sigmaDepth;
+	wz = 1.0f / (1.0f + r * r);
+}
+
+/* The variance prefilter: the guide-weighted mean of the raw variance over the 5 x 5 neighbours (no spline coefficient), into the records' fourth component.
+ * The centre's weight is 1, so the sum of the weights is at least 1. */
+__global__ __launch_bounds__(CRH_BLOCK) void k_denoise_variance(const float *Vraw, const f4 *G, f4 *C, const DnParams P) {
+	const int x = (int)blockIdx.x * CRH_DN_TW + (int)threadIdx.x % CRH_DN_TW, y = (int)blockIdx.y * CRH_DN_TH + (int)threadIdx.x / CRH_DN_TW;
+	if (x >= P.W || y >= P.H) return;
+	const size_t p = (size_t)y * (size_t)P.W + (size_t)x;
+	const f4 Gp = G[p];
+	float acc = 0.0f, ws = 0.0f;
+#pragma unroll 1
+	for (int dy = -2; dy <= 2; ++dy) {
+		const int qy = y + dy;
+#pragma unroll
+		for (int dx = -2; dx <= 2; ++dx) {
+			const int qx = x + dx;
+			if (qx < 0 || qx >= P.W || qy < 0 || qy >= P.H) continue;
+			const size_t q = (size_t)qy * (size_t)P.W + (size_t)qx;
+			float wn, wz;
+			dnGuideWeights(Gp, G[q], P, wn, wz);
+			const float wg = wn * wz;
+			acc = acc + wg * Vraw[q];
+			ws = ws + wg;
+		}
+	}
+	((float *)(C + p))[3] = acc / ws;
+}
+
+/* One iteration, the direct form. P.sigmaColor is in standard deviations and is NOT scaled by the step: the variance shrinks by itself. The colour weight's
+ * denominator is per pixel (the sqrt is outside the loop) but a tap still divides by it — the result depends on the division, not on a reciprocal —, so a tap is
+ * five divisions like dnTap's, with two additions and a product fewer, five VALU instructions more for the luminance and three for the variance. */
+__global__ __launch_bounds__(CRH_BLOCK) void k_denoise_iter_v(const f4 *Cin, const f4 *G, f4 *Cout, const float *aovArg, float *out, const DnParams P) {
+	const int x = (int)blockIdx.x * CRH_DN_TW + (int)threadIdx.x % CRH_DN_TW, y = (int)blockIdx.y * CRH_DN_TH + (int)threadIdx.x / CRH_DN_TW;
+	if (x >= P.W || y >= P.H) return;
+	const size_t p = (size_t)y * (size_t)P.W + (size_t)x;
+	const f4 Cp = Cin[p], Gp = G[p];
+	const float Lp = dnLum(Cp.x, Cp.y, Cp.z);
+	const float den = P.sigmaColor * sqrtf(Cp.w) + CRH_DN_EPS_LUM;
+	DnAcc acc = DnAcc{0.0f, 0.0f, 0.0f, 0.0f};
+	float va = 0.0f;
+	const float k[3] = {0.375f, 0.25f, 0.0625f};
+#pragma unroll 1
+	for (int dy = -2; dy <= 2; ++dy) {
+		const int qy = y + dy * P.step;
+		const float ky = dy == 0 ? k[0] : (dy == 1 || dy == -1) ? k[1] : k[2];
+#pragma unroll
+		for (int dx = -2; dx <= 2; ++dx) {
+			const int qx = x + dx * P.step;
+			if (qx < 0 || qx >= P.W || qy < 0 || qy >= P.H) continue;
+			const float h = k[dx < 0 ? -dx : dx] * ky;
+			const size_t q = (size_t)qy * (size_t)P.W + (size_t)qx;
+			const f4 Cq = Cin[q];
+			float wn, wz;
+			dnGuideWeights(Gp, G[q], P, wn, wz);
+			const float e = (Lp - dnLum(Cq.x, Cq.y, Cq.z)) / den;
+			const float wc = 1.0f / (1.0f + e * e);
+			const float w = ((h * wn) * wz) * wc;
+			acc.r = acc.r + w * Cq.x; acc.g = acc.g + w * Cq.y; acc.b = acc.b + w * Cq.z;
+			acc.w = acc.w + w;
+			va = va + (w * w) * Cq.w;
+		}
+	}
+	const float ir = acc.r / acc.w, ig = acc.g / acc.w, ib = acc.b / acc.w;
+	if (out) {
+		float ar, ag, ab;
+		dnAlbedo(((const f4 *)aovArg)[2 * p], ((const f4 *)aovArg)[2 * p + 1], ar, ag, ab);
+		out[3 * p] = ir * ar; out[3 * p + 1] = ig * ag; out[3 * p + 2] = ib * ab;
+	} else Cout[p] = f4{ir, ig, ib, va / (acc.w * acc.w)};
 }

@@ -36,7 +36,9 @@
  * a denoiser or a compositor asks for — albedo, normal, depth of every camera ray's first hit, n passes of them (crh_render_aov) — and writes them beside the frame
  * through the reference's own encoders (writeAovs below); CRH_DUMP_AOV_F32=<path> dumps their floats. CRAY_HIP_DENOISE=<iterations> (user-facing): GPU 0 renders the guides,
  * filters the frame with them (crh_denoise) into a buffer of its own and writes <imgFileName>_denoised beside the frame (writeDenoised below); CRH_DUMP_DENOISED_F32=<path>
- * dumps its floats. The frame, its image and the returned texture are untouched.
+ * dumps its floats. The frame, its image and the returned texture are untouched. CRAY_HIP_DENOISE_VARIANCE=1 beside it: the filter is crh_denoise_variance — every GPU
+ * thread ends a dispatch exactly at pass sampleCount / 2 and keeps a copy of its frame buffer there (crh_framebuffer_copy), the copies are assembled on GPU 0 like
+ * the frame; consecutive pass ranges compose bit for bit, so the frame is the one of a run without the variable.
  * No GPU => logr(error, ...) (which exits, src/utils/logging.c:69-73): there is no CPU fallback in this file.
  */
 #include <stdlib.h>
@@ -89,6 +91,7 @@ struct gpuWorker {
 	struct timeval frameStart;   /* renderFrame() entry */
 	crh_ctx *ctx;
 	float *fb;
+	float *half;          /* CRAY_HIP_DENOISE_VARIANCE: the frame buffer as it was after the first sampleCount / 2 passes */
 	int device;
 	int failed;
 	char error[256];      /* crh_last_error() is per thread: the failing dispatch thread keeps its message here */
@@ -272,6 +275,14 @@ static void poolDestroy(void) {
 	}
 }
 
+/* CRAY_HIP_DENOISE=<iterations> with CRAY_HIP_DENOISE_VARIANCE=1: the pass at which every GPU thread copies its frame buffer, h = sampleCount / 2; 0: no copy
+ * (the variable is unset, means nothing without CRAY_HIP_DENOISE, or the frame has fewer than two passes to split) */
+static int varianceHalfPasses(const struct renderer *r) {
+	const char *d = getenv("CRAY_HIP_DENOISE"), *v = getenv("CRAY_HIP_DENOISE_VARIANCE");
+	if (!d || atoi(d) <= 0 || !v || atoi(v) <= 0 || r->prefs.sampleCount < 2) return 0;
+	return r->prefs.sampleCount / 2;
+}
+
 static void announceLaunch(struct gpuWorker *w) {
 	if (w->announced) return;
 	w->announced = 1;
@@ -309,7 +320,9 @@ static void *gpuThread(void *arg) {
 	w->ctx = poolAcquire(w->device);
 	const long preparedUs = getUs(phase);
 	/* (a pooled context has rendered before in this process: the frame's ray count starts at zero — ADVICE r05) */
-	int ok = w->ctx != NULL && crh_counters_reset(w->ctx) == CRH_OK && crh_framebuffer_alloc(w->ctx, W, H, &w->fb) == CRH_OK;
+	const int halfAt = varianceHalfPasses(r);
+	int ok = w->ctx != NULL && crh_counters_reset(w->ctx) == CRH_OK && crh_framebuffer_alloc(w->ctx, W, H, &w->fb) == CRH_OK
+		&& (!halfAt || crh_framebuffer_alloc(w->ctx, W, H, &w->half) == CRH_OK);
 	if (getenv("CRH_TRACE_UPLOAD"))
 		fprintf(stderr, "gpuThread trace: GPU %d has its context (pool, or created + code objects + per-wave buffers) after %.1f ms, its framebuffer after %.1f ms\n",
 				w->device, preparedUs / 1e3, getUs(phase) / 1e3);
@@ -348,6 +361,7 @@ static void *gpuThread(void *arg) {
 	for (int done = 0; done < r->prefs.sampleCount && r->state.isRendering && !r->state.renderAborted; ) {
 		p.first_pass = done;
 		p.pass_count = r->prefs.sampleCount - done < passes ? r->prefs.sampleCount - done : passes;
+		if (done < halfAt && done + p.pass_count > halfAt) p.pass_count = halfAt - done;          /* a dispatch ends exactly where the copy is taken */
 		struct timeval tl;
 		startTimer(&tl);
 		int rc = n ? crh_render_tiles(w->ctx, &p, share, n, w->fb) : CRH_OK;
@@ -364,6 +378,12 @@ static void *gpuThread(void *arg) {
 		done += p.pass_count;
 		w->state->completedSamples = done;
 		w->state->totalSamples = pixels * (uint64_t)done;
+		if (halfAt && done == halfAt && crh_framebuffer_copy(w->ctx, w->fb, w->half, W, H) != CRH_OK) {          /* (in stream order: before the next dispatch folds into fb) */
+			snprintf(w->error, sizeof(w->error), "%s", crh_last_error());
+			logr(warning, "GPU %d: %s\n", w->device, w->error);
+			w->failed = 1;
+			break;
+		}
 		if (done < r->prefs.sampleCount) {
 			/* more to come: show what there is, and size the next dispatch by what this one cost */
 			if (n && refreshOutput(w->ctx, w->fb, W, H, w->output, w->device, G) != CRH_OK) logr(warning, "GPU %d: preview: %s\n", w->device, crh_last_error());
@@ -613,13 +633,16 @@ static void writeAovs(struct renderer *r, crh_ctx *ctx, int W, int H) {
 	free(host);
 }
 
-/* CRAY_HIP_DENOISE=<iterations, 1..8>: the frame on GPU 0, filtered by crh_denoise into a second buffer with guides rendered here — CRAY_HIP_AOV's n passes if that
+/* CRAY_HIP_DENOISE=<iterations, 1..8>: the frame on GPU 0, filtered by crh_denoise — with `half`, the frame after its first halfPasses passes, by
+ * crh_denoise_variance (CRAY_HIP_DENOISE_VARIANCE=1) — into a second buffer with guides rendered here — CRAY_HIP_AOV's n passes if that
  * is set, min(16, sampleCount) otherwise —, written as <imgFileName>_denoised beside the frame (8-bit exactly as the frame's: crh_framebuffer_to_srgb8, then the
  * reference's newImageFile / writeImage); CRH_DUMP_DENOISED_F32=<path> dumps the [H, W, 3] floats. Unset: nothing is allocated, nothing is written. */
-static void writeDenoised(struct renderer *r, crh_ctx *ctx, const float *fb, int W, int H) {
+static void writeDenoised(struct renderer *r, crh_ctx *ctx, const float *fb, const float *half, int halfPasses, int W, int H) {
 	const char *e = getenv("CRAY_HIP_DENOISE");
 	const int iterations = e ? atoi(e) : 0;
 	if (iterations <= 0 || !ctx || !fb) return;
+	const char *v = getenv("CRAY_HIP_DENOISE_VARIANCE");
+	if (v && atoi(v) > 0 && !half) logr(warning, "c-ray-hip: CRAY_HIP_DENOISE_VARIANCE needs at least 2 samples to split; using the plain filter\n");
 	const char *a = getenv("CRAY_HIP_AOV");
 	int n = a ? atoi(a) : 0;
 	if (n <= 0) n = 16;
@@ -634,9 +657,12 @@ static void writeDenoised(struct renderer *r, crh_ctx *ctx, const float *fb, int
 	crh_denoise_params d;
 	crh_denoise_params_default(&d);
 	d.width = W; d.height = H; d.iterations = iterations;
+	crh_denoise_variance_params dv;
+	crh_denoise_variance_params_default(&dv, halfPasses, r->prefs.sampleCount);
+	dv.width = W; dv.height = H; dv.iterations = iterations;
 	float ms = 0.0f;
 	const bool ok = host && crh_aov_alloc(ctx, W, H, &aov) == CRH_OK && crh_framebuffer_alloc(ctx, W, H, &out) == CRH_OK && crh_render_aov(ctx, &p, NULL, 0, aov) == CRH_OK
-		&& crh_denoise(ctx, &d, fb, aov, out) == CRH_OK && crh_denoise_time_ms(ctx, &ms) == CRH_OK && crh_framebuffer_to_srgb8(ctx, out, W, H, t->data.byte_p) == CRH_OK
+		&& (half ? crh_denoise_variance(ctx, &dv, fb, half, aov, out) : crh_denoise(ctx, &d, fb, aov, out)) == CRH_OK && crh_denoise_time_ms(ctx, &ms) == CRH_OK && crh_framebuffer_to_srgb8(ctx, out, W, H, t->data.byte_p) == CRH_OK
 		&& crh_framebuffer_download(ctx, out, W, H, host) == CRH_OK;
 	if (!ok) logr(warning, "c-ray-hip: the frame could not be denoised: %s\n", host ? crh_last_error() : "out of memory");
 	if (aov) crh_aov_free(ctx, aov);
@@ -654,7 +680,7 @@ static void writeDenoised(struct renderer *r, crh_ctx *ctx, const float *fb, int
 		writeImage(file);
 		destroyImageFile(file);          /* (the texture goes with it) */
 		free(name);
-		logr(info, "Denoised frame written (%i iteration%s, %i guide pass%s, %.3f ms).\n", iterations, iterations == 1 ? "" : "s", n, n == 1 ? "" : "es", (double)ms);
+		logr(info, "Denoised frame written (%s%i iteration%s, %i guide pass%s, %.3f ms).\n", half ? "variance-guided, " : "", iterations, iterations == 1 ? "" : "s", n, n == 1 ? "" : "es", (double)ms);
 	} else destroyTexture(t);
 	free(host);
 }
@@ -818,10 +844,20 @@ struct texture *renderFrame(struct renderer *r) {
 	}
 	logr(info, "%llu rays traced on %i GPU%s.\n", (unsigned long long)rays, gpus, PLURAL(gpus));
 	if (!workers[0].failed && !r->state.renderAborted) writeAovs(r, workers[0].ctx, W, H);
-	if (!failed && !r->state.renderAborted) writeDenoised(r, workers[0].ctx, workers[0].fb, W, H);          /* (a frame assembled on the host is not on GPU 0) */
+	if (!failed && !r->state.renderAborted) {          /* (a frame assembled on the host is not on GPU 0) */
+		const int halfAt = varianceHalfPasses(r);
+		if (halfAt && gpus > 1) {          /* the half-sample frame: the same strips, the same way to GPU 0 */
+			crh_ctx *ctxs[MAX_GPUS];
+			float *halves[MAX_GPUS];
+			for (int g = 0; g < gpus; ++g) { ctxs[g] = workers[g].ctx; halves[g] = workers[g].half; }
+			assembleFrame(ctxs, halves, gpus, W, H);
+		}
+		writeDenoised(r, workers[0].ctx, workers[0].fb, halfAt ? workers[0].half : NULL, halfAt, W, H);
+	}
 
 	for (int g = 0; g < gpus; ++g) {
 		if (workers[g].ctx && workers[g].fb) crh_framebuffer_free(workers[g].ctx, workers[g].fb);
+		if (workers[g].ctx && workers[g].half) crh_framebuffer_free(workers[g].ctx, workers[g].half);
 		poolRelease(g, workers[g].ctx, !workers[g].failed);
 	}
 	pthread_mutex_destroy(&sync.mu);

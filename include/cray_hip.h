@@ -465,10 +465,48 @@ typedef struct crh_denoise_params {
 } crh_denoise_params;
 void crh_denoise_params_default(crh_denoise_params *params);          /* the defaults; width and height 0 */
 int crh_denoise(crh_ctx *ctx, const crh_denoise_params *params, const float *dev_fb, const float *dev_aov, float *dev_out);
-/* Milliseconds of the most recent crh_denoise: the sum over its launches, each between two events of the library's own (waits for the last); 0 before the first call. */
+/* Milliseconds of the most recent crh_denoise or crh_denoise_variance: the sum over its launches, each between two events of the library's own (waits for the
+ * last); 0 before the first call. */
 int crh_denoise_time_ms(crh_ctx *ctx, float *last_ms);
-/* ... one by one (dev): ms[0] the prepare launch, ms[1 + i] iteration i; returns the number of launches (at most cap are written) or an error code. */
+/* ... one by one (dev): ms[0] the prepare launch, ms[1 + i] iteration i — after a crh_denoise_variance of at least one iteration ms[1] is the variance prefilter and
+ * ms[2 + i] iteration i; returns the number of launches (at most cap are written) or an error code. */
 int crh_debug_denoise_launch_ms(crh_ctx *ctx, float *ms, uint32_t cap);
+
+/* The same filter with a colour weight in units of each pixel's own standard deviation (additive to ABI 5). crh_denoise stops at luminance edges by a fixed relative
+ * difference, so it blurs illumination features the guides do not mark — shadow edges, reflections — by an amount that does not shrink as samples are added. Here the
+ * variance of the frame is estimated from a second frame buffer, dev_half = the frame after the first h of its n passes (consecutive pass ranges compose bit for bit,
+ * so: render [0, h), crh_framebuffer_copy, render [h, n) on top): half - frame = (n - h) / n (mean of the first h - mean of the rest), hence
+ * Var(frame) ~ variance_scale (L(half) - L(frame))^2 with variance_scale = h / (n - h).
+ *   dev_fb, dev_half   float RGB [H, W, 3]      dev_aov   [H, W, 8]      dev_out   float RGB [H, W, 3]; may be dev_fb, must not be dev_half or dev_aov
+ * The arithmetic, under the rules stated for crh_denoise; ea, ez, el, lum, k, a, c, I, L, n^, z, h, wn and wz are exactly crh_denoise's:
+ * Prepare, per pixel: I and G from dev_fb as above; Lh = lum(ch / a) with ch_c = half_c if it is finite and > 0, else 0; d = Lh - L; v = variance_scale (d d);
+ *   Vraw = v < 2^100 ? v : 2^100 (NaN and overflow included).
+ * Variance prefilter, per pixel p: acc = 0, ws = 0; for dy = -2 .. 2 (stored rows), for dx = -2 .. 2, q = p + (dx, dy), skipped when outside the image:
+ *     wg = wn wz; acc = acc + wg Vraw_q; ws = ws + wg
+ *   V = acc / ws.
+ * Iteration i = 0 .. iterations - 1 (s = 2^i; sigma_color is in standard deviations and is NOT scaled by 2^-i), per pixel p: sd = sqrt(V_p);
+ *   den = sigma_color sd + el; sum = 0, wsum = 0, vsum = 0; the taps in crh_denoise's order, skipped alike:
+ *     e = (Lp - Lq) / den; wc = 1 / (1 + e e); w = ((h wn) wz) wc; sum_c = sum_c + w I_q,c; wsum = wsum + w; vsum = vsum + (w w) V_q
+ *   I'_c = sum_c / wsum; L' = lum(I'); V' = vsum / (wsum wsum); G never changes.
+ * Finish: out_c = I_c a_c; with iterations == 0, out_c = (c_c / a_c) a_c from the prepare launch alone.
+ * Asynchronous on the context's stream, scratch of the context as crh_denoise's (one more plane of floats); a crh_denoise after a crh_denoise_variance gives its own
+ * bits, and the reverse. Launches: prepare, the prefilter, the iterations (iterations + 2; 1 when iterations == 0).
+ * CRH_ERR_INVALID: a NULL argument, a size <= 0, iterations outside 0..8, a sigma or variance_scale that is not a positive finite number, dev_out == dev_half or
+ * dev_aov. Like every denoise, the call leaves crh_counters, crh_kernel_time_ms and crh_last_kernel_name as they were. */
+typedef struct crh_denoise_variance_params {
+	int32_t width, height;
+	int32_t iterations;          /* 0..8; default 5 */
+	float sigma_normal;          /* default 1 */
+	float sigma_depth;           /* default 0.05 */
+	float sigma_color;           /* default 3: standard deviations */
+	float variance_scale;        /* h / (n - h); crh_denoise_variance_params_default sets it from its arguments */
+} crh_denoise_variance_params;
+/* the defaults; width and height 0; variance_scale = half_passes / (passes - half_passes), or 0 (which crh_denoise_variance refuses) with half_passes outside
+ * 1 .. passes - 1. NULL is a no-op. */
+void crh_denoise_variance_params_default(crh_denoise_variance_params *params, int half_passes, int passes);
+int crh_denoise_variance(crh_ctx *ctx, const crh_denoise_variance_params *params, const float *dev_fb, const float *dev_half, const float *dev_aov, float *dev_out);
+/* dev_dst = dev_src, [height, width, 3] floats, device to device, asynchronous on the context's stream (behind the dispatches queued so far). */
+int crh_framebuffer_copy(crh_ctx *ctx, const float *dev_src, float *dev_dst, int width, int height);
 
 /* Multi-GPU inside one process (the C host, c-ray_amd/host/renderer_hip.c: one crh_ctx + one dispatch thread per
  * GPU): sum the n per-GPU float framebuffers onto ctxs[0]'s with ONE RCCL reduce over xGMI (ncclReduce, float,
