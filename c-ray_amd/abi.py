@@ -127,6 +127,11 @@ class DenoiseVarianceParams(C.Structure):
     _fields_ = DenoiseParams._fields_ + [("variance_scale", C.c_float)]
 
 
+class AdaptiveParams(C.Structure):
+    """crh_adaptive_params (crh_adaptive_params_default fills the defaults)."""
+    _fields_ = [("min_passes", C.c_int32), ("threshold", C.c_float)]
+
+
 # numpy dtype of crh_hit for bulk comparisons
 HIT_DTYPE = [("inst", "<i4"), ("poly", "<i4"), ("distance", "<f4"), ("uv", "<f4", (2,)), ("point", "<f4", (3,)),
              ("normal", "<f4", (3,)), ("node_tests", "<u4"), ("tri_tests", "<u4"), ("material", "<u4")]
@@ -143,6 +148,7 @@ EXPORTED_SYMBOLS = [
     "crh_aov_alloc", "crh_aov_free", "crh_aov_clear", "crh_aov_download", "crh_render_aov", "crh_aov_kernel_time_ms",
     "crh_denoise_params_default", "crh_denoise", "crh_denoise_time_ms", "crh_debug_denoise_launch_ms",
     "crh_denoise_variance_params_default", "crh_denoise_variance", "crh_framebuffer_copy",
+    "crh_adaptive_step", "crh_adaptive_time_ms", "crh_adaptive_params_default", "crh_render_adaptive",
     "crh_debug_ray_dump", "crh_debug_ray_dump_counts", "crh_debug_ray_dump_fetch", "crh_debug_walk_probe", "crh_debug_walk_probe_fetch", "crh_debug_walk_probe_compare",
 ]
 MATH_FUNCTIONS = ("sinf", "cosf", "sincosf_sin", "sincosf_cos", "logf", "log10f", "atanf", "acosf", "asinf", "tanf", "powf", "atan2f")   # enum crh_math_function

@@ -81,6 +81,11 @@ def library():
         "crh_denoise_variance_params_default": (None, [C.POINTER(abi.DenoiseVarianceParams), C.c_int, C.c_int]),
         "crh_denoise_variance": (C.c_int, [ctx, C.POINTER(abi.DenoiseVarianceParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
         "crh_framebuffer_copy": (C.c_int, [ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+        "crh_adaptive_step": (C.c_int, [ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(abi.Tile), C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]),
+        "crh_adaptive_time_ms": (C.c_int, [ctx, C.POINTER(C.c_float)]),
+        "crh_adaptive_params_default": (None, [C.POINTER(abi.AdaptiveParams)]),
+        "crh_render_adaptive": (C.c_int, [ctx, C.POINTER(abi.RenderParams), C.POINTER(abi.Tile), C.c_uint32, C.POINTER(abi.AdaptiveParams), C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
         "crh_synchronize": (C.c_int, [ctx]),
         "crh_frames_reduce": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
         "crh_frames_gather": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -121,6 +126,15 @@ def _check(rc, where):
 
 def device_count():
     return library().crh_device_count()
+
+
+def sample_count_map(width, height, tiles, passes):
+    """What a compositor asks of an adaptive frame: the int32 [height, width] map of samples per pixel in stored order (row 0 = the top of the image) from
+    Context.render_adaptive's per-tile pass counts; 0 where no tile lies."""
+    out = np.zeros((height, width), np.int32)
+    for (x0, y0, x1, y1), n in zip(tiles, passes):
+        out[height - y1:height - y0, x0:x1] = n
+    return out
 
 
 class CompiledScene:
@@ -337,6 +351,34 @@ class Context:
     def copy_framebuffer(self, src, dst, width, height):
         """dst = src on the device, in stream order (crh_framebuffer_copy)."""
         _check(self.L.crh_framebuffer_copy(self.h, src, dst, width, height), "crh_framebuffer_copy")
+
+    # ---- adaptive sampling at tile granularity (include/cray_hip.h: crh_adaptive_step, crh_render_adaptive) ----
+    def adaptive_step(self, fb, half, width, height, tiles, threshold):
+        """One step over `tiles` (a list of x0, y0, x1, y1): (errors float32 [n], flags bool [n]); where a tile's flag is set — its error is not <= threshold —
+        half := fb over it. Waits for the result. threshold = inf measures only."""
+        n = len(tiles)
+        arr = (abi.Tile * n)(*[abi.Tile(*t) for t in tiles]) if n else None
+        errors, flags = np.zeros(n, np.float32), np.zeros(n, np.uint8)
+        _check(self.L.crh_adaptive_step(self.h, fb, half, width, height, arr, n, threshold, errors.ctypes.data, flags.ctypes.data), "crh_adaptive_step")
+        return errors, flags.astype(bool)
+
+    def render_adaptive(self, fb, half, width, height, max_samples, bounces, tiles, min_passes=16, threshold=0.05, passes=None):
+        """crh_render_adaptive: min_passes on every tile, then every tile doubles its pass count until its error is at most `threshold` or it reaches the cap
+        `passes` (None: max_samples, which seeds the sampler). Returns (passes per tile int32 [n], error per tile float32 [n]); fb holds each tile's mean of its
+        passes, half the mean of the first half of them."""
+        n = len(tiles)
+        p = abi.RenderParams(0, 0, 0, 0, width, height, 0, max_samples if passes is None else passes, max_samples, bounces)
+        a = abi.AdaptiveParams(min_passes, threshold)
+        arr = (abi.Tile * n)(*[abi.Tile(*t) for t in tiles]) if n else None
+        count, errors = np.zeros(n, np.int32), np.zeros(n, np.float32)
+        _check(self.L.crh_render_adaptive(self.h, C.byref(p), arr, n, C.byref(a), fb, half, count.ctypes.data, errors.ctypes.data), "crh_render_adaptive")
+        return count, errors
+
+    def adaptive_time_ms(self):
+        """Milliseconds of the most recent adaptive step's kernel (render_adaptive's count); 0.0 before the first one."""
+        ms = C.c_float(0.0)
+        _check(self.L.crh_adaptive_time_ms(self.h, C.byref(ms)), "crh_adaptive_time_ms")
+        return float(ms.value)
 
     def denoise_time_ms(self):
         """Milliseconds of the most recent denoise() or denoise_variance(), summed over its launches (waits for it); 0.0 before the first one."""

@@ -485,6 +485,7 @@ __global__ __launch_bounds__(CRH_BLOCK) void k_trace_rays(const DScene Sarg, con
 #include "walk_probe.h"              /* k_walk_probe: the walk of k_pathtrace_roll on its own, on the path tracer's own rays (round 6: a measurement entry, crh_debug_walk_probe) */
 #include "aov.h"                     /* k_aov: albedo, normal, depth and coverage of every camera ray's first hit (crh_render_aov) */
 #include "denoise.h"                 /* k_denoise_prepare / k_denoise_iter: the guided a-trous filter that consumes them (crh_denoise) */
+#include "adaptive.h"                /* k_adaptive_step: a tile's error against the half-sample frame, whether it goes on, and the half-sample frame's advance (crh_adaptive_step) */
 
 /* bounces <= 0: pathTrace() returns black (pathtrace.c:36); only the running mean moves (renderer.c:288-291) */
 __global__ void k_fold_black(const crh_render_params P, const crh_tile *tiles, uint32_t ntiles, float *fb, unsigned long long *counters) {
@@ -674,6 +675,12 @@ struct crh_ctx {
 	bool denoiseTimed = false;
 	float denoiseLaunchMs[CRH_DN_MAX_ITERATIONS + 2] = {};
 	float denoiseLastMs = 0.0f;
+	/* crh_adaptive_step (adaptive.h): the call's tile list, errors and flags go through one pinned host buffer and its device twin (the call waits for its result,
+	 * so one of each serves), and two events around the kernel */
+	void *dAdaptive = nullptr, *hAdaptive = nullptr;
+	size_t adaptiveCap = 0;
+	hipEvent_t adaptiveEv[2] = {};
+	float adaptiveLastMs = 0.0f;
 };
 #define CRH_WORK_SLOTS 64
 static_assert(sizeof(((crh_ctx *)nullptr)->tileSlots) / sizeof(crh_ctx::TileSlot) == CRH_WORK_SLOTS, "one tile slot per work counter");
@@ -979,6 +986,9 @@ int crh_context_destroy(crh_ctx *c) {
 	if (c->aovEvB) (void)hipEventDestroy(c->aovEvB);
 	if (c->dDenoise) (void)hipFree(c->dDenoise);
 	for (hipEvent_t e : c->denoiseEv) if (e) (void)hipEventDestroy(e);
+	if (c->dAdaptive) (void)hipFree(c->dAdaptive);
+	if (c->hAdaptive) (void)hipHostFree(c->hAdaptive);
+	for (hipEvent_t e : c->adaptiveEv) if (e) (void)hipEventDestroy(e);
 	if (c->hErr) (void)hipHostFree(c->hErr);
 	if (c->pinned) (void)hipHostFree(c->pinned);
 	releaseJanitor(c, true);
@@ -2232,6 +2242,140 @@ int crh_debug_denoise_launch_ms(crh_ctx *c, float *ms, uint32_t cap) {
 	if ((rc = dnFetchTimes(c))) return rc;
 	for (uint32_t i = 0; i < c->denoiseLaunches && i < cap; ++i) ms[i] = c->denoiseLaunchMs[i];
 	return (int)c->denoiseLaunches;
+}
+
+/* ---- adaptive sampling at tile granularity (adaptive.h: k_adaptive_step) ------------------------------------------------------------------ */
+static int adCheckTiles(const char *who, const crh_tile *tiles, uint32_t tile_count, int width, int height) {
+	for (uint32_t i = 0; i < tile_count; ++i) {
+		const crh_tile &t = tiles[i];
+		if (t.x0 < 0 || t.y0 < 0 || t.x1 > width || t.y1 > height) return fail(CRH_ERR_INVALID, std::string(who) + ": rectangle " + std::to_string(i) + " lies outside the image");
+		if (t.x1 <= t.x0 || t.y1 <= t.y0) return fail(CRH_ERR_INVALID, std::string(who) + ": rectangle " + std::to_string(i) + " is empty");
+		if ((uint64_t)(t.x1 - t.x0) * (uint64_t)(t.y1 - t.y0) > (1ull << 30)) return fail(CRH_ERR_INVALID, std::string(who) + ": rectangle " + std::to_string(i) + " holds more than 2^30 pixels");
+	}
+	return CRH_OK;
+}
+
+/* One launch over validated tiles, behind whatever the stream holds; waits for it. advanceAll: half := fb over every tile, nothing measured or reported. */
+static int adLaunch(crh_ctx *c, const float *dev_fb, float *dev_half, int width, int height, const crh_tile *tiles, uint32_t tile_count, float threshold, bool advanceAll,
+                    float *errors_host, uint8_t *continue_host) {
+	int rc = setDevice(c);
+	if (rc) return rc;
+	const size_t tileBytes = (size_t)tile_count * sizeof(crh_tile), wordBytes = (size_t)tile_count * sizeof(uint32_t), need = tileBytes + 2 * wordBytes;
+	if (need > c->adaptiveCap) {
+		HIP_TRY(hipStreamSynchronize(c->stream));
+		if (c->dAdaptive) HIP_TRY(hipFree(c->dAdaptive));
+		if (c->hAdaptive) HIP_TRY(hipHostFree(c->hAdaptive));
+		c->dAdaptive = c->hAdaptive = nullptr; c->adaptiveCap = 0;
+		const size_t cap = std::max<size_t>(4096, 2 * need);
+		HIP_TRY(hipMalloc(&c->dAdaptive, cap));
+		HIP_TRY(hipHostMalloc(&c->hAdaptive, cap, hipHostMallocDefault));
+		c->adaptiveCap = cap;
+	}
+	if (!c->adaptiveEv[0]) for (hipEvent_t &e : c->adaptiveEv) HIP_TRY(hipEventCreate(&e));
+	memcpy(c->hAdaptive, tiles, tileBytes);
+	HIP_TRY(hipMemcpyAsync(c->dAdaptive, c->hAdaptive, tileBytes, hipMemcpyHostToDevice, c->stream));
+	AdaptiveArgs A;
+	A.fb = dev_fb; A.half = dev_half;
+	A.tiles = (const crh_tile *)c->dAdaptive;
+	A.errors = (float *)((char *)c->dAdaptive + tileBytes);
+	A.flags = (uint32_t *)((char *)c->dAdaptive + tileBytes + wordBytes);
+	A.W = width; A.H = height; A.threshold = threshold; A.advanceAll = advanceAll ? 1 : 0;
+	HIP_TRY(hipEventRecord(c->adaptiveEv[0], c->stream));
+	hipLaunchKernelGGL(k_adaptive_step, dim3(tile_count), dim3(CRH_BLOCK), 0, c->stream, A);
+	const hipError_t e = hipGetLastError();
+	HIP_TRY(hipEventRecord(c->adaptiveEv[1], c->stream));
+	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string("k_adaptive_step launch: ") + hipGetErrorString(e));
+	if (!advanceAll) HIP_TRY(hipMemcpyAsync((char *)c->hAdaptive + tileBytes, (char *)c->dAdaptive + tileBytes, 2 * wordBytes, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	HIP_TRY(hipEventElapsedTime(&c->adaptiveLastMs, c->adaptiveEv[0], c->adaptiveEv[1]));
+	if (!advanceAll) {
+		const float *err = (const float *)((const char *)c->hAdaptive + tileBytes);
+		const uint32_t *flag = (const uint32_t *)((const char *)c->hAdaptive + tileBytes + wordBytes);
+		if (errors_host) memcpy(errors_host, err, wordBytes);
+		if (continue_host) for (uint32_t i = 0; i < tile_count; ++i) continue_host[i] = flag[i] ? 1 : 0;
+	}
+	return CRH_OK;
+}
+
+int crh_adaptive_step(crh_ctx *c, const float *dev_fb, float *dev_half, int width, int height, const crh_tile *tiles, uint32_t tile_count, float threshold,
+                      float *errors_host, uint8_t *continue_host) {
+	if (!c || !dev_fb || !dev_half || (!tiles && tile_count)) return fail(CRH_ERR_INVALID, "crh_adaptive_step: NULL argument");
+	if (width <= 0 || height <= 0) return fail(CRH_ERR_INVALID, "crh_adaptive_step: bad size");
+	if (std::isnan(threshold) || std::signbit(threshold)) return fail(CRH_ERR_INVALID, "crh_adaptive_step: the threshold is NaN or negative");
+	if ((const float *)dev_half == dev_fb) return fail(CRH_ERR_INVALID, "crh_adaptive_step: the half-sample frame is the frame");
+	const int rc = adCheckTiles("crh_adaptive_step", tiles, tile_count, width, height);
+	if (rc) return rc;
+	if (tile_count == 0) return CRH_OK;
+	return adLaunch(c, dev_fb, dev_half, width, height, tiles, tile_count, threshold, false, errors_host, continue_host);
+}
+
+/* The kernel of the most recent step (crh_render_adaptive's included), between two events of the library's own; 0 before the first one. */
+int crh_adaptive_time_ms(crh_ctx *c, float *last_ms) {
+	if (!c || !last_ms) return fail(CRH_ERR_INVALID, "crh_adaptive_time_ms: NULL argument");
+	*last_ms = c->adaptiveLastMs;
+	return CRH_OK;
+}
+
+void crh_adaptive_params_default(crh_adaptive_params *p) {
+	if (!p) return;
+	p->min_passes = 16; p->threshold = 0.05f;
+}
+
+/* The loop: min_passes everywhere, then every tile doubles its pass count until its error is at most the threshold or the cap is reached. */
+int crh_render_adaptive(crh_ctx *c, const crh_render_params *P, const crh_tile *tiles, uint32_t tile_count, const crh_adaptive_params *A, float *dev_fb, float *dev_half,
+                        int32_t *passes_host, float *errors_host) {
+	if (!c || !P || !A || !dev_fb || !dev_half || (!tiles && tile_count)) return fail(CRH_ERR_INVALID, "crh_render_adaptive: NULL argument");
+	if (!c->haveScene) return fail(CRH_ERR_INVALID, "crh_render_adaptive: no scene uploaded");
+	if (P->image_width <= 0 || P->image_height <= 0 || P->first_pass != 0 || P->pass_count <= 0 || P->max_passes < P->pass_count)
+		return fail(CRH_ERR_INVALID, "crh_render_adaptive: bad render parameters (first_pass must be 0, pass_count is the cap and must not exceed max_passes)");
+	const int m = A->min_passes, cap = P->pass_count;
+	if (m < 2 || (m & 1)) return fail(CRH_ERR_INVALID, "crh_render_adaptive: min_passes must be even and at least 2");
+	{
+		int64_t n = m;
+		while (n < cap) n *= 2;
+		if (n != cap) return fail(CRH_ERR_INVALID, "crh_render_adaptive: the cap (pass_count) must be min_passes times a power of two");
+	}
+	if (std::isnan(A->threshold) || std::signbit(A->threshold)) return fail(CRH_ERR_INVALID, "crh_render_adaptive: the threshold is NaN or negative");
+	if (dev_half == dev_fb) return fail(CRH_ERR_INVALID, "crh_render_adaptive: the half-sample frame is the frame");
+	const int W = P->image_width, H = P->image_height;
+	int rc = adCheckTiles("crh_render_adaptive", tiles, tile_count, W, H);
+	if (rc) return rc;
+	if (tile_count == 0) return CRH_OK;
+	crh_render_params p = *P;
+	auto render = [&](const std::vector<crh_tile> &list, int first, int count) {
+		p.first_pass = first; p.pass_count = count;
+		return crh_render_tiles(c, &p, list.data(), (uint32_t)list.size(), dev_fb);
+	};
+	std::vector<crh_tile> live(tiles, tiles + tile_count);
+	std::vector<uint32_t> index(tile_count);          /* live[j] is tiles[index[j]] */
+	for (uint32_t i = 0; i < tile_count; ++i) index[i] = i;
+	if ((rc = render(live, 0, m / 2))) return rc;
+	if ((rc = adLaunch(c, dev_fb, dev_half, W, H, live.data(), tile_count, 0.0f, true, nullptr, nullptr))) return rc;
+	if ((rc = render(live, m / 2, m - m / 2))) return rc;
+	std::vector<float> err;
+	std::vector<uint8_t> go;
+	for (int n = m; !live.empty(); n *= 2) {
+		const uint32_t count = (uint32_t)live.size();
+		const bool last = n == cap;          /* measure only: nothing is left to render, so no half-sample frame moves */
+		err.resize(count); go.resize(count);
+		if ((rc = adLaunch(c, dev_fb, dev_half, W, H, live.data(), count, last ? __builtin_inff() : A->threshold, false, err.data(), go.data()))) return rc;
+		if (!last && A->threshold == 0.0f) {
+			/* threshold 0 asks for the uniform frame: a tile whose error is exactly 0 — the same colour in every pass so far, which is not the colour the
+			 * running mean of more passes rounds to — goes on like the others, so its half-sample frame moves too */
+			std::vector<crh_tile> still;
+			for (uint32_t j = 0; j < count; ++j) if (!go[j]) { still.push_back(live[j]); go[j] = 1; }
+			if (!still.empty() && (rc = adLaunch(c, dev_fb, dev_half, W, H, still.data(), (uint32_t)still.size(), 0.0f, true, nullptr, nullptr))) return rc;
+		}
+		uint32_t kept = 0;
+		for (uint32_t j = 0; j < count; ++j) {
+			if (errors_host) errors_host[index[j]] = err[j];
+			if (go[j] && !last) { live[kept] = live[j]; index[kept] = index[j]; ++kept; }
+			else if (passes_host) passes_host[index[j]] = n;
+		}
+		live.resize(kept); index.resize(kept);
+		if (kept && (rc = render(live, n, n))) return rc;
+	}
+	return CRH_OK;
 }
 
 /* ---- RCCL (loaded lazily: single-GPU users never need it) ---------------------------------------- */

@@ -39,6 +39,9 @@
  * dumps its floats. The frame, its image and the returned texture are untouched. CRAY_HIP_DENOISE_VARIANCE=1 beside it: the filter is crh_denoise_variance — every GPU
  * thread ends a dispatch exactly at pass sampleCount / 2 and keeps a copy of its frame buffer there (crh_framebuffer_copy), the copies are assembled on GPU 0 like
  * the frame; consecutive pass ranges compose bit for bit, so the frame is the one of a run without the variable.
+ * CRAY_HIP_ADAPTIVE=<threshold> (user-facing; CRAY_HIP_ADAPTIVE_MIN=<m>, default 16): adaptive sampling at tile granularity — every GPU thread hands its rectangles
+ * (one GPU: the scene's tileWidth x tileHeight grid; several: its strips cut every tileWidth columns) to crh_render_adaptive, which gives every rectangle m passes
+ * and doubles that until its error is at most the threshold or sampleCount is reached; a sampleCount that is not m 2^r: a warning and the uniform frame.
  * No GPU => logr(error, ...) (which exits, src/utils/logging.c:69-73): there is no CPU fallback in this file.
  */
 #include <stdlib.h>
@@ -91,7 +94,10 @@ struct gpuWorker {
 	struct timeval frameStart;   /* renderFrame() entry */
 	crh_ctx *ctx;
 	float *fb;
-	float *half;          /* CRAY_HIP_DENOISE_VARIANCE: the frame buffer as it was after the first sampleCount / 2 passes */
+	float *half;          /* CRAY_HIP_DENOISE_VARIANCE: the frame buffer as it was after the first sampleCount / 2 passes; CRAY_HIP_ADAPTIVE: every rectangle's after the first half of ITS passes */
+	crh_tile *adaptTiles;     /* CRAY_HIP_ADAPTIVE: this GPU's rectangles and the pass count each stopped at */
+	int32_t *adaptPasses;
+	uint32_t adaptCount;
 	int device;
 	int failed;
 	char error[256];      /* crh_last_error() is per thread: the failing dispatch thread keeps its message here */
@@ -283,6 +289,45 @@ static int varianceHalfPasses(const struct renderer *r) {
 	return r->prefs.sampleCount / 2;
 }
 
+/* CRAY_HIP_ADAPTIVE=<threshold> [CRAY_HIP_ADAPTIVE_MIN=<m>, default 16]: 1 and the two settings when the frame is rendered adaptively; 0 when the variable is unset
+ * or the settings cannot be used (a threshold that is no number or negative, an m that is odd or below 2, a sampleCount that is not m 2^r) — the frame is
+ * then rendered uniformly, as without the variable (renderFrame says so once) */
+static int adaptiveSettings(const struct renderer *r, crh_adaptive_params *out) {
+	const char *t = getenv("CRAY_HIP_ADAPTIVE"), *m = getenv("CRAY_HIP_ADAPTIVE_MIN");
+	if (!t || !*t) return 0;
+	crh_adaptive_params a;
+	crh_adaptive_params_default(&a);
+	char *end = NULL;
+	a.threshold = strtof(t, &end);
+	if (end == t || a.threshold != a.threshold || a.threshold < 0.0f) return 0;
+	if (m && *m) a.min_passes = atoi(m);
+	if (a.min_passes < 2 || (a.min_passes & 1)) return 0;
+	long n = a.min_passes;
+	while (n < r->prefs.sampleCount) n *= 2;
+	if (n != r->prefs.sampleCount) return 0;
+	if (out) *out = a;
+	return 1;
+}
+
+/* The rectangles crh_render_adaptive decides on, from a GPU's share: one GPU — the whole frame — gets the scene's tile grid (tile.c:66-117 without the ordering,
+ * which is a preview preference), a GPU of several gets its strips cut every tileWidth columns. */
+static uint32_t adaptiveRectangles(const struct renderer *r, const crh_tile *share, uint32_t n, int G, crh_tile **out) {
+	const int tw = r->prefs.tileWidth >= 1 ? (int)r->prefs.tileWidth : 1, th = r->prefs.tileHeight >= 1 ? (int)r->prefs.tileHeight : 1;
+	size_t count = 0;
+	for (int pass = 0; pass < 2; ++pass) {          /* count, then fill */
+		size_t k = 0;
+		for (uint32_t i = 0; i < n; ++i) {
+			const crh_tile s = share[i];
+			const int stepY = G == 1 ? th : s.y1 - s.y0;
+			for (int y = s.y0; y < s.y1; y += stepY)
+				for (int x = s.x0; x < s.x1; x += tw, ++k)
+					if (pass) (*out)[k] = (crh_tile){x, y, x + tw < s.x1 ? x + tw : s.x1, y + stepY < s.y1 ? y + stepY : s.y1};
+		}
+		if (!pass) { count = k; *out = calloc(count ? count : 1, sizeof(**out)); if (!*out) return 0; }
+	}
+	return (uint32_t)count;
+}
+
 static void announceLaunch(struct gpuWorker *w) {
 	if (w->announced) return;
 	w->announced = 1;
@@ -320,9 +365,11 @@ static void *gpuThread(void *arg) {
 	w->ctx = poolAcquire(w->device);
 	const long preparedUs = getUs(phase);
 	/* (a pooled context has rendered before in this process: the frame's ray count starts at zero — ADVICE r05) */
-	const int halfAt = varianceHalfPasses(r);
+	crh_adaptive_params adaptive;
+	const int adapt = adaptiveSettings(r, &adaptive);
+	const int halfAt = adapt ? 0 : varianceHalfPasses(r);          /* (an adaptive render keeps the half-sample frame itself) */
 	int ok = w->ctx != NULL && crh_counters_reset(w->ctx) == CRH_OK && crh_framebuffer_alloc(w->ctx, W, H, &w->fb) == CRH_OK
-		&& (!halfAt || crh_framebuffer_alloc(w->ctx, W, H, &w->half) == CRH_OK);
+		&& ((!halfAt && !adapt) || crh_framebuffer_alloc(w->ctx, W, H, &w->half) == CRH_OK);
 	if (getenv("CRH_TRACE_UPLOAD"))
 		fprintf(stderr, "gpuThread trace: GPU %d has its context (pool, or created + code objects + per-wave buffers) after %.1f ms, its framebuffer after %.1f ms\n",
 				w->device, preparedUs / 1e3, getUs(phase) / 1e3);
@@ -358,7 +405,27 @@ static void *gpuThread(void *arg) {
 	const int fixedPasses = getenv("CRH_DROPIN_PASSES") ? atoi(getenv("CRH_DROPIN_PASSES")) : 0;          /* dev / tests: that many passes per dispatch */
 	if (fixedPasses > 0) passes = fixedPasses;
 	if (passes < 1) passes = 1;
-	for (int done = 0; done < r->prefs.sampleCount && r->state.isRendering && !r->state.renderAborted; ) {
+	if (adapt && n) {
+		/* the whole frame in one call: the library's loop renders, measures and decides, rectangle by rectangle (no preview, no pause in between) */
+		w->adaptCount = adaptiveRectangles(r, share, n, G, &w->adaptTiles);
+		w->adaptPasses = calloc(w->adaptCount ? w->adaptCount : 1, sizeof(*w->adaptPasses));
+		p.first_pass = 0; p.pass_count = r->prefs.sampleCount;
+		struct timeval tl;
+		startTimer(&tl);
+		const int rc = w->adaptTiles && w->adaptPasses ? crh_render_adaptive(w->ctx, &p, w->adaptTiles, w->adaptCount, &adaptive, w->fb, w->half, w->adaptPasses, NULL) : CRH_ERR_NOMEM;
+		w->launchUs += getUs(tl);
+		announceLaunch(w);
+		if (rc != CRH_OK || crh_synchronize(w->ctx) != CRH_OK) {
+			snprintf(w->error, sizeof(w->error), "%s", rc == CRH_ERR_NOMEM ? "out of memory" : crh_last_error());
+			logr(warning, "GPU %d: %s\n", w->device, w->error);
+			w->failed = 1;
+		} else {
+			w->dispatches++;
+			w->state->completedSamples = r->prefs.sampleCount;
+			w->state->totalSamples = pixels * (uint64_t)r->prefs.sampleCount;
+		}
+	}
+	for (int done = adapt ? r->prefs.sampleCount : 0; done < r->prefs.sampleCount && r->state.isRendering && !r->state.renderAborted; ) {
 		p.first_pass = done;
 		p.pass_count = r->prefs.sampleCount - done < passes ? r->prefs.sampleCount - done : passes;
 		if (done < halfAt && done + p.pass_count > halfAt) p.pass_count = halfAt - done;          /* a dispatch ends exactly where the copy is taken */
@@ -843,9 +910,27 @@ struct texture *renderFrame(struct renderer *r) {
 		if (f) { fwrite(buf->data.float_p, sizeof(float), (size_t)W * H * 3, f); fclose(f); }
 	}
 	logr(info, "%llu rays traced on %i GPU%s.\n", (unsigned long long)rays, gpus, PLURAL(gpus));
+	crh_adaptive_params adaptive;
+	const int adapt = adaptiveSettings(r, &adaptive);
+	if (getenv("CRAY_HIP_ADAPTIVE") && *getenv("CRAY_HIP_ADAPTIVE") && !adapt)
+		logr(warning, "c-ray-hip: CRAY_HIP_ADAPTIVE needs a threshold >= 0, an even CRAY_HIP_ADAPTIVE_MIN >= 2 (default 16) and a sample count of that times a power of two; "
+			"%i samples rendered uniformly\n", r->prefs.sampleCount);
+	if (adapt && !failed) {
+		/* the rays spent and where: the share of the rectangles that stopped at each pass count */
+		char line[512];
+		int at = 0;
+		uint32_t all = 0;
+		for (int g = 0; g < gpus; ++g) all += workers[g].adaptCount;
+		for (long n = adaptive.min_passes; n <= r->prefs.sampleCount; n *= 2) {
+			uint32_t k = 0;
+			for (int g = 0; g < gpus; ++g) for (uint32_t i = 0; i < workers[g].adaptCount; ++i) k += workers[g].adaptPasses[i] == n;
+			if (at < (int)sizeof(line) - 32) at += snprintf(line + at, sizeof(line) - (size_t)at, "%s%ld: %.1f %%", at ? ", " : "", n, all ? 100.0 * k / all : 0.0);
+		}
+		logr(info, "Adaptive sampling (threshold %g, at least %i passes): %llu rays, %u tiles by pass count: %s.\n", (double)adaptive.threshold, adaptive.min_passes, (unsigned long long)rays, all, line);
+	}
 	if (!workers[0].failed && !r->state.renderAborted) writeAovs(r, workers[0].ctx, W, H);
 	if (!failed && !r->state.renderAborted) {          /* (a frame assembled on the host is not on GPU 0) */
-		const int halfAt = varianceHalfPasses(r);
+		const int halfAt = varianceHalfPasses(r);          /* (sampleCount / 2 also describes an adaptive frame: every rectangle's half holds the first half of its passes, scale 1) */
 		if (halfAt && gpus > 1) {          /* the half-sample frame: the same strips, the same way to GPU 0 */
 			crh_ctx *ctxs[MAX_GPUS];
 			float *halves[MAX_GPUS];
@@ -858,6 +943,8 @@ struct texture *renderFrame(struct renderer *r) {
 	for (int g = 0; g < gpus; ++g) {
 		if (workers[g].ctx && workers[g].fb) crh_framebuffer_free(workers[g].ctx, workers[g].fb);
 		if (workers[g].ctx && workers[g].half) crh_framebuffer_free(workers[g].ctx, workers[g].half);
+		free(workers[g].adaptTiles);
+		free(workers[g].adaptPasses);
 		poolRelease(g, workers[g].ctx, !workers[g].failed);
 	}
 	pthread_mutex_destroy(&sync.mu);

@@ -508,6 +508,54 @@ int crh_denoise_variance(crh_ctx *ctx, const crh_denoise_variance_params *params
 /* dev_dst = dev_src, [height, width, 3] floats, device to device, asynchronous on the context's stream (behind the dispatches queued so far). */
 int crh_framebuffer_copy(crh_ctx *ctx, const float *dev_src, float *dev_dst, int width, int height);
 
+/* Adaptive sampling at tile granularity (additive to ABI 5). The half-sample frame above is an error estimate the renderer has in hand while it renders: a tile
+ * whose frame barely differs from the mean of its first half of the passes has converged and needs no more of them. Consecutive pass ranges compose bit for bit
+ * and the result does not depend on the tile list, so every tile of an adaptive frame equals, bit for bit, the uniform render of that tile at the pass count it
+ * stopped at; the render kernel is untouched.
+ *
+ * One step: for every rectangle of the list, its error E and whether it goes on; where it does, dev_half := dev_fb over the rectangle (so that after the tile's
+ * next n passes dev_half again holds the mean of the first half of them).
+ *   dev_fb, dev_half   float RGB [H, W, 3] in the frame buffer's stored order; dev_fb is never written, pixels in no rectangle are never touched
+ * The arithmetic is part of the interface, under the rules stated for the denoiser: correctly rounded float32 + - * / sqrt, comparisons and |x|, no contraction.
+ * A rectangle x0, y0, x1, y1 is in reference tile coordinates (y counts from the bottom); tw = x1 - x0, th = y1 - y0. Its pixels are enumerated k = 0 .. tw th - 1:
+ * stored rows H - y1 .. H - 1 - y0 ascending, x ascending within a row. Per pixel k:
+ *   F_c = fb_c if it is finite and > 0, else 0; A_c likewise from half
+ *   d = (|F_r - A_r| + |F_g - A_g|) + |F_b - A_b|; s = (F_r + F_g) + F_b; e = d / sqrt(s + 1e-4f); e_k = e < 2^100 ? e : 2^100
+ *   (NaN and overflow take the second branch: a pixel that is not a number never declares a tile converged)
+ * Sum: P_t = 0.0f, then P_t = P_t + e_k for k = t, t + 256, ... ascending, for t = 0 .. 255; then for stride = 128, 64, .., 1: P_t = P_t + P_(t + stride) for every
+ * t < stride. E = P_0 / (float)(tw th). Decision: goes on = !(E <= threshold). Where it goes on, the rectangle's raw bits of dev_fb are copied into dev_half, all
+ * three channels, no guard (NaNs included); a rectangle that stops keeps its half.
+ * The call launches behind whatever is queued on the context's stream, waits for the result and fills errors_host and continue_host (one entry per rectangle;
+ * either may be NULL). threshold = +inf measures without advancing anything. Rectangles must not overlap. tile_count == 0 (with or without a list) is CRH_OK and
+ * writes nothing. CRH_ERR_INVALID: a NULL context or buffer, a size <= 0, a NULL list with a nonzero count, an empty rectangle, a rectangle outside the image or
+ * of more than 2^30 pixels, a NaN or negative threshold (-0.0f included), dev_half == dev_fb. Like a denoise, a step leaves crh_counters, crh_kernel_time_ms and
+ * crh_last_kernel_name as they were. */
+int crh_adaptive_step(crh_ctx *ctx, const float *dev_fb, float *dev_half, int width, int height, const crh_tile *tiles, uint32_t tile_count, float threshold,
+                      float *errors_host, uint8_t *continue_host);
+/* Milliseconds of the most recent step's kernel (those of crh_render_adaptive count), between two events of the library's own; 0 before the first step. */
+int crh_adaptive_time_ms(crh_ctx *ctx, float *last_ms);
+
+/* The loop that drives it. params->pass_count is the cap, params->first_pass must be 0, params->max_passes seeds the sampler as always and must not be below the
+ * cap; x0 .. y1 of params are ignored. min_passes = m must be even and at least 2, and the cap must be m 2^r for an r >= 0; the threshold as above.
+ *   render passes [0, m / 2) on every rectangle; dev_half := dev_fb over every rectangle; render [m / 2, m); n = m
+ *   while n < cap: one step over the rectangles still live; those that stop are done at n passes; the others render [n, 2 n); n = 2 n
+ *   at the cap: one measure-only step (threshold +inf) over the rectangles that got there
+ * threshold == 0 asks for the uniform frame: every rectangle goes on to the cap, one whose error is exactly 0 included (the step's rule would stop it: such a
+ * rectangle had the same colour in every pass so far, which is not the colour the running mean of more passes rounds to), and its half-sample frame moves along.
+ * passes_host[i] is the pass count rectangle i stopped at, errors_host[i] its error at that count (either may be NULL). Afterwards, for every rectangle, dev_fb
+ * holds the mean of its n_i passes and dev_half the mean of its first n_i / 2 — which is why the schedule doubles: the half-sample frame of the next round is the
+ * frame of this one, and whatever the mix of pass counts, variance_scale is 1 everywhere, so crh_denoise_variance works on an adaptive frame unchanged.
+ * The render dispatches are ordinary ones: crh_counters, crh_kernel_time_ms and crh_last_kernel_name behave as for crh_render_tiles and accumulate over the
+ * rounds. The call returns when the last step has been waited for; dispatches it queued behind that step, if any, are still asynchronous. Every argument is
+ * checked before anything is rendered. tile_count == 0 is CRH_OK and renders nothing. */
+typedef struct crh_adaptive_params {
+	int32_t min_passes;          /* default 16 */
+	float threshold;             /* default 0.05 */
+} crh_adaptive_params;
+void crh_adaptive_params_default(crh_adaptive_params *params);          /* NULL is a no-op */
+int crh_render_adaptive(crh_ctx *ctx, const crh_render_params *params, const crh_tile *tiles, uint32_t tile_count, const crh_adaptive_params *adaptive,
+                        float *dev_fb, float *dev_half, int32_t *passes_host, float *errors_host);
+
 /* Multi-GPU inside one process (the C host, c-ray_amd/host/renderer_hip.c: one crh_ctx + one dispatch thread per
  * GPU): sum the n per-GPU float framebuffers onto ctxs[0]'s with ONE RCCL reduce over xGMI (ncclReduce, float,
  * sum, root 0; communicators from ncclCommInitAll). Tiles are disjoint and non-owned pixels are 0, so the sum is

@@ -1,0 +1,504 @@
+"""Adaptive sampling at tile granularity (crh_adaptive_step, crh_render_adaptive; c-ray_amd/csrc/adaptive.h): a tile's error is the mean over its pixels of
+|frame - half| / sqrt(frame), `half` being the mean of the first half of the frame's passes; a tile whose error is at most the threshold stops, the others double
+their pass count, and k_adaptive_step moves their half-sample frame along.
+
+The step's arithmetic is part of the interface (include/cray_hip.h). `restatement` below is that arithmetic in NumPy float32 — the same enumeration of a tile's
+pixels, the same 256 strided partial sums, the same tree — and the GPU tier holds the kernel to it bit for bit: errors, flags and the half-sample frame afterwards.
+On a rendered scene every tile of an adaptive frame is, bit for bit, the uniform render at the pass count the tile stopped at, and its half-sample frame the
+uniform render at half of that, so crh_denoise_variance works on it with scale 1. Without the renderer: passes go where the noise is. The CPU tier runs this
+file's GPU tests on the kernel emulation (tests/emu)."""
+import ctypes as C
+import json
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from test_denoise import DeviceArray, assert_bit_equal, bits, f32, poisoned, synthetic
+from test_denoise_variance import dropin_paths, poisoned_half, restatement_v
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EMU_DIR = os.path.join(REPO, "tests", "emu")
+EMAX = f32(2.0 ** 100)
+INF = float("inf")
+
+
+# ---- the restatement (include/cray_hip.h: crh_adaptive_step) ---------------------------------------------------------------------------------
+def guard(a):
+    return np.where(np.isfinite(a) & (a > 0), a, f32(0)).astype(f32)
+
+
+def pixel_errors(fb, half):
+    """e of every pixel, [H, W] in stored order."""
+    F, A = guard(fb), guard(half)
+    with np.errstate(all="ignore"):
+        d = (np.abs(F[..., 0] - A[..., 0]) + np.abs(F[..., 1] - A[..., 1])) + np.abs(F[..., 2] - A[..., 2])
+        s = (F[..., 0] + F[..., 1]) + F[..., 2]
+        e = d / np.sqrt(s + f32(1e-4))
+        e = np.where(e < EMAX, e, EMAX).astype(f32)
+    assert e.dtype == np.float32
+    return e
+
+
+def tile_error(e, H, tile):
+    """E of one tile: thread t adds e_k for k = t, t + 256, ... in ascending order, then the tree over the 256 partials."""
+    x0, y0, x1, y1 = tile
+    ek = e[H - y1:H - y0, x0:x1].ravel()          # stored rows H - y1 .. H - 1 - y0 ascending, x ascending within a row
+    n = ek.size
+    P = np.zeros(256, f32)
+    for first in range(0, n, 256):
+        m = min(256, n - first)
+        P[:m] = P[:m] + ek[first:first + m]
+    stride = 128
+    while stride >= 1:
+        P[:stride] = P[:stride] + P[stride:2 * stride]
+        stride //= 2
+    E = P[0] / f32(n)
+    assert E.dtype == np.float32
+    return E
+
+
+def restatement(fb, half, tiles, threshold):
+    """errors float32 [n], flags bool [n], and the half-sample frame afterwards."""
+    H = fb.shape[0]
+    e = pixel_errors(fb, half)
+    errors = np.array([tile_error(e, H, t) for t in tiles], f32)
+    flags = ~(errors <= f32(threshold))
+    after = half.copy()
+    for (x0, y0, x1, y1), go in zip(tiles, flags):
+        if go:
+            after[H - y1:H - y0, x0:x1] = fb[H - y1:H - y0, x0:x1]
+    return errors, flags, after
+
+
+def same_bits(got, want, what):
+    diff = int((bits(got) != bits(want)).sum())
+    print(f"{what}: {diff} of {want.size} floats differ")
+    assert got.shape == want.shape and diff == 0, f"{what}: {diff} floats differ"
+
+
+def grid(pkg, w, h, tw, th):
+    return pkg.tiles.quantize_image(w, h, tw, th, pkg.tiles.ORDER_NORMAL)
+
+
+# ---- plumbing -----------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def ctx(pkg):
+    if pkg.api.device_count() < 1:
+        pytest.fail("GPU tier needs a HIP device; libcray_hip has no CPU fallback")
+    c = pkg.api.Context(0)
+    yield c
+    c.close()
+
+
+def gpu_step(pkg, ctx, fb, half, tiles, threshold):
+    """Context.adaptive_step on copies of fb and half: errors, flags, the half-sample frame afterwards; the frame must come back untouched."""
+    h, w = fb.shape[:2]
+    dfb, dhalf = DeviceArray(pkg, fb), DeviceArray(pkg, half)
+    errors, flags = ctx.adaptive_step(dfb.ptr, dhalf.ptr, w, h, tiles, threshold)
+    assert np.array_equal(bits(dfb.read(ctx)), bits(fb)), "the frame was written"
+    return errors, flags, dhalf.read(ctx)
+
+
+# ---- 1. the step equals the restatement bit for bit --------------------------------------------------------------------------------------------
+def tile_lists(pkg):
+    whole = lambda w, h: [(0, 0, w, h)]
+    cut = grid(pkg, 161, 75, 64, 64)                                 # 3 x 2 tiles, ragged on the right (33 wide) and at the top (11 high: y counts from the bottom)
+    sparse = [t for i, t in enumerate(cut) if i not in (1, 3)] + [(70, 5, 99, 31)]          # two tiles left out, a rectangle inside one of the holes
+    corners = [(0, 0, 1, 1), (160, 0, 161, 1), (0, 74, 1, 75), (160, 74, 161, 75)]
+    return {"1x1": (1, 1, whole(1, 1)), "3x2": (3, 2, whole(3, 2)), "37x29": (37, 29, whole(37, 29)), "300x5": (300, 5, whole(300, 5)),
+            "161x75-64x64": (161, 75, cut), "161x75-sparse": (161, 75, sparse), "161x75-corners": (161, 75, corners)}
+
+
+_frames = {}
+
+
+def frames(w, h):
+    """The poisoned synthetic frame of a shape and a poisoned second realisation of it as the half-sample frame (made once, never modified)."""
+    if (w, h) not in _frames:
+        fb, half = poisoned(synthetic(w, h)[0]), poisoned_half(synthetic(w, h, seed=11)[0])
+        if w > 2 and h > 2:          # a pixel whose sum overflows: d and sqrt(s) are both inf, e is a NaN and takes the clamp's second branch
+            fb[1, 1, 0:2] = 3.0e38
+        for a in (fb, half):
+            a.setflags(write=False)
+        _frames[(w, h)] = (fb, half)
+    return _frames[(w, h)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["1x1", "3x2", "37x29", "300x5", "161x75-64x64", "161x75-sparse", "161x75-corners"])
+def test_step_equals_the_restatement_bit_for_bit(name, pkg, ctx):
+    w, h, tiles = tile_lists(pkg)[name]
+    fb, half = frames(w, h)
+    for a in (fb, half):
+        assert np.isnan(a).any() and np.isinf(a).any() and (a < 0).any(), "the frame and the half-sample frame hold a NaN, an inf and a negative channel each"
+    covered = np.zeros((h, w), bool)
+    for x0, y0, x1, y1 in tiles:
+        assert not covered[h - y1:h - y0, x0:x1].any(), "tiles must not overlap"
+        covered[h - y1:h - y0, x0:x1] = True
+    assert covered.all() == (name not in ("161x75-sparse", "161x75-corners"))
+    if w > 2 and h > 2:
+        assert pixel_errors(fb, half)[1, 1] == EMAX
+    base = restatement(fb, half, tiles, INF)[0]
+    assert np.isfinite(base).all() and (base >= 0).all()
+    median = float(np.median(base))
+    exact = float(base[len(base) // 2])          # one tile's own error: E <= threshold holds with equality, the tile stops
+    for what, threshold in (("0", 0.0), ("inf", INF), ("median", median), ("exact", exact)):
+        want_e, want_f, want_half = restatement(fb, half, tiles, threshold)
+        got_e, got_f, got_half = gpu_step(pkg, ctx, fb, half, tiles, threshold)
+        print(f"{name} threshold {what} = {threshold!r}: errors {want_e[:6]}, continuing {int(want_f.sum())} of {len(tiles)}")
+        assert_bit_equal(got_e, want_e, f"{name} {what}: errors")
+        assert np.array_equal(got_f, want_f), (name, what, got_f, want_f)
+        same_bits(got_half, want_half, f"{name} {what}: the half-sample frame afterwards")
+        # (what the restatement's answer means, spelled out on the device's buffers)
+        for (x0, y0, x1, y1), go in zip(tiles, got_f):
+            sel = np.s_[h - y1:h - y0, x0:x1]
+            assert np.array_equal(bits(got_half[sel]), bits(fb[sel] if go else half[sel]))
+        assert np.array_equal(bits(got_half[~covered]), bits(half[~covered])), "a pixel in no tile was touched"
+        if what == "inf":
+            assert not got_f.any() and np.array_equal(bits(got_half), bits(half))
+        if what == "median" and len(tiles) > 1:
+            assert got_f.any() and not got_f.all(), "both flag values occur"
+        if what == "exact":
+            assert not got_f[len(base) // 2], "E <= threshold with equality: the tile stops"
+            if exact > 0:          # ... and one ulp below it goes on
+                below = float(np.nextafter(f32(exact), f32(0)))
+                assert gpu_step(pkg, ctx, fb, half, tiles, below)[1][len(base) // 2]
+
+
+# ---- 2. every tile of an adaptive frame is a uniform frame --------------------------------------------------------------------------------------
+W2, H2, CAP = 160, 100, 16
+
+
+@pytest.fixture(scope="module")
+def rendered(pkg, ctx, manifest, golden_blob):
+    """glowmetal at 160 x 100, tiles 32 x 20, min_passes 2, cap 16 of max_passes 16: the uniform frames at 1, 2, 4, 8 and 16 passes (once each), the errors of a
+    measure-only step at 2 passes done by hand, and the adaptive render at their median."""
+    w, h = W2, H2
+    bounces = manifest["glowmetal"]["bounces"]
+    ctx.upload(pkg.api.Scene(golden_blob("glowmetal")))
+    tiles = grid(pkg, w, h, 32, 20)
+    assert len(tiles) == 25
+    uniform = {}
+    for n in (1, 2, 4, 8, 16):
+        fb = ctx.framebuffer(w, h)
+        ctx.render_region(fb, w, h, CAP, bounces, first_pass=0, pass_count=n)
+        uniform[n] = ctx.download(fb, w, h)
+        uniform[n].setflags(write=False)
+    # by hand: [0, 1), copy, [1, 2), a step at +inf
+    fb, half = ctx.framebuffer(w, h), ctx.framebuffer(w, h)
+    ctx.render_tiles(fb, w, h, CAP, bounces, tiles, first_pass=0, pass_count=1)
+    ctx.copy_framebuffer(fb, half, w, h)
+    ctx.render_tiles(fb, w, h, CAP, bounces, tiles, first_pass=1, pass_count=1)
+    first, flags = ctx.adaptive_step(fb, half, w, h, tiles, INF)
+    assert not flags.any() and len(set(first.tolist())) > 1, "the 25 errors at 2 passes are not all equal"
+    assert np.array_equal(bits(ctx.download(half, w, h)), bits(uniform[1])) and np.array_equal(bits(ctx.download(fb, w, h)), bits(uniform[2]))
+    threshold = float(np.median(first))
+    fb, half = ctx.framebuffer(w, h), ctx.framebuffer(w, h)
+    ctx.reset_counters()
+    passes, errors = ctx.render_adaptive(fb, half, w, h, CAP, bounces, tiles, min_passes=2, threshold=threshold)
+    ctx.synchronize()
+    paths = ctx.counters()["paths"]
+    return dict(tiles=tiles, uniform=uniform, first=first, threshold=threshold, passes=passes, errors=errors, paths=paths, bounces=bounces,
+                fb=fb, half=half, frame=ctx.download(fb, w, h), halfframe=ctx.download(half, w, h))
+
+
+@pytest.mark.gpu
+def test_every_tile_of_an_adaptive_frame_is_a_uniform_frame(pkg, ctx, rendered):
+    w, h, R = W2, H2, rendered
+    tiles, uniform, passes, errors = R["tiles"], R["uniform"], R["passes"], R["errors"]
+    print(f"threshold {R['threshold']!r}; errors at 2 passes {np.sort(R['first'])}; passes per tile {passes.tolist()}; errors {errors}")
+    assert set(passes.tolist()) <= {2, 4, 8, 16}
+    assert (passes == 2).any(), "at least one tile stopped at 2"
+    assert (passes > 2).any(), "at least one tile went on"
+    assert np.array_equal(passes == 2, R["first"] <= f32(R["threshold"])), "the tiles that stopped at 2 are those of the measure-only step at or below the threshold"
+    for i, (t, n) in enumerate(zip(tiles, passes.tolist())):
+        x0, y0, x1, y1 = t
+        sel = np.s_[h - y1:h - y0, x0:x1]
+        assert np.array_equal(bits(R["frame"][sel]), bits(uniform[n][sel])), f"tile {i} {t}: the frame is not the uniform {n}-pass frame"
+        assert np.array_equal(bits(R["halfframe"][sel]), bits(uniform[n // 2][sel])), f"tile {i} {t}: the half-sample frame is not the uniform {n // 2}-pass frame"
+        want = restatement(uniform[n], uniform[n // 2], [t], INF)[0][0]
+        assert bits(errors[i:i + 1])[0] == bits(np.array([want], f32))[0], f"tile {i}: error {errors[i]!r}, the restatement on the two uniform frames {want!r}"
+        assert n == CAP or errors[i] <= f32(R["threshold"])
+    assert R["paths"] == sum((x1 - x0) * (y1 - y0) * n for (x0, y0, x1, y1), n in zip(tiles, passes.tolist())), "paths = sum of tile pixels x passes"
+    counts = pkg.api.sample_count_map(w, h, tiles, passes)
+    assert counts.dtype == np.int32 and counts.shape == (h, w) and int(counts.sum()) == R["paths"]
+    x0, y0, x1, y1 = tiles[3]
+    assert (counts[h - y1:h - y0, x0:x1] == passes[3]).all()
+
+
+@pytest.mark.gpu
+def test_threshold_extremes(pkg, ctx, rendered):
+    """Threshold 0: every tile reaches the cap — the ones whose error at 2 passes is exactly 0 too (glowmetal has a few: a constant background, the same bits in
+    every pass, whose 16-pass running mean rounds to another colour) — and the frame is the uniform 16-pass frame bit for bit, its half-sample frame the uniform
+    8-pass one. +inf: every tile stops at min_passes."""
+    w, h, R = W2, H2, rendered
+    fb, half = ctx.framebuffer(w, h), ctx.framebuffer(w, h)
+    passes, errors = ctx.render_adaptive(fb, half, w, h, CAP, R["bounces"], R["tiles"], min_passes=2, threshold=0.0)
+    print(f"threshold 0: passes {passes.tolist()}; {int((R['first'] == 0).sum())} tiles with error 0 at 2 passes")
+    assert (passes == CAP).all(), passes
+    same_bits(ctx.download(fb, w, h), R["uniform"][16], "threshold 0: the frame")
+    same_bits(ctx.download(half, w, h), R["uniform"][8], "threshold 0: the half-sample frame")
+    assert_bit_equal(errors, restatement(R["uniform"][16], R["uniform"][8], R["tiles"], INF)[0], "threshold 0: errors at the cap")
+    ctx.clear(fb, w, h)
+    ctx.clear(half, w, h)
+    passes, errors = ctx.render_adaptive(fb, half, w, h, CAP, R["bounces"], R["tiles"], min_passes=2, threshold=INF)
+    assert (passes == 2).all(), passes
+    same_bits(ctx.download(fb, w, h), R["uniform"][2], "threshold inf: the frame")
+    same_bits(ctx.download(half, w, h), R["uniform"][1], "threshold inf: the half-sample frame")
+    assert_bit_equal(errors, R["first"], "threshold inf: errors")
+    # min_passes == the cap: one measure-only step
+    ctx.clear(fb, w, h)
+    passes, _ = ctx.render_adaptive(fb, half, w, h, CAP, R["bounces"], R["tiles"], min_passes=4, threshold=0.0, passes=4)
+    assert (passes == 4).all()
+    same_bits(ctx.download(fb, w, h), R["uniform"][4], "min_passes 4 = cap: the frame")
+    same_bits(ctx.download(half, w, h), R["uniform"][2], "min_passes 4 = cap: the half-sample frame")
+
+
+# ---- 3. it spends passes where the noise is (no renderer) ----------------------------------------------------------------------------------------
+def two_noise_levels(w, h, n, seed=7):
+    """test_denoise_variance.sampled with a relative sigma of 0.6 on the left half of the image and 0.05 on the right: the mean of n samples and of the first n / 2."""
+    clean = synthetic(w, h)[2]
+    rs = np.where(np.mgrid[0:h, 0:w][1] < w // 2, 0.6, 0.05)[..., None]
+    rng = np.random.default_rng(seed)
+    samples = [np.maximum(clean * (1 + rs * rng.standard_normal(clean.shape)), 0) for _ in range(n)]
+    return np.mean(samples, 0).astype(f32), np.mean(samples[:n // 2], 0).astype(f32)
+
+
+@pytest.mark.gpu
+def test_passes_go_where_the_noise_is(pkg, ctx):
+    w, h = 128, 100
+    tiles = grid(pkg, w, h, 32, 20)          # 4 x 5: two columns of tiles on each side
+    left = np.array([x1 <= w // 2 for x0, y0, x1, y1 in tiles])
+    assert left.sum() == 10 and all(x0 >= w // 2 for (x0, y0, x1, y1), l in zip(tiles, left) if not l)
+    fb, half = two_noise_levels(w, h, 8)
+    want = restatement(fb, half, tiles, INF)[0]
+    quiet, noisy = float(want[~left].max()), float(want[left].min())
+    print(f"n = 8: errors of the right half up to {quiet:.5f}, of the left half from {noisy:.5f}")
+    assert quiet < noisy, "input condition: the noise levels separate the tiles"
+    threshold = float(np.sqrt(quiet * noisy))
+    errors8, flags, after = gpu_step(pkg, ctx, fb, half, tiles, threshold)
+    assert np.array_equal(flags, left), "exactly the tiles of the noisy half go on"
+    assert_bit_equal(errors8, want, "n = 8")
+    fb, half = two_noise_levels(w, h, 128)
+    errors128, _, _ = gpu_step(pkg, ctx, fb, half, tiles, INF)
+    print(f"n = 128 / n = 8, per tile: {errors128 / errors8}")
+    assert (errors128 < errors8).all()
+
+
+# ---- 4. composition with the denoiser ----------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_variance_guided_denoise_of_an_adaptive_frame(pkg, ctx, rendered):
+    """The adaptive frame with its mix of pass counts, its half-sample frame and 16 passes of guides: crh_denoise_variance at scale 1 (half_passes 1 of 2) is
+    the restatement's answer bit for bit."""
+    w, h, R = W2, H2, rendered
+    assert len(set(R["passes"].tolist())) > 1
+    buf = ctx.aov_buffer(w, h)
+    ctx.render_aov(buf, w, h, CAP)
+    aov = ctx.download_aov(buf, w, h)
+    out = ctx.framebuffer(w, h)
+    ctx.denoise_variance(R["fb"], R["half"], buf, w, h, 1, 2, out=out)
+    assert_bit_equal(ctx.download(out, w, h), restatement_v(R["frame"], R["halfframe"], aov, 1.0), "denoise_variance of the adaptive frame")
+    assert np.array_equal(bits(ctx.download(R["fb"], w, h)), bits(R["frame"])) and np.array_equal(bits(ctx.download(R["half"], w, h)), bits(R["halfframe"]))
+
+
+# ---- 5. entry points -----------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_entry_point_behaviour(pkg, manifest, golden_blob, tmp_path):
+    api, abi = pkg.api, pkg.abi
+    L = api.library()
+    if api.device_count() < 1:
+        pytest.fail("GPU tier needs a HIP device; libcray_hip has no CPU fallback")
+    assert abi.ABI_VERSION == 5 and L.crh_abi_version() == 5, "the entry points are additive to ABI 5"
+    src = tmp_path / "size.c"
+    src.write_text('#include <stdio.h>\n#include "cray_hip.h"\nint main(void){printf("%zu %i\\n", sizeof(crh_adaptive_params), CRH_ABI_VERSION);return 0;}\n')
+    subprocess.check_call(["gcc", "-I" + os.path.join(REPO, "include"), str(src), "-o", str(tmp_path / "size")])
+    size, version = subprocess.check_output([str(tmp_path / "size")]).decode().split()
+    assert int(size) == C.sizeof(abi.AdaptiveParams) == 8 and int(version) == 5
+    p = abi.AdaptiveParams(-1, -1.0)
+    L.crh_adaptive_params_default(C.byref(p))
+    assert (p.min_passes, p.threshold) == (16, f32(0.05))
+    L.crh_adaptive_params_default(None)
+    w, h = 160, 100
+    tiles = [(0, 0, 80, 100), (80, 0, 160, 50)]
+    c = api.Context(0)
+    try:
+        assert c.adaptive_time_ms() == 0.0
+        fb, half = c.framebuffer(w, h), c.framebuffer(w, h)
+        errors, flags = np.full(2, -7.0, np.float32), np.full(2, 9, np.uint8)
+
+        def step(ctxh=c.h, fb_=fb, half_=half, w_=w, h_=h, tiles_=tiles, count=None, threshold=0.5):
+            arr = (abi.Tile * max(len(tiles_), 1))(*[abi.Tile(*t) for t in tiles_]) if tiles_ is not None else None
+            return L.crh_adaptive_step(ctxh, fb_, half_, w_, h_, arr, len(tiles_) if count is None else count, threshold, errors.ctypes.data, flags.ctypes.data)
+        assert step(ctxh=None) == abi.ERR_INVALID and step(fb_=None) == abi.ERR_INVALID and step(half_=None) == abi.ERR_INVALID
+        assert step(w_=0) == abi.ERR_INVALID and step(h_=-1) == abi.ERR_INVALID
+        assert step(tiles_=None, count=2) == abi.ERR_INVALID
+        for bad in ((10, 10, 10, 20), (10, 10, 20, 10), (20, 10, 10, 20), (-1, 0, 10, 10), (0, -1, 10, 10), (0, 0, 161, 10), (0, 0, 10, 101)):
+            assert step(tiles_=[tiles[0], bad]) == abi.ERR_INVALID, bad
+        for bad in (float("nan"), -1.0, -0.0, -INF):
+            assert step(threshold=bad) == abi.ERR_INVALID, bad
+        assert step(half_=fb) == abi.ERR_INVALID
+        assert step(tiles_=[], count=0) == abi.OK and step(tiles_=None, count=0) == abi.OK
+        assert (errors == -7.0).all() and (flags == 9).all(), "a refused or empty call writes nothing"
+        assert c.adaptive_time_ms() == 0.0, "refused calls are no calls"
+        # no scene is needed; NULL result arrays; the step leaves the render path's counters, time and kernel name alone
+        c.upload(api.Scene(golden_blob("glowmetal")))
+        bounces = manifest["glowmetal"]["bounces"]
+        c.render_region(fb, w, h, 2, bounces, first_pass=0, pass_count=1)
+        c.copy_framebuffer(fb, half, w, h)
+        c.render_region(fb, w, h, 2, bounces, first_pass=1, pass_count=1)
+        c.synchronize()
+        before = (c.counters(), c.kernel_time_ms(), c.last_kernel_name())
+        assert before[0]["paths"] == 2 * w * h
+        assert L.crh_adaptive_step(c.h, fb, half, w, h, (abi.Tile * 2)(*[abi.Tile(*t) for t in tiles]), 2, INF, None, None) == abi.OK
+        assert step(threshold=INF) == abi.OK
+        assert (errors > 0).all() and (flags == 0).all()
+        assert c.adaptive_time_ms() > 0.0
+        assert (c.counters(), c.kernel_time_ms(), c.last_kernel_name()) == before
+
+        # crh_render_adaptive
+        def loop(ctxh=c.h, fb_=fb, half_=half, tiles_=tiles, count=None, min_passes=2, threshold=0.5, first_pass=0, cap=16, max_passes=16, null_params=False, null_adaptive=False):
+            q = abi.RenderParams(0, 0, 0, 0, w, h, first_pass, cap, max_passes, bounces)
+            a = abi.AdaptiveParams(min_passes, threshold)
+            arr = (abi.Tile * max(len(tiles_), 1))(*[abi.Tile(*t) for t in tiles_]) if tiles_ is not None else None
+            return L.crh_render_adaptive(ctxh, None if null_params else C.byref(q), arr, len(tiles_) if count is None else count, None if null_adaptive else C.byref(a),
+                                         fb_, half_, None, None)
+        assert loop(ctxh=None) == abi.ERR_INVALID and loop(null_params=True) == abi.ERR_INVALID and loop(null_adaptive=True) == abi.ERR_INVALID
+        assert loop(fb_=None) == abi.ERR_INVALID and loop(half_=None) == abi.ERR_INVALID and loop(half_=fb) == abi.ERR_INVALID
+        assert loop(tiles_=None, count=2) == abi.ERR_INVALID and loop(tiles_=[(0, 0, 161, 10)]) == abi.ERR_INVALID and loop(tiles_=[(5, 5, 5, 9)]) == abi.ERR_INVALID
+        assert loop(min_passes=3) == abi.ERR_INVALID and loop(min_passes=0) == abi.ERR_INVALID and loop(min_passes=-2) == abi.ERR_INVALID
+        assert loop(min_passes=16, cap=24, max_passes=24) == abi.ERR_INVALID, "the cap is not min_passes times a power of two"
+        assert loop(min_passes=16, cap=8) == abi.ERR_INVALID and loop(cap=0) == abi.ERR_INVALID
+        assert loop(first_pass=1) == abi.ERR_INVALID
+        assert loop(cap=16, max_passes=8) == abi.ERR_INVALID, "the cap exceeds max_passes"
+        for bad in (float("nan"), -1.0, -0.0):
+            assert loop(threshold=bad) == abi.ERR_INVALID, bad
+        c.synchronize()
+        assert c.counters() == before[0], "a refused render renders nothing"
+        assert loop(tiles_=[], count=0) == abi.OK and c.counters() == before[0]
+        assert loop(threshold=INF, cap=4, max_passes=4) == abi.OK
+        c.synchronize()
+        assert c.counters()["paths"] == before[0]["paths"] + 2 * (80 * 100 + 80 * 50), "the render dispatches of the loop count like any other"
+        with pytest.raises(api.CrhError):
+            c.render_adaptive(fb, half, w, h, 24, bounces, tiles)          # the defaults: min_passes 16
+        no_scene = api.Context(0)
+        try:
+            f2, h2 = no_scene.framebuffer(w, h), no_scene.framebuffer(w, h)
+            assert loop(ctxh=no_scene.h, fb_=f2, half_=h2) == abi.ERR_INVALID, "no scene uploaded"
+        finally:
+            no_scene.close()
+    finally:
+        c.close()
+
+
+# ---- 6. the drop-in program ------------------------------------------------------------------------------------------------------------------------
+TILE = (64, 40)          # cfg1_scene at 320 x 200: 5 x 5 tiles
+
+
+def run_dropin(manifest, out_dir, extra_env):
+    """c-ray-hip on cfg1_scene with 64 x 40 tiles and `extra_env`, its images in out_dir: the frame's floats, the image files written, the output."""
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    import refrun
+    exe, overlay, _ = dropin_paths()
+    m = manifest["cfg1_scene"]
+    w, h, s, b = m["width"], m["height"], m["samples"], m["bounces"]
+    os.makedirs(out_dir, exist_ok=True)
+    scene = refrun.rewrite_scene("scene.json", w, h, s, b, tile=TILE, out_dir=str(out_dir))
+    frame = os.path.join(out_dir, "frame.f32")
+    env = dict(os.environ, CRH_DUMP_F32=frame, CRAY_HIP_DEVICES="1")
+    for k in ("CRAY_HIP_AOV", "CRAY_HIP_DENOISE", "CRAY_HIP_DENOISE_VARIANCE", "CRAY_HIP_ADAPTIVE", "CRAY_HIP_ADAPTIVE_MIN", "CRH_DROPIN_PASSES"):
+        env.pop(k, None)
+    env.update(extra_env)
+    proc = subprocess.run([exe], input=json.dumps(scene).encode(), cwd=overlay, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+    text = proc.stdout.decode(errors="replace")
+    assert proc.returncode == 0, text[-2000:]
+    files = {f: open(os.path.join(out_dir, f), "rb").read() for f in sorted(os.listdir(out_dir)) if f.endswith(".bmp")}
+    return np.fromfile(frame, dtype=np.float32).reshape(h, w, 3), files, text
+
+
+def api_threshold_and_frame(pkg, ctx, manifest, golden_blob, tiles):
+    """cfg1_scene through the API over `tiles`, min_passes 2 of its 4 samples: the median error of a measure-only step at 2 passes, and render_adaptive's frame
+    and pass counts at that threshold."""
+    m = manifest["cfg1_scene"]
+    w, h, s, b = m["width"], m["height"], m["samples"], m["bounces"]
+    assert s == 4
+    ctx.upload(pkg.api.Scene(golden_blob("cfg1_scene")))
+    fb, half = ctx.framebuffer(w, h), ctx.framebuffer(w, h)
+    ctx.render_tiles(fb, w, h, s, b, tiles, first_pass=0, pass_count=1)
+    ctx.copy_framebuffer(fb, half, w, h)
+    ctx.render_tiles(fb, w, h, s, b, tiles, first_pass=1, pass_count=1)
+    first, _ = ctx.adaptive_step(fb, half, w, h, tiles, INF)
+    threshold = float(np.median(first))
+    ctx.clear(fb, w, h)
+    ctx.clear(half, w, h)
+    passes, _ = ctx.render_adaptive(fb, half, w, h, s, b, tiles, min_passes=2, threshold=threshold)
+    assert (passes == 2).any() and (passes == 4).any()
+    return threshold, ctx.download(fb, w, h), passes
+
+
+@pytest.mark.gpu
+def test_dropin_program_renders_adaptively(pkg, ctx, manifest, golden_blob, tmp_path):
+    """c-ray-hip: CRAY_HIP_ADAPTIVE=0 (every tile goes to the cap) writes the frame and the image of a run without it; a finite threshold writes the frame
+    Context.render_adaptive gives over the scene's tile grid, and says where the passes went; a sample count that is not min 2^r warns and renders uniformly."""
+    from test_gpu_parity import dropin_env
+    if not dropin_paths()[2]:
+        pytest.skip("c-ray-hip or the asset overlay is not built (needs the reference's sources at build time)")
+    m = manifest["cfg1_scene"]
+    w, h = m["width"], m["height"]
+    plain, plain_files, plain_text = run_dropin(manifest, str(tmp_path / "plain"), dropin_env())
+    assert "Adaptive sampling" not in plain_text and len(plain_files) == 1
+    zero, zero_files, text = run_dropin(manifest, str(tmp_path / "zero"), dict(dropin_env(), CRAY_HIP_ADAPTIVE="0", CRAY_HIP_ADAPTIVE_MIN="2"))
+    assert "Adaptive sampling" in text and "25 tiles" in text and "4: 100.0 %" in text, text[-1500:]
+    assert np.array_equal(bits(zero), bits(plain)) and zero_files == plain_files, "threshold 0: the uniform frame, byte for byte"
+    tiles = grid(pkg, w, h, *TILE)
+    assert len(tiles) == 25
+    threshold, want, passes = api_threshold_and_frame(pkg, ctx, manifest, golden_blob, tiles)
+    got, files, text = run_dropin(manifest, str(tmp_path / "adaptive"), dict(dropin_env(), CRAY_HIP_ADAPTIVE=repr(threshold), CRAY_HIP_ADAPTIVE_MIN="2"))
+    same_bits(got, want, "drop-in against Context.render_adaptive")
+    assert (bits(got) != bits(plain)).any()
+    line = [l for l in text.splitlines() if "Adaptive sampling" in l]
+    assert len(line) == 1 and "25 tiles" in line[0], text[-1500:]
+    share = 100.0 * float((passes == 2).sum()) / 25
+    assert f"2: {share:.1f} %" in line[0] and f"4: {100 - share:.1f} %" in line[0], line
+    # 4 samples are not 16 2^r (the default minimum): a warning and the uniform frame
+    frame, files, text = run_dropin(manifest, str(tmp_path / "warn"), dict(dropin_env(), CRAY_HIP_ADAPTIVE=repr(threshold)))
+    assert "CRAY_HIP_ADAPTIVE needs" in text and "rendered uniformly" in text and "Adaptive sampling" not in text, text[-1500:]
+    assert np.array_equal(bits(frame), bits(plain)) and files == plain_files
+    # two devices, where there are two (the emulation tier has): every GPU thread decides on its own strips cut every tileWidth columns, and the gathered frame
+    # is the one Context.render_adaptive gives over all those rectangles
+    if pkg.api.device_count() >= 2:
+        tiles = strip_cut_rectangles(w, h, 2)
+        threshold, want, passes = api_threshold_and_frame(pkg, ctx, manifest, golden_blob, tiles)
+        got, _, text = run_dropin(manifest, str(tmp_path / "two"), dict(dropin_env(), CRAY_HIP_DEVICES="2", CRAY_HIP_ADAPTIVE=repr(threshold), CRAY_HIP_ADAPTIVE_MIN="2"))
+        same_bits(got, want, "two devices against Context.render_adaptive over the strip-cut rectangles")
+        assert f"{len(tiles)} tiles" in text, text[-1500:]
+
+
+def strip_cut_rectangles(w, h, devices):
+    """What the program's GPU threads decide on when there are several: GPU g's 4-row strips (every devices-th one), cut every tileWidth columns."""
+    return [(x, y, min(x + TILE[0], w), min(y + 4, h)) for g in range(devices) for i, y in enumerate(range(0, h, 4)) if i % devices == g for x in range(0, w, TILE[0])]
+
+
+# ---- 7. the CPU tier ---------------------------------------------------------------------------------------------------------------------------------
+def test_adaptive_kernel_on_the_emulation():
+    """CPU tier: this file's GPU tests run by a child pytest against the kernel emulation (tests/emu/libcray_hip_emu.so: k_adaptive_step and the two entry points
+    compiled unmodified on the HIP-on-CPU shim, two emulated devices) — every one of them runs and passes there, none skipped (the drop-in tests where the drop-in
+    program is built)."""
+    from conftest import locked_make
+    locked_make(["make", "-s", "-C", EMU_DIR, "libcray_hip_emu.so"])
+    libdir = os.path.join(EMU_DIR, "_dropin_libs")
+    dropin = dropin_paths()[2] and os.path.isdir(libdir)
+    env = dict(os.environ, CRH_LIB=os.path.join(EMU_DIR, "libcray_hip_emu.so"), CRH_ALLOW_EMULATION="1", CRH_DROPIN_LIBDIR=libdir, HIPEMU_CUS="2", HIPEMU_THREADS="3",
+               HIPEMU_DEVICES="2")
+    cmd = [sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-s", "-p", "no:cacheprovider"] + ([] if dropin else ["-k", "not dropin"])
+    r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=1700)
+    tail = (r.stdout + r.stderr)[-4000:]
+    assert r.returncode == 0, tail
+    m = re.search(r"(\d+) passed", r.stdout)
+    assert m and int(m.group(1)) == (13 if dropin else 12), tail
+    assert "skipped" not in r.stdout.strip().splitlines()[-1], tail
+    if dropin:
+        assert "two devices against Context.render_adaptive" in r.stdout, tail
