@@ -92,6 +92,7 @@ static int fail(int code, const std::string &msg) { t_err = msg; return code; }
 		hipError_t e_ = (expr);                                                                     \
 		if (e_ != hipSuccess) return fail(CRH_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
 	} while (0)
+#include "ctx_buffers.h"             /* DevBuf, StagedBuf, TimedPool: the owners of a context's per-dispatch buffers (HIP_TRY above is the macro it asks for) */
 
 /* ---- device-side helpers ------------------------------------------------------------------------ */
 /* Per-lane traversal stack: the first CRH_STACK_LDS entries live in LDS (entry-major: entry i of lane l at
@@ -586,24 +587,19 @@ struct crh_ctx {
 	Sched sched = {70, 160, 120, 16, 160, 4, 12, 12, 48, 0, 20, 0, 2000000000};
 	int kernel = CRH_KERNEL_ROLL;            /* CRH_OPT_KERNEL */
 	SchedWg schedWg = {70, 160, 120, 16, 768, 4, 12, 12, 8, 192, 1, 16, 32};
-	uint32_t *dOvf = nullptr;                /* workgroup kernel: traversal-stack overflow columns */
-	size_t ovfWords = 0;
+	DevBuf<uint32_t> dOvf;                   /* traversal-stack overflow columns, CRH_OVF_WORDS_PER_WAVE per wave of the grid (growWaveBuffers; k_aov borrows them) */
 	unsigned int *hErr = nullptr, *dErr = nullptr;   /* the dispatches' error word: pinned host memory the kernels OR bits into (CRH_ERRFLAG_*), and its device address */
 	std::vector<int> preloaded;              /* kernel instantiations whose code object is loaded (variantKey) */
-	float *dGather = nullptr;                /* crh_frames_gather: this GPU's strips packed (senders) / every sender's slab (GPU 0) */
-	size_t gatherFloats = 0;
-	uint8_t *dSrgb = nullptr;                /* crh_framebuffer_to_srgb8: the 8-bit frame on the device (grown on demand, kept) */
-	size_t srgbBytes = 0;
+	DevBuf<float> dGather;                   /* crh_frames_gather: this GPU's strips packed (senders) / every sender's slab (GPU 0) */
+	DevBuf<uint8_t> dSrgb;                   /* crh_framebuffer_to_srgb8: the 8-bit frame on the device (grown on demand, kept: an interactive host converts after every pass chunk) */
 	bool traceExactSlabs = false;            /* CRH_OPT_TRACE_SLABS: crh_trace_rays walks degenerate rays like the render kernels do (exact slabs) instead of like the reference (NaN arithmetic) */
-	float *dQueues = nullptr;
-	size_t queueFloats = 0;
+	DevBuf<float> dQueues;                   /* the per-wave path tables, CRH_WAVE_QUEUE_FLOATS per wave (growWaveBuffers) */
 	int wavesPerSimd = 4;
 	int sampler = CRH_SAMPLER_RANDOM;
 	int tailPercent = 16;       /* share of a dispatch's pixels that is cut into quarter-size blocks at the end of the work queue */
 	int tail2Percent = 4;       /* ... and the share at the very end that is cut into sixteenth-size blocks */
 	int tailSplit = CRH_TAIL_SPLIT_DEFAULT;   /* CRH_OPT_TAIL_SPLIT: 64-path units per wave at the very end of the queue (rolling kernel); 0 = none */
-	float *dDefer = nullptr;    /* samples of the split pixels of the dispatch in flight (k_fold_deferred folds them) */
-	size_t deferFloats = 0;
+	DevBuf<float> dDefer;       /* samples of the split pixels of the dispatch in flight (k_fold_deferred folds them) */
 	unsigned long long *dWaveStats = nullptr;   /* debug (CRH_OPT_WAVE_STATS) */
 	/* debug (crh_debug_ray_dump / crh_debug_walk_probe): the rays the counting kernel's waves started, one region of dumpCap rays per wave; the probe's two outputs, its
 	 * unit list / counter and its own stack-overflow columns (up to eight workgroups per CU) */
@@ -612,30 +608,25 @@ struct crh_ctx {
 	f4 *dProbeHits[2] = {nullptr, nullptr};
 	int32_t *dProbeInst[2] = {nullptr, nullptr};
 	uint32_t *dProbeOvf = nullptr;
-	void *dProbeUnits = nullptr;
-	size_t probeUnitCap = 0;
+	DevBuf<ProbeUnit> dProbeUnits;
 	/* the streaming form (CRH_KERNEL_STREAM; pathtrace_stream.h): two path pools of streamSlots slots (eight 16-byte planes), the walk's hit records, the cohorts' fill
 	 * levels, the ring of sample slabs, the dispatch's state, the walk kernel's stack-overflow columns, and the host-visible word that says a dispatch is over */
 	int streamCohorts = 16384;               /* CRH_OPT_STREAM_COHORTS: cohorts of 1024 paths in a pool (the most; small dispatches take fewer) */
 	int streamGroup = 8;                     /* iterations enqueued between two looks at the completion word */
-	f4 *dStreamPlanes = nullptr;
-	f4 *dStreamHit = nullptr;
-	int32_t *dStreamHitInst = nullptr;
-	uint32_t *dStreamCount = nullptr;
-	size_t streamSlots = 0;
-	float *dStreamSlab = nullptr;
-	size_t streamSlabFloats = 0;
+	DevBuf<f4> dStreamPlanes, dStreamHit;
+	DevBuf<int32_t> dStreamHitInst;
+	DevBuf<uint32_t> dStreamCount;
+	size_t streamSlots = 0;                  /* what the four above hold: they grow together */
+	DevBuf<float> dStreamSlab;
 	StreamCtl *dStreamCtl = nullptr;
-	uint32_t *dStreamOvf = nullptr;
-	size_t streamOvfWords = 0;
+	DevBuf<uint32_t> dStreamOvf;
 	unsigned int *hStreamDone = nullptr, *dStreamDone = nullptr;
 	unsigned int streamSeq = 0;
 	uint64_t streamIterations = 0;           /* iterations the last streamed dispatch enqueued (crh_debug_stream_stats) */
 	hipEvent_t streamEv[2] = {nullptr, nullptr};
 	uint32_t lastGrid = 0;
 	char lastKernel[64] = "";               /* the instantiation launchPathtrace launched last (crh_last_kernel_name) */
-	float *dStage = nullptr;
-	size_t stageFloats = 0;
+	DevBuf<float> dStage;                    /* the waves' sample slabs (growWaveBuffers) */
 	bool haveScene = false;
 	bool hasPrograms = true;     /* the compiled scene contains node programs -> kernel variant with runProgram() */
 	bool hasVolumes = false;     /* walks draw from the path's sampler: crh_trace_rays (caller rays, no path) refuses such scenes */
@@ -649,11 +640,9 @@ struct crh_ctx {
 	uint32_t workSlot = 0;
 	/* per-launch tile lists: a ring of persistent device buffers, each with a pinned host twin (no hipMalloc and no blocking copy per
 	 * launch: one hipMemcpyAsync on the launch stream); a slot is reused only after the launch that read it has finished */
-	struct TileSlot { void *dev = nullptr; void *host = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool inFlight = false; };
-	TileSlot tileSlots[64];
-	struct Timed { hipEvent_t a, b; };
-	std::vector<Timed> pendingTimes;
-	std::vector<Timed> eventPool;
+	StagedBuf tileSlots[64];
+	std::vector<TimedPair> pendingTimes;
+	TimedPool eventPool;
 	float lastMs = 0.0f;
 	double totalMs = 0.0;
 	uint64_t launches = 0;
@@ -661,15 +650,13 @@ struct crh_ctx {
 	 * starts go through one pinned host buffer and its device twin; the work counter is reset behind the kernel */
 	uint32_t aovDepth = 0;                   /* CompiledScene::max_albedo_depth of the resident scene */
 	uint32_t *dAovCounter = nullptr;
-	void *dAovTiles = nullptr, *hAovTiles = nullptr;
-	size_t aovTileCap = 0;
-	hipEvent_t aovDone = nullptr, aovEvA = nullptr, aovEvB = nullptr;
-	bool aovInFlight = false, aovTimed = false;
+	StagedBuf aovTiles;
+	hipEvent_t aovEvA = nullptr, aovEvB = nullptr;
+	bool aovTimed = false;
 	float aovLastMs = 0.0f;
 	/* crh_denoise / crh_denoise_variance (denoise.h): three planes of 16-byte records (C ping, C pong, G) — and, for the variance kind, a plane of floats behind
 	 * them — sized lazily for the largest call so far, and one event around every launch (prepare, the variance prefilter, the iterations) */
-	f4 *dDenoise = nullptr;
-	size_t denoiseBytes = 0;
+	DevBuf<uint8_t> dDenoise;
 	hipEvent_t denoiseEv[CRH_DN_MAX_ITERATIONS + 3] = {};
 	uint32_t denoiseLaunches = 0;            /* of the most recent denoise of either kind */
 	bool denoiseTimed = false;
@@ -677,13 +664,12 @@ struct crh_ctx {
 	float denoiseLastMs = 0.0f;
 	/* crh_adaptive_step (adaptive.h): the call's tile list, errors and flags go through one pinned host buffer and its device twin (the call waits for its result,
 	 * so one of each serves), and two events around the kernel */
-	void *dAdaptive = nullptr, *hAdaptive = nullptr;
-	size_t adaptiveCap = 0;
+	StagedBuf adaptive;
 	hipEvent_t adaptiveEv[2] = {};
 	float adaptiveLastMs = 0.0f;
 };
 #define CRH_WORK_SLOTS 64
-static_assert(sizeof(((crh_ctx *)nullptr)->tileSlots) / sizeof(crh_ctx::TileSlot) == CRH_WORK_SLOTS, "one tile slot per work counter");
+static_assert(sizeof(((crh_ctx *)nullptr)->tileSlots) / sizeof(StagedBuf) == CRH_WORK_SLOTS, "one tile slot per work counter");
 
 static int setDevice(crh_ctx *c) {
 	HIP_TRY(hipSetDevice(c->device));
@@ -705,7 +691,7 @@ static int resolveTimes(crh_ctx *c, bool wait) {
 		HIP_TRY(hipEventElapsedTime(&ms, t.a, t.b));
 		c->lastMs = ms;
 		c->totalMs += ms;
-		c->eventPool.push_back(t);
+		c->eventPool.give(t);
 		++done;
 	}
 	c->pendingTimes.erase(c->pendingTimes.begin(), c->pendingTimes.begin() + done);
@@ -745,10 +731,10 @@ static bool wideWalk(const crh_ctx *c) {
 static hipError_t launchPathtrace(crh_ctx *c, uint32_t grid, const crh_render_params *P, const BlockQueue &Q, float *dev_fb, int chunk) {
 #define CRH_LAUNCH_ROLL(LEVEL, PROG, SAMP) do { snprintf(c->lastKernel, sizeof(c->lastKernel), "k_pathtrace_roll<%d,4,%s,%d>", LEVEL, PROG ? "true" : "false", SAMP); \
 		hipLaunchKernelGGL((k_pathtrace_roll<LEVEL, 4, PROG, SAMP>), dim3(grid), dim3(CRH_BLOCK), 0, c->stream, c->d, *P, Q, dev_fb, \
-						   c->dCounters, c->dStage, chunk, c->dWaveStats, c->sched, c->dQueues, c->dOvf, c->dErr); } while (0)
+						   c->dCounters, c->dStage.p, chunk, c->dWaveStats, c->sched, c->dQueues.p, c->dOvf.p, c->dErr); } while (0)
 #define CRH_LAUNCH_ROLL_WIDE(LEVEL) do { snprintf(c->lastKernel, sizeof(c->lastKernel), "k_pathtrace_roll<%d,4,false,0,wide4>", LEVEL); \
 		hipLaunchKernelGGL((k_pathtrace_roll<LEVEL, 4, false, 0, true>), dim3(grid), dim3(CRH_BLOCK), 0, c->stream, dw, *P, Q, dev_fb, \
-						   c->dCounters, c->dStage, chunk, c->dWaveStats, c->sched, c->dQueues, c->dOvf, c->dErr); } while (0)
+						   c->dCounters, c->dStage.p, chunk, c->dWaveStats, c->sched, c->dQueues.p, c->dOvf.p, c->dErr); } while (0)
 	const bool halton = c->sampler == CRH_SAMPLER_HALTON;
 	(void)halton;
 	if (rollForm(c)) {
@@ -792,11 +778,11 @@ static hipError_t launchPathtrace(crh_ctx *c, uint32_t grid, const crh_render_pa
 	const bool wg = c->kernel == CRH_KERNEL_WG;
 #define CRH_LAUNCH(LEVEL, WPS, PROG, SAMP) do { snprintf(c->lastKernel, sizeof(c->lastKernel), "k_pathtrace<%d,%d,%s,%d>", LEVEL, WPS, PROG ? "true" : "false", SAMP); \
 		hipLaunchKernelGGL((k_pathtrace<LEVEL, WPS, PROG, SAMP>), dim3(grid), dim3(CRH_BLOCK), 0, c->stream, c->d, *P, Q, dev_fb, \
-						   c->dCounters, c->dStage, chunk, c->dWaveStats, c->sched, c->dQueues, c->dOvf); } while (0)
+						   c->dCounters, c->dStage.p, chunk, c->dWaveStats, c->sched, c->dQueues.p, c->dOvf.p); } while (0)
 #define CRH_LAUNCH2(LEVEL, WPS) do { if (c->hasPrograms) CRH_LAUNCH(LEVEL, WPS, true, 0); else CRH_LAUNCH(LEVEL, WPS, false, 0); } while (0)
 #define CRH_LAUNCH_WG(LEVEL, PROG, SAMP) do { snprintf(c->lastKernel, sizeof(c->lastKernel), "k_pathtrace_wg<%d,%s,%d>", LEVEL, PROG ? "true" : "false", SAMP); \
 		hipLaunchKernelGGL((k_pathtrace_wg<LEVEL, PROG, SAMP>), dim3(grid), dim3(CRH_BLOCK), 0, c->stream, c->d, *P, Q, dev_fb, \
-						   c->dCounters, c->dStage, chunk, c->schedWg, c->dQueues, c->dOvf, c->dErr); } while (0)
+						   c->dCounters, c->dStage.p, chunk, c->schedWg, c->dQueues.p, c->dOvf.p, c->dErr); } while (0)
 #ifdef CRH_DEV_ONLY_BENCH_VARIANT
 #ifdef CRH_DEV_ONLY_PROG
 	if (wg) CRH_LAUNCH_WG(1, true, 0); else CRH_LAUNCH(1, 4, true, 0);
@@ -829,6 +815,21 @@ static hipError_t launchPathtrace(crh_ctx *c, uint32_t grid, const crh_render_pa
 #endif
 }
 
+/* The three per-wave buffers of a dispatch of `grid` workgroups: a sample slab of slabItems samples per wave (per workgroup for the workgroup kernel: wg) and open
+ * job, the path table, the stack-overflow columns. preloadKernel sizes them for a full grid at the default unit size, crh_render_tiles for what it launches. */
+static int growWaveBuffers(crh_ctx *c, size_t grid, size_t slabItems, bool wg) {
+	const size_t waves = grid * (CRH_BLOCK / 64);
+	static_assert(CRH_WG_PATHS * CRH_PATH_F4 * 4u == (CRH_BLOCK / 64) * CRH_WAVE_QUEUE_FLOATS, "both kernels use the same path-table footprint per workgroup");
+	int rc = c->dStage.grow(c->stream, (wg ? grid : waves) * (rollForm(c) ? CRH_ROLL_SLOTS : 1u) * slabItems * 3);      /* one sample slab per open job */
+	if (rc == CRH_OK) rc = c->dQueues.grow(c->stream, waves * CRH_WAVE_QUEUE_FLOATS);      /* = grid x CRH_WG_PATHS records for the workgroup kernel */
+	if (rc == CRH_OK && ((uintptr_t)c->dQueues.p & 63u) != 0u) {
+		c->dQueues.release();
+		return fail(CRH_ERR_HIP, "path table: the allocation is not 64-byte aligned (PathTab::loadRec4 / storeRec4 move aligned 64-B lines)");
+	}
+	if (rc == CRH_OK) rc = c->dOvf.grow(c->stream, waves * CRH_OVF_WORDS_PER_WAVE);
+	return rc;
+}
+
 /* Load the code object of the selected instantiation now (HIP loads kernels lazily, ~40 ms on first launch) with a launch that finds
  * an empty work queue: crh_scene_upload calls it, so a renderer's first frame is not the one that pays for it. */
 static int variantKey(const crh_ctx *c) { return (c->hasPrograms ? 1 : 0) | (c->sampler << 1) | (c->counterLevel << 2) | (c->wavesPerSimd << 4) | (c->kernel << 8) | (wideWalk(c) ? 1 << 12 : 0); }
@@ -840,38 +841,17 @@ static int preloadKernel(crh_ctx *c, bool again = false) {
 	Q.counter = c->dWork;                 /* any valid counter: total = 0, every wave leaves at once */
 	Q.bw = Q.bh = Q.sbw = Q.sbh = Q.tbw = Q.tbh = Q.mbw = Q.mbh = Q.segs = 1;
 	/* the per-wave path tables, stack-overflow columns and sample slabs of a full-size dispatch at the default unit size: allocated here rather than by the first frame */
-	const size_t waves = (size_t)c->cuCount * c->blocksPerCU * (CRH_BLOCK / 64);
-	if (waves * CRH_OVF_WORDS_PER_WAVE > c->ovfWords) {
-		if (c->dOvf) HIP_TRY(hipFree(c->dOvf));
-		c->dOvf = nullptr; c->ovfWords = 0;
-		HIP_TRY(hipMalloc((void **)&c->dOvf, waves * CRH_OVF_WORDS_PER_WAVE * sizeof(uint32_t)));
-		c->ovfWords = waves * CRH_OVF_WORDS_PER_WAVE;
-	}
-	if (waves * CRH_WAVE_QUEUE_FLOATS > c->queueFloats) {
-		if (c->dQueues) HIP_TRY(hipFree(c->dQueues));
-		c->dQueues = nullptr; c->queueFloats = 0;
-		HIP_TRY(hipMalloc((void **)&c->dQueues, waves * CRH_WAVE_QUEUE_FLOATS * sizeof(float)));
-		if (((uintptr_t)c->dQueues & 63u) != 0u) return fail(CRH_ERR_HIP, "path table: the allocation is not 64-byte aligned (PathTab::loadRec4 / storeRec4 move aligned 64-B lines)");
-		c->queueFloats = waves * CRH_WAVE_QUEUE_FLOATS;
-	}
-	const size_t slabs = rollForm(c) ? CRH_ROLL_SLOTS : 1u;        /* one sample slab per open job */
-	if (waves * slabs * (size_t)c->unitItems * 3 > c->stageFloats) {
-		if (c->dStage) HIP_TRY(hipFree(c->dStage));
-		c->dStage = nullptr; c->stageFloats = 0;
-		HIP_TRY(hipMalloc((void **)&c->dStage, waves * slabs * (size_t)c->unitItems * 3 * sizeof(float)));
-		c->stageFloats = waves * slabs * (size_t)c->unitItems * 3;
-	}
+	int rc = growWaveBuffers(c, (size_t)c->cuCount * c->blocksPerCU, (size_t)c->unitItems, false);
+	if (rc) return rc;
 	const int key = variantKey(c);
 	const bool known = std::find(c->preloaded.begin(), c->preloaded.end(), key) != c->preloaded.end();
 	if (known && !again) return CRH_OK;      /* crh_context_prepare has been here */
 	{   /* the copy paths a dispatch uses — pinned host -> device (its tile list) and back — are set up by the runtime on first use (measured: the first
 		 * dispatch's kernel started 7-15 ms after its launch, behind its own 64-byte tile list): first use is here */
-		crh_ctx::TileSlot &ts = c->tileSlots[0];
+		StagedBuf &ts = c->tileSlots[0];
 		if (!ts.dev) {
-			HIP_TRY(hipMalloc(&ts.dev, 4096));
-			HIP_TRY(hipHostMalloc(&ts.host, 4096, hipHostMallocDefault));
-			ts.cap = 4096;
-			memset(ts.host, 0, 4096);
+			if ((rc = ts.reserve(64))) return rc;
+			memset(ts.host, 0, ts.cap);
 		}
 		HIP_TRY(hipMemcpyAsync(ts.dev, ts.host, 64, hipMemcpyHostToDevice, c->stream));
 		HIP_TRY(hipMemcpyAsync(ts.host, ts.dev, 64, hipMemcpyDeviceToHost, c->stream));
@@ -881,13 +861,12 @@ static int preloadKernel(crh_ctx *c, bool again = false) {
 	 * and allocates it when a dispatch first needs that much — for a one-workgroup preload that was the first frame: its kernel started 8-24 ms after its
 	 * launch (round 3, CRH_TRACE_SYNC; an empty launch and every synchronize the API offers directly in front of it changed nothing) */
 	/* ... between the two timing events a dispatch records around its kernel (their first use on a stream is a set-up step of the runtime as well) */
-	crh_ctx::Timed ev;
-	if (!c->eventPool.empty()) { ev = c->eventPool.back(); c->eventPool.pop_back(); }
-	else { HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b)); }
+	TimedPair ev;
+	if ((rc = c->eventPool.take(ev))) return rc;
 	HIP_TRY(hipEventRecord(ev.a, c->stream));
 	const hipError_t e = launchPathtrace(c, (uint32_t)(c->cuCount * c->blocksPerCU), &P, Q, nullptr, 1);
 	HIP_TRY(hipEventRecord(ev.b, c->stream));
-	c->eventPool.push_back(ev);
+	c->eventPool.give(ev);
 	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string("kernel preload: ") + hipGetErrorString(e));
 	HIP_TRY(hipMemsetAsync(c->dWork, 0, sizeof(uint32_t), c->stream));          /* its waves have drawn from the counter: zero again for the dispatch that takes slot 0 */
 	HIP_TRY(hipStreamSynchronize(c->stream));
@@ -965,49 +944,31 @@ int crh_context_destroy(crh_ctx *c) {
 	(void)hipSetDevice(c->device);
 	if (c->stream) (void)hipStreamSynchronize(c->stream);
 	freeScene(c);
-	for (auto &ts : c->tileSlots) {
-		if (ts.dev) (void)hipFree(ts.dev);
-		if (ts.host) (void)hipHostFree(ts.host);
-		if (ts.done) (void)hipEventDestroy(ts.done);
-	}
-	for (auto &t : c->pendingTimes) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
-	for (auto &t : c->eventPool) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
-	if (c->dCounters) (void)hipFree(c->dCounters);
-	if (c->dWork) (void)hipFree(c->dWork);
-	if (c->dStage) (void)hipFree(c->dStage);
-	if (c->dDefer) (void)hipFree(c->dDefer);
-	if (c->dQueues) (void)hipFree(c->dQueues);
-	if (c->dOvf) (void)hipFree(c->dOvf);
-	if (c->dAovCounter) (void)hipFree(c->dAovCounter);
-	if (c->dAovTiles) (void)hipFree(c->dAovTiles);
-	if (c->hAovTiles) (void)hipHostFree(c->hAovTiles);
-	if (c->aovDone) (void)hipEventDestroy(c->aovDone);
-	if (c->aovEvA) (void)hipEventDestroy(c->aovEvA);
-	if (c->aovEvB) (void)hipEventDestroy(c->aovEvB);
-	if (c->dDenoise) (void)hipFree(c->dDenoise);
-	for (hipEvent_t e : c->denoiseEv) if (e) (void)hipEventDestroy(e);
-	if (c->dAdaptive) (void)hipFree(c->dAdaptive);
-	if (c->hAdaptive) (void)hipHostFree(c->hAdaptive);
-	for (hipEvent_t e : c->adaptiveEv) if (e) (void)hipEventDestroy(e);
+	/* what the buffer types of ctx_buffers.h own goes with their release(); the rest — allocated once, at a fixed size — by hand */
+	auto drop = [](void *p) { if (p) (void)hipFree(p); };
+	auto dropEvent = [](hipEvent_t e) { if (e) (void)hipEventDestroy(e); };
+	for (StagedBuf &ts : c->tileSlots) ts.release();
+	for (const TimedPair &t : c->pendingTimes) c->eventPool.give(t);
+	c->pendingTimes.clear();
+	c->eventPool.release();
+	drop(c->dCounters); drop(c->dWork);
+	c->dStage.release(); c->dDefer.release(); c->dQueues.release(); c->dOvf.release();
+	drop(c->dAovCounter); c->aovTiles.release(); dropEvent(c->aovEvA); dropEvent(c->aovEvB);
+	c->dDenoise.release();
+	for (hipEvent_t e : c->denoiseEv) dropEvent(e);
+	c->adaptive.release();
+	for (hipEvent_t e : c->adaptiveEv) dropEvent(e);
 	if (c->hErr) (void)hipHostFree(c->hErr);
 	if (c->pinned) (void)hipHostFree(c->pinned);
 	releaseJanitor(c, true);
-	if (c->dSrgb) (void)hipFree(c->dSrgb);
-	if (c->dGather) (void)hipFree(c->dGather);
-	if (c->dWaveStats) (void)hipFree(c->dWaveStats);
-	if (c->dDump) (void)hipFree(c->dDump);
-	for (int i = 0; i < 2; ++i) { if (c->dProbeHits[i]) (void)hipFree(c->dProbeHits[i]); if (c->dProbeInst[i]) (void)hipFree(c->dProbeInst[i]); }
-	if (c->dProbeOvf) (void)hipFree(c->dProbeOvf);
-	if (c->dProbeUnits) (void)hipFree(c->dProbeUnits);
-	if (c->dStreamPlanes) (void)hipFree(c->dStreamPlanes);
-	if (c->dStreamHit) (void)hipFree(c->dStreamHit);
-	if (c->dStreamHitInst) (void)hipFree(c->dStreamHitInst);
-	if (c->dStreamCount) (void)hipFree(c->dStreamCount);
-	if (c->dStreamSlab) (void)hipFree(c->dStreamSlab);
-	if (c->dStreamCtl) (void)hipFree(c->dStreamCtl);
-	if (c->dStreamOvf) (void)hipFree(c->dStreamOvf);
+	c->dSrgb.release(); c->dGather.release();
+	drop(c->dWaveStats); drop(c->dDump);
+	for (int i = 0; i < 2; ++i) { drop(c->dProbeHits[i]); drop(c->dProbeInst[i]); }
+	drop(c->dProbeOvf); c->dProbeUnits.release();
+	c->dStreamPlanes.release(); c->dStreamHit.release(); c->dStreamHitInst.release(); c->dStreamCount.release(); c->dStreamSlab.release();
+	drop(c->dStreamCtl); c->dStreamOvf.release();
 	if (c->hStreamDone) (void)hipHostFree(c->hStreamDone);
-	for (int i = 0; i < 2; ++i) if (c->streamEv[i]) (void)hipEventDestroy(c->streamEv[i]);
+	for (hipEvent_t e : c->streamEv) dropEvent(e);
 	if (c->ownStream && c->stream) (void)hipStreamDestroy(c->stream);
 	delete c;
 	return CRH_OK;
@@ -1371,16 +1332,11 @@ int crh_framebuffer_to_srgb8(crh_ctx *c, const float *dev_fb, int width, int hei
 	int rc = setDevice(c);
 	if (rc) return rc;
 	const size_t n = (size_t)width * height * 3;
-	if (n > c->srgbBytes) {               /* kept by the context: an interactive host converts after every pass chunk */
-		if (c->dSrgb) HIP_TRY(hipFree(c->dSrgb));
-		c->dSrgb = nullptr; c->srgbBytes = 0;
-		HIP_TRY(hipMalloc((void **)&c->dSrgb, n));
-		c->srgbBytes = n;
-	}
+	if ((rc = c->dSrgb.grow(c->stream, n))) return rc;
 	const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
-	hipLaunchKernelGGL(k_to_srgb8, dim3(grid), dim3(256), 0, c->stream, dev_fb, n, c->dSrgb);
+	hipLaunchKernelGGL(k_to_srgb8, dim3(grid), dim3(256), 0, c->stream, dev_fb, n, c->dSrgb.p);
 	hipError_t e = hipGetLastError();
-	if (e == hipSuccess) e = hipMemcpyAsync(host_rgb8, c->dSrgb, n, hipMemcpyDeviceToHost, c->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(host_rgb8, c->dSrgb.p, n, hipMemcpyDeviceToHost, c->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
 	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string("crh_framebuffer_to_srgb8: ") + hipGetErrorString(e));
 	return CRH_OK;
@@ -1395,14 +1351,9 @@ int crh_framebuffer_strips_to_srgb8(crh_ctx *c, const float *dev_fb, int width, 
 	int rc = setDevice(c);
 	if (rc) return rc;
 	const size_t n = (size_t)width * height * 3, rowBytes = (size_t)width * 3;
-	if (n > c->srgbBytes) {
-		if (c->dSrgb) HIP_TRY(hipFree(c->dSrgb));
-		c->dSrgb = nullptr; c->srgbBytes = 0;
-		HIP_TRY(hipMalloc((void **)&c->dSrgb, n));
-		c->srgbBytes = n;
-	}
+	if ((rc = c->dSrgb.grow(c->stream, n))) return rc;
 	const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
-	hipLaunchKernelGGL(k_to_srgb8, dim3(grid), dim3(256), 0, c->stream, dev_fb, n, c->dSrgb);
+	hipLaunchKernelGGL(k_to_srgb8, dim3(grid), dim3(256), 0, c->stream, dev_fb, n, c->dSrgb.p);
 	hipError_t e = hipGetLastError();
 	/* strip k of this GPU covers image rows [(k n + g) R, ... + R) = framebuffer rows [H - y1, H - y0) (texture.c:24-28: row H - 1 - y): the full strips are
 	 * R-row blocks a constant n R rows apart — one 2-D copy, from the block nearest the top of the buffer (the last full strip) downwards */
@@ -1411,9 +1362,9 @@ int crh_framebuffer_strips_to_srgb8(crh_ctx *c, const float *dev_fb, int width, 
 	for (int y0 = g * R; y0 < height; y0 += period) { if (y0 + R <= height) ++fullStrips; else raggedY0 = y0; }
 	if (e == hipSuccess && fullStrips > 0) {
 		const size_t base = (size_t)(height - (g * R + (fullStrips - 1) * period) - R) * rowBytes;
-		e = hipMemcpy2DAsync(host_rgb8 + base, (size_t)period * rowBytes, c->dSrgb + base, (size_t)period * rowBytes, (size_t)R * rowBytes, (size_t)fullStrips, hipMemcpyDeviceToHost, c->stream);
+		e = hipMemcpy2DAsync(host_rgb8 + base, (size_t)period * rowBytes, c->dSrgb.p + base, (size_t)period * rowBytes, (size_t)R * rowBytes, (size_t)fullStrips, hipMemcpyDeviceToHost, c->stream);
 	}
-	if (e == hipSuccess && raggedY0 >= 0) e = hipMemcpyAsync(host_rgb8, c->dSrgb, (size_t)(height - raggedY0) * rowBytes, hipMemcpyDeviceToHost, c->stream);      /* the frame's last, shorter strip: the buffer's first rows */
+	if (e == hipSuccess && raggedY0 >= 0) e = hipMemcpyAsync(host_rgb8, c->dSrgb.p, (size_t)(height - raggedY0) * rowBytes, hipMemcpyDeviceToHost, c->stream);      /* the frame's last, shorter strip: the buffer's first rows */
 	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
 	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string("crh_framebuffer_strips_to_srgb8: ") + hipGetErrorString(e));
 	return CRH_OK;
@@ -1606,15 +1557,6 @@ int crh_debug_plan_units(const crh_render_params *P, const crh_tile *tiles, uint
 static bool streamServes(const crh_ctx *c, const crh_render_params *P) {
 	return c->kernel == CRH_KERNEL_STREAM && !c->hasVolumes && c->sampler == CRH_SAMPLER_RANDOM && !(c->walk == CRH_WALK_WIDE4 && c->haveWide) && P->bounces > 0;
 }
-static int growDevice(crh_ctx *c, void **p, size_t *have, size_t need, size_t elemBytes) {
-	if (need <= *have) return CRH_OK;
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	if (*p) HIP_TRY(hipFree(*p));
-	*p = nullptr; *have = 0;
-	HIP_TRY(hipMalloc(p, need * elemBytes));
-	*have = need;
-	return CRH_OK;
-}
 /* walk-kernel instantiations: waves per SIMD the register allocator leaves room for / traversal-stack entries in LDS. One-instance scenes (the triangle soups) walk ONE deep
  * BVH and want the deeper LDS stack at five workgroups per CU; everything else the shallower one at six (profiles/r06c_probe_walk.log) */
 #define CRH_STREAM_WALK_A_WPS 6
@@ -1650,28 +1592,16 @@ static int renderStream(crh_ctx *c, const crh_render_params *P, const crh_tile *
 	const size_t slabFloats = (size_t)std::min<uint32_t>(CRH_SF_RING, chunkCount) * chunkItems * 3;
 
 	int rc;
-	{
-		size_t have = c->streamSlots;
-		if (slots > have) {
-			HIP_TRY(hipStreamSynchronize(c->stream));
-			if (c->dStreamPlanes) HIP_TRY(hipFree(c->dStreamPlanes));
-			if (c->dStreamHit) HIP_TRY(hipFree(c->dStreamHit));
-			if (c->dStreamHitInst) HIP_TRY(hipFree(c->dStreamHitInst));
-			if (c->dStreamCount) HIP_TRY(hipFree(c->dStreamCount));
-			c->dStreamPlanes = nullptr; c->dStreamHit = nullptr; c->dStreamHitInst = nullptr; c->dStreamCount = nullptr; c->streamSlots = 0;
-			HIP_TRY(hipMalloc((void **)&c->dStreamPlanes, slots * 8 * sizeof(f4)));
-			HIP_TRY(hipMalloc((void **)&c->dStreamHit, slots * sizeof(f4)));
-			HIP_TRY(hipMalloc((void **)&c->dStreamHitInst, slots * sizeof(int32_t)));
-			HIP_TRY(hipMalloc((void **)&c->dStreamCount, (slots / CRH_SF_COHORT) * 2 * sizeof(uint32_t)));
-			c->streamSlots = slots;
-		}
+	if (slots > c->streamSlots) {          /* the pools grow together: streamSlots is what all four hold */
+		c->streamSlots = 0;
+		if ((rc = c->dStreamPlanes.grow(c->stream, slots * 8)) || (rc = c->dStreamHit.grow(c->stream, slots)) || (rc = c->dStreamHitInst.grow(c->stream, slots)) ||
+			(rc = c->dStreamCount.grow(c->stream, (slots / CRH_SF_COHORT) * 2))) return rc;
+		c->streamSlots = slots;
 	}
-	rc = growDevice(c, (void **)&c->dStreamSlab, &c->streamSlabFloats, slabFloats, sizeof(float));
-	if (rc) return rc;
+	if ((rc = c->dStreamSlab.grow(c->stream, slabFloats))) return rc;
 	const bool deepStack = c->d.instance_count == 1u && c->d.tlas_node_count == 1u;
 	const uint32_t walkGrid = (uint32_t)c->cuCount * (uint32_t)(deepStack ? CRH_STREAM_WALK_B_WPS : CRH_STREAM_WALK_A_WPS);
-	rc = growDevice(c, (void **)&c->dStreamOvf, &c->streamOvfWords, (size_t)walkGrid * (CRH_BLOCK / 64) * CRH_OVF_WORDS_PER_WAVE, sizeof(uint32_t));
-	if (rc) return rc;
+	if ((rc = c->dStreamOvf.grow(c->stream, (size_t)walkGrid * (CRH_BLOCK / 64) * CRH_OVF_WORDS_PER_WAVE))) return rc;
 	if (!c->dStreamCtl) HIP_TRY(hipMalloc((void **)&c->dStreamCtl, sizeof(StreamCtl)));
 	if (!c->hStreamDone) {
 		HIP_TRY(hipHostMalloc((void **)&c->hStreamDone, sizeof(unsigned int), hipHostMallocDefault));
@@ -1682,19 +1612,9 @@ static int renderStream(crh_ctx *c, const crh_render_params *P, const crh_tile *
 
 	/* the tile list: pinned host slot, copied into the device slot by the dispatch's first kernel (no copy engine in front of a kernel: see crh_render_tiles) */
 	const uint32_t slot = c->workSlot % CRH_WORK_SLOTS;
-	crh_ctx::TileSlot &ts = c->tileSlots[slot];
+	StagedBuf &ts = c->tileSlots[slot];
 	const size_t tileBytes = ntiles * sizeof(crh_tile), startBytes = (ntiles + 1) * sizeof(uint32_t);
-	if (ts.inFlight) { HIP_TRY(hipEventSynchronize(ts.done)); ts.inFlight = false; }
-	if (tileBytes + startBytes > ts.cap) {
-		if (ts.dev) HIP_TRY(hipFree(ts.dev));
-		if (ts.host) HIP_TRY(hipHostFree(ts.host));
-		ts.dev = ts.host = nullptr; ts.cap = 0;
-		const size_t cap = std::max<size_t>(4096, 2 * (tileBytes + startBytes));
-		HIP_TRY(hipMalloc(&ts.dev, cap));
-		HIP_TRY(hipHostMalloc(&ts.host, cap, hipHostMallocDefault));
-		ts.cap = cap;
-	}
-	if (!ts.done) HIP_TRY(hipEventCreateWithFlags(&ts.done, hipEventDisableTiming));
+	if ((rc = ts.reserve(tileBytes + startBytes))) return rc;
 	memcpy(ts.host, work.data(), tileBytes);
 	memcpy((char *)ts.host + tileBytes, start.data(), startBytes);
 	void *hostView = nullptr;
@@ -1707,19 +1627,18 @@ static int renderStream(crh_ctx *c, const crh_render_params *P, const crh_tile *
 	Pl.ntiles = ntiles; Pl.npix = npix; Pl.cohorts = cohorts;
 	Pl.passesPerChunk = C; Pl.lastPasses = lastPasses; Pl.chunkCount = chunkCount; Pl.chunkItems = chunkItems;
 	Pl.genTotal = totalItems;
-	Pl.slab = c->dStreamSlab; Pl.hit = c->dStreamHit; Pl.hitInst = c->dStreamHitInst;
+	Pl.slab = c->dStreamSlab.p; Pl.hit = c->dStreamHit.p; Pl.hitInst = c->dStreamHitInst.p;
 	Pl.done = c->dStreamDone; Pl.seq = ++c->streamSeq;
 	if (Pl.seq == 0u) Pl.seq = ++c->streamSeq;
 	StreamPool pool[2];
 	for (int b = 0; b < 2; ++b) {
-		f4 *base = c->dStreamPlanes + (size_t)b * 4 * c->streamSlots;
+		f4 *base = c->dStreamPlanes.p + (size_t)b * 4 * c->streamSlots;
 		pool[b].p0 = base; pool[b].p1 = base + c->streamSlots; pool[b].p2 = base + 2 * c->streamSlots; pool[b].p3 = base + 3 * c->streamSlots;
-		pool[b].count = c->dStreamCount + (size_t)b * (c->streamSlots / CRH_SF_COHORT);
+		pool[b].count = c->dStreamCount.p + (size_t)b * (c->streamSlots / CRH_SF_COHORT);
 	}
 
-	crh_ctx::Timed ev;
-	if (!c->eventPool.empty()) { ev = c->eventPool.back(); c->eventPool.pop_back(); }
-	else { HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b)); }
+	TimedPair ev;
+	if ((rc = c->eventPool.take(ev))) return rc;
 	HIP_TRY(hipEventRecord(ev.a, c->stream));
 	hipLaunchKernelGGL(k_stream_init, dim3(std::min<uint32_t>(64u, (cohorts + 255u) / 256u)), dim3(256), 0, c->stream, Pl, pool[0].count, pool[1].count, c->dStreamCtl,
 	                   (const uint32_t *)hostView, (uint32_t *)ts.dev, (uint32_t)((tileBytes + startBytes) / 4));
@@ -1731,8 +1650,8 @@ static int renderStream(crh_ctx *c, const crh_render_params *P, const crh_tile *
 	c->lastGrid = walkGrid;
 	auto iteration = [&](uint64_t it) {
 		const StreamPool &in = pool[it & 1u], &out = pool[(it + 1u) & 1u];
-#define CRH_STREAM_WALK(W, N, L) hipLaunchKernelGGL((k_stream_walk<W, N, true, L>), dim3(walkGrid), dim3(CRH_BLOCK), 0, c->stream, c->d, in, c->dStreamHit, c->dStreamHitInst, cohorts, \
-		                                             c->dStreamCtl, c->sched, c->dStreamOvf, c->dCounters)
+#define CRH_STREAM_WALK(W, N, L) hipLaunchKernelGGL((k_stream_walk<W, N, true, L>), dim3(walkGrid), dim3(CRH_BLOCK), 0, c->stream, c->d, in, c->dStreamHit.p, c->dStreamHitInst.p, cohorts, \
+		                                             c->dStreamCtl, c->sched, c->dStreamOvf.p, c->dCounters)
 #define CRH_STREAM_SHADE(L, PROG) hipLaunchKernelGGL((k_stream_shade<L, PROG, 0>), dim3(shadeGrid), dim3(CRH_BLOCK), 0, c->stream, c->d, *P, Pl, in, out, c->dStreamCtl, c->dCounters)
 #ifdef CRH_DEV_ONLY_BENCH_VARIANT
 		if (deepStack) CRH_STREAM_WALK(CRH_STREAM_WALK_B_WPS, CRH_STREAM_WALK_B_NLDS, 1); else CRH_STREAM_WALK(CRH_STREAM_WALK_A_WPS, CRH_STREAM_WALK_A_NLDS, 1);
@@ -1768,14 +1687,13 @@ static int renderStream(crh_ctx *c, const crh_render_params *P, const crh_tile *
 		if (!over && it > iterLimit) {
 			HIP_TRY(hipStreamSynchronize(c->stream));
 			if (*(volatile unsigned int *)c->hStreamDone == Pl.seq) break;
-			c->eventPool.push_back(ev);
+			c->eventPool.give(ev);
 			return fail(CRH_ERR_HIP, "k_stream: the dispatch did not finish within its iteration limit: incomplete frame");
 		}
 	}
 	c->streamIterations = it;
 	HIP_TRY(hipEventRecord(ev.b, c->stream));
-	HIP_TRY(hipEventRecord(ts.done, c->stream));
-	ts.inFlight = true;
+	if ((rc = ts.markInFlight(c->stream))) return rc;
 	c->pendingTimes.push_back(ev);
 	c->launches++;
 	if (c->janitorWaiting.load(std::memory_order_relaxed)) releaseJanitor(c, false);
@@ -1810,68 +1728,15 @@ int crh_render_tiles(crh_ctx *c, const crh_render_params *P, const crh_tile *til
 	const uint32_t firstSmall = plan.firstSmall, firstTiny = plan.firstTiny, grid = plan.grid;
 	c->lastGrid = grid;
 	if (c->dWaveStats && grid * (CRH_BLOCK / 64) > CRH_WAVE_STATS_MAX) return fail(CRH_ERR_INVALID, "wave stats: grid too large");
-	{
-		size_t need = (size_t)grid * (wg ? 1 : CRH_BLOCK / 64) * (size_t)(bw * bh) * (size_t)chunk * 3;
-		if (rollForm(c)) need *= CRH_ROLL_SLOTS;      /* one sample slab per open job */
-		if (need > c->stageFloats) {
-			HIP_TRY(hipStreamSynchronize(c->stream));
-			if (c->dStage) HIP_TRY(hipFree(c->dStage));
-			c->dStage = nullptr; c->stageFloats = 0;
-			HIP_TRY(hipMalloc((void **)&c->dStage, need * sizeof(float)));
-			c->stageFloats = need;
-		}
-	}
-
+	if ((rc = growWaveBuffers(c, grid, (size_t)(bw * bh) * (size_t)chunk, wg))) return rc;
 	const uint32_t deferUnits = plan.segs > 1 ? (uint32_t)total - start[plan.firstMicro] : 0u;       /* split pixels x segments */
-	if (deferUnits) {
-		const size_t need = (size_t)deferUnits * (size_t)plan.segPasses * 3;
-		if (need > c->deferFloats) {
-			HIP_TRY(hipStreamSynchronize(c->stream));
-			if (c->dDefer) HIP_TRY(hipFree(c->dDefer));
-			c->dDefer = nullptr; c->deferFloats = 0;
-			HIP_TRY(hipMalloc((void **)&c->dDefer, need * sizeof(float)));
-			c->deferFloats = need;
-		}
-	}
-	{
-		const size_t need = (size_t)grid * (CRH_BLOCK / 64) * CRH_WAVE_QUEUE_FLOATS;      /* = grid x CRH_WG_PATHS records for the workgroup kernel */
-		static_assert(CRH_WG_PATHS * CRH_PATH_F4 * 4u == (CRH_BLOCK / 64) * CRH_WAVE_QUEUE_FLOATS, "both kernels use the same path-table footprint per workgroup");
-		if (need > c->queueFloats) {
-			HIP_TRY(hipStreamSynchronize(c->stream));
-			if (c->dQueues) HIP_TRY(hipFree(c->dQueues));
-			c->dQueues = nullptr; c->queueFloats = 0;
-			HIP_TRY(hipMalloc((void **)&c->dQueues, need * sizeof(float)));
-			if (((uintptr_t)c->dQueues & 63u) != 0u) return fail(CRH_ERR_HIP, "path table: the allocation is not 64-byte aligned (PathTab::loadRec4 / storeRec4 move aligned 64-B lines)");
-			c->queueFloats = need;
-		}
-	}
-
-	{
-		const size_t need = (size_t)grid * (CRH_BLOCK / 64) * CRH_OVF_WORDS_PER_WAVE;
-		if (need > c->ovfWords) {
-			HIP_TRY(hipStreamSynchronize(c->stream));
-			if (c->dOvf) HIP_TRY(hipFree(c->dOvf));
-			c->dOvf = nullptr; c->ovfWords = 0;
-			HIP_TRY(hipMalloc((void **)&c->dOvf, need * sizeof(uint32_t)));
-			c->ovfWords = need;
-		}
-	}
+	if ((rc = c->dDefer.grow(c->stream, (size_t)deferUnits * (size_t)plan.segPasses * 3))) return rc;
 
 	/* per-launch tile list: pinned host slot -> device slot, asynchronously on the launch stream */
 	const uint32_t slot = c->workSlot % CRH_WORK_SLOTS;          /* consumed below, once nothing can fail before the launch */
-	crh_ctx::TileSlot &ts = c->tileSlots[slot];
+	StagedBuf &ts = c->tileSlots[slot];
 	const size_t tileBytes = work_count * sizeof(crh_tile), startBytes = (work_count + 1) * sizeof(uint32_t);
-	if (ts.inFlight) { HIP_TRY(hipEventSynchronize(ts.done)); ts.inFlight = false; }
-	if (tileBytes + startBytes > ts.cap) {
-		if (ts.dev) HIP_TRY(hipFree(ts.dev));
-		if (ts.host) HIP_TRY(hipHostFree(ts.host));
-		ts.dev = ts.host = nullptr; ts.cap = 0;
-		const size_t cap = std::max<size_t>(4096, 2 * (tileBytes + startBytes));
-		HIP_TRY(hipMalloc(&ts.dev, cap));
-		HIP_TRY(hipHostMalloc(&ts.host, cap, hipHostMallocDefault));
-		ts.cap = cap;
-	}
-	if (!ts.done) HIP_TRY(hipEventCreateWithFlags(&ts.done, hipEventDisableTiming));
+	if ((rc = ts.reserve(tileBytes + startBytes))) return rc;
 	memcpy(ts.host, work.data(), tileBytes);
 	memcpy((char *)ts.host + tileBytes, start.data(), startBytes);
 	/* Nothing but the kernel itself is put on the stream in front of the kernel. Measured in round 3 (CRH_TRACE_SYNC, the drop-in's first dispatch): behind a
@@ -1895,20 +1760,17 @@ int crh_render_tiles(crh_ctx *c, const crh_render_params *P, const crh_tile *til
 	Q.firstSmall = firstSmall; Q.sbw = sbw; Q.sbh = sbh;
 	Q.firstTiny = firstTiny; Q.tbw = tbw; Q.tbh = tbh;
 	Q.firstMicro = plan.firstMicro; Q.mbw = plan.mbw; Q.mbh = plan.mbh; Q.segs = plan.segs; Q.segPasses = plan.segPasses;
-	Q.unit0 = start[plan.firstMicro]; Q.defer = deferUnits ? c->dDefer : nullptr;
+	Q.unit0 = start[plan.firstMicro]; Q.defer = deferUnits ? c->dDefer.p : nullptr;
 	c->workSlot++;
 
 	if (P->bounces <= 0) {           /* every sample is black: no walk, only the running mean moves; paths are still counted */
 		hipLaunchKernelGGL(k_fold_black, dim3(64, std::min<uint32_t>(work_count, 1024u)), dim3(256), 0, c->stream, *P, Q.tiles, work_count, dev_fb, c->dCounters);
 		hipError_t e0 = hipGetLastError();
 		if (e0 != hipSuccess) return fail(CRH_ERR_HIP, std::string("k_fold_black launch: ") + hipGetErrorString(e0));
-		HIP_TRY(hipEventRecord(ts.done, c->stream));
-		ts.inFlight = true;
-		return CRH_OK;                                                   /* (k_fold_black takes no work units: the counter stays zero) */
+		return ts.markInFlight(c->stream);                               /* (k_fold_black takes no work units: the counter stays zero) */
 	}
-	crh_ctx::Timed ev;
-	if (!c->eventPool.empty()) { ev = c->eventPool.back(); c->eventPool.pop_back(); }
-	else { HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b)); }
+	TimedPair ev;
+	if ((rc = c->eventPool.take(ev))) return rc;
 	HIP_TRY(hipEventRecord(ev.a, c->stream));
 	hipError_t e = launchPathtrace(c, grid, P, Q, dev_fb, chunk);
 	if (e == hipSuccess && deferUnits) {              /* the split pixels' samples -> the frame, in pass order (part of the dispatch and of its time) */
@@ -1918,8 +1780,7 @@ int crh_render_tiles(crh_ctx *c, const crh_render_params *P, const crh_tile *til
 	}
 	HIP_TRY(hipEventRecord(ev.b, c->stream));
 	HIP_TRY(hipMemsetAsync(Q.counter, 0, sizeof(uint32_t), c->stream));          /* ready for the dispatch that takes this slot next */
-	HIP_TRY(hipEventRecord(ts.done, c->stream));
-	ts.inFlight = true;
+	if ((rc = ts.markInFlight(c->stream))) return rc;
 	c->pendingTimes.push_back(ev);
 	c->launches++;
 	if (c->janitorWaiting.load(std::memory_order_relaxed)) {          /* a dispatch of some length is on the device: the host memory of the last upload can go back now */
@@ -1936,6 +1797,19 @@ int crh_render_region(crh_ctx *c, const crh_render_params *P, float *dev_fb) {
 	if (!P) return fail(CRH_ERR_INVALID, "crh_render_region: params is NULL");
 	const crh_tile t{P->x0, P->y0, P->x1, P->y1};
 	return crh_render_tiles(c, P, &t, 1, dev_fb);
+}
+
+/* The rectangle rule of crh_render_aov and of the adaptive entry points (crh_render_tiles has planWork's): every rectangle inside the image; `strict` (adaptive):
+ * none empty, none of more than 2^30 pixels. */
+static int checkRects(const char *who, const crh_tile *tiles, uint32_t tile_count, int width, int height, bool strict) {
+	for (uint32_t i = 0; i < tile_count; ++i) {
+		const crh_tile &t = tiles[i];
+		if (t.x0 < 0 || t.y0 < 0 || t.x1 > width || t.y1 > height) return fail(CRH_ERR_INVALID, std::string(who) + ": rectangle " + std::to_string(i) + " lies outside the image");
+		if (!strict) continue;
+		if (t.x1 <= t.x0 || t.y1 <= t.y0) return fail(CRH_ERR_INVALID, std::string(who) + ": rectangle " + std::to_string(i) + " is empty");
+		if ((uint64_t)(t.x1 - t.x0) * (uint64_t)(t.y1 - t.y0) > (1ull << 30)) return fail(CRH_ERR_INVALID, std::string(who) + ": rectangle " + std::to_string(i) + " holds more than 2^30 pixels");
+	}
+	return CRH_OK;
 }
 
 /* ---- AOV buffers: albedo, normal, depth, coverage of the first hit (aov.h) ----------------------- */
@@ -1974,7 +1848,7 @@ int crh_aov_download(crh_ctx *c, const float *dev_aov, int width, int height, fl
 	if (rc) return rc;
 	HIP_TRY(hipMemcpyAsync(host_whc8, dev_aov, (size_t)width * height * CRH_AOV_CHANNELS * sizeof(float), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	c->aovInFlight = false;
+	c->aovTiles.inFlight = false;
 	return CRH_OK;
 }
 
@@ -1985,10 +1859,8 @@ int crh_render_aov(crh_ctx *c, const crh_render_params *P, const crh_tile *tiles
 		return fail(CRH_ERR_INVALID, "crh_render_aov: bad render parameters");
 	const crh_tile whole{P->x0, P->y0, P->x1, P->y1};
 	if (!tiles || !tile_count) { tiles = &whole; tile_count = 1; }
-	for (uint32_t i = 0; i < tile_count; ++i) {
-		const crh_tile &t = tiles[i];
-		if (t.x0 < 0 || t.y0 < 0 || t.x1 > P->image_width || t.y1 > P->image_height) return fail(CRH_ERR_INVALID, "crh_render_aov: rectangle " + std::to_string(i) + " lies outside the image");
-	}
+	int rc = checkRects("crh_render_aov", tiles, tile_count, P->image_width, P->image_height, false);
+	if (rc) return rc;
 	if (c->aovDepth > CRH_AOV_STACK)
 		return fail(CRH_ERR_UNSUPPORTED, "crh_render_aov: a material nests mix / add nodes " + std::to_string(c->aovDepth) + " deep (the albedo evaluator holds " + std::to_string(CRH_AOV_STACK) + " frames)");
 	if (P->pass_count == 0) return CRH_OK;
@@ -2017,55 +1889,37 @@ int crh_render_aov(crh_ctx *c, const crh_render_params *P, const crh_tile *tiles
 		total += (tileGroups + groups - 1u) / groups;
 	}
 	start.push_back((uint32_t)total);
-	int rc = setDevice(c);
-	if (rc) return rc;
+	if ((rc = setDevice(c))) return rc;
 	const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)c->cuCount * CRH_AOV_BLOCKS_PER_CU, (total + CRH_BLOCK / 64 - 1) / (CRH_BLOCK / 64));          /* (as many workgroups as a CU holds: aov.h) */
-	{
-		const size_t need = (size_t)grid * (CRH_BLOCK / 64) * CRH_OVF_WORDS_PER_WAVE;          /* the render kernels' overflow columns: the same stream, one dispatch at a time */
-		if (need > c->ovfWords) {
-			HIP_TRY(hipStreamSynchronize(c->stream));
-			if (c->dOvf) HIP_TRY(hipFree(c->dOvf));
-			c->dOvf = nullptr; c->ovfWords = 0;
-			HIP_TRY(hipMalloc((void **)&c->dOvf, need * sizeof(uint32_t)));
-			c->ovfWords = need;
-		}
-	}
+	/* the render kernels' overflow columns: the same stream, one dispatch at a time */
+	if ((rc = c->dOvf.grow(c->stream, (size_t)grid * (CRH_BLOCK / 64) * CRH_OVF_WORDS_PER_WAVE))) return rc;
 	if (!c->dAovCounter) {
 		HIP_TRY(hipMalloc((void **)&c->dAovCounter, sizeof(uint32_t)));
 		HIP_TRY(hipMemsetAsync(c->dAovCounter, 0, sizeof(uint32_t), c->stream));
-		HIP_TRY(hipEventCreateWithFlags(&c->aovDone, hipEventDisableTiming));
 		HIP_TRY(hipEventCreate(&c->aovEvA));
 		HIP_TRY(hipEventCreate(&c->aovEvB));
 	}
-	if (c->aovInFlight) { HIP_TRY(hipEventSynchronize(c->aovDone)); c->aovInFlight = false; }          /* the dispatch before this one has read the list */
+	StagedBuf &ts = c->aovTiles;
 	const size_t tileBytes = work.size() * sizeof(crh_tile), startBytes = start.size() * sizeof(uint32_t);
-	if (tileBytes + startBytes > c->aovTileCap) {
-		if (c->dAovTiles) HIP_TRY(hipFree(c->dAovTiles));
-		if (c->hAovTiles) HIP_TRY(hipHostFree(c->hAovTiles));
-		c->dAovTiles = c->hAovTiles = nullptr; c->aovTileCap = 0;
-		const size_t cap = std::max<size_t>(4096, 2 * (tileBytes + startBytes));
-		HIP_TRY(hipMalloc(&c->dAovTiles, cap));
-		HIP_TRY(hipHostMalloc(&c->hAovTiles, cap, hipHostMallocDefault));
-		c->aovTileCap = cap;
-	}
-	memcpy(c->hAovTiles, work.data(), tileBytes);
-	memcpy((char *)c->hAovTiles + tileBytes, start.data(), startBytes);
-	HIP_TRY(hipMemcpyAsync(c->dAovTiles, c->hAovTiles, tileBytes + startBytes, hipMemcpyHostToDevice, c->stream));
+	if ((rc = ts.reserve(tileBytes + startBytes))) return rc;          /* (waits until the dispatch before this one has read the list) */
+	memcpy(ts.host, work.data(), tileBytes);
+	memcpy((char *)ts.host + tileBytes, start.data(), startBytes);
+	HIP_TRY(hipMemcpyAsync(ts.dev, ts.host, tileBytes + startBytes, hipMemcpyHostToDevice, c->stream));
 	AovUnits U;
-	U.tiles = (const crh_tile *)c->dAovTiles;
-	U.start = (const uint32_t *)((const char *)c->dAovTiles + tileBytes);
+	U.tiles = (const crh_tile *)ts.dev;
+	U.start = (const uint32_t *)((const char *)ts.dev + tileBytes);
 	U.ntiles = (uint32_t)work.size(); U.total = (uint32_t)total; U.counter = c->dAovCounter; U.group = group; U.groups = groups;
 	const uint32_t rayFlags = (uint32_t)c->sched.rayFlags;
 	HIP_TRY(hipEventRecord(c->aovEvA, c->stream));
-#define CRH_LAUNCH_AOV(SAMP, RARE) hipLaunchKernelGGL((k_aov<SAMP, RARE>), dim3(grid), dim3(CRH_BLOCK), 0, c->stream, c->d, *P, U, dev_aov, rayFlags, c->dOvf)
+#define CRH_LAUNCH_AOV(SAMP, RARE) hipLaunchKernelGGL((k_aov<SAMP, RARE>), dim3(grid), dim3(CRH_BLOCK), 0, c->stream, c->d, *P, U, dev_aov, rayFlags, c->dOvf.p)
 	if (c->sampler == CRH_SAMPLER_HALTON) { if (c->hasPrograms) CRH_LAUNCH_AOV(1, true); else CRH_LAUNCH_AOV(1, false); }
 	else { if (c->hasPrograms) CRH_LAUNCH_AOV(0, true); else CRH_LAUNCH_AOV(0, false); }
 #undef CRH_LAUNCH_AOV
 	const hipError_t e = hipGetLastError();
 	HIP_TRY(hipEventRecord(c->aovEvB, c->stream));
 	HIP_TRY(hipMemsetAsync(c->dAovCounter, 0, sizeof(uint32_t), c->stream));          /* ready for the next dispatch */
-	HIP_TRY(hipEventRecord(c->aovDone, c->stream));
-	c->aovInFlight = true; c->aovTimed = true;
+	if ((rc = ts.markInFlight(c->stream))) return rc;
+	c->aovTimed = true;
 	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string("k_aov launch: ") + hipGetErrorString(e));
 	return CRH_OK;
 }
@@ -2097,36 +1951,37 @@ void crh_denoise_params_default(crh_denoise_params *p) {
  * the steps 2, 4 and 8 are compiled only with -DCRH_DENOISE_ALL_FORMS (the A/B variant library) or -DCRH_WITH_ALT_KERNELS (the emulation tier). */
 static char dnDefaultForm(int) { return 'd'; }
 
-/* the context's scratch, at least `bytes` large, and the events */
-static int dnScratch(crh_ctx *c, size_t bytes) {
-	if (bytes > c->denoiseBytes) {
-		HIP_TRY(hipStreamSynchronize(c->stream));
-		if (c->dDenoise) HIP_TRY(hipFree(c->dDenoise));
-		c->dDenoise = nullptr; c->denoiseBytes = 0;
-		HIP_TRY(hipMalloc((void **)&c->dDenoise, bytes));
-		c->denoiseBytes = bytes;
-	}
+/* What the two kinds share. The check: size, iteration count, every value of `positive` (the sigmas; `what` names them in the message) ... */
+static int dnCheck(const char *who, int width, int height, int iterations, std::initializer_list<float> positive, const char *what) {
+	if (width <= 0 || height <= 0 || iterations < 0 || iterations > CRH_DN_MAX_ITERATIONS)
+		return fail(CRH_ERR_INVALID, std::string(who) + ": bad size or iteration count (0.." + std::to_string(CRH_DN_MAX_ITERATIONS) + ")");
+	for (float s : positive)
+		if (!(s > 0.0f) || !std::isfinite(s)) return fail(CRH_ERR_INVALID, std::string(who) + ": " + what + " is not a positive finite number");
+	return CRH_OK;
+}
+/* ... and the prologue: the context's scratch — three planes of records G, C, C', then `tailBytes` — and the events, the first of them recorded */
+static int dnBegin(crh_ctx *c, size_t pixels, size_t tailBytes, f4 *&G, f4 *&Cin, f4 *&Cout) {
+	int rc = setDevice(c);
+	if (rc == CRH_OK) rc = c->dDenoise.grow(c->stream, pixels * 3 * sizeof(f4) + tailBytes);
+	if (rc) return rc;
 	if (!c->denoiseEv[0]) for (hipEvent_t &e : c->denoiseEv) HIP_TRY(hipEventCreate(&e));
+	G = (f4 *)c->dDenoise.p; Cin = G + pixels; Cout = G + 2 * pixels;
+	c->denoiseTimed = false;
+	HIP_TRY(hipEventRecord(c->denoiseEv[0], c->stream));
 	return CRH_OK;
 }
 
 int crh_denoise(crh_ctx *c, const crh_denoise_params *P, const float *dev_fb, const float *dev_aov, float *dev_out) {
 	if (!c || !P || !dev_fb || !dev_aov || !dev_out) return fail(CRH_ERR_INVALID, "crh_denoise: NULL argument");
-	if (P->width <= 0 || P->height <= 0 || P->iterations < 0 || P->iterations > CRH_DN_MAX_ITERATIONS)
-		return fail(CRH_ERR_INVALID, "crh_denoise: bad size or iteration count (0.." + std::to_string(CRH_DN_MAX_ITERATIONS) + ")");
-	for (float s : {P->sigma_normal, P->sigma_depth, P->sigma_color})
-		if (!(s > 0.0f) || !std::isfinite(s)) return fail(CRH_ERR_INVALID, "crh_denoise: a sigma is not a positive finite number");
-	if ((const float *)dev_out == dev_aov) return fail(CRH_ERR_INVALID, "crh_denoise: the output aliases the guide buffers");
-	int rc = setDevice(c);
+	int rc = dnCheck("crh_denoise", P->width, P->height, P->iterations, {P->sigma_normal, P->sigma_depth, P->sigma_color}, "a sigma");
 	if (rc) return rc;
+	if ((const float *)dev_out == dev_aov) return fail(CRH_ERR_INVALID, "crh_denoise: the output aliases the guide buffers");
 	const size_t pixels = (size_t)P->width * (size_t)P->height;
-	if ((rc = dnScratch(c, pixels * 3 * sizeof(f4)))) return rc;
-	f4 *const G = c->dDenoise, *Cin = c->dDenoise + pixels, *Cout = c->dDenoise + 2 * pixels;
 	const int N = P->iterations;
 	const char *forms = getenv("CRH_DENOISE_FORM");
 	const size_t nforms = forms ? strlen(forms) : 0;
-	c->denoiseTimed = false;
-	HIP_TRY(hipEventRecord(c->denoiseEv[0], c->stream));
+	f4 *G, *Cin, *Cout;
+	if ((rc = dnBegin(c, pixels, 0, G, Cin, Cout))) return rc;
 	hipLaunchKernelGGL(k_denoise_prepare, dim3((uint32_t)((pixels + CRH_BLOCK - 1) / CRH_BLOCK)), dim3(CRH_BLOCK), 0, c->stream, dev_fb, dev_aov, Cin, G, N == 0 ? dev_out : (float *)nullptr, (uint64_t)pixels);
 	hipError_t e = hipGetLastError();
 	HIP_TRY(hipEventRecord(c->denoiseEv[1], c->stream));
@@ -2170,25 +2025,19 @@ void crh_denoise_variance_params_default(crh_denoise_variance_params *p, int hal
 
 int crh_denoise_variance(crh_ctx *c, const crh_denoise_variance_params *P, const float *dev_fb, const float *dev_half, const float *dev_aov, float *dev_out) {
 	if (!c || !P || !dev_fb || !dev_half || !dev_aov || !dev_out) return fail(CRH_ERR_INVALID, "crh_denoise_variance: NULL argument");
-	if (P->width <= 0 || P->height <= 0 || P->iterations < 0 || P->iterations > CRH_DN_MAX_ITERATIONS)
-		return fail(CRH_ERR_INVALID, "crh_denoise_variance: bad size or iteration count (0.." + std::to_string(CRH_DN_MAX_ITERATIONS) + ")");
-	for (float s : {P->sigma_normal, P->sigma_depth, P->sigma_color, P->variance_scale})
-		if (!(s > 0.0f) || !std::isfinite(s)) return fail(CRH_ERR_INVALID, "crh_denoise_variance: a sigma or the variance scale is not a positive finite number");
-	if ((const float *)dev_out == dev_aov || (const float *)dev_out == dev_half) return fail(CRH_ERR_INVALID, "crh_denoise_variance: the output aliases the guide buffers or the half-sample frame");
-	int rc = setDevice(c);
+	int rc = dnCheck("crh_denoise_variance", P->width, P->height, P->iterations, {P->sigma_normal, P->sigma_depth, P->sigma_color, P->variance_scale}, "a sigma or the variance scale");
 	if (rc) return rc;
+	if ((const float *)dev_out == dev_aov || (const float *)dev_out == dev_half) return fail(CRH_ERR_INVALID, "crh_denoise_variance: the output aliases the guide buffers or the half-sample frame");
 	const size_t pixels = (size_t)P->width * (size_t)P->height;
-	if ((rc = dnScratch(c, pixels * (3 * sizeof(f4) + sizeof(float))))) return rc;
-	f4 *const G = c->dDenoise, *Cin = c->dDenoise + pixels, *Cout = c->dDenoise + 2 * pixels;
-	float *const Vraw = (float *)(c->dDenoise + 3 * pixels);
 	const int N = P->iterations;
 	DnParams D;
 	D.W = P->width; D.H = P->height; D.step = 1; D.stride = 1;
 	D.sigmaNormal = P->sigma_normal; D.sigmaDepth = P->sigma_depth; D.sigmaColor = P->sigma_color;
 	const dim3 grid(((uint32_t)P->width + CRH_DN_TW - 1) / CRH_DN_TW, ((uint32_t)P->height + CRH_DN_TH - 1) / CRH_DN_TH);
 	uint32_t launches = 0;
-	c->denoiseTimed = false;
-	HIP_TRY(hipEventRecord(c->denoiseEv[0], c->stream));
+	f4 *G, *Cin, *Cout;
+	if ((rc = dnBegin(c, pixels, pixels * sizeof(float), G, Cin, Cout))) return rc;          /* (the raw variance behind the three planes) */
+	float *const Vraw = (float *)(G + 3 * pixels);
 	hipLaunchKernelGGL(k_denoise_prepare_v, dim3((uint32_t)((pixels + CRH_BLOCK - 1) / CRH_BLOCK)), dim3(CRH_BLOCK), 0, c->stream, dev_fb, dev_half, dev_aov, Cin, G, Vraw,
 	                   N == 0 ? dev_out : (float *)nullptr, P->variance_scale, (uint64_t)pixels);
 	hipError_t e = hipGetLastError();
@@ -2245,52 +2094,37 @@ int crh_debug_denoise_launch_ms(crh_ctx *c, float *ms, uint32_t cap) {
 }
 
 /* ---- adaptive sampling at tile granularity (adaptive.h: k_adaptive_step) ------------------------------------------------------------------ */
-static int adCheckTiles(const char *who, const crh_tile *tiles, uint32_t tile_count, int width, int height) {
-	for (uint32_t i = 0; i < tile_count; ++i) {
-		const crh_tile &t = tiles[i];
-		if (t.x0 < 0 || t.y0 < 0 || t.x1 > width || t.y1 > height) return fail(CRH_ERR_INVALID, std::string(who) + ": rectangle " + std::to_string(i) + " lies outside the image");
-		if (t.x1 <= t.x0 || t.y1 <= t.y0) return fail(CRH_ERR_INVALID, std::string(who) + ": rectangle " + std::to_string(i) + " is empty");
-		if ((uint64_t)(t.x1 - t.x0) * (uint64_t)(t.y1 - t.y0) > (1ull << 30)) return fail(CRH_ERR_INVALID, std::string(who) + ": rectangle " + std::to_string(i) + " holds more than 2^30 pixels");
-	}
-	return CRH_OK;
-}
-
 /* One launch over validated tiles, behind whatever the stream holds; waits for it. advanceAll: half := fb over every tile, nothing measured or reported. */
 static int adLaunch(crh_ctx *c, const float *dev_fb, float *dev_half, int width, int height, const crh_tile *tiles, uint32_t tile_count, float threshold, bool advanceAll,
                     float *errors_host, uint8_t *continue_host) {
 	int rc = setDevice(c);
 	if (rc) return rc;
-	const size_t tileBytes = (size_t)tile_count * sizeof(crh_tile), wordBytes = (size_t)tile_count * sizeof(uint32_t), need = tileBytes + 2 * wordBytes;
-	if (need > c->adaptiveCap) {
-		HIP_TRY(hipStreamSynchronize(c->stream));
-		if (c->dAdaptive) HIP_TRY(hipFree(c->dAdaptive));
-		if (c->hAdaptive) HIP_TRY(hipHostFree(c->hAdaptive));
-		c->dAdaptive = c->hAdaptive = nullptr; c->adaptiveCap = 0;
-		const size_t cap = std::max<size_t>(4096, 2 * need);
-		HIP_TRY(hipMalloc(&c->dAdaptive, cap));
-		HIP_TRY(hipHostMalloc(&c->hAdaptive, cap, hipHostMallocDefault));
-		c->adaptiveCap = cap;
-	}
+	const size_t tileBytes = (size_t)tile_count * sizeof(crh_tile), wordBytes = (size_t)tile_count * sizeof(uint32_t);
+	/* the buffer is never marked in flight — a call that succeeds ends with the stream drained —, but one that failed half-way may have left its copy queued:
+	 * the stream is drained before the blocks are given up */
+	StagedBuf &sb = c->adaptive;
+	if (tileBytes + 2 * wordBytes > sb.cap) HIP_TRY(hipStreamSynchronize(c->stream));
+	if ((rc = sb.reserve(tileBytes + 2 * wordBytes))) return rc;
 	if (!c->adaptiveEv[0]) for (hipEvent_t &e : c->adaptiveEv) HIP_TRY(hipEventCreate(&e));
-	memcpy(c->hAdaptive, tiles, tileBytes);
-	HIP_TRY(hipMemcpyAsync(c->dAdaptive, c->hAdaptive, tileBytes, hipMemcpyHostToDevice, c->stream));
+	memcpy(sb.host, tiles, tileBytes);
+	HIP_TRY(hipMemcpyAsync(sb.dev, sb.host, tileBytes, hipMemcpyHostToDevice, c->stream));
 	AdaptiveArgs A;
 	A.fb = dev_fb; A.half = dev_half;
-	A.tiles = (const crh_tile *)c->dAdaptive;
-	A.errors = (float *)((char *)c->dAdaptive + tileBytes);
-	A.flags = (uint32_t *)((char *)c->dAdaptive + tileBytes + wordBytes);
+	A.tiles = (const crh_tile *)sb.dev;
+	A.errors = (float *)((char *)sb.dev + tileBytes);
+	A.flags = (uint32_t *)((char *)sb.dev + tileBytes + wordBytes);
 	A.W = width; A.H = height; A.threshold = threshold; A.advanceAll = advanceAll ? 1 : 0;
 	HIP_TRY(hipEventRecord(c->adaptiveEv[0], c->stream));
 	hipLaunchKernelGGL(k_adaptive_step, dim3(tile_count), dim3(CRH_BLOCK), 0, c->stream, A);
 	const hipError_t e = hipGetLastError();
 	HIP_TRY(hipEventRecord(c->adaptiveEv[1], c->stream));
 	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string("k_adaptive_step launch: ") + hipGetErrorString(e));
-	if (!advanceAll) HIP_TRY(hipMemcpyAsync((char *)c->hAdaptive + tileBytes, (char *)c->dAdaptive + tileBytes, 2 * wordBytes, hipMemcpyDeviceToHost, c->stream));
+	if (!advanceAll) HIP_TRY(hipMemcpyAsync((char *)sb.host + tileBytes, (char *)sb.dev + tileBytes, 2 * wordBytes, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	HIP_TRY(hipEventElapsedTime(&c->adaptiveLastMs, c->adaptiveEv[0], c->adaptiveEv[1]));
 	if (!advanceAll) {
-		const float *err = (const float *)((const char *)c->hAdaptive + tileBytes);
-		const uint32_t *flag = (const uint32_t *)((const char *)c->hAdaptive + tileBytes + wordBytes);
+		const float *err = (const float *)((const char *)sb.host + tileBytes);
+		const uint32_t *flag = (const uint32_t *)((const char *)sb.host + tileBytes + wordBytes);
 		if (errors_host) memcpy(errors_host, err, wordBytes);
 		if (continue_host) for (uint32_t i = 0; i < tile_count; ++i) continue_host[i] = flag[i] ? 1 : 0;
 	}
@@ -2303,7 +2137,7 @@ int crh_adaptive_step(crh_ctx *c, const float *dev_fb, float *dev_half, int widt
 	if (width <= 0 || height <= 0) return fail(CRH_ERR_INVALID, "crh_adaptive_step: bad size");
 	if (std::isnan(threshold) || std::signbit(threshold)) return fail(CRH_ERR_INVALID, "crh_adaptive_step: the threshold is NaN or negative");
 	if ((const float *)dev_half == dev_fb) return fail(CRH_ERR_INVALID, "crh_adaptive_step: the half-sample frame is the frame");
-	const int rc = adCheckTiles("crh_adaptive_step", tiles, tile_count, width, height);
+	const int rc = checkRects("crh_adaptive_step", tiles, tile_count, width, height, true);
 	if (rc) return rc;
 	if (tile_count == 0) return CRH_OK;
 	return adLaunch(c, dev_fb, dev_half, width, height, tiles, tile_count, threshold, false, errors_host, continue_host);
@@ -2338,7 +2172,7 @@ int crh_render_adaptive(crh_ctx *c, const crh_render_params *P, const crh_tile *
 	if (std::isnan(A->threshold) || std::signbit(A->threshold)) return fail(CRH_ERR_INVALID, "crh_render_adaptive: the threshold is NaN or negative");
 	if (dev_half == dev_fb) return fail(CRH_ERR_INVALID, "crh_render_adaptive: the half-sample frame is the frame");
 	const int W = P->image_width, H = P->image_height;
-	int rc = adCheckTiles("crh_render_adaptive", tiles, tile_count, W, H);
+	int rc = checkRects("crh_render_adaptive", tiles, tile_count, W, H, true);
 	if (rc) return rc;
 	if (tile_count == 0) return CRH_OK;
 	crh_render_params p = *P;
@@ -2492,30 +2326,26 @@ int crh_frames_gather(crh_ctx **ctxs, float **fbs, int n, int width, int height,
 	size_t total = 0;
 	for (int g = 1; g < n; ++g) { rows[g] = (size_t)stripRowsOwned(height, strip_rows, g, n); at[g] = total; total += rows[g] * rowFloats; }
 	auto room = [](crh_ctx *c, size_t floats) -> int {
-		if (floats <= c->gatherFloats) return CRH_OK;
+		if (floats <= c->dGather.n) return CRH_OK;
 		HIP_TRY(hipSetDevice(c->device));
-		if (c->dGather) HIP_TRY(hipFree(c->dGather));
-		c->dGather = nullptr; c->gatherFloats = 0;
-		HIP_TRY(hipMalloc((void **)&c->dGather, std::max<size_t>(floats, 1) * sizeof(float)));
-		c->gatherFloats = floats;
-		return CRH_OK;
+		return c->dGather.grow(c->stream, floats);
 	};
 	if ((rc = room(ctxs[0], total)) != CRH_OK) return rc;
 	for (int g = 1; g < n; ++g) {
 		if ((rc = room(ctxs[g], rows[g] * rowFloats)) != CRH_OK) return rc;
 		if (!rows[g]) continue;
 		HIP_TRY(hipSetDevice(devs[g]));
-		hipLaunchKernelGGL(k_strip_rows, dim3(1024), dim3(256), 0, ctxs[g]->stream, fbs[g], ctxs[g]->dGather, width, height, strip_rows, g, n, (int)rows[g], 0);
+		hipLaunchKernelGGL(k_strip_rows, dim3(1024), dim3(256), 0, ctxs[g]->stream, fbs[g], ctxs[g]->dGather.p, width, height, strip_rows, g, n, (int)rows[g], 0);
 		HIP_TRY(hipGetLastError());
 	}
 	rc = g_rccl.GroupStart();
 	for (int g = 1; g < n && rc == 0; ++g) {
 		if (!rows[g]) continue;
 		if (hipSetDevice(devs[g]) != hipSuccess) { rc = -1; break; }
-		rc = g_rccl.Send(ctxs[g]->dGather, rows[g] * rowFloats, kNcclFloat32, 0, g_rccl.comms[g], ctxs[g]->stream);
+		rc = g_rccl.Send(ctxs[g]->dGather.p, rows[g] * rowFloats, kNcclFloat32, 0, g_rccl.comms[g], ctxs[g]->stream);
 		if (rc != 0) break;
 		if (hipSetDevice(devs[0]) != hipSuccess) { rc = -1; break; }
-		rc = g_rccl.Recv(ctxs[0]->dGather + at[g], rows[g] * rowFloats, kNcclFloat32, g, g_rccl.comms[0], ctxs[0]->stream);
+		rc = g_rccl.Recv(ctxs[0]->dGather.p + at[g], rows[g] * rowFloats, kNcclFloat32, g, g_rccl.comms[0], ctxs[0]->stream);
 	}
 	const int rcEnd = g_rccl.GroupEnd();
 	if (rc == 0) rc = rcEnd;
@@ -2523,7 +2353,7 @@ int crh_frames_gather(crh_ctx **ctxs, float **fbs, int n, int width, int height,
 	HIP_TRY(hipSetDevice(devs[0]));
 	for (int g = 1; g < n; ++g) {
 		if (!rows[g]) continue;
-		hipLaunchKernelGGL(k_strip_rows, dim3(1024), dim3(256), 0, ctxs[0]->stream, fbs[0], ctxs[0]->dGather + at[g], width, height, strip_rows, g, n, (int)rows[g], 1);
+		hipLaunchKernelGGL(k_strip_rows, dim3(1024), dim3(256), 0, ctxs[0]->stream, fbs[0], ctxs[0]->dGather.p + at[g], width, height, strip_rows, g, n, (int)rows[g], 1);
 		HIP_TRY(hipGetLastError());
 	}
 	for (int i = 0; i < n; ++i) {
@@ -2540,7 +2370,7 @@ int crh_synchronize(crh_ctx *c) {
 	if (getenv("CRH_TRACE_SYNC") && !c->pendingTimes.empty()) {        /* dev: when does the stream reach the kernel, when does it leave it, when does the host notice? */
 		const auto t0 = std::chrono::steady_clock::now();
 		auto us = [&]() { return (long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count(); };
-		const crh_ctx::Timed ev = c->pendingTimes.back();
+		const TimedPair ev = c->pendingTimes.back();
 		while (hipEventQuery(ev.a) == hipErrorNotReady) {}
 		const long ta = us();
 		while (hipEventQuery(ev.b) == hipErrorNotReady) {}
@@ -2776,20 +2606,14 @@ int crh_debug_walk_probe(crh_ctx *c, int wps, int stack_lds, int inst_lds, int f
 			if (k * unit_rays < cnt[w]) units.push_back(ProbeUnit{(uint32_t)(w * c->dumpCap + k * unit_rays), (uint32_t)std::min<unsigned long long>(unit_rays, cnt[w] - k * unit_rays)});
 	if (rays_out) *rays_out = total;
 	if (units.empty()) return fail(CRH_ERR_INVALID, "crh_debug_walk_probe: the ray list is empty");
-	if ((units.size() + 1) * sizeof(ProbeUnit) > c->probeUnitCap) {
-		if (c->dProbeUnits) (void)hipFree(c->dProbeUnits);
-		c->dProbeUnits = nullptr; c->probeUnitCap = 0;
-		HIP_TRY(hipMalloc(&c->dProbeUnits, (units.size() + 1) * sizeof(ProbeUnit)));
-		c->probeUnitCap = (units.size() + 1) * sizeof(ProbeUnit);
-	}
 	/* word 0 of the buffer is the queue's counter, the units follow */
-	HIP_TRY(hipMemset(c->dProbeUnits, 0, sizeof(ProbeUnit)));
-	HIP_TRY(hipMemcpy((ProbeUnit *)c->dProbeUnits + 1, units.data(), units.size() * sizeof(ProbeUnit), hipMemcpyHostToDevice));
+	if ((rc = c->dProbeUnits.grow(c->stream, units.size() + 1))) return rc;
+	HIP_TRY(hipMemset(c->dProbeUnits.p, 0, sizeof(ProbeUnit)));
+	HIP_TRY(hipMemcpy(c->dProbeUnits.p + 1, units.data(), units.size() * sizeof(ProbeUnit), hipMemcpyHostToDevice));
 	const size_t ovfWords = (size_t)c->cuCount * 8u * (CRH_BLOCK / 64) * CRH_OVF_WORDS_PER_WAVE;
 	if (!c->dProbeOvf) HIP_TRY(hipMalloc((void **)&c->dProbeOvf, ovfWords * sizeof(uint32_t)));
-	crh_ctx::Timed ev;
-	if (!c->eventPool.empty()) { ev = c->eventPool.back(); c->eventPool.pop_back(); }
-	else { HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b)); }
+	TimedPair ev;
+	if ((rc = c->eventPool.take(ev))) return rc;
 	hipError_t e = hipSuccess;
 	bool launched = false;
 	const uint32_t slots = (uint32_t)(dumpWaves * c->dumpCap);
@@ -2817,8 +2641,8 @@ int crh_debug_walk_probe(crh_ctx *c, int wps, int stack_lds, int inst_lds, int f
 		CRH_PROBE_ALLOW_LDS((k_walk_probe<W, N, I, F>), pad); \
 		snprintf(c->lastKernel, sizeof(c->lastKernel), "k_walk_probe<%d,%d,%s,%s> vgpr %d lds %zu+%zu", W, N, I ? "true" : "false", F == 1 ? "fused" : F == 2 ? "flat" : F == 3 ? "lean1" : "lean", fa.numRegs, (size_t)fa.sharedSizeBytes, pad); \
 		HIP_TRY(hipEventRecord(ev.a, c->stream)); \
-		hipLaunchKernelGGL((k_walk_probe<W, N, I, F>), dim3((uint32_t)c->cuCount * W), dim3(CRH_BLOCK), pad, c->stream, c->d, c->dDump, (const ProbeUnit *)c->dProbeUnits + 1, (uint32_t)units.size(), \
-		                   (uint32_t *)c->dProbeUnits, c->dProbeHits[slot], c->dProbeInst[slot], c->sched, c->dProbeOvf); \
+		hipLaunchKernelGGL((k_walk_probe<W, N, I, F>), dim3((uint32_t)c->cuCount * W), dim3(CRH_BLOCK), pad, c->stream, c->d, c->dDump, (const ProbeUnit *)c->dProbeUnits.p + 1, (uint32_t)units.size(), \
+		                   (uint32_t *)c->dProbeUnits.p, c->dProbeHits[slot], c->dProbeInst[slot], c->sched, c->dProbeOvf); \
 		e = hipGetLastError(); \
 		HIP_TRY(hipEventRecord(ev.b, c->stream)); \
 		launched = true; \
@@ -2837,12 +2661,12 @@ int crh_debug_walk_probe(crh_ctx *c, int wps, int stack_lds, int inst_lds, int f
 	CRH_PROBE_VARIANT(7, 3, true, 3)
 	CRH_PROBE_VARIANT(8, 4, false, 3)
 #undef CRH_PROBE_VARIANT
-	if (!launched) { c->eventPool.push_back(ev); return fail(CRH_ERR_INVALID, "crh_debug_walk_probe: no such variant (wps, stack_lds, inst_lds)"); }
-	if (e != hipSuccess) { c->eventPool.push_back(ev); return fail(CRH_ERR_HIP, std::string("crh_debug_walk_probe: ") + hipGetErrorString(e)); }
+	if (!launched) { c->eventPool.give(ev); return fail(CRH_ERR_INVALID, "crh_debug_walk_probe: no such variant (wps, stack_lds, inst_lds)"); }
+	if (e != hipSuccess) { c->eventPool.give(ev); return fail(CRH_ERR_HIP, std::string("crh_debug_walk_probe: ") + hipGetErrorString(e)); }
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	float ms = 0.0f;
 	HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
-	c->eventPool.push_back(ev);
+	c->eventPool.give(ev);
 	if (ms_out) *ms_out = ms;
 	return CRH_OK;
 }

@@ -3,13 +3,14 @@
  * (crh_denoise, include/cray_hip.h). A capability beside the render path, like k_aov: nothing of k_pathtrace_roll includes or calls anything in here.
  *
  * Semantics (include/cray_hip.h states the arithmetic operation by operation; tests/test_denoise.py restates it in NumPy float32 and holds these kernels to it
- * bit for bit — only correctly rounded + - * / sqrt, comparisons and fabsf in a fixed order, no libm, no contraction). Prepare turns a pixel of the frame and
- * of the guides into two 16-byte records: C = {irradiance r g b (the colour divided by the albedo; a miss counts as albedo 1), its luminance} and
- * G = {unit normal x y z, depth / coverage}. Iteration i filters C with the 5 x 5 B3-spline taps at step 2^i, every tap weighted by how well its normal, depth
- * and luminance agree with the centre's; G never changes. The last iteration multiplies the albedo back in and writes the frame.
+ * bit for bit — only correctly rounded + - * / sqrt, comparisons and fabsf in a fixed order, no libm, no contraction). Prepare (both kinds' through dnAlbedo,
+ * dnIrradiance and dnGuideRecord) turns a pixel of the frame and of the guides into two 16-byte records: C = {irradiance r g b (the colour divided by the
+ * albedo; a miss counts as albedo 1), its luminance} and G = {unit normal x y z, depth / coverage}. Iteration i filters C with the 5 x 5 B3-spline taps at step
+ * 2^i, every tap weighted by how well its normal, depth and luminance agree with the centre's; G never changes. The last iteration multiplies the albedo back
+ * in and writes the frame.
  *
  * Shape. One thread per pixel, 32 x 8 pixels per workgroup. A tap is two 16-byte reads, and the iteration kernel comes in three forms that differ only in
- * where the taps are read (the arithmetic is one function, dnTap):
+ * where the taps are read (the arithmetic is one function, dnTap; its guide weights, dnGuideWeights, are the variance kernels' too):
  *   direct (LS = 0)       every tap from global memory: the two planes of a 1280 x 720 frame are 29 MB — they stay in the Infinity Cache, a workgroup's
  *                         neighbourhood in L2 / L1;
  *   dense tile (LS = s)   the workgroup stages its tile plus a halo of 2 s records in LDS (16-byte writes) and reads the taps s records apart
@@ -65,37 +66,53 @@ __device__ __forceinline__ void dnAlbedo(const f4 a0, const f4 a1, float &r, flo
 	r = dnMax(a0.x + miss, CRH_DN_EPS_ALBEDO); g = dnMax(a0.y + miss, CRH_DN_EPS_ALBEDO); b = dnMax(a0.z + miss, CRH_DN_EPS_ALBEDO);
 }
 
-/* Prepare: the records of every pixel; with out != null (a denoise of no iterations) the frame at once: (c / a) * a */
-__global__ __launch_bounds__(CRH_BLOCK) void k_denoise_prepare(const float *fb, const float *aovArg, f4 *C, f4 *G, float *out, uint64_t pixels) {
-	const uint64_t i = (uint64_t)blockIdx.x * CRH_BLOCK + threadIdx.x;
-	if (i >= pixels) return;
-	const f4 a0 = ((const f4 *)aovArg)[2 * i], a1 = ((const f4 *)aovArg)[2 * i + 1];          /* albedo r g b, normal x | normal y z, depth, coverage */
-	float ar, ag, ab;
-	dnAlbedo(a0, a1, ar, ag, ab);
-	const float fr = fb[3 * i], fg = fb[3 * i + 1], fbl = fb[3 * i + 2];
-	const float inf = __builtin_inff();
-	const float cr = (fr > 0.0f && fr < inf) ? fr : 0.0f, cg = (fg > 0.0f && fg < inf) ? fg : 0.0f, cb = (fbl > 0.0f && fbl < inf) ? fbl : 0.0f;          /* NaN, inf, negative -> 0 */
-	const float ir = cr / ar, ig = cg / ag, ib = cb / ab;
-	if (out) { out[3 * i] = ir * ar; out[3 * i + 1] = ig * ag; out[3 * i + 2] = ib * ab; return; }
+__device__ __forceinline__ float dnGuard(float v) { return (v > 0.0f && v < __builtin_inff()) ? v : 0.0f; }          /* NaN, inf, negative -> 0 */
+
+/* G of a pixel from its two AOV records (albedo r g b, normal x | normal y z, depth, coverage): the unit normal (zero where there is none), depth / coverage */
+__device__ __forceinline__ f4 dnGuideRecord(const f4 a0, const f4 a1) {
 	const float nx = a0.w, ny = a1.x, nz = a1.y;
 	const float nn = (nx * nx + ny * ny) + nz * nz;
 	f4 g = f4{0.0f, 0.0f, 0.0f, 0.0f};
 	if (nn > 0.0f) { const float len = sqrtf(nn); g.x = nx / len; g.y = ny / len; g.z = nz / len; }
 	if (a1.w > 0.0f) g.w = a1.z / a1.w;
+	return g;
+}
+/* a frame's pixel (px: its three floats), guarded and divided by the pixel's albedo */
+__device__ __forceinline__ void dnIrradiance(const float *px, float ar, float ag, float ab, float &ir, float &ig, float &ib) {
+	ir = dnGuard(px[0]) / ar; ig = dnGuard(px[1]) / ag; ib = dnGuard(px[2]) / ab;
+}
+
+/* Prepare: the records of every pixel; with out != null (a denoise of no iterations) the frame at once: (c / a) * a */
+__global__ __launch_bounds__(CRH_BLOCK) void k_denoise_prepare(const float *fb, const float *aovArg, f4 *C, f4 *G, float *out, uint64_t pixels) {
+	const uint64_t i = (uint64_t)blockIdx.x * CRH_BLOCK + threadIdx.x;
+	if (i >= pixels) return;
+	const f4 a0 = ((const f4 *)aovArg)[2 * i], a1 = ((const f4 *)aovArg)[2 * i + 1];          /* albedo r g b, normal x | normal y z, depth, coverage */
+	float ar, ag, ab, ir, ig, ib;
+	dnAlbedo(a0, a1, ar, ag, ab);
+	dnIrradiance(fb + 3 * i, ar, ag, ab, ir, ig, ib);
+	if (out) { out[3 * i] = ir * ar; out[3 * i + 1] = ig * ag; out[3 * i + 2] = ib * ab; return; }
+	const f4 g = dnGuideRecord(a0, a1);
 	C[i] = f4{ir, ig, ib, dnLum(ir, ig, ib)};
 	G[i] = g;
 }
 
 struct DnAcc { float r, g, b, w; };
 
-/* one tap: q's colour weighted by the B3 coefficient h and by how well q's normal, depth and luminance agree with p's */
-__device__ __forceinline__ void dnTap(DnAcc &acc, const f4 Cp, const f4 Gp, const f4 Cq, const f4 Gq, float h, const DnParams &P) {
+/* how well q's normal (wn) and depth (wz) agree with p's */
+__device__ __forceinline__ void dnGuideWeights(const f4 Gp, const f4 Gq, const DnParams &P, float &wn, float &wz) {
 	const float dx = Gp.x - Gq.x, dy = Gp.y - Gq.y, dz = Gp.z - Gq.z;
 	const float d2 = (dx * dx + dy * dy) + dz * dz;
 	const float t = dnMax(1.0f - P.sigmaNormal * d2, 0.0f);
-	const float t2 = t * t, wn = t2 * t2;
+	const float t2 = t * t;
+	wn = t2 * t2;
 	const float r = (fabsf(Gp.w - Gq.w) / (dnMax(Gp.w, Gq.w) + CRH_DN_EPS_DEPTH)) / P.sigmaDepth;
-	const float wz = 1.0f / (1.0f + r * r);
+	wz = 1.0f / (1.0f + r * r);
+}
+
+/* one tap: q's colour weighted by the B3 coefficient h and by how well q's normal, depth and luminance agree with p's */
+__device__ __forceinline__ void dnTap(DnAcc &acc, const f4 Cp, const f4 Gp, const f4 Cq, const f4 Gq, float h, const DnParams &P) {
+	float wn, wz;
+	dnGuideWeights(Gp, Gq, P, wn, wz);
 	const float e = (Cp.w - Cq.w) / (P.sigmaColor * ((Cp.w + Cq.w) + CRH_DN_EPS_LUM));
 	const float wc = 1.0f / (1.0f + e * e);
 	const float w = ((h * wn) * wz) * wc;
@@ -164,38 +181,21 @@ __global__ __launch_bounds__(CRH_BLOCK) void k_denoise_iter(const f4 *Cin, const
  * scale (L(half) - L(frame))^2, NaN and anything above 2^100 -> 2^100 (a zero weight times an infinite variance would be a NaN). out != null: as above. */
 #define CRH_DN_VARIANCE_MAX 0x1p100f
 
-__device__ __forceinline__ float dnGuard(float v) { return (v > 0.0f && v < __builtin_inff()) ? v : 0.0f; }          /* NaN, inf, negative -> 0 */
-
 __global__ __launch_bounds__(CRH_BLOCK) void k_denoise_prepare_v(const float *fb, const float *half, const float *aovArg, f4 *C, f4 *G, float *Vraw, float *out, float scale, uint64_t pixels) {
 	const uint64_t i = (uint64_t)blockIdx.x * CRH_BLOCK + threadIdx.x;
 	if (i >= pixels) return;
 	const f4 a0 = ((const f4 *)aovArg)[2 * i], a1 = ((const f4 *)aovArg)[2 * i + 1];
-	float ar, ag, ab;
+	float ar, ag, ab, ir, ig, ib, hr, hg, hb;
 	dnAlbedo(a0, a1, ar, ag, ab);
-	const float ir = dnGuard(fb[3 * i]) / ar, ig = dnGuard(fb[3 * i + 1]) / ag, ib = dnGuard(fb[3 * i + 2]) / ab;
+	dnIrradiance(fb + 3 * i, ar, ag, ab, ir, ig, ib);
 	if (out) { out[3 * i] = ir * ar; out[3 * i + 1] = ig * ag; out[3 * i + 2] = ib * ab; return; }
-	const float hr = dnGuard(half[3 * i]) / ar, hg = dnGuard(half[3 * i + 1]) / ag, hb = dnGuard(half[3 * i + 2]) / ab;
+	dnIrradiance(half + 3 * i, ar, ag, ab, hr, hg, hb);
 	const float d = dnLum(hr, hg, hb) - dnLum(ir, ig, ib);
 	const float v = scale * (d * d);
-	const float nx = a0.w, ny = a1.x, nz = a1.y;
-	const float nn = (nx * nx + ny * ny) + nz * nz;
-	f4 g = f4{0.0f, 0.0f, 0.0f, 0.0f};
-	if (nn > 0.0f) { const float len = sqrtf(nn); g.x = nx / len; g.y = ny / len; g.z = nz / len; }
-	if (a1.w > 0.0f) g.w = a1.z / a1.w;
+	const f4 g = dnGuideRecord(a0, a1);
 	C[i] = f4{ir, ig, ib, 0.0f};
 	G[i] = g;
 	Vraw[i] = v < CRH_DN_VARIANCE_MAX ? v : CRH_DN_VARIANCE_MAX;
-}
-
-/* wn and wz of dnTap: how well q's normal and depth agree with p's */
-__device__ __forceinline__ void dnGuideWeights(const f4 Gp, const f4 Gq, const DnParams &P, float &wn, float &wz) {
-	const float dx = Gp.x - Gq.x, dy = Gp.y - Gq.y, dz = Gp.z - Gq.z;
-	const float d2 = (dx * dx + dy * dy) + dz * dz;
-	const float t = dnMax(1.0f - P.sigmaNormal * d2, 0.0f);
-	const float t2 = t * t;
-	wn = t2 * t2;
-	const float r = (fabsf(Gp.w - Gq.w) / (dnMax(Gp.w, Gq.w) + CRH_DN_EPS_DEPTH)) / P.sigmaDepth;
-	wz = 1.0f / (1.0f + r * r);
 }
 
 /* The variance prefilter: the guide-weighted mean of the raw variance over the 5 x 5 neighbours (no spline coefficient), into the records' fourth component.

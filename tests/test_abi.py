@@ -130,3 +130,16 @@ def test_podbuf_allocation_regimes(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "podbuf_check ok" in r.stdout, r.stdout + r.stderr
 
+
+def test_context_buffer_owners_under_the_sanitizers(tmp_path):
+    """csrc/ctx_buffers.h — the grow-only device buffer, the staged buffer and the timed event pairs that own a context's per-dispatch memory — on the HIP-on-CPU
+    shim, whose allocations are malloc and new, built with AddressSanitizer and UBSan and run as a program of its own (tests/emu/ctx_buffers_check.cpp): growth, the
+    no-op when the need fits, release twice, the staged buffer's floor and 2 x policy, reserve while in flight, every pair destroyed — and no leak at exit."""
+    emu = os.path.join(REPO, "tests", "emu")
+    exe = str(tmp_path / "ctx_buffers_check")
+    # (the sanitizers' runtimes are linked into the program: it runs in whatever environment it inherits)
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
+                           "-I" + os.path.join(emu, "hipemu"),
+                           os.path.join(emu, "ctx_buffers_check.cpp"), os.path.join(emu, "hipemu", "hipemu.cpp"), "-o", exe])
+    r = subprocess.run([exe], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "ctx_buffers_check ok" in r.stdout, r.stdout + r.stderr

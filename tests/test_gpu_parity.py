@@ -696,6 +696,101 @@ def test_upload_lifecycle_callers_arrays_poisoned_and_one_compile_for_two_contex
             x.close()
 
 
+def test_buffers_are_reused_and_regrown_across_entry_points(pkg, manifest, golden_blob):
+    """The context owns its per-dispatch device memory (csrc/ctx_buffers.h) and keeps it from call to call: ONE context walks a small frame, a larger one — cut
+    into 640 rectangles of 2 x 2 pixels, so that the render, AOV and adaptive lists each outgrow their first 4096 bytes of staging and every per-wave buffer that
+    depends on the dispatch is sized again — and the small one again, and at each size calls render_tiles (pass 1, a copy for the half-sample frame, pass 2),
+    render_aov, denoise, denoise_variance and adaptive_step. Every output — frame, half-sample frame, AOV buffer, both denoised frames, the tiles' errors and
+    continue flags and the advanced half-sample frame — equals bit for bit what a FRESH context gives for that single call on the same inputs (device pointers
+    are the device's, so the fresh context reads the walking context's buffers). Correctness of each output is the other tests' business."""
+    api = pkg.api
+    b = manifest["fence"]["bounces"]
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint8)
+    fresh_results = {}
+
+    def scene_at(w, h):
+        return resize_camera(api.Scene(golden_blob("fence")), w, h)
+
+    def fresh(w, h, call, upload=False):
+        """call(context) on a context that has done nothing else, closed afterwards"""
+        c = api.Context(0)
+        try:
+            if upload:
+                c.upload(scene_at(w, h))
+            return call(c)
+        finally:
+            c.close()
+
+    walker = api.Context(0)
+    try:
+        for w, h, cut in ((32, 20, None), (64, 40, 2), (32, 20, None)):
+            tiles = [(0, 0, w, h)] if cut is None else [(x, y, x + cut, y + cut) for y in range(0, h, cut) for x in range(0, w, cut)]
+            assert cut is None or len(tiles) >= 205
+            walker.upload(scene_at(w, h))
+            fb, half, half0, out, out_v, aov = [walker.framebuffer(w, h) for _ in range(5)] + [walker.aov_buffer(w, h)]
+            got = {}
+            walker.render_tiles(fb, w, h, 2, b, tiles, first_pass=0, pass_count=1)
+            walker.copy_framebuffer(fb, half, w, h)
+            walker.copy_framebuffer(fb, half0, w, h)
+            got["pass 1"] = walker.download(half, w, h)
+            walker.render_tiles(fb, w, h, 2, b, tiles, first_pass=1, pass_count=1)
+            got["frame"] = walker.download(fb, w, h)
+            walker.render_aov(aov, w, h, 2, tiles=tiles)
+            got["aov"] = walker.download_aov(aov, w, h)
+            walker.denoise(fb, aov, w, h, out=out)
+            got["denoise"] = walker.download(out, w, h)
+            walker.denoise_variance(fb, half, aov, w, h, 1, 2, out=out_v)
+            got["denoise_variance"] = walker.download(out_v, w, h)
+            got["errors"], got["flags"] = walker.adaptive_step(fb, half, w, h, tiles, 0.05)
+            got["half advanced"] = walker.download(half, w, h)
+            if (w, h) not in fresh_results:          # (the stream is drained: a fresh context may read the walker's buffers)
+                want = {}
+
+                def pass1(c):
+                    f = c.framebuffer(w, h)
+                    c.render_tiles(f, w, h, 2, b, tiles, first_pass=0, pass_count=1)
+                    return c.download(f, w, h)
+
+                def pass2(c):
+                    f = c.framebuffer(w, h)
+                    c.copy_framebuffer(half0, f, w, h)
+                    c.render_tiles(f, w, h, 2, b, tiles, first_pass=1, pass_count=1)
+                    return c.download(f, w, h)
+
+                def first_hits(c):
+                    a = c.aov_buffer(w, h)
+                    c.render_aov(a, w, h, 2, tiles=tiles)
+                    return c.download_aov(a, w, h)
+
+                def denoised(c, variance):
+                    o = c.framebuffer(w, h)
+                    if variance:
+                        c.denoise_variance(fb, half0, aov, w, h, 1, 2, out=o)
+                    else:
+                        c.denoise(fb, aov, w, h, out=o)
+                    return c.download(o, w, h)
+
+                def step(c):
+                    hcopy = c.framebuffer(w, h)
+                    c.copy_framebuffer(half0, hcopy, w, h)
+                    errors, flags = c.adaptive_step(fb, hcopy, w, h, tiles, 0.05)
+                    return errors, flags, c.download(hcopy, w, h)
+
+                want["pass 1"] = fresh(w, h, pass1, upload=True)
+                want["frame"] = fresh(w, h, pass2, upload=True)
+                want["aov"] = fresh(w, h, first_hits, upload=True)
+                want["denoise"] = fresh(w, h, lambda c: denoised(c, False))
+                want["denoise_variance"] = fresh(w, h, lambda c: denoised(c, True))
+                want["errors"], want["flags"], want["half advanced"] = fresh(w, h, step)
+                fresh_results[(w, h)] = want
+            want = fresh_results[(w, h)]
+            assert got["flags"].any() and np.isfinite(got["frame"]).all() and got["aov"][..., 7].any(), "the walk renders something and at least one tile goes on"
+            for what in want:
+                assert np.array_equal(bits(got[what]), bits(want[what])), (w, h, what)
+    finally:
+        walker.close()
+
+
 def test_wide_walk_option_renders_the_fixtures(pkg, manifest, golden_blob, golden_ref):
     """CRH_OPT_WALK = CRH_WALK_WIDE4 (round 5, an experiment kept as an option; the binary walk is the contract): the 4-ary walk renders these fixtures to the
     reference's frames bit for bit — no ray of theirs meets a tie or a near tie (tools/wide_walk_study.py counts where others do) — with the same ray count, fewer
