@@ -17,8 +17,13 @@ import numpy as np
 NONE = 0xFFFFFFFF
 # enum crh_node_kind (include/cray_hip.h)
 DIFFUSE, METAL, GLASS, PLASTIC, MIX, ADD, TRANSPARENT, EMISSION, ISOTROPIC, BACKGROUND = range(1, 11)
-COLOR_CONSTANT, COLOR_IMAGE = 32, 33
-VALUE_CONSTANT, VALUE_ALPHA, VALUE_GRAYSCALE = 64, 65, 66
+COLOR_CONSTANT, COLOR_IMAGE, COLOR_CHECKER, COLOR_GRADIENT, COLOR_BLACKBODY, COLOR_COMBINE, COLOR_COMBINERGB, COLOR_VECTOCOLOR = range(32, 40)
+VALUE_CONSTANT, VALUE_ALPHA, VALUE_GRAYSCALE, VALUE_MATH, VALUE_FRESNEL, VALUE_RAYLENGTH = range(64, 70)
+VEC_CONSTANT, VEC_NORMAL, VEC_VECMATH = 96, 97, 98
+# enum mathOp (math.h:11-27) and enum vecOp (vecmath.h:11-22): field c of a math / vecMath node
+(MATH_ADD, MATH_SUBTRACT, MATH_MULTIPLY, MATH_DIVIDE, MATH_POWER, MATH_LOG, MATH_SQRT, MATH_ABS, MATH_MIN, MATH_MAX, MATH_SIN, MATH_COS, MATH_TAN, MATH_TO_RADIANS,
+ MATH_TO_DEGREES) = range(15)
+VEC_ADD, VEC_SUBTRACT, VEC_MULTIPLY, VEC_AVERAGE, VEC_DOT, VEC_CROSS, VEC_NORMALIZE, VEC_REFLECT, VEC_LENGTH, VEC_ABS = range(10)
 IMAGE_SRGB_TRANSFORM, IMAGE_NO_BILINEAR = 1, 2
 BSDF_KINDS = (DIFFUSE, METAL, GLASS, PLASTIC, MIX, ADD, TRANSPARENT, EMISSION, ISOTROPIC)
 
@@ -109,6 +114,46 @@ class SynthScene:
     def grayscale(self, color):
         return self.node(VALUE_GRAYSCALE, a=color, children=(color,))
 
+    def checker(self, a, b, scale):
+        return self.node(COLOR_CHECKER, a, b, scale, children=(a, b, scale))
+
+    def gradient(self, down, up):
+        """down, up: rgba."""
+        return self.node(COLOR_GRADIENT, f=tuple(down) + tuple(up))
+
+    def blackbody(self, temperature):
+        return self.node(COLOR_BLACKBODY, a=temperature, children=(temperature,))
+
+    def combine(self, value):
+        return self.node(COLOR_COMBINE, a=value, children=(value,))
+
+    def combine_rgb(self, r, g, b):
+        return self.node(COLOR_COMBINERGB, r, g, b, children=(r, g, b))
+
+    def vec_to_color(self, vector):
+        return self.node(COLOR_VECTOCOLOR, a=vector, children=(vector,))
+
+    def math(self, op, a, b):
+        """Field c is the op (enum mathOp), not a child; the unary ops ignore b, which must still be a value node."""
+        return self.node(VALUE_MATH, a, b, op, children=(a, b))
+
+    def fresnel(self, ior, normal=NONE):
+        """The reference's node never reads its normal operand (fresnel.c:39-51)."""
+        return self.node(VALUE_FRESNEL, a=ior, b=normal, children=[x for x in (ior, normal) if x != NONE])
+
+    def ray_length(self):
+        return self.node(VALUE_RAYLENGTH)
+
+    def vec(self, x, y, z):
+        return self.node(VEC_CONSTANT, f=(x, y, z))
+
+    def normal(self):
+        return self.node(VEC_NORMAL)
+
+    def vecmath(self, op, a, b):
+        """Field c is the op (enum vecOp), not a child; normalize, length and abs ignore b, which must still be a vector node."""
+        return self.node(VEC_VECMATH, a, b, op, children=(a, b))
+
     def bsdf(self, kind, a=NONE, b=NONE, c=NONE):
         assert kind in BSDF_KINDS
         return self.node(kind, a, b, c, children=[x for x in (a, b, c) if x != NONE])
@@ -126,6 +171,10 @@ class SynthScene:
         self._desc.texture_count = 0
         self._lists["textures"] = []
         self._tex_bytes = bytearray()
+
+    def texture_total(self):
+        """Textures of the scene, those added and not yet flushed included."""
+        return self._desc.texture_count + len(self._lists.get("textures", []))
 
     def texture(self, pixels, has_alpha=None):
         """pixels: uint8 or float32 [H, W, channels] (channels 1, 3 or 4) in the stored row order (texture.c:39: row 0 is y = height - 1)."""

@@ -25,8 +25,9 @@ import numpy as np
 import pytest
 
 from conftest import resize_camera
-from scene_synth import (ADD, DIFFUSE, EMISSION, GLASS, IMAGE_NO_BILINEAR, IMAGE_SRGB_TRANSFORM, ISOTROPIC, METAL, MIX, NONE, PLASTIC, TRANSPARENT, COLOR_CONSTANT,
-                         COLOR_IMAGE, VALUE_ALPHA, VALUE_CONSTANT, VALUE_GRAYSCALE, SynthScene)
+from scene_synth import (ADD, DIFFUSE, EMISSION, GLASS, IMAGE_NO_BILINEAR, IMAGE_SRGB_TRANSFORM, ISOTROPIC, METAL, MIX, NONE, PLASTIC, TRANSPARENT, COLOR_BLACKBODY,
+                         COLOR_CHECKER, COLOR_COMBINE, COLOR_COMBINERGB, COLOR_CONSTANT, COLOR_GRADIENT, COLOR_IMAGE, COLOR_VECTOCOLOR, VALUE_ALPHA, VALUE_CONSTANT,
+                         VALUE_FRESNEL, VALUE_GRAYSCALE, VALUE_MATH, VALUE_RAYLENGTH, VEC_CONSTANT, VEC_NORMAL, VEC_VECMATH, SynthScene)
 from test_aov import DeviceArray, fold, geometry_expected
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -44,12 +45,88 @@ _libm.powf.restype = C.c_float
 _libm.powf.argtypes = [C.c_float, C.c_float]
 
 
+for _f in ("log10f", "logf", "sinf", "cosf", "tanf"):
+    getattr(_libm, _f).restype = C.c_float
+    getattr(_libm, _f).argtypes = [C.c_float]
+
+
 def powf(x, y):
-    """The C library's powf on every element (numpy's power is not that function); one call per distinct bit pattern."""
+    """The C library's powf on every element (numpy's power is not that function), y a scalar or an array like x; one call per distinct pair of bit patterns."""
     x = np.ascontiguousarray(x, F)
+    y = np.ascontiguousarray(np.broadcast_to(F(y), x.shape))
+    key = (x.view(np.uint32).astype(np.uint64) << np.uint64(32)) | y.view(np.uint32).astype(np.uint64)
+    pairs, inverse = np.unique(key, return_inverse=True)
+    xs, ys = (pairs >> np.uint64(32)).astype(np.uint32).view(F), (pairs & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(F)
+    vals = np.array([_libm.powf(float(a), float(b)) for a, b in zip(xs, ys)], F)
+    return vals[inverse.reshape(-1)].reshape(x.shape)
+
+
+def libm1(name, x):
+    """A one-argument function of the C library on every element of a float32 array; one call per distinct bit pattern."""
+    x = np.ascontiguousarray(x, F)
+    fn = getattr(_libm, name)
     bits, inverse = np.unique(x.view(np.uint32), return_inverse=True)
-    vals = np.array([_libm.powf(float(v), float(F(y))) for v in bits.view(F)], F)
-    return vals[inverse].reshape(x.shape)
+    vals = np.array([fn(float(v)) for v in bits.view(F)], F)
+    return vals[inverse.reshape(-1)].reshape(x.shape)
+
+
+PI = F(3.141592653589793238462643383279502)          # includes.h:13, a float
+
+
+def rmin(a, b):
+    """includes.h:20: ((a) < (b)) ? (a) : (b) — b when either is NaN, b for (+0, -0) and (-0, +0)."""
+    return np.where(a < b, a, b)
+
+
+def rmax(a, b):
+    """includes.h:21: ((a) > (b)) ? (a) : (b)."""
+    return np.where(a > b, a, b)
+
+
+def vdot(a, b):
+    """vector.h:92-94: v1.x * v2.x + v1.y * v2.y + v1.z * v2.z, every operation rounded to float32, left to right."""
+    return a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1] + a[:, 2] * b[:, 2]
+
+
+def vlength(a):
+    return np.sqrt(vdot(a, a))          # vector.h:152-164
+
+
+def vnormalize(a):
+    return a / vlength(a)[:, None]          # vector.h:173-176: three divisions by the length
+
+
+def vcross(a, b):
+    """vector.h:122-127."""
+    return np.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2], a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], axis=1)
+
+
+def vreflect(i, n):
+    """vector.h:211-213: vecSub(I, vecScale(N, vecDot(N, I) * 2.0f))."""
+    return i - n * (vdot(n, i) * F(2.0))[:, None]
+
+
+def color_for_kelvin(kelvin):
+    """color.c:28-70 on a float32 array: [n, 4]. Every comparison is the source's own, so a NaN takes the branch the source's comparison gives it and
+    passes through both clamps (x < 0 and x > 255 are false for it)."""
+    with np.errstate(all="ignore"):
+        temp = np.where(kelvin >= F(40000.0), F(40000.0), kelvin) / F(100.0)
+
+        def clamp(x):
+            x = np.where(x < F(0.0), F(0.0), x)
+            return np.where(x > F(255.0), F(255.0), x)
+        low = temp <= F(66.0)
+        r = np.where(low, F(255.0), clamp(F(329.698727446) * powf(temp - F(60.0), -0.1332047592)))
+        g = clamp(np.where(low, F(99.4708025861) * libm1("logf", temp) - F(161.1195681661), F(288.1221695283) * powf(temp - F(60.0), -0.0755148492)))
+        b = np.where(temp >= F(66.0), F(255.0), np.where(temp <= F(19.0), F(0.0), clamp(F(138.5177312231) * libm1("logf", temp - F(10.0)) - F(305.0447927307))))
+        return np.stack([r / F(255.0), g / F(255.0), b / F(255.0), np.zeros_like(r)], axis=1).astype(F)
+
+
+def schlick(cosine, ior):
+    """vector.h:268-272."""
+    r0 = (F(1.0) - ior) / (F(1.0) + ior)
+    r0 = r0 * r0
+    return r0 + (F(1.0) - r0) * powf(F(1.0) - cosine, 5.0)
 
 
 def srgb_to_linear(c):
@@ -136,7 +213,91 @@ class Restatement:
             return np.tile(F(list(n.f[0:4])), (len(hits), 1))
         if n.kind == COLOR_IMAGE:
             return self.image(n, hits["uv"])
+        with np.errstate(all="ignore"):
+            if n.kind == COLOR_CHECKER:          # checker.c:31-54: one branch on sines < 0 (a NaN picks B); the point form where uv.x < 0
+                coef = self.value(n.c, hits)
+                uv, p = hits["uv"], hits["point"]
+                mapped = libm1("sinf", coef * uv[:, 0]) * libm1("sinf", coef * uv[:, 1])
+                unmapped = libm1("sinf", coef * p[:, 0]) * libm1("sinf", coef * p[:, 1]) * libm1("sinf", coef * p[:, 2])
+                sines = np.where(uv[:, 0] >= 0, mapped, unmapped)
+                return np.where((sines < F(0.0))[:, None], self.color(n.a, hits), self.color(n.b, hits))
+            if n.kind == COLOR_GRADIENT:          # gradient.c:40-45
+                t = F(0.5) * (vnormalize(hits["dir"])[:, 1] + F(1.0))
+                return (F(1.0) - t)[:, None] * F(list(n.f[0:4])) + t[:, None] * F(list(n.f[4:8]))
+            if n.kind == COLOR_BLACKBODY:          # blackbody.c:38-42
+                return color_for_kelvin(self.value(n.a, hits))
+            if n.kind == COLOR_COMBINE:          # combine.c:38-43
+                v = self.value(n.a, hits)
+                return np.stack([v, v, v, np.ones_like(v)], axis=1)
+            if n.kind == COLOR_COMBINERGB:          # combinergb.c:42-51
+                r = self.value(n.a, hits)
+                return np.stack([r, self.value(n.b, hits), self.value(n.c, hits), np.ones_like(r)], axis=1)
+            if n.kind == COLOR_VECTOCOLOR:          # vectocolor.c:38-43
+                v = self.vector(n.a, hits)
+                return np.concatenate([v, np.zeros((len(v), 1), F)], axis=1)
         raise NotImplementedError(f"colour node kind {n.kind}")
+
+    def vector(self, j, hits):
+        """float32 [n, 3]: the .v of the node's vectorValue (dot and length answer in .f, their .v is zero: vecmath.c:60-62, 72-74)."""
+        n = self.d.gnodes[j]
+        if n.kind == VEC_CONSTANT:
+            return np.tile(F(list(n.f[0:3])), (len(hits), 1))
+        if n.kind == VEC_NORMAL:
+            return hits["normal"].astype(F)
+        if n.kind == VEC_VECMATH:          # vecmath.c:41-81
+            a, b = self.vector(n.a, hits), self.vector(n.b, hits)
+            with np.errstate(all="ignore"):
+                if n.c == 0:
+                    return a + b
+                if n.c == 1:
+                    return a - b
+                if n.c == 2:
+                    return a * b
+                if n.c == 3:
+                    return (a + b) * F(0.5)
+                if n.c in (4, 8):
+                    return np.zeros_like(a)
+                if n.c == 5:
+                    return vcross(a, b)
+                if n.c == 6:
+                    return vnormalize(a)
+                if n.c == 7:
+                    return vreflect(a, b)
+                if n.c == 9:
+                    return np.abs(a)
+        raise NotImplementedError(f"vector node kind {n.kind} op {n.c}")
+
+    @staticmethod
+    def math(op, a, b):
+        """math.c:42-95."""
+        with np.errstate(all="ignore"):
+            if op == 0:
+                return a + b
+            if op == 1:
+                return a - b
+            if op == 2:
+                return a * b
+            if op == 3:
+                return a / b
+            if op == 4:
+                return powf(a, b)
+            if op == 5:
+                return libm1("log10f", a)
+            if op == 6:
+                return np.sqrt(a)
+            if op == 7:
+                return np.abs(a)
+            if op == 8:
+                return rmin(a, b)
+            if op == 9:
+                return rmax(a, b)
+            if op in (10, 11, 12):
+                return libm1(("sinf", "cosf", "tanf")[op - 10], a)
+            if op == 13:
+                return (a * PI) / F(180.0)          # transforms.c:18-20
+            if op == 14:
+                return a * (F(180.0) / PI)          # transforms.c:22-24
+        raise NotImplementedError(f"math op {op}")
 
     def value(self, j, hits):
         n = self.d.gnodes[j]
@@ -148,8 +309,20 @@ class Restatement:
             # color.h:42-45: 0.587 and 0.114 are double constants, so the sum is carried in double; sqrtf takes it as a float. The source's powf(x, 2) is x * x
             # in the reference binary (its compiler folds the constant exponent; the C library's powf(x, 2) differs from x * x by an ulp for one x in 1300)
             c = self.color(n.a, hits)
-            s = (F(0.299) * (c[:, 0] * c[:, 0])).astype(np.float64) + 0.587 * (c[:, 1] * c[:, 1]).astype(np.float64) + 0.114 * (c[:, 2] * c[:, 2]).astype(np.float64)
-            return np.sqrt(s.astype(F))
+            with np.errstate(all="ignore"):
+                s = (F(0.299) * (c[:, 0] * c[:, 0])).astype(np.float64) + 0.587 * (c[:, 1] * c[:, 1]).astype(np.float64) + 0.114 * (c[:, 2] * c[:, 2]).astype(np.float64)
+                return np.sqrt(s.astype(F))
+        if n.kind == VALUE_MATH:
+            return self.math(n.c, self.value(n.a, hits), self.value(n.b, hits)).astype(F)
+        if n.kind == VALUE_RAYLENGTH:          # raylength.c:36-40
+            return hits["distance"].astype(F)
+        if n.kind == VALUE_FRESNEL:          # fresnel.c:39-51 (the normal operand is never read)
+            with np.errstate(all="ignore"):
+                ior = self.value(n.a, hits)
+                d, nrm = hits["dir"], hits["normal"]
+                dot, length = vdot(d, nrm), vlength(d)
+                cosine = np.where(dot > F(0.0), ior * dot / length, -(dot / length))
+                return schlick(cosine, ior)
         raise NotImplementedError(f"value node kind {n.kind}")
 
     def albedo(self, j, hits):
@@ -347,15 +520,23 @@ def size_of(view):
 _rays = {}
 
 
-def scene_hits(oracle, s, view, passes=(0,), max_passes=1):
-    """hits[k][row, col] of the camera rays of `passes` (the rays depend on the view alone and are shared by the variants)."""
+def scene_hits(oracle, s, view, passes=(0,), max_passes=1, dirs=False):
+    """hits[k][row, col] of the camera rays of `passes` (the rays depend on the view alone and are shared by the variants). With `dirs`, every record also
+    carries its ray's direction as the field "dir" (incident.direction of the hit record: fresnel.c and gradient.c read it)."""
     w, h = size_of(view)
     out = []
     for p in passes:
         key = (view, p, max_passes)
         if key not in _rays:
             _rays[key] = np.array([[oracle.camera_ray(s, x, y, p, max_passes) for x in range(w)] for y in reversed(range(h))], F)
-        out.append(oracle.trace_rays(s, _rays[key].reshape(-1, 6)).reshape(h, w))
+        hits = oracle.trace_rays(s, _rays[key].reshape(-1, 6)).reshape(h, w)
+        if dirs:
+            wide = np.zeros(hits.shape, hits.dtype.descr + [("dir", "<f4", (3,))])
+            for name in hits.dtype.names:
+                wide[name] = hits[name]
+            wide["dir"] = _rays[key][..., 3:6]
+            hits = wide
+        out.append(hits)
     return np.stack(out)
 
 
@@ -583,9 +764,16 @@ def gpu_aov(pkg, ctx, s, w, h, samples):
         ctx._owned_aovs.remove(buf)
 
 
-def assert_aov(got, want_albedo, hits, passes, what):
+def same_bits(a, b, nan_equal=False):
+    """Elementwise: the same bits — with `nan_equal`, also a NaN against a NaN of any payload or sign (x86 and the GPU produce different default NaNs;
+    tests/test_exact_math.py sets the same bar)."""
+    same = np.ascontiguousarray(a, F).view(np.uint32) == np.ascontiguousarray(b, F).view(np.uint32)
+    return same | (np.isnan(a) & np.isnan(b)) if nan_equal else same
+
+
+def assert_aov(got, want_albedo, hits, passes, what, nan_equal=False):
     geo = geometry_expected(hits, passes)
-    bad = (got[..., 0:3].view(np.uint32) != want_albedo.view(np.uint32)).any(axis=2)
+    bad = ~same_bits(got[..., 0:3], want_albedo, nan_equal).all(axis=2)
     assert not bad.any(), f"{what}: the albedo of {int(bad.sum())} pixels differs, first at {np.argwhere(bad)[:3].tolist()}"
     assert np.array_equal(got[..., 3:8].view(np.uint32), geo.view(np.uint32)), f"{what}: normal / depth / coverage differ"
     miss = hits[-1]["inst"] < 0 if len(passes) == 1 else np.zeros(got.shape[0:2], bool)
