@@ -31,6 +31,7 @@
 #include <cstring>
 #include <condition_variable>
 #include <atomic>
+#include <cassert>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -651,22 +652,15 @@ struct crh_ctx {
 	uint32_t aovDepth = 0;                   /* CompiledScene::max_albedo_depth of the resident scene */
 	uint32_t *dAovCounter = nullptr;
 	StagedBuf aovTiles;
-	hipEvent_t aovEvA = nullptr, aovEvB = nullptr;
-	bool aovTimed = false;
-	float aovLastMs = 0.0f;
+	Stopwatch<1> aovWatch;                   /* around the kernel (crh_aov_kernel_time_ms) */
 	/* crh_denoise / crh_denoise_variance (denoise.h): three planes of 16-byte records (C ping, C pong, G) — and, for the variance kind, a plane of floats behind
-	 * them — sized lazily for the largest call so far, and one event around every launch (prepare, the variance prefilter, the iterations) */
+	 * them — sized lazily for the largest call so far, and a lap for every launch (prepare, the variance prefilter, the iterations) of the most recent denoise of either kind */
 	DevBuf<uint8_t> dDenoise;
-	hipEvent_t denoiseEv[CRH_DN_MAX_ITERATIONS + 3] = {};
-	uint32_t denoiseLaunches = 0;            /* of the most recent denoise of either kind */
-	bool denoiseTimed = false;
-	float denoiseLaunchMs[CRH_DN_MAX_ITERATIONS + 2] = {};
-	float denoiseLastMs = 0.0f;
+	Stopwatch<CRH_DN_MAX_ITERATIONS + 2> denoiseWatch;
 	/* crh_adaptive_step (adaptive.h): the call's tile list, errors and flags go through one pinned host buffer and its device twin (the call waits for its result,
-	 * so one of each serves), and two events around the kernel */
+	 * so one of each serves), and a lap around the kernel */
 	StagedBuf adaptive;
-	hipEvent_t adaptiveEv[2] = {};
-	float adaptiveLastMs = 0.0f;
+	Stopwatch<1> adaptiveWatch;
 };
 #define CRH_WORK_SLOTS 64
 static_assert(sizeof(((crh_ctx *)nullptr)->tileSlots) / sizeof(StagedBuf) == CRH_WORK_SLOTS, "one tile slot per work counter");
@@ -727,92 +721,103 @@ static bool wideWalk(const crh_ctx *c) {
 	return c->walk == CRH_WALK_WIDE4 && c->haveWide && rollForm(c) && !c->hasPrograms && c->sampler == CRH_SAMPLER_RANDOM;
 }
 
+/* ---- which instantiation a dispatch launches ---------------------------------------------------------- */
+/* A row of a kernel table: the options an instantiation serves, the instantiation and its name (crh_last_kernel_name); the row macros write the template arguments
+ * once for all three. `variant` is what else tells the rows of a table apart: the 4-ary walk of k_pathtrace_roll, the waves per SIMD of k_pathtrace, the stack form of
+ * k_stream_walk. ROWS STAND IN THE ORDER IN WHICH THE KERNELS LIE IN THE CODE OBJECT — the order this file has always named them in, not a numeric one: another order
+ * moves every kernel's PC-relative constants and with them bench.py's kernel_source_md5. Append; do not sort. */
+template <class Fn> struct KernelRow { int level; bool rare; int samp, variant; Fn fn; const char *name; };
+/* The row of (level, rare, samp) among those of `variant`. Development builds (CRH_DEV_ONLY_BENCH_VARIANT: tools/build_variant.sh, tools/kernel_regs.py — one
+ * instantiation compiles in seconds) hold one row per variant and launch it whatever the options say; in every other build the exact row exists. */
+template <class Fn, size_t N> static const KernelRow<Fn> *pickRow(const KernelRow<Fn> (&rows)[N], int level, bool rare, int samp, int variant) {
+	const KernelRow<Fn> *first = nullptr;
+	for (const KernelRow<Fn> &r : rows) {
+		if (r.variant != variant) continue;
+		if (r.level == level && r.rare == rare && r.samp == samp) return &r;
+		if (!first) first = &r;
+	}
+#ifdef CRH_DEV_ONLY_BENCH_VARIANT
+	return first ? first : &rows[0];
+#else
+	assert(!"a kernel table lacks the row of a valid option set");
+	return nullptr;          /* (NDEBUG: the caller reports hipErrorInvalidDeviceFunction — a missing kernel is an error) */
+#endif
+}
+
+#define CRH_ROLL_ROW(LEVEL, RARE, SAMP) {LEVEL, RARE, SAMP, 0, k_pathtrace_roll<LEVEL, 4, RARE, SAMP>, "k_pathtrace_roll<" #LEVEL ",4," #RARE "," #SAMP ">"}
+/* CRH_OPT_WALK = CRH_WALK_WIDE4 (an option, round 5): scenes without rare features, the random sampler */
+#define CRH_ROLL_ROW_WIDE(LEVEL) {LEVEL, false, 0, 1, k_pathtrace_roll<LEVEL, 4, false, 0, true>, "k_pathtrace_roll<" #LEVEL ",4,false,0,wide4>"}
+static const KernelRow<decltype(&k_pathtrace_roll<1, 4, false, 0>)> kRollRows[] = {
+#ifndef CRH_DEV_ONLY_BENCH_VARIANT
+	CRH_ROLL_ROW_WIDE(2), CRH_ROLL_ROW_WIDE(1),
+	CRH_ROLL_ROW(2, true, 1), CRH_ROLL_ROW(2, true, 0), CRH_ROLL_ROW(2, false, 1), CRH_ROLL_ROW(2, false, 0),
+	CRH_ROLL_ROW(1, true, 1), CRH_ROLL_ROW(1, true, 0), CRH_ROLL_ROW(1, false, 1), CRH_ROLL_ROW(1, false, 0),
+#elif defined(CRH_DEV_ONLY_LEVEL2)              /* the counting instantiation (tools/emu_sched_stats.py) */
+	CRH_ROLL_ROW_WIDE(2), CRH_ROLL_ROW(2, true, 0),
+#elif defined(CRH_DEV_ONLY_PROG)
+	CRH_ROLL_ROW_WIDE(1), CRH_ROLL_ROW(1, true, 0),
+#else
+	CRH_ROLL_ROW_WIDE(1), CRH_ROLL_ROW(1, false, 0),
+#endif
+};
+#undef CRH_ROLL_ROW
+#undef CRH_ROLL_ROW_WIDE
+#ifdef CRH_WITH_ALT_KERNELS
+#define CRH_WG_ROW(LEVEL, RARE, SAMP) {LEVEL, RARE, SAMP, 0, k_pathtrace_wg<LEVEL, RARE, SAMP>, "k_pathtrace_wg<" #LEVEL "," #RARE "," #SAMP ">"}
+static const KernelRow<decltype(&k_pathtrace_wg<1, false, 0>)> kWgRows[] = {
+#ifndef CRH_DEV_ONLY_BENCH_VARIANT
+	CRH_WG_ROW(2, true, 1), CRH_WG_ROW(2, true, 0), CRH_WG_ROW(2, false, 1), CRH_WG_ROW(2, false, 0),
+	CRH_WG_ROW(1, true, 1), CRH_WG_ROW(1, true, 0), CRH_WG_ROW(1, false, 1), CRH_WG_ROW(1, false, 0),
+#elif defined(CRH_DEV_ONLY_PROG)
+	CRH_WG_ROW(1, true, 0),
+#else
+	CRH_WG_ROW(1, false, 0),
+#endif
+};
+#undef CRH_WG_ROW
+/* variant = WPS; the Halton sampler (interactive mode) has the 128-register instantiations only */
+#define CRH_WAVE_ROW(LEVEL, WPS, RARE, SAMP) {LEVEL, RARE, SAMP, WPS, k_pathtrace<LEVEL, WPS, RARE, SAMP>, "k_pathtrace<" #LEVEL "," #WPS "," #RARE "," #SAMP ">"}
+static const KernelRow<decltype(&k_pathtrace<1, 4, false, 0>)> kWaveRows[] = {
+#ifndef CRH_DEV_ONLY_BENCH_VARIANT
+	CRH_WAVE_ROW(2, 4, true, 1), CRH_WAVE_ROW(2, 4, false, 1), CRH_WAVE_ROW(1, 4, true, 1), CRH_WAVE_ROW(1, 4, false, 1),
+	CRH_WAVE_ROW(2, 4, true, 0), CRH_WAVE_ROW(2, 4, false, 0), CRH_WAVE_ROW(2, 1, true, 0), CRH_WAVE_ROW(2, 1, false, 0),
+	CRH_WAVE_ROW(1, 4, true, 0), CRH_WAVE_ROW(1, 4, false, 0), CRH_WAVE_ROW(1, 1, true, 0), CRH_WAVE_ROW(1, 1, false, 0),
+#elif defined(CRH_DEV_ONLY_PROG)
+	CRH_WAVE_ROW(1, 4, true, 0),
+#else
+	CRH_WAVE_ROW(1, 4, false, 0),
+#endif
+};
+#undef CRH_WAVE_ROW
+#endif
+
 /* Launch the instantiation the context's options select (counter level, rare features, sampler; the kernel form in builds that hold more than one). */
 static hipError_t launchPathtrace(crh_ctx *c, uint32_t grid, const crh_render_params *P, const BlockQueue &Q, float *dev_fb, int chunk) {
-#define CRH_LAUNCH_ROLL(LEVEL, PROG, SAMP) do { snprintf(c->lastKernel, sizeof(c->lastKernel), "k_pathtrace_roll<%d,4,%s,%d>", LEVEL, PROG ? "true" : "false", SAMP); \
-		hipLaunchKernelGGL((k_pathtrace_roll<LEVEL, 4, PROG, SAMP>), dim3(grid), dim3(CRH_BLOCK), 0, c->stream, c->d, *P, Q, dev_fb, \
-						   c->dCounters, c->dStage.p, chunk, c->dWaveStats, c->sched, c->dQueues.p, c->dOvf.p, c->dErr); } while (0)
-#define CRH_LAUNCH_ROLL_WIDE(LEVEL) do { snprintf(c->lastKernel, sizeof(c->lastKernel), "k_pathtrace_roll<%d,4,false,0,wide4>", LEVEL); \
-		hipLaunchKernelGGL((k_pathtrace_roll<LEVEL, 4, false, 0, true>), dim3(grid), dim3(CRH_BLOCK), 0, c->stream, dw, *P, Q, dev_fb, \
-						   c->dCounters, c->dStage.p, chunk, c->dWaveStats, c->sched, c->dQueues.p, c->dOvf.p, c->dErr); } while (0)
-	const bool halton = c->sampler == CRH_SAMPLER_HALTON;
-	(void)halton;
+	const int level = c->counterLevel >= 2 ? 2 : 1, samp = c->sampler == CRH_SAMPLER_HALTON ? 1 : 0;
+	const char *name = nullptr;
 	if (rollForm(c)) {
-		/* CRH_OPT_WALK = CRH_WALK_WIDE4 (an option, round 5): scenes without rare features, the random sampler */
-		if (wideWalk(c)) {
-			DScene dw = c->d;
-			if (dw.tlas_node_count > 1u) dw.tlas_root = c->wideTlasRoot;
-#ifdef CRH_DEV_ONLY_BENCH_VARIANT
-#if defined(CRH_DEV_ONLY_LEVEL2)
-			CRH_LAUNCH_ROLL_WIDE(2);
-#else
-			CRH_LAUNCH_ROLL_WIDE(1);
-#endif
-#else
-			if (c->counterLevel >= 2) CRH_LAUNCH_ROLL_WIDE(2); else CRH_LAUNCH_ROLL_WIDE(1);
-#endif
-			return hipGetLastError();
+		const bool wide = wideWalk(c);
+		DScene d = c->d;
+		if (wide && d.tlas_node_count > 1u) d.tlas_root = c->wideTlasRoot;
+		if (const auto *r = pickRow(kRollRows, level, c->hasPrograms, samp, wide ? 1 : 0)) {
+			name = r->name;
+			hipLaunchKernelGGL((r->fn), dim3(grid), dim3(CRH_BLOCK), 0, c->stream, d, *P, Q, dev_fb, c->dCounters, c->dStage.p, chunk, c->dWaveStats, c->sched, c->dQueues.p, c->dOvf.p, c->dErr);
 		}
-#ifdef CRH_DEV_ONLY_BENCH_VARIANT                 /* development builds (tools/build_variant.sh, tools/kernel_regs.py): one instantiation compiles in seconds */
-#if defined(CRH_DEV_ONLY_LEVEL2)              /* the counting instantiation (tools/emu_sched_stats.py) */
-		CRH_LAUNCH_ROLL(2, true, 0);
-#elif defined(CRH_DEV_ONLY_PROG)
-		CRH_LAUNCH_ROLL(1, true, 0);
-#else
-		CRH_LAUNCH_ROLL(1, false, 0);
-#endif
-#else
-		if (c->counterLevel >= 2) {
-			if (c->hasPrograms) { if (halton) CRH_LAUNCH_ROLL(2, true, 1); else CRH_LAUNCH_ROLL(2, true, 0); }
-			else { if (halton) CRH_LAUNCH_ROLL(2, false, 1); else CRH_LAUNCH_ROLL(2, false, 0); }
-		} else {
-			if (c->hasPrograms) { if (halton) CRH_LAUNCH_ROLL(1, true, 1); else CRH_LAUNCH_ROLL(1, true, 0); }
-			else { if (halton) CRH_LAUNCH_ROLL(1, false, 1); else CRH_LAUNCH_ROLL(1, false, 0); }
-		}
-#endif
-		return hipGetLastError();
 	}
-#undef CRH_LAUNCH_ROLL
-#undef CRH_LAUNCH_ROLL_WIDE
 #ifdef CRH_WITH_ALT_KERNELS
-	const bool wg = c->kernel == CRH_KERNEL_WG;
-#define CRH_LAUNCH(LEVEL, WPS, PROG, SAMP) do { snprintf(c->lastKernel, sizeof(c->lastKernel), "k_pathtrace<%d,%d,%s,%d>", LEVEL, WPS, PROG ? "true" : "false", SAMP); \
-		hipLaunchKernelGGL((k_pathtrace<LEVEL, WPS, PROG, SAMP>), dim3(grid), dim3(CRH_BLOCK), 0, c->stream, c->d, *P, Q, dev_fb, \
-						   c->dCounters, c->dStage.p, chunk, c->dWaveStats, c->sched, c->dQueues.p, c->dOvf.p); } while (0)
-#define CRH_LAUNCH2(LEVEL, WPS) do { if (c->hasPrograms) CRH_LAUNCH(LEVEL, WPS, true, 0); else CRH_LAUNCH(LEVEL, WPS, false, 0); } while (0)
-#define CRH_LAUNCH_WG(LEVEL, PROG, SAMP) do { snprintf(c->lastKernel, sizeof(c->lastKernel), "k_pathtrace_wg<%d,%s,%d>", LEVEL, PROG ? "true" : "false", SAMP); \
-		hipLaunchKernelGGL((k_pathtrace_wg<LEVEL, PROG, SAMP>), dim3(grid), dim3(CRH_BLOCK), 0, c->stream, c->d, *P, Q, dev_fb, \
-						   c->dCounters, c->dStage.p, chunk, c->schedWg, c->dQueues.p, c->dOvf.p, c->dErr); } while (0)
-#ifdef CRH_DEV_ONLY_BENCH_VARIANT
-#ifdef CRH_DEV_ONLY_PROG
-	if (wg) CRH_LAUNCH_WG(1, true, 0); else CRH_LAUNCH(1, 4, true, 0);
-#else
-	if (wg) CRH_LAUNCH_WG(1, false, 0); else CRH_LAUNCH(1, 4, false, 0);
-#endif
-#else
-	if (wg) {
-		if (c->counterLevel >= 2) {
-			if (c->hasPrograms) { if (halton) CRH_LAUNCH_WG(2, true, 1); else CRH_LAUNCH_WG(2, true, 0); }
-			else { if (halton) CRH_LAUNCH_WG(2, false, 1); else CRH_LAUNCH_WG(2, false, 0); }
-		} else {
-			if (c->hasPrograms) { if (halton) CRH_LAUNCH_WG(1, true, 1); else CRH_LAUNCH_WG(1, true, 0); }
-			else { if (halton) CRH_LAUNCH_WG(1, false, 1); else CRH_LAUNCH_WG(1, false, 0); }
+	else if (c->kernel == CRH_KERNEL_WG) {
+		if (const auto *r = pickRow(kWgRows, level, c->hasPrograms, samp, 0)) {
+			name = r->name;
+			hipLaunchKernelGGL((r->fn), dim3(grid), dim3(CRH_BLOCK), 0, c->stream, c->d, *P, Q, dev_fb, c->dCounters, c->dStage.p, chunk, c->schedWg, c->dQueues.p, c->dOvf.p, c->dErr);
 		}
-	} else
-	if (halton) {          /* interactive mode: the 128-register variants only */
-		if (c->counterLevel >= 2) { if (c->hasPrograms) CRH_LAUNCH(2, 4, true, 1); else CRH_LAUNCH(2, 4, false, 1); }
-		else { if (c->hasPrograms) CRH_LAUNCH(1, 4, true, 1); else CRH_LAUNCH(1, 4, false, 1); }
+	} else if (const auto *r = pickRow(kWaveRows, level, c->hasPrograms, samp, samp || c->wavesPerSimd >= 4 ? 4 : 1)) {
+		name = r->name;
+		hipLaunchKernelGGL((r->fn), dim3(grid), dim3(CRH_BLOCK), 0, c->stream, c->d, *P, Q, dev_fb, c->dCounters, c->dStage.p, chunk, c->dWaveStats, c->sched, c->dQueues.p, c->dOvf.p);
 	}
-	else if (c->counterLevel >= 2) { if (c->wavesPerSimd >= 4) CRH_LAUNCH2(2, 4); else CRH_LAUNCH2(2, 1); }
-	else { if (c->wavesPerSimd >= 4) CRH_LAUNCH2(1, 4); else CRH_LAUNCH2(1, 1); }
 #endif
-#undef CRH_LAUNCH2
-#undef CRH_LAUNCH
-#undef CRH_LAUNCH_WG
+	if (!name) return hipErrorInvalidDeviceFunction;          /* (crh_set_option refuses the other forms in a build without them) */
+	snprintf(c->lastKernel, sizeof(c->lastKernel), "%s", name);
 	return hipGetLastError();
-#else
-	return hipErrorInvalidDeviceFunction;          /* (crh_set_option refuses the other forms in this build) */
-#endif
 }
 
 /* The three per-wave buffers of a dispatch of `grid` workgroups: a sample slab of slabItems samples per wave (per workgroup for the workgroup kernel: wg) and open
@@ -861,12 +866,11 @@ static int preloadKernel(crh_ctx *c, bool again = false) {
 	 * and allocates it when a dispatch first needs that much — for a one-workgroup preload that was the first frame: its kernel started 8-24 ms after its
 	 * launch (round 3, CRH_TRACE_SYNC; an empty launch and every synchronize the API offers directly in front of it changed nothing) */
 	/* ... between the two timing events a dispatch records around its kernel (their first use on a stream is a set-up step of the runtime as well) */
-	TimedPair ev;
-	if ((rc = c->eventPool.take(ev))) return rc;
-	HIP_TRY(hipEventRecord(ev.a, c->stream));
+	TimedLease lease(c->eventPool);
+	if ((rc = lease.take())) return rc;
+	HIP_TRY(hipEventRecord(lease.ev.a, c->stream));
 	const hipError_t e = launchPathtrace(c, (uint32_t)(c->cuCount * c->blocksPerCU), &P, Q, nullptr, 1);
-	HIP_TRY(hipEventRecord(ev.b, c->stream));
-	c->eventPool.give(ev);
+	HIP_TRY(hipEventRecord(lease.ev.b, c->stream));
 	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string("kernel preload: ") + hipGetErrorString(e));
 	HIP_TRY(hipMemsetAsync(c->dWork, 0, sizeof(uint32_t), c->stream));          /* its waves have drawn from the counter: zero again for the dispatch that takes slot 0 */
 	HIP_TRY(hipStreamSynchronize(c->stream));
@@ -953,11 +957,9 @@ int crh_context_destroy(crh_ctx *c) {
 	c->eventPool.release();
 	drop(c->dCounters); drop(c->dWork);
 	c->dStage.release(); c->dDefer.release(); c->dQueues.release(); c->dOvf.release();
-	drop(c->dAovCounter); c->aovTiles.release(); dropEvent(c->aovEvA); dropEvent(c->aovEvB);
-	c->dDenoise.release();
-	for (hipEvent_t e : c->denoiseEv) dropEvent(e);
-	c->adaptive.release();
-	for (hipEvent_t e : c->adaptiveEv) dropEvent(e);
+	drop(c->dAovCounter); c->aovTiles.release(); c->aovWatch.release();
+	c->dDenoise.release(); c->denoiseWatch.release();
+	c->adaptive.release(); c->adaptiveWatch.release();
 	if (c->hErr) (void)hipHostFree(c->hErr);
 	if (c->pinned) (void)hipHostFree(c->pinned);
 	releaseJanitor(c, true);
@@ -1552,6 +1554,27 @@ int crh_debug_plan_units(const crh_render_params *P, const crh_tile *tiles, uint
 }
 
 /* ---- the streaming form (CRH_KERNEL_STREAM; csrc/pathtrace_stream.h) ------------------------------------------------------------------------------------------------ */
+/* What crh_render_tiles and crh_render_aov ask of their arguments before anything else (`buffers`: the frame and, if it has entries, the tile list are there). */
+static int checkRenderParams(const char *who, const crh_ctx *c, const crh_render_params *P, bool buffers) {
+	if (!c || !P || !buffers) return fail(CRH_ERR_INVALID, std::string(who) + ": NULL argument");
+	if (!c->haveScene) return fail(CRH_ERR_INVALID, std::string(who) + ": no scene uploaded");
+	if (P->image_width <= 0 || P->image_height <= 0 || P->pass_count < 0 || P->first_pass < 0 || P->max_passes < P->first_pass + P->pass_count)
+		return fail(CRH_ERR_INVALID, std::string(who) + ": bad render parameters");
+	return CRH_OK;
+}
+
+/* A dispatch's tile list in the host side of a staging buffer: the tiles, and from byte `tileBytes` on their start words (one more than tiles); `listBytes` in all.
+ * Whether the kernels read the list there or in the device side, and what brings it there, is the caller's business. */
+static int stageTileList(StagedBuf &sb, const std::vector<crh_tile> &work, const std::vector<uint32_t> &start, size_t &tileBytes, size_t &listBytes) {
+	tileBytes = work.size() * sizeof(crh_tile);
+	listBytes = tileBytes + start.size() * sizeof(uint32_t);
+	const int rc = sb.reserve(listBytes);
+	if (rc) return rc;
+	memcpy(sb.host, work.data(), tileBytes);
+	memcpy((char *)sb.host + tileBytes, start.data(), listBytes - tileBytes);
+	return CRH_OK;
+}
+
 /* can this dispatch be streamed? (the forms it cannot serve are rendered by the rolling kernel: a sampler draw inside the walk (volumes), the Halton sampler of the
  * interactive mode, the 4-ary walk; bounces <= 0 never reaches the path tracer) */
 static bool streamServes(const crh_ctx *c, const crh_render_params *P) {
@@ -1563,6 +1586,22 @@ static bool streamServes(const crh_ctx *c, const crh_render_params *P) {
 #define CRH_STREAM_WALK_A_NLDS 7
 #define CRH_STREAM_WALK_B_WPS 5
 #define CRH_STREAM_WALK_B_NLDS 12
+#define CRH_WALK_ROW(FORM, DEEP, LEVEL) {LEVEL, false, 0, DEEP, k_stream_walk<CRH_STREAM_WALK_##FORM##_WPS, CRH_STREAM_WALK_##FORM##_NLDS, true, LEVEL>, nullptr}
+static const KernelRow<decltype(&k_stream_walk<CRH_STREAM_WALK_A_WPS, CRH_STREAM_WALK_A_NLDS, true, 1>)> kStreamWalkRows[] = {          /* variant 1: the deep stack */
+#ifndef CRH_DEV_ONLY_BENCH_VARIANT
+	CRH_WALK_ROW(B, 1, 2), CRH_WALK_ROW(A, 0, 2),
+#endif
+	CRH_WALK_ROW(B, 1, 1), CRH_WALK_ROW(A, 0, 1),
+};
+#undef CRH_WALK_ROW
+#define CRH_SHADE_ROW(LEVEL, RARE) {LEVEL, RARE, 0, 0, k_stream_shade<LEVEL, RARE, 0>, nullptr}
+static const KernelRow<decltype(&k_stream_shade<1, false, 0>)> kStreamShadeRows[] = {
+#ifndef CRH_DEV_ONLY_BENCH_VARIANT
+	CRH_SHADE_ROW(2, true), CRH_SHADE_ROW(2, false), CRH_SHADE_ROW(1, true),
+#endif
+	CRH_SHADE_ROW(1, false),
+};
+#undef CRH_SHADE_ROW
 static int renderStream(crh_ctx *c, const crh_render_params *P, const crh_tile *tiles, uint32_t tile_count, float *dev_fb) {
 	/* the dispatch's pixels in list order */
 	std::vector<crh_tile> work;
@@ -1600,6 +1639,10 @@ static int renderStream(crh_ctx *c, const crh_render_params *P, const crh_tile *
 	}
 	if ((rc = c->dStreamSlab.grow(c->stream, slabFloats))) return rc;
 	const bool deepStack = c->d.instance_count == 1u && c->d.tlas_node_count == 1u;
+	const int level = c->counterLevel >= 2 ? 2 : 1;
+	const auto *const walk = pickRow(kStreamWalkRows, level, false, 0, deepStack ? 1 : 0);
+	const auto *const shade = pickRow(kStreamShadeRows, level, c->hasPrograms, 0, 0);
+	if (!walk || !shade) return fail(CRH_ERR_HIP, std::string("k_stream launch: ") + hipGetErrorString(hipErrorInvalidDeviceFunction));
 	const uint32_t walkGrid = (uint32_t)c->cuCount * (uint32_t)(deepStack ? CRH_STREAM_WALK_B_WPS : CRH_STREAM_WALK_A_WPS);
 	if ((rc = c->dStreamOvf.grow(c->stream, (size_t)walkGrid * (CRH_BLOCK / 64) * CRH_OVF_WORDS_PER_WAVE))) return rc;
 	if (!c->dStreamCtl) HIP_TRY(hipMalloc((void **)&c->dStreamCtl, sizeof(StreamCtl)));
@@ -1613,10 +1656,8 @@ static int renderStream(crh_ctx *c, const crh_render_params *P, const crh_tile *
 	/* the tile list: pinned host slot, copied into the device slot by the dispatch's first kernel (no copy engine in front of a kernel: see crh_render_tiles) */
 	const uint32_t slot = c->workSlot % CRH_WORK_SLOTS;
 	StagedBuf &ts = c->tileSlots[slot];
-	const size_t tileBytes = ntiles * sizeof(crh_tile), startBytes = (ntiles + 1) * sizeof(uint32_t);
-	if ((rc = ts.reserve(tileBytes + startBytes))) return rc;
-	memcpy(ts.host, work.data(), tileBytes);
-	memcpy((char *)ts.host + tileBytes, start.data(), startBytes);
+	size_t tileBytes, listBytes;
+	if ((rc = stageTileList(ts, work, start, tileBytes, listBytes))) return rc;
 	void *hostView = nullptr;
 	HIP_TRY(hipHostGetDevicePointer(&hostView, ts.host, 0));
 	c->workSlot++;
@@ -1637,33 +1678,21 @@ static int renderStream(crh_ctx *c, const crh_render_params *P, const crh_tile *
 		pool[b].count = c->dStreamCount.p + (size_t)b * (c->streamSlots / CRH_SF_COHORT);
 	}
 
-	TimedPair ev;
-	if ((rc = c->eventPool.take(ev))) return rc;
-	HIP_TRY(hipEventRecord(ev.a, c->stream));
+	TimedLease lease(c->eventPool);
+	if ((rc = lease.take())) return rc;
+	HIP_TRY(hipEventRecord(lease.ev.a, c->stream));
 	hipLaunchKernelGGL(k_stream_init, dim3(std::min<uint32_t>(64u, (cohorts + 255u) / 256u)), dim3(256), 0, c->stream, Pl, pool[0].count, pool[1].count, c->dStreamCtl,
-	                   (const uint32_t *)hostView, (uint32_t *)ts.dev, (uint32_t)((tileBytes + startBytes) / 4));
+	                   (const uint32_t *)hostView, (uint32_t *)ts.dev, (uint32_t)(listBytes / 4));
 	hipError_t e = hipGetLastError();
 	const uint32_t shadeGrid = std::min<uint32_t>((uint32_t)c->cuCount * (uint32_t)CRH_STREAM_SHADE_WPS, cohorts);
 	const uint32_t foldGrid = std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)c->cuCount * 4u, (npix + CRH_BLOCK - 1u) / CRH_BLOCK));
-	snprintf(c->lastKernel, sizeof(c->lastKernel), "k_stream<%d,%s> walk<%d,%d>", c->counterLevel >= 2 ? 2 : 1, c->hasPrograms ? "true" : "false",
+	snprintf(c->lastKernel, sizeof(c->lastKernel), "k_stream<%d,%s> walk<%d,%d>", level, c->hasPrograms ? "true" : "false",
 	         deepStack ? CRH_STREAM_WALK_B_WPS : CRH_STREAM_WALK_A_WPS, deepStack ? CRH_STREAM_WALK_B_NLDS : CRH_STREAM_WALK_A_NLDS);
 	c->lastGrid = walkGrid;
 	auto iteration = [&](uint64_t it) {
 		const StreamPool &in = pool[it & 1u], &out = pool[(it + 1u) & 1u];
-#define CRH_STREAM_WALK(W, N, L) hipLaunchKernelGGL((k_stream_walk<W, N, true, L>), dim3(walkGrid), dim3(CRH_BLOCK), 0, c->stream, c->d, in, c->dStreamHit.p, c->dStreamHitInst.p, cohorts, \
-		                                             c->dStreamCtl, c->sched, c->dStreamOvf.p, c->dCounters)
-#define CRH_STREAM_SHADE(L, PROG) hipLaunchKernelGGL((k_stream_shade<L, PROG, 0>), dim3(shadeGrid), dim3(CRH_BLOCK), 0, c->stream, c->d, *P, Pl, in, out, c->dStreamCtl, c->dCounters)
-#ifdef CRH_DEV_ONLY_BENCH_VARIANT
-		if (deepStack) CRH_STREAM_WALK(CRH_STREAM_WALK_B_WPS, CRH_STREAM_WALK_B_NLDS, 1); else CRH_STREAM_WALK(CRH_STREAM_WALK_A_WPS, CRH_STREAM_WALK_A_NLDS, 1);
-		CRH_STREAM_SHADE(1, false);
-#else
-		if (c->counterLevel >= 2) { if (deepStack) CRH_STREAM_WALK(CRH_STREAM_WALK_B_WPS, CRH_STREAM_WALK_B_NLDS, 2); else CRH_STREAM_WALK(CRH_STREAM_WALK_A_WPS, CRH_STREAM_WALK_A_NLDS, 2); }
-		else { if (deepStack) CRH_STREAM_WALK(CRH_STREAM_WALK_B_WPS, CRH_STREAM_WALK_B_NLDS, 1); else CRH_STREAM_WALK(CRH_STREAM_WALK_A_WPS, CRH_STREAM_WALK_A_NLDS, 1); }
-		if (c->counterLevel >= 2) { if (c->hasPrograms) CRH_STREAM_SHADE(2, true); else CRH_STREAM_SHADE(2, false); }
-		else { if (c->hasPrograms) CRH_STREAM_SHADE(1, true); else CRH_STREAM_SHADE(1, false); }
-#endif
-#undef CRH_STREAM_WALK
-#undef CRH_STREAM_SHADE
+		hipLaunchKernelGGL((walk->fn), dim3(walkGrid), dim3(CRH_BLOCK), 0, c->stream, c->d, in, c->dStreamHit.p, c->dStreamHitInst.p, cohorts, c->dStreamCtl, c->sched, c->dStreamOvf.p, c->dCounters);
+		hipLaunchKernelGGL((shade->fn), dim3(shadeGrid), dim3(CRH_BLOCK), 0, c->stream, c->d, *P, Pl, in, out, c->dStreamCtl, c->dCounters);
 		hipLaunchKernelGGL(k_stream_fold, dim3(foldGrid), dim3(CRH_BLOCK), 0, c->stream, *P, Pl, c->dStreamCtl, dev_fb);
 	};
 	/* iterations in groups; behind every group an event. With group g + 1 enqueued the host waits for group g and looks at the completion word: the device always has a
@@ -1687,14 +1716,13 @@ static int renderStream(crh_ctx *c, const crh_render_params *P, const crh_tile *
 		if (!over && it > iterLimit) {
 			HIP_TRY(hipStreamSynchronize(c->stream));
 			if (*(volatile unsigned int *)c->hStreamDone == Pl.seq) break;
-			c->eventPool.give(ev);
 			return fail(CRH_ERR_HIP, "k_stream: the dispatch did not finish within its iteration limit: incomplete frame");
 		}
 	}
 	c->streamIterations = it;
-	HIP_TRY(hipEventRecord(ev.b, c->stream));
+	HIP_TRY(hipEventRecord(lease.ev.b, c->stream));
 	if ((rc = ts.markInFlight(c->stream))) return rc;
-	c->pendingTimes.push_back(ev);
+	c->pendingTimes.push_back(lease.keep());
 	c->launches++;
 	if (c->janitorWaiting.load(std::memory_order_relaxed)) releaseJanitor(c, false);
 	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string("k_stream launch: ") + hipGetErrorString(e));
@@ -1702,11 +1730,8 @@ static int renderStream(crh_ctx *c, const crh_render_params *P, const crh_tile *
 }
 
 int crh_render_tiles(crh_ctx *c, const crh_render_params *P, const crh_tile *tiles, uint32_t tile_count, float *dev_fb) {
-	if (!c || !P || !dev_fb || (!tiles && tile_count)) return fail(CRH_ERR_INVALID, "crh_render_tiles: NULL argument");
-	if (!c->haveScene) return fail(CRH_ERR_INVALID, "crh_render_tiles: no scene uploaded");
-	if (P->image_width <= 0 || P->image_height <= 0 || P->pass_count < 0 || P->first_pass < 0 || P->max_passes < P->first_pass + P->pass_count)
-		return fail(CRH_ERR_INVALID, "crh_render_tiles: bad render parameters");
-	int rc = setDevice(c);
+	int rc = checkRenderParams("crh_render_tiles", c, P, dev_fb && (tiles || !tile_count));
+	if (rc == CRH_OK) rc = setDevice(c);
 	if (rc) return rc;
 	(void)resolveTimes(c, false);
 	if (streamServes(c, P)) return renderStream(c, P, tiles, tile_count, dev_fb);
@@ -1735,10 +1760,8 @@ int crh_render_tiles(crh_ctx *c, const crh_render_params *P, const crh_tile *til
 	/* per-launch tile list: pinned host slot -> device slot, asynchronously on the launch stream */
 	const uint32_t slot = c->workSlot % CRH_WORK_SLOTS;          /* consumed below, once nothing can fail before the launch */
 	StagedBuf &ts = c->tileSlots[slot];
-	const size_t tileBytes = work_count * sizeof(crh_tile), startBytes = (work_count + 1) * sizeof(uint32_t);
-	if ((rc = ts.reserve(tileBytes + startBytes))) return rc;
-	memcpy(ts.host, work.data(), tileBytes);
-	memcpy((char *)ts.host + tileBytes, start.data(), startBytes);
+	size_t tileBytes, listBytes;
+	if ((rc = stageTileList(ts, work, start, tileBytes, listBytes))) return rc;
 	/* Nothing but the kernel itself is put on the stream in front of the kernel. Measured in round 3 (CRH_TRACE_SYNC, the drop-in's first dispatch): behind a
 	 * 64-byte host-to-device copy and a 4-byte memset the kernel started 9-22 ms after its launch, whatever had been warmed up or waited for before — the copy
 	 * engine's wake-up is the frame's. A short tile list (a frame, a GPU's strips) is therefore read by the waves straight from the pinned host slot (a wave
@@ -1748,7 +1771,7 @@ int crh_render_tiles(crh_ctx *c, const crh_render_params *P, const crh_tile *til
 	const bool zeroCopy = work_count <= 16 && !forceCopy;
 	void *dTiles = ts.dev;
 	if (zeroCopy) HIP_TRY(hipHostGetDevicePointer(&dTiles, ts.host, 0));
-	else HIP_TRY(hipMemcpyAsync(ts.dev, ts.host, tileBytes + startBytes, hipMemcpyHostToDevice, c->stream));
+	else HIP_TRY(hipMemcpyAsync(ts.dev, ts.host, listBytes, hipMemcpyHostToDevice, c->stream));
 
 	BlockQueue Q;
 	Q.tiles = (const crh_tile *)dTiles;
@@ -1769,19 +1792,19 @@ int crh_render_tiles(crh_ctx *c, const crh_render_params *P, const crh_tile *til
 		if (e0 != hipSuccess) return fail(CRH_ERR_HIP, std::string("k_fold_black launch: ") + hipGetErrorString(e0));
 		return ts.markInFlight(c->stream);                               /* (k_fold_black takes no work units: the counter stays zero) */
 	}
-	TimedPair ev;
-	if ((rc = c->eventPool.take(ev))) return rc;
-	HIP_TRY(hipEventRecord(ev.a, c->stream));
+	TimedLease lease(c->eventPool);
+	if ((rc = lease.take())) return rc;
+	HIP_TRY(hipEventRecord(lease.ev.a, c->stream));
 	hipError_t e = launchPathtrace(c, grid, P, Q, dev_fb, chunk);
 	if (e == hipSuccess && deferUnits) {              /* the split pixels' samples -> the frame, in pass order (part of the dispatch and of its time) */
 		const uint32_t px = deferUnits / (uint32_t)plan.segs;
 		hipLaunchKernelGGL(k_fold_deferred, dim3((px + 255u) / 256u), dim3(256), 0, c->stream, *P, Q, px, dev_fb);
 		e = hipGetLastError();
 	}
-	HIP_TRY(hipEventRecord(ev.b, c->stream));
+	HIP_TRY(hipEventRecord(lease.ev.b, c->stream));
 	HIP_TRY(hipMemsetAsync(Q.counter, 0, sizeof(uint32_t), c->stream));          /* ready for the dispatch that takes this slot next */
 	if ((rc = ts.markInFlight(c->stream))) return rc;
-	c->pendingTimes.push_back(ev);
+	c->pendingTimes.push_back(lease.keep());
 	c->launches++;
 	if (c->janitorWaiting.load(std::memory_order_relaxed)) {          /* a dispatch of some length is on the device: the host memory of the last upload can go back now */
 		uint64_t paths = 0;
@@ -1852,14 +1875,15 @@ int crh_aov_download(crh_ctx *c, const float *dev_aov, int width, int height, fl
 	return CRH_OK;
 }
 
+#define CRH_AOV_ROW(SAMP, RARE) {0, RARE, SAMP, 0, k_aov<SAMP, RARE>, nullptr}
+static const KernelRow<decltype(&k_aov<0, false>)> kAovRows[] = {CRH_AOV_ROW(1, true), CRH_AOV_ROW(1, false), CRH_AOV_ROW(0, true), CRH_AOV_ROW(0, false)};
+#undef CRH_AOV_ROW
 int crh_render_aov(crh_ctx *c, const crh_render_params *P, const crh_tile *tiles, uint32_t tile_count, float *dev_aov) {
-	if (!c || !P || !dev_aov || (!tiles && tile_count)) return fail(CRH_ERR_INVALID, "crh_render_aov: NULL argument");
-	if (!c->haveScene) return fail(CRH_ERR_INVALID, "crh_render_aov: no scene uploaded");
-	if (P->image_width <= 0 || P->image_height <= 0 || P->pass_count < 0 || P->first_pass < 0 || P->max_passes < P->first_pass + P->pass_count)
-		return fail(CRH_ERR_INVALID, "crh_render_aov: bad render parameters");
+	int rc = checkRenderParams("crh_render_aov", c, P, dev_aov && (tiles || !tile_count));
+	if (rc) return rc;
 	const crh_tile whole{P->x0, P->y0, P->x1, P->y1};
 	if (!tiles || !tile_count) { tiles = &whole; tile_count = 1; }
-	int rc = checkRects("crh_render_aov", tiles, tile_count, P->image_width, P->image_height, false);
+	rc = checkRects("crh_render_aov", tiles, tile_count, P->image_width, P->image_height, false);
 	if (rc) return rc;
 	if (c->aovDepth > CRH_AOV_STACK)
 		return fail(CRH_ERR_UNSUPPORTED, "crh_render_aov: a material nests mix / add nodes " + std::to_string(c->aovDepth) + " deep (the albedo evaluator holds " + std::to_string(CRH_AOV_STACK) + " frames)");
@@ -1889,6 +1913,8 @@ int crh_render_aov(crh_ctx *c, const crh_render_params *P, const crh_tile *tiles
 		total += (tileGroups + groups - 1u) / groups;
 	}
 	start.push_back((uint32_t)total);
+	const auto *const kernel = pickRow(kAovRows, 0, c->hasPrograms, c->sampler == CRH_SAMPLER_HALTON ? 1 : 0, 0);
+	if (!kernel) return fail(CRH_ERR_HIP, std::string("k_aov launch: ") + hipGetErrorString(hipErrorInvalidDeviceFunction));
 	if ((rc = setDevice(c))) return rc;
 	const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)c->cuCount * CRH_AOV_BLOCKS_PER_CU, (total + CRH_BLOCK / 64 - 1) / (CRH_BLOCK / 64));          /* (as many workgroups as a CU holds: aov.h) */
 	/* the render kernels' overflow columns: the same stream, one dispatch at a time */
@@ -1896,31 +1922,24 @@ int crh_render_aov(crh_ctx *c, const crh_render_params *P, const crh_tile *tiles
 	if (!c->dAovCounter) {
 		HIP_TRY(hipMalloc((void **)&c->dAovCounter, sizeof(uint32_t)));
 		HIP_TRY(hipMemsetAsync(c->dAovCounter, 0, sizeof(uint32_t), c->stream));
-		HIP_TRY(hipEventCreate(&c->aovEvA));
-		HIP_TRY(hipEventCreate(&c->aovEvB));
 	}
 	StagedBuf &ts = c->aovTiles;
-	const size_t tileBytes = work.size() * sizeof(crh_tile), startBytes = start.size() * sizeof(uint32_t);
-	if ((rc = ts.reserve(tileBytes + startBytes))) return rc;          /* (waits until the dispatch before this one has read the list) */
-	memcpy(ts.host, work.data(), tileBytes);
-	memcpy((char *)ts.host + tileBytes, start.data(), startBytes);
-	HIP_TRY(hipMemcpyAsync(ts.dev, ts.host, tileBytes + startBytes, hipMemcpyHostToDevice, c->stream));
+	size_t tileBytes, listBytes;
+	if ((rc = stageTileList(ts, work, start, tileBytes, listBytes))) return rc;          /* (waits until the dispatch before this one has read the list) */
+	HIP_TRY(hipMemcpyAsync(ts.dev, ts.host, listBytes, hipMemcpyHostToDevice, c->stream));
 	AovUnits U;
 	U.tiles = (const crh_tile *)ts.dev;
 	U.start = (const uint32_t *)((const char *)ts.dev + tileBytes);
 	U.ntiles = (uint32_t)work.size(); U.total = (uint32_t)total; U.counter = c->dAovCounter; U.group = group; U.groups = groups;
 	const uint32_t rayFlags = (uint32_t)c->sched.rayFlags;
-	HIP_TRY(hipEventRecord(c->aovEvA, c->stream));
-#define CRH_LAUNCH_AOV(SAMP, RARE) hipLaunchKernelGGL((k_aov<SAMP, RARE>), dim3(grid), dim3(CRH_BLOCK), 0, c->stream, c->d, *P, U, dev_aov, rayFlags, c->dOvf.p)
-	if (c->sampler == CRH_SAMPLER_HALTON) { if (c->hasPrograms) CRH_LAUNCH_AOV(1, true); else CRH_LAUNCH_AOV(1, false); }
-	else { if (c->hasPrograms) CRH_LAUNCH_AOV(0, true); else CRH_LAUNCH_AOV(0, false); }
-#undef CRH_LAUNCH_AOV
+	if ((rc = c->aovWatch.start(c->stream))) return rc;
+	hipLaunchKernelGGL((kernel->fn), dim3(grid), dim3(CRH_BLOCK), 0, c->stream, c->d, *P, U, dev_aov, rayFlags, c->dOvf.p);
 	const hipError_t e = hipGetLastError();
-	HIP_TRY(hipEventRecord(c->aovEvB, c->stream));
+	if ((rc = c->aovWatch.mark(c->stream))) return rc;
 	HIP_TRY(hipMemsetAsync(c->dAovCounter, 0, sizeof(uint32_t), c->stream));          /* ready for the next dispatch */
 	if ((rc = ts.markInFlight(c->stream))) return rc;
-	c->aovTimed = true;
 	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string("k_aov launch: ") + hipGetErrorString(e));
+	c->aovWatch.stop();
 	return CRH_OK;
 }
 
@@ -1929,12 +1948,8 @@ int crh_aov_kernel_time_ms(crh_ctx *c, float *last_ms) {
 	if (!c || !last_ms) return fail(CRH_ERR_INVALID, "crh_aov_kernel_time_ms: NULL argument");
 	int rc = setDevice(c);
 	if (rc) return rc;
-	if (c->aovTimed) {
-		HIP_TRY(hipEventSynchronize(c->aovEvB));
-		HIP_TRY(hipEventElapsedTime(&c->aovLastMs, c->aovEvA, c->aovEvB));
-		c->aovTimed = false;
-	}
-	*last_ms = c->aovLastMs;
+	if ((rc = c->aovWatch.read())) return rc;
+	*last_ms = c->aovWatch.sum;
 	return CRH_OK;
 }
 
@@ -1959,16 +1974,13 @@ static int dnCheck(const char *who, int width, int height, int iterations, std::
 		if (!(s > 0.0f) || !std::isfinite(s)) return fail(CRH_ERR_INVALID, std::string(who) + ": " + what + " is not a positive finite number");
 	return CRH_OK;
 }
-/* ... and the prologue: the context's scratch — three planes of records G, C, C', then `tailBytes` — and the events, the first of them recorded */
+/* ... and the prologue: the context's scratch — three planes of records G, C, C', then `tailBytes` — and the stopwatch started */
 static int dnBegin(crh_ctx *c, size_t pixels, size_t tailBytes, f4 *&G, f4 *&Cin, f4 *&Cout) {
 	int rc = setDevice(c);
 	if (rc == CRH_OK) rc = c->dDenoise.grow(c->stream, pixels * 3 * sizeof(f4) + tailBytes);
 	if (rc) return rc;
-	if (!c->denoiseEv[0]) for (hipEvent_t &e : c->denoiseEv) HIP_TRY(hipEventCreate(&e));
 	G = (f4 *)c->dDenoise.p; Cin = G + pixels; Cout = G + 2 * pixels;
-	c->denoiseTimed = false;
-	HIP_TRY(hipEventRecord(c->denoiseEv[0], c->stream));
-	return CRH_OK;
+	return c->denoiseWatch.start(c->stream);
 }
 
 int crh_denoise(crh_ctx *c, const crh_denoise_params *P, const float *dev_fb, const float *dev_aov, float *dev_out) {
@@ -1984,7 +1996,7 @@ int crh_denoise(crh_ctx *c, const crh_denoise_params *P, const float *dev_fb, co
 	if ((rc = dnBegin(c, pixels, 0, G, Cin, Cout))) return rc;
 	hipLaunchKernelGGL(k_denoise_prepare, dim3((uint32_t)((pixels + CRH_BLOCK - 1) / CRH_BLOCK)), dim3(CRH_BLOCK), 0, c->stream, dev_fb, dev_aov, Cin, G, N == 0 ? dev_out : (float *)nullptr, (uint64_t)pixels);
 	hipError_t e = hipGetLastError();
-	HIP_TRY(hipEventRecord(c->denoiseEv[1], c->stream));
+	if ((rc = c->denoiseWatch.mark(c->stream))) return rc;
 	for (int i = 0; i < N && e == hipSuccess; ++i) {
 		DnParams D;
 		D.W = P->width; D.H = P->height; D.step = 1 << i; D.stride = 1;
@@ -2006,12 +2018,11 @@ int crh_denoise(crh_ctx *c, const crh_denoise_params *P, const float *dev_fb, co
 #endif
 #undef CRH_LAUNCH_DN
 		e = hipGetLastError();
-		HIP_TRY(hipEventRecord(c->denoiseEv[2 + i], c->stream));
+		if ((rc = c->denoiseWatch.mark(c->stream))) return rc;
 		std::swap(Cin, Cout);
 	}
 	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string("k_denoise launch: ") + hipGetErrorString(e));
-	c->denoiseLaunches = (uint32_t)N + 1u;
-	c->denoiseTimed = true;
+	c->denoiseWatch.stop();
 	return CRH_OK;
 }
 
@@ -2034,42 +2045,27 @@ int crh_denoise_variance(crh_ctx *c, const crh_denoise_variance_params *P, const
 	D.W = P->width; D.H = P->height; D.step = 1; D.stride = 1;
 	D.sigmaNormal = P->sigma_normal; D.sigmaDepth = P->sigma_depth; D.sigmaColor = P->sigma_color;
 	const dim3 grid(((uint32_t)P->width + CRH_DN_TW - 1) / CRH_DN_TW, ((uint32_t)P->height + CRH_DN_TH - 1) / CRH_DN_TH);
-	uint32_t launches = 0;
 	f4 *G, *Cin, *Cout;
 	if ((rc = dnBegin(c, pixels, pixels * sizeof(float), G, Cin, Cout))) return rc;          /* (the raw variance behind the three planes) */
 	float *const Vraw = (float *)(G + 3 * pixels);
 	hipLaunchKernelGGL(k_denoise_prepare_v, dim3((uint32_t)((pixels + CRH_BLOCK - 1) / CRH_BLOCK)), dim3(CRH_BLOCK), 0, c->stream, dev_fb, dev_half, dev_aov, Cin, G, Vraw,
 	                   N == 0 ? dev_out : (float *)nullptr, P->variance_scale, (uint64_t)pixels);
 	hipError_t e = hipGetLastError();
-	HIP_TRY(hipEventRecord(c->denoiseEv[++launches], c->stream));
+	if ((rc = c->denoiseWatch.mark(c->stream))) return rc;
 	if (N > 0 && e == hipSuccess) {
 		hipLaunchKernelGGL(k_denoise_variance, grid, dim3(CRH_BLOCK), 0, c->stream, (const float *)Vraw, (const f4 *)G, Cin, D);
 		e = hipGetLastError();
-		HIP_TRY(hipEventRecord(c->denoiseEv[++launches], c->stream));
+		if ((rc = c->denoiseWatch.mark(c->stream))) return rc;
 	}
 	for (int i = 0; i < N && e == hipSuccess; ++i) {
 		D.step = 1 << i;
 		hipLaunchKernelGGL(k_denoise_iter_v, grid, dim3(CRH_BLOCK), 0, c->stream, (const f4 *)Cin, (const f4 *)G, Cout, dev_aov, i == N - 1 ? dev_out : (float *)nullptr, D);
 		e = hipGetLastError();
-		HIP_TRY(hipEventRecord(c->denoiseEv[++launches], c->stream));
+		if ((rc = c->denoiseWatch.mark(c->stream))) return rc;
 		std::swap(Cin, Cout);
 	}
 	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string("k_denoise launch: ") + hipGetErrorString(e));
-	c->denoiseLaunches = launches;
-	c->denoiseTimed = true;
-	return CRH_OK;
-}
-
-static int dnFetchTimes(crh_ctx *c) {
-	if (!c->denoiseTimed) return CRH_OK;
-	HIP_TRY(hipEventSynchronize(c->denoiseEv[c->denoiseLaunches]));
-	float sum = 0.0f;
-	for (uint32_t i = 0; i < c->denoiseLaunches; ++i) {
-		HIP_TRY(hipEventElapsedTime(&c->denoiseLaunchMs[i], c->denoiseEv[i], c->denoiseEv[i + 1]));
-		sum += c->denoiseLaunchMs[i];
-	}
-	c->denoiseLastMs = sum;
-	c->denoiseTimed = false;
+	c->denoiseWatch.stop();
 	return CRH_OK;
 }
 
@@ -2078,8 +2074,8 @@ int crh_denoise_time_ms(crh_ctx *c, float *last_ms) {
 	if (!c || !last_ms) return fail(CRH_ERR_INVALID, "crh_denoise_time_ms: NULL argument");
 	int rc = setDevice(c);
 	if (rc) return rc;
-	if ((rc = dnFetchTimes(c))) return rc;
-	*last_ms = c->denoiseLastMs;
+	if ((rc = c->denoiseWatch.read())) return rc;
+	*last_ms = c->denoiseWatch.sum;
 	return CRH_OK;
 }
 
@@ -2088,9 +2084,9 @@ int crh_debug_denoise_launch_ms(crh_ctx *c, float *ms, uint32_t cap) {
 	if (!c || (!ms && cap)) return fail(CRH_ERR_INVALID, "crh_debug_denoise_launch_ms: NULL argument");
 	int rc = setDevice(c);
 	if (rc) return rc;
-	if ((rc = dnFetchTimes(c))) return rc;
-	for (uint32_t i = 0; i < c->denoiseLaunches && i < cap; ++i) ms[i] = c->denoiseLaunchMs[i];
-	return (int)c->denoiseLaunches;
+	if ((rc = c->denoiseWatch.read())) return rc;
+	for (uint32_t i = 0; i < (uint32_t)c->denoiseWatch.laps && i < cap; ++i) ms[i] = c->denoiseWatch.ms[i];
+	return c->denoiseWatch.laps;
 }
 
 /* ---- adaptive sampling at tile granularity (adaptive.h: k_adaptive_step) ------------------------------------------------------------------ */
@@ -2105,7 +2101,6 @@ static int adLaunch(crh_ctx *c, const float *dev_fb, float *dev_half, int width,
 	StagedBuf &sb = c->adaptive;
 	if (tileBytes + 2 * wordBytes > sb.cap) HIP_TRY(hipStreamSynchronize(c->stream));
 	if ((rc = sb.reserve(tileBytes + 2 * wordBytes))) return rc;
-	if (!c->adaptiveEv[0]) for (hipEvent_t &e : c->adaptiveEv) HIP_TRY(hipEventCreate(&e));
 	memcpy(sb.host, tiles, tileBytes);
 	HIP_TRY(hipMemcpyAsync(sb.dev, sb.host, tileBytes, hipMemcpyHostToDevice, c->stream));
 	AdaptiveArgs A;
@@ -2114,14 +2109,15 @@ static int adLaunch(crh_ctx *c, const float *dev_fb, float *dev_half, int width,
 	A.errors = (float *)((char *)sb.dev + tileBytes);
 	A.flags = (uint32_t *)((char *)sb.dev + tileBytes + wordBytes);
 	A.W = width; A.H = height; A.threshold = threshold; A.advanceAll = advanceAll ? 1 : 0;
-	HIP_TRY(hipEventRecord(c->adaptiveEv[0], c->stream));
+	if ((rc = c->adaptiveWatch.start(c->stream))) return rc;
 	hipLaunchKernelGGL(k_adaptive_step, dim3(tile_count), dim3(CRH_BLOCK), 0, c->stream, A);
 	const hipError_t e = hipGetLastError();
-	HIP_TRY(hipEventRecord(c->adaptiveEv[1], c->stream));
+	if ((rc = c->adaptiveWatch.mark(c->stream))) return rc;
 	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string("k_adaptive_step launch: ") + hipGetErrorString(e));
 	if (!advanceAll) HIP_TRY(hipMemcpyAsync((char *)sb.host + tileBytes, (char *)sb.dev + tileBytes, 2 * wordBytes, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	HIP_TRY(hipEventElapsedTime(&c->adaptiveLastMs, c->adaptiveEv[0], c->adaptiveEv[1]));
+	c->adaptiveWatch.stop();
+	if ((rc = c->adaptiveWatch.read())) return rc;
 	if (!advanceAll) {
 		const float *err = (const float *)((const char *)sb.host + tileBytes);
 		const uint32_t *flag = (const uint32_t *)((const char *)sb.host + tileBytes + wordBytes);
@@ -2146,7 +2142,7 @@ int crh_adaptive_step(crh_ctx *c, const float *dev_fb, float *dev_half, int widt
 /* The kernel of the most recent step (crh_render_adaptive's included), between two events of the library's own; 0 before the first one. */
 int crh_adaptive_time_ms(crh_ctx *c, float *last_ms) {
 	if (!c || !last_ms) return fail(CRH_ERR_INVALID, "crh_adaptive_time_ms: NULL argument");
-	*last_ms = c->adaptiveLastMs;
+	*last_ms = c->adaptiveWatch.sum;          /* (adLaunch has read its lap) */
 	return CRH_OK;
 }
 
@@ -2612,8 +2608,9 @@ int crh_debug_walk_probe(crh_ctx *c, int wps, int stack_lds, int inst_lds, int f
 	HIP_TRY(hipMemcpy(c->dProbeUnits.p + 1, units.data(), units.size() * sizeof(ProbeUnit), hipMemcpyHostToDevice));
 	const size_t ovfWords = (size_t)c->cuCount * 8u * (CRH_BLOCK / 64) * CRH_OVF_WORDS_PER_WAVE;
 	if (!c->dProbeOvf) HIP_TRY(hipMalloc((void **)&c->dProbeOvf, ovfWords * sizeof(uint32_t)));
-	TimedPair ev;
-	if ((rc = c->eventPool.take(ev))) return rc;
+	TimedLease lease(c->eventPool);          /* (back in the pool wherever this function ends) */
+	if ((rc = lease.take())) return rc;
+	const TimedPair &ev = lease.ev;
 	hipError_t e = hipSuccess;
 	bool launched = false;
 	const uint32_t slots = (uint32_t)(dumpWaves * c->dumpCap);
@@ -2661,12 +2658,11 @@ int crh_debug_walk_probe(crh_ctx *c, int wps, int stack_lds, int inst_lds, int f
 	CRH_PROBE_VARIANT(7, 3, true, 3)
 	CRH_PROBE_VARIANT(8, 4, false, 3)
 #undef CRH_PROBE_VARIANT
-	if (!launched) { c->eventPool.give(ev); return fail(CRH_ERR_INVALID, "crh_debug_walk_probe: no such variant (wps, stack_lds, inst_lds)"); }
-	if (e != hipSuccess) { c->eventPool.give(ev); return fail(CRH_ERR_HIP, std::string("crh_debug_walk_probe: ") + hipGetErrorString(e)); }
+	if (!launched) return fail(CRH_ERR_INVALID, "crh_debug_walk_probe: no such variant (wps, stack_lds, inst_lds)");
+	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string("crh_debug_walk_probe: ") + hipGetErrorString(e));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	float ms = 0.0f;
 	HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
-	c->eventPool.give(ev);
 	if (ms_out) *ms_out = ms;
 	return CRH_OK;
 }

@@ -2,7 +2,8 @@
  * ctx_buffers.h — who owns a context's per-dispatch device memory (cray_hip.hip: crh_ctx). Three idioms of the host code, each said once:
  *   DevBuf<T>    a grow-only device array: "grow this buffer if the dispatch needs more";
  *   StagedBuf    a device buffer with a pinned host twin, a `done` event and an in-flight flag: the per-dispatch list staging (tile lists, the adaptive step's results);
- *   TimedPool    the {a, b} event pairs around a timed kernel (crh_kernel_time_ms), taken from a pool and given back.
+ *   TimedPool    the {a, b} event pairs around a timed kernel (crh_kernel_time_ms), taken from a pool and given back — by a TimedLease on every path that does not keep them;
+ *   Stopwatch    up to LAPS laps on a stream, read later: the events around the launches of an entry point that has one run in flight at a time (AOV, denoise, adaptive).
  * HIP runtime API only — nothing of the context, the scene or the kernels. The includer defines HIP_TRY(expr) first: it returns a non-zero int from the enclosing
  * function when expr is not hipSuccess (cray_hip.hip's sets crh_last_error; tests/emu/ctx_buffers_check.cpp includes this file over the HIP-on-CPU shim).
  * Every function that can fail returns 0 (CRH_OK) or what HIP_TRY returned. release() is explicit: a context is torn down under hipSetDevice, behind a stream drain,
@@ -92,5 +93,63 @@ struct TimedPool {
 	void release() {
 		for (const TimedPair &t : idle) { if (t.a) (void)hipEventDestroy(t.a); if (t.b) (void)hipEventDestroy(t.b); }
 		idle.clear();
+	}
+};
+/* A pair out of the pool for the length of a scope: whoever leaves the scope without keep() — every early return — gives the pair back. */
+struct TimedLease {
+	TimedPool &pool;
+	TimedPair ev;
+	bool held = false;
+	explicit TimedLease(TimedPool &p) : pool(p) {}
+	TimedLease(const TimedLease &) = delete;
+	TimedLease &operator=(const TimedLease &) = delete;
+	~TimedLease() { if (held) pool.give(ev); }
+	int take() {
+		const int rc = pool.take(ev);
+		held = rc == 0;
+		return rc;
+	}
+	/* the pair is the caller's now (the render path queues it until its times are read) */
+	TimedPair keep() { held = false; return ev; }
+};
+
+/* Up to LAPS laps between LAPS + 1 timing events on a stream: start(), a mark() behind every timed launch, stop() once the run is complete; read() waits for a
+ * complete run once and keeps its times — `laps` of them in `ms`, summed in launch order in `sum`. A run that never reached stop() (a launch failed in between)
+ * is no run: the times stay those of the last complete one, and zero laps / 0.0 before the first. */
+template <int LAPS> struct Stopwatch {
+	hipEvent_t ev[LAPS + 1] = {};
+	int marks = 0;                      /* laps recorded since start() */
+	bool fresh = false;                 /* a complete run that read() has not taken yet */
+	int laps = 0;
+	float ms[LAPS] = {};
+	float sum = 0.0f;
+	int start(hipStream_t stream) {
+		fresh = false; marks = 0;
+		for (hipEvent_t &e : ev) if (!e) HIP_TRY(hipEventCreate(&e));
+		HIP_TRY(hipEventRecord(ev[0], stream));
+		return 0;
+	}
+	int mark(hipStream_t stream) {
+		HIP_TRY(marks < LAPS ? hipSuccess : hipErrorInvalidValue);
+		HIP_TRY(hipEventRecord(ev[marks + 1], stream));
+		++marks;
+		return 0;
+	}
+	void stop() { fresh = marks > 0; }
+	int read() {
+		if (!fresh) return 0;
+		HIP_TRY(hipEventSynchronize(ev[marks]));
+		float lap[LAPS], total = 0.0f;
+		for (int i = 0; i < marks; ++i) {
+			HIP_TRY(hipEventElapsedTime(&lap[i], ev[i], ev[i + 1]));
+			total += lap[i];
+		}
+		std::copy(lap, lap + marks, ms);
+		laps = marks; sum = total; fresh = false;
+		return 0;
+	}
+	void release() {
+		for (hipEvent_t &e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+		marks = 0; fresh = false;
 	}
 };

@@ -1,5 +1,5 @@
 /* ctx_buffers_check.cpp — test infrastructure: csrc/ctx_buffers.h (the owners of a context's per-dispatch buffers) on the HIP-on-CPU shim, whose allocations are
- * malloc and new: built with -fsanitize=address,undefined (tests/test_abi.py), every overrun, use after a growth, double free and leak of the three types is an
+ * malloc and new: built with -fsanitize=address,undefined (tests/test_abi.py), every overrun, use after a growth, double free and leak of its types is an
  * error of this program — the leak check at exit is part of the assertion. */
 #include <cstdint>
 #include <cstdio>
@@ -76,10 +76,68 @@ static int timedPairs(hipStream_t stream) {
 	return 0;
 }
 
+/* what a dispatch path does with a pair: out of the pool, and back on every way out that does not keep it */
+static int leased(TimedPool &pool, bool failEarly, bool keepIt, TimedPair &kept) {
+	TimedLease lease(pool);
+	if (lease.take()) return 1;
+	if (failEarly) return 2;                           /* (a HIP_TRY between take and push) */
+	if (keepIt) kept = lease.keep();
+	return 0;
+}
+
+static int timedLease() {
+	TimedPool pool;
+	TimedPair kept;
+	if (leased(pool, true, false, kept) != 2 || pool.idle.size() != 1) return fail("TimedLease: the pair of an early return is not back in the pool");
+	const TimedPair first = pool.idle[0];
+	if (leased(pool, false, false, kept) != 0 || pool.idle.size() != 1 || pool.idle[0].a != first.a) return fail("TimedLease: a lease that ends takes the pool's pair and gives it back");
+	if (leased(pool, false, true, kept) != 0 || !pool.idle.empty() || kept.a != first.a || kept.b != first.b) return fail("TimedLease: a kept pair went back to the pool");
+	pool.give(kept);
+	pool.release();
+	return 0;
+}
+
+/* a run of `laps` laps, complete or abandoned before stop() */
+template <int LAPS> static int run(Stopwatch<LAPS> &w, hipStream_t stream, int laps, bool complete) {
+	if (w.start(stream)) return 1;
+	for (int i = 0; i < laps; ++i) if (w.mark(stream)) return 1;
+	if (complete) w.stop();
+	return 0;
+}
+
+static int stopwatch(hipStream_t stream) {
+	constexpr int MAX = 5;
+	Stopwatch<MAX> w;
+	w.release();                                       /* never started */
+	if (w.read() || w.laps != 0 || w.sum != 0.0f) return fail("Stopwatch: not zero laps and 0.0 before any run");
+	if (run(w, stream, 1, true) || w.read() || w.laps != 1 || !(w.ms[0] >= 0.0f) || w.sum != w.ms[0]) return fail("Stopwatch: a run of one lap");
+	if (run(w, stream, MAX, true)) return fail("Stopwatch: a run of the maximum number of laps");
+	if (w.laps != 1) return fail("Stopwatch: a run changed the times before read()");
+	if (w.mark(stream) == 0) return fail("Stopwatch: a lap beyond the last event");
+	if (w.read() || w.laps != MAX) return fail("Stopwatch: reading the maximum number of laps");
+	float sum = 0.0f, laps[MAX];
+	for (int i = 0; i < MAX; ++i) { if (!(w.ms[i] >= 0.0f)) return fail("Stopwatch: a lap is negative"); laps[i] = w.ms[i]; sum += w.ms[i]; }
+	if (sum != w.sum) return fail("Stopwatch: the sum is not the laps' float sum in launch order");
+	if (w.read() || w.laps != MAX || w.sum != sum || memcmp(laps, w.ms, sizeof(laps))) return fail("Stopwatch: read() twice differs");
+	if (run(w, stream, 2, false) || w.read() || w.laps != MAX || w.sum != sum || memcmp(laps, w.ms, sizeof(laps))) return fail("Stopwatch: a run that never stopped changed the times");
+	/* what a creation that failed half-way leaves: some events, not all */
+	HIP_TRY(hipEventDestroy(w.ev[2]));
+	w.ev[2] = nullptr;
+	hipEvent_t const e0 = w.ev[0];
+	if (run(w, stream, 3, true) || !w.ev[2] || w.ev[0] != e0 || w.read() || w.laps != 3) return fail("Stopwatch: start() did not complete a partial set of events");
+	const float sum3 = w.sum;
+	w.release(); w.release();
+	for (hipEvent_t e : w.ev) if (e) return fail("Stopwatch: an event after release");
+	if (w.read() || w.laps != 3 || w.sum != sum3) return fail("Stopwatch: release lost the times");
+	if (run(w, stream, 1, true) || w.read() || w.laps != 1) return fail("Stopwatch: a run after release");
+	w.release();
+	return 0;
+}
+
 int main() {
 	hipStream_t stream = nullptr;
 	HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-	if (deviceBuffer(stream) || stagedBuffer(stream) || timedPairs(stream)) return 1;
+	if (deviceBuffer(stream) || stagedBuffer(stream) || timedPairs(stream) || timedLease() || stopwatch(stream)) return 1;
 	HIP_TRY(hipStreamDestroy(stream));
 	std::printf("ctx_buffers_check ok\n");
 	return 0;

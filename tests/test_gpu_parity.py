@@ -812,6 +812,75 @@ def test_wide_walk_option_renders_the_fixtures(pkg, manifest, golden_blob, golde
         c.close()
 
 
+# crh_last_kernel_name() of every instantiation a dispatch can select, written out: (form, counter level, rare features, sampler[, waves per SIMD]) -> name
+KERNEL_NAMES = {
+    ("roll", 1, False, 0): "k_pathtrace_roll<1,4,false,0>", ("roll", 1, False, 1): "k_pathtrace_roll<1,4,false,1>",
+    ("roll", 1, True, 0): "k_pathtrace_roll<1,4,true,0>", ("roll", 1, True, 1): "k_pathtrace_roll<1,4,true,1>",
+    ("roll", 2, False, 0): "k_pathtrace_roll<2,4,false,0>", ("roll", 2, False, 1): "k_pathtrace_roll<2,4,false,1>",
+    ("roll", 2, True, 0): "k_pathtrace_roll<2,4,true,0>", ("roll", 2, True, 1): "k_pathtrace_roll<2,4,true,1>",
+    ("wide", 1, False, 0): "k_pathtrace_roll<1,4,false,0,wide4>", ("wide", 2, False, 0): "k_pathtrace_roll<2,4,false,0,wide4>",
+    ("wave", 1, False, 0, 4): "k_pathtrace<1,4,false,0>", ("wave", 1, False, 0, 1): "k_pathtrace<1,1,false,0>",
+    ("wave", 1, True, 0, 4): "k_pathtrace<1,4,true,0>", ("wave", 1, True, 0, 1): "k_pathtrace<1,1,true,0>",
+    ("wave", 2, False, 0, 4): "k_pathtrace<2,4,false,0>", ("wave", 2, False, 0, 1): "k_pathtrace<2,1,false,0>",
+    ("wave", 2, True, 0, 4): "k_pathtrace<2,4,true,0>", ("wave", 2, True, 0, 1): "k_pathtrace<2,1,true,0>",
+    # the Halton sampler has the 128-register instantiations only: waves per SIMD = 1 launches them too
+    ("wave", 1, False, 1, 4): "k_pathtrace<1,4,false,1>", ("wave", 1, False, 1, 1): "k_pathtrace<1,4,false,1>",
+    ("wave", 1, True, 1, 4): "k_pathtrace<1,4,true,1>", ("wave", 1, True, 1, 1): "k_pathtrace<1,4,true,1>",
+    ("wave", 2, False, 1, 4): "k_pathtrace<2,4,false,1>", ("wave", 2, False, 1, 1): "k_pathtrace<2,4,false,1>",
+    ("wave", 2, True, 1, 4): "k_pathtrace<2,4,true,1>", ("wave", 2, True, 1, 1): "k_pathtrace<2,4,true,1>",
+    ("wg", 1, False, 0): "k_pathtrace_wg<1,false,0>", ("wg", 1, False, 1): "k_pathtrace_wg<1,false,1>",
+    ("wg", 1, True, 0): "k_pathtrace_wg<1,true,0>", ("wg", 1, True, 1): "k_pathtrace_wg<1,true,1>",
+    ("wg", 2, False, 0): "k_pathtrace_wg<2,false,0>", ("wg", 2, False, 1): "k_pathtrace_wg<2,false,1>",
+    ("wg", 2, True, 0): "k_pathtrace_wg<2,true,0>", ("wg", 2, True, 1): "k_pathtrace_wg<2,true,1>",
+}
+
+
+def test_every_option_set_launches_the_instantiation_it_names(pkg, ctx, manifest, golden_blob):
+    """The kernel tables of cray_hip.hip: counter level x rare features (a scene without node programs, one with; CRH_FORCE_PROGRAMS makes every scene one with) x
+    sampler, the 4-ary walk, and — where the library holds them — the one-unit-at-a-time form at both register budgets and the workgroup form. Every dispatch (a
+    16 x 8 region, one pass, two bounces) reports exactly the name above, and neither the counter level nor the form changes a frame: each equals the first frame
+    of its scene and sampler bit for bit."""
+    import os
+    abi = pkg.abi
+    forced = "CRH_FORCE_PROGRAMS" in os.environ
+    forms = kernel_forms(pkg, ctx)
+    first = {}
+    try:
+        for name, wide in (("cfg1_scene", False), ("nodezoo", False), ("cfg1_scene", True)):
+            m = manifest[name]
+            w, h = m["width"], m["height"]
+            region = (w // 2 - 8, h // 2 - 4, w // 2 + 8, h // 2 + 4)
+            rare = name == "nodezoo" or forced
+            ctx.set_option(abi.OPT_WALK, abi.WALK_WIDE4 if wide else abi.WALK_BINARY)          # (what the next upload prepares)
+            ctx.upload(pkg.api.Scene(golden_blob(m.get("blob") or name)))
+            fb = ctx.framebuffer(w, h)
+            cases = [(abi.KERNEL_ROLL, 4, ("wide" if wide and not rare else "roll", level, rare, samp)) for level in (1, 2) for samp in ((0,) if wide else (0, 1))]
+            if not wide and abi.KERNEL_WAVE in forms:
+                cases += [(abi.KERNEL_WAVE, wps, ("wave", level, rare, samp, wps)) for level in (1, 2) for samp in (0, 1) for wps in (4, 1)]
+            if not wide and abi.KERNEL_WG in forms:
+                cases += [(abi.KERNEL_WG, 4, ("wg", level, rare, samp)) for level in (1, 2) for samp in (0, 1)]
+            for kernel, wps, key in cases:
+                level, samp = key[1], key[3]
+                ctx.set_option(abi.OPT_KERNEL, kernel)
+                ctx.set_option(abi.OPT_WAVES_PER_SIMD, wps)
+                ctx.set_option(abi.OPT_COUNTER_LEVEL, level)
+                ctx.set_option(abi.OPT_SAMPLER, abi.SAMPLER_HALTON if samp else abi.SAMPLER_RANDOM)
+                ctx.clear(fb, w, h)
+                ctx.render_region(fb, w, h, 1, 2, region=region)
+                img = ctx.download(fb, w, h)
+                assert ctx.last_kernel_name() == KERNEL_NAMES[key], (name, key, ctx.last_kernel_name())
+                ref = first.setdefault((name, samp), img)
+                assert np.array_equal(img.view(np.uint32), ref.view(np.uint32)), (name, key)
+            x0, y0, x1, y1 = region
+            assert first[(name, 0)][h - y1:h - y0, x0:x1].any() and not first[(name, 0)][:h - y1].any(), name          # (the region was rendered, and nothing else)
+    finally:
+        ctx.set_option(abi.OPT_WALK, abi.WALK_BINARY)
+        ctx.set_option(abi.OPT_KERNEL, abi.KERNEL_ROLL)
+        ctx.set_option(abi.OPT_WAVES_PER_SIMD, 4)
+        ctx.set_option(abi.OPT_COUNTER_LEVEL, 2)
+        ctx.set_option(abi.OPT_SAMPLER, abi.SAMPLER_RANDOM)
+
+
 @pytest.mark.parametrize("name", ["cfg2_hdr_small", "cfg4_statues_small"])
 def test_wide_walk_meets_the_tolerance_gates(name, pkg, manifest, golden_ref):
     """The 4-ary walk at north_star's own bar on two BASELINE configs: the binary walk is the bit-exact contract and the default; WIDE4 reaches
