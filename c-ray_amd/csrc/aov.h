@@ -157,12 +157,7 @@ __global__ __launch_bounds__(CRH_BLOCK, RARE ? 4 : CRH_AOV_WPS) void k_aov(const
 	AovStack stk;
 	stk.col = (lds_u32 *)&s_lane[threadIdx.x];
 	stk.ovf = (glb_u32 *)ovfAll + (size_t)__builtin_amdgcn_readfirstlane(wave) * CRH_OVF_WORDS_PER_WAVE;
-	stk.inst0 = nullptr;
-	if (CRH_AOV_INST_LDS && S.instance_count <= CRH_INST_LDS0_MAX) {
-		for (uint32_t i = threadIdx.x; i < S.instance_count * 16u; i += CRH_BLOCK) s_inst0[i] = ((const uint32_t *)(S.instances + (i >> 4)))[i & 15u];
-		__syncthreads();
-		stk.inst0 = (const lds_u32 *)s_inst0;
-	}
+	stk.inst0 = CRH_AOV_INST_LDS ? stageInstLine0(S, s_inst0) : nullptr;          /* (walk_machine.h) */
 	const lds_u32 *const waveCols = (const lds_u32 *)&s_lane[threadIdx.x & ~63u];          /* column of lane l of this wave: waveCols + l */
 	const int passEnd = P.first_pass + P.pass_count;
 	for (;;) {

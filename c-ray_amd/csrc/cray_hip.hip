@@ -245,6 +245,23 @@ __device__ __forceinline__ uint32_t waveSum(uint32_t v) {
 	for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
 	return v;
 }
+/* a wave's sum of a lane counter into a global one: one atomic per wave and counter (`lead` = the wave's lane 0) */
+__device__ __forceinline__ void flushCounter(bool lead, uint32_t laneCount, unsigned long long *counter) {
+	const uint32_t v = waveSum(laneCount);
+	if (lead && v) atomicAdd(counter, (unsigned long long)v);
+}
+/* the walk's counters (crh_counters: 1 rays; from level 2 on 2 node tests .. 6 sphere tests) */
+template <class Cnt>
+__device__ __forceinline__ void flushWalkCounters(bool lead, const Cnt &cnt, unsigned long long *counters) {
+	flushCounter(lead, cnt.rays, &counters[1]);
+	if constexpr (Cnt::level >= 2) {
+		flushCounter(lead, cnt.node_tests, &counters[2]);
+		flushCounter(lead, cnt.tri_tests, &counters[3]);
+		flushCounter(lead, cnt.inst_visits, &counters[4]);
+		flushCounter(lead, cnt.inst_hits, &counters[5]);
+		flushCounter(lead, cnt.sphere_tests, &counters[6]);
+	}
+}
 
 #define CRH_NCOUNTERS 32
 /* the counter block of a context: CRH_NCOUNTERS global 64-bit counters, then CRH_NCOUNTERS 64-bit words per wave (the rolling kernel's wave-level numbers of the counting
@@ -483,6 +500,7 @@ __global__ __launch_bounds__(CRH_BLOCK) void k_trace_rays(const DScene Sarg, con
 	}
 }
 
+#include "walk_machine.h"            /* WalkStack, walkOnlyMachine: the walk-only wave machine that k_stream_walk and k_walk_probe form 3 share */
 #include "pathtrace_stream.h"        /* k_stream_walk / k_stream_shade / k_stream_fold: the streaming form (CRH_KERNEL_STREAM, round 6) */
 #include "walk_probe.h"              /* k_walk_probe: the walk of k_pathtrace_roll on its own, on the path tracer's own rays (round 6: a measurement entry, crh_debug_walk_probe) */
 #include "aov.h"                     /* k_aov: albedo, normal, depth and coverage of every camera ray's first hit (crh_render_aov) */
@@ -2636,7 +2654,7 @@ int crh_debug_walk_probe(crh_ctx *c, int wps, int stack_lds, int inst_lds, int f
 		if ((W + 1) * want <= 163840u) return fail(CRH_ERR_INVALID, "crh_debug_walk_probe: this variant's LDS does not pin its occupancy"); \
 		const size_t pad = want - fa.sharedSizeBytes; \
 		CRH_PROBE_ALLOW_LDS((k_walk_probe<W, N, I, F>), pad); \
-		snprintf(c->lastKernel, sizeof(c->lastKernel), "k_walk_probe<%d,%d,%s,%s> vgpr %d lds %zu+%zu", W, N, I ? "true" : "false", F == 1 ? "fused" : F == 2 ? "flat" : F == 3 ? "lean1" : "lean", fa.numRegs, (size_t)fa.sharedSizeBytes, pad); \
+		snprintf(c->lastKernel, sizeof(c->lastKernel), "k_walk_probe<%d,%d,%s,%s> vgpr %d lds %zu+%zu", W, N, I ? "true" : "false", F == 1 ? "fused" : F == 3 ? "lean1" : "lean", fa.numRegs, (size_t)fa.sharedSizeBytes, pad); \
 		HIP_TRY(hipEventRecord(ev.a, c->stream)); \
 		hipLaunchKernelGGL((k_walk_probe<W, N, I, F>), dim3((uint32_t)c->cuCount * W), dim3(CRH_BLOCK), pad, c->stream, c->d, c->dDump, (const ProbeUnit *)c->dProbeUnits.p + 1, (uint32_t)units.size(), \
 		                   (uint32_t *)c->dProbeUnits.p, c->dProbeHits[slot], c->dProbeInst[slot], c->sched, c->dProbeOvf); \

@@ -375,36 +375,30 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace(const
 	}
 	/* one atomic per wave and counter */
 	const bool lead = (lane == 0);
-	uint32_t v;
-	v = waveSum(cnt.paths); if (lead && v) atomicAdd(&counters[0], (unsigned long long)v);
-	v = waveSum(cnt.rays); if (lead && v) atomicAdd(&counters[1], (unsigned long long)v);
+	flushCounter(lead, cnt.paths, &counters[0]);
+	flushWalkCounters(lead, cnt, counters);
 	if constexpr (LEVEL >= 2) {
-		v = waveSum(cnt.node_tests); if (lead && v) atomicAdd(&counters[2], (unsigned long long)v);
-		v = waveSum(cnt.tri_tests); if (lead && v) atomicAdd(&counters[3], (unsigned long long)v);
-		v = waveSum(cnt.inst_visits); if (lead && v) atomicAdd(&counters[4], (unsigned long long)v);
-		v = waveSum(cnt.inst_hits); if (lead && v) atomicAdd(&counters[5], (unsigned long long)v);
-		v = waveSum(cnt.sphere_tests); if (lead && v) atomicAdd(&counters[6], (unsigned long long)v);
-		v = waveSum(cnt.tex_fetches); if (lead && v) atomicAdd(&counters[7], (unsigned long long)v);
+		flushCounter(lead, cnt.tex_fetches, &counters[7]);
 		if (lead) {   /* debug phase clocks: one sample per wave (lane 0) */
 			atomicAdd(&counters[8], (unsigned long long)cnt.t_setup);
 			atomicAdd(&counters[9], (unsigned long long)cnt.t_trav);
 			atomicAdd(&counters[10], (unsigned long long)cnt.t_shade);
 		}
-		v = waveSum(cnt.w_node); if (lead && v) atomicAdd(&counters[11], (unsigned long long)v);
-		v = waveSum(cnt.w_tri); if (lead && v) atomicAdd(&counters[12], (unsigned long long)v);
-		v = waveSum(cnt.w_ctrl); if (lead && v) atomicAdd(&counters[13], (unsigned long long)v);
-		v = waveSum(cnt.w_round); if (lead && v) atomicAdd(&counters[14], (unsigned long long)v);
-		v = waveSum(cnt.w_shade); if (lead && v) atomicAdd(&counters[15], (unsigned long long)v);
-		v = waveSum(cnt.w_setup); if (lead && v) atomicAdd(&counters[16], (unsigned long long)v);
-		v = waveSum(cnt.u_node); if (lead && v) atomicAdd(&counters[17], (unsigned long long)v);
-		v = waveSum(cnt.u_shade); if (lead && v) atomicAdd(&counters[18], (unsigned long long)v);
-		v = waveSum(cnt.t_swap); if (lead && v) atomicAdd(&counters[19], (unsigned long long)v);
-		v = waveSum(cnt.t_gen); if (lead && v) atomicAdd(&counters[20], (unsigned long long)v);
-		v = waveSum(cnt.n_swap); if (lead && v) atomicAdd(&counters[21], (unsigned long long)v);
-		v = waveSum(cnt.n_gen); if (lead && v) atomicAdd(&counters[22], (unsigned long long)v);
-		v = waveSum(cnt.u_swap); if (lead && v) atomicAdd(&counters[23], (unsigned long long)v);
-		v = waveSum(cnt.u_tri); if (lead && v) atomicAdd(&counters[24], (unsigned long long)v);
-		v = waveSum(cnt.u_ctrl); if (lead && v) atomicAdd(&counters[25], (unsigned long long)v);
+		flushCounter(lead, cnt.w_node, &counters[11]);
+		flushCounter(lead, cnt.w_tri, &counters[12]);
+		flushCounter(lead, cnt.w_ctrl, &counters[13]);
+		flushCounter(lead, cnt.w_round, &counters[14]);
+		flushCounter(lead, cnt.w_shade, &counters[15]);
+		flushCounter(lead, cnt.w_setup, &counters[16]);
+		flushCounter(lead, cnt.u_node, &counters[17]);
+		flushCounter(lead, cnt.u_shade, &counters[18]);
+		flushCounter(lead, cnt.t_swap, &counters[19]);
+		flushCounter(lead, cnt.t_gen, &counters[20]);
+		flushCounter(lead, cnt.n_swap, &counters[21]);
+		flushCounter(lead, cnt.n_gen, &counters[22]);
+		flushCounter(lead, cnt.u_swap, &counters[23]);
+		flushCounter(lead, cnt.u_tri, &counters[24]);
+		flushCounter(lead, cnt.u_ctrl, &counters[25]);
 	}
 }
 
@@ -776,16 +770,10 @@ __global__ __launch_bounds__(CRH_BLOCK, 4) void k_pathtrace_wg(const DScene Sarg
 		__syncthreads();                           /* everyone has read CT_UNIT before thread 0 replaces it */
 	}
 	const bool lead = (lane == 0);
-	uint32_t v;
-	v = waveSum(cnt.paths); if (lead && v) atomicAdd(&counters[0], (unsigned long long)v);
-	v = waveSum(cnt.rays); if (lead && v) atomicAdd(&counters[1], (unsigned long long)v);
+	flushCounter(lead, cnt.paths, &counters[0]);
+	flushWalkCounters(lead, cnt, counters);
 	if constexpr (LEVEL >= 2) {
-		v = waveSum(cnt.node_tests); if (lead && v) atomicAdd(&counters[2], (unsigned long long)v);
-		v = waveSum(cnt.tri_tests); if (lead && v) atomicAdd(&counters[3], (unsigned long long)v);
-		v = waveSum(cnt.inst_visits); if (lead && v) atomicAdd(&counters[4], (unsigned long long)v);
-		v = waveSum(cnt.inst_hits); if (lead && v) atomicAdd(&counters[5], (unsigned long long)v);
-		v = waveSum(cnt.sphere_tests); if (lead && v) atomicAdd(&counters[6], (unsigned long long)v);
-		v = waveSum(cnt.tex_fetches); if (lead && v) atomicAdd(&counters[7], (unsigned long long)v);
+		flushCounter(lead, cnt.tex_fetches, &counters[7]);
 	}
 }
 

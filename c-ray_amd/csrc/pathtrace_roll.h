@@ -663,16 +663,10 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 	}
 	const bool lead = (lane == 0);
 	if constexpr (LEVEL >= 2) { if (dumpRays && lead) waveStats[CRH_DUMP_HDR + 2 + wave] = min(dumpCount, dumpCap); }
-	uint32_t v;
-	v = waveSum(cnt.paths); if (lead && v) atomicAdd(&counters[0], (unsigned long long)v);
-	v = waveSum(cnt.rays); if (lead && v) atomicAdd(&counters[1], (unsigned long long)v);
+	flushCounter(lead, cnt.paths, &counters[0]);
+	flushWalkCounters(lead, cnt, counters);
 	if constexpr (LEVEL >= 2) {
-		v = waveSum(cnt.node_tests); if (lead && v) atomicAdd(&counters[2], (unsigned long long)v);
-		v = waveSum(cnt.tri_tests); if (lead && v) atomicAdd(&counters[3], (unsigned long long)v);
-		v = waveSum(cnt.inst_visits); if (lead && v) atomicAdd(&counters[4], (unsigned long long)v);
-		v = waveSum(cnt.inst_hits); if (lead && v) atomicAdd(&counters[5], (unsigned long long)v);
-		v = waveSum(cnt.sphere_tests); if (lead && v) atomicAdd(&counters[6], (unsigned long long)v);
-		v = waveSum(cnt.tex_fetches); if (lead && v) atomicAdd(&counters[7], (unsigned long long)v);
+		flushCounter(lead, cnt.tex_fetches, &counters[7]);
 	}
 }
 #undef CRH_WCTR

@@ -6,7 +6,7 @@
  * The paths live in a POOL in global memory: `cohorts` x 1024 slots, one path per slot, structure-of-arrays in four 16-byte planes (origin | depth, direction | item,
  * weight | sampler lo, radiance | sampler hi — the four quarters of the megakernel's path record) so that the 64 lanes of a wave read and write consecutive 16-byte words.
  * There are two pools; an ITERATION reads one and writes the other:
- *   k_stream_walk   persistent waves (the walk-only machine of walk_probe.h, one site per step kind): a unit = 128 consecutive slots of a cohort; lanes take rays from the
+ *   k_stream_walk   persistent waves (the walk-only machine of walk_machine.h, one site per step kind): a unit = 128 consecutive slots of a cohort; lanes take rays from the
  *                   unit in hand as they fall idle, walk them with the megakernel's lane code (walkBegin / stepNode / stepTri / stepCtrl), and leave the closest hit
  *                   (t, u, v, prim slot | instance) in the slot's hit record.
  *   k_stream_shade  one workgroup per cohort (persistent, cohorts from a counter): sorts the cohort's slots into surface hits and misses (an ordered list in LDS), runs
@@ -93,36 +93,6 @@ CRH_DEV void streamPixel(const StreamPlan &Pl, uint32_t p, int &x, int &y) {
 	streamPixelOf(Pl.tiles[lo], p - Pl.start[lo], x, y);
 }
 
-/* the walk kernel's traversal stack: NLDS entries in LDS (entry-major), deeper ones in the wave's overflow columns; the 15 park slots; line 0 of the instance records in LDS
- * when the scene has at most CRH_INST_LDS0_MAX instances (INST) */
-template <int NLDS, bool INST>
-struct WalkStack {
-	lds_u32 *lds;
-	lds_u32 *parkp;
-	glb_u32 *ovf;
-	const lds_u32 *inst0;
-	__device__ __forceinline__ InstLine instLine(const DScene &S, int32_t idx, int line) const {
-		if (INST && line == 0 && inst0) {
-			const lds_u32 *p = inst0 + (uint32_t)idx * 16u;
-			return InstLine{ldsLoadF4(p), ldsLoadF4(p + 4), ldsLoadF4(p + 8), ldsLoadF4(p + 12)};
-		}
-		const f4 *g = (const f4 *)(S.instances + idx) + 4 * line;
-		return InstLine{g[0], g[1], g[2], g[3]};
-	}
-	__device__ __forceinline__ void park(int i, uint32_t v) { parkp[i * CRH_BLOCK] = v; }
-	__device__ __forceinline__ uint32_t unpark(int i) { return parkp[i * CRH_BLOCK]; }
-	__device__ __forceinline__ void push(uint32_t i, uint32_t v) {
-		if (__builtin_expect(i < (uint32_t)NLDS, 1)) lds[i * CRH_BLOCK] = v;
-		else ovf[(i - (uint32_t)NLDS) * 64u + (threadIdx.x & 63u)] = v;
-	}
-	__device__ __forceinline__ uint32_t pop(uint32_t i) {
-		uint32_t v;
-		if (__builtin_expect(i < (uint32_t)NLDS, 1)) v = lds[i * CRH_BLOCK];
-		else v = ovf[(i - (uint32_t)NLDS) * 64u + (threadIdx.x & 63u)];
-		return v;
-	}
-};
-
 /* start of a dispatch: the pools empty, the ring's first slabs waiting for the first chunks, the tile list (tiles, then their first pixels) fetched from the host's pinned copy */
 __global__ void k_stream_init(const StreamPlan Pl, uint32_t *countA, uint32_t *countB, StreamCtl *ctl, const uint32_t *listHost, uint32_t *listDev, uint32_t listWords) {
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < Pl.cohorts; i += gridDim.x * blockDim.x) { countA[i] = 0u; countB[i] = 0u; }
@@ -135,7 +105,42 @@ __global__ void k_stream_init(const StreamPlan Pl, uint32_t *countA, uint32_t *c
 	}
 }
 
-/* WALK. WPS / NLDS / INST as in walk_probe.h (the kernel is its form 3: a lean run with one site per step kind); LEVEL: counter level (1: rays; 2: every walk counter) */
+/* the walk kernel's ray source (walk_machine.h): a unit = CRH_SF_UNIT consecutive slots of a cohort of the pool the iteration reads, of which the cohort's live ones hold rays */
+struct StreamSource : WalkSource {
+	const f4 *rayO, *rayD;
+	const uint32_t *count;
+	StreamCtl *ctl;
+	uint32_t nUnits;
+	uint32_t part, partsDry = 0;                 /* wave-uniform: the counter in use, and how many have been seen dry */
+	static constexpr uint32_t unitsPerCohort = CRH_SF_COHORT / CRH_SF_UNIT;
+	__device__ __forceinline__ StreamSource(const StreamPool &in, StreamCtl *ctl_, uint32_t cohorts, uint32_t wave)
+		: rayO(asGlobal(in.p0)), rayD(asGlobal(in.p1)), count(asGlobal(in.count)), ctl(ctl_), nUnits(cohorts * unitsPerCohort), part(wave & (CRH_SF_COUNTERS - 1u)) {}
+	__device__ __forceinline__ void fill() {
+		for (int tries = 0; tries < 8 && cur == end && !dry; ++tries) {          /* (a unit beyond its cohort's live slots is empty: try the next one) */
+			/* the units are dealt over CRH_SF_COUNTERS counters (unit = k * CRH_SF_COUNTERS + counter: sixteen addresses, sixteen L2 channels — one counter served an
+			 * atomic every 15 ns, a floor of 2 ms per iteration whatever the pool held); a wave starts at its own counter and moves on when one runs out */
+			uint32_t k = 0;
+			if ((threadIdx.x & 63u) == 0) k = atomicAdd((uint32_t *)&ctl->walkCtr[part * CRH_SF_CTR_STRIDE], 1u);
+			k = __builtin_amdgcn_readfirstlane(k);
+			const uint32_t u = k * CRH_SF_COUNTERS + part;
+			if (u < nUnits) {
+				const uint32_t t = u / unitsPerCohort, off = (u % unitsPerCohort) * CRH_SF_UNIT;
+				const uint32_t n = __builtin_amdgcn_readfirstlane(count[t]);
+				if (off < n) { cur = t * CRH_SF_COHORT + off; end = t * CRH_SF_COHORT + (n < off + CRH_SF_UNIT ? n : off + CRH_SF_UNIT); }
+			} else {
+				part = (part + 1u) & (CRH_SF_COUNTERS - 1u);
+				if (++partsDry == CRH_SF_COUNTERS) dry = true;          /* every counter has run past its last unit */
+			}
+		}
+	}
+	__device__ __forceinline__ void ray(uint32_t i, v3 &o, v3 &d) const {
+		const f4 q0 = rayO[i], q1 = rayD[i];
+		o = v3{q0.x, q0.y, q0.z}; d = v3{q1.x, q1.y, q1.z};
+	}
+};
+
+/* WALK: persistent waves of the walk-only machine (walk_machine.h) on the pool's slots. WPS = waves per SIMD the register allocator must leave room for, NLDS = traversal-stack
+ * entries in LDS, INST = line 0 of the instance records staged in LDS (as in walk_probe.h, which measured them); LEVEL: counter level (1: rays; 2: every walk counter) */
 template <int WPS, int NLDS, bool INST, int LEVEL>
 __global__ __launch_bounds__(CRH_BLOCK, WPS) void k_stream_walk(const DScene Sarg, const StreamPool in, f4 *hitsArg, int32_t *hitInstArg, uint32_t cohorts, StreamCtl *ctlArg,
                                                                 const Sched K, uint32_t *ovfAll, unsigned long long *counters) {
@@ -145,22 +150,11 @@ __global__ __launch_bounds__(CRH_BLOCK, WPS) void k_stream_walk(const DScene Sar
 	StreamCtl *const ctl = (StreamCtl *)(__attribute__((address_space(1))) StreamCtl *)ctlArg;
 	if (ctl->liveIn == 0u) return;               /* nothing to walk (the first iteration of a dispatch, and the iterations a group holds beyond the dispatch's end) */
 	const DScene S = globalize(Sarg);
-	const f4 *const rayO = asGlobal(in.p0), *const rayD = asGlobal(in.p1);
-	const uint32_t *const count = asGlobal(in.count);
 	f4 *const hits = (f4 *)(__attribute__((address_space(1))) f4 *)hitsArg;
 	int32_t *const hitInst = (int32_t *)(__attribute__((address_space(1))) int32_t *)hitInstArg;
 	WalkStack<NLDS, INST> stk;
-	stk.lds = (lds_u32 *)&s_stack[threadIdx.x];
-	stk.parkp = (lds_u32 *)&s_park[threadIdx.x];
-	stk.inst0 = nullptr;
-	if (INST && S.instance_count <= CRH_INST_LDS0_MAX) {
-		for (uint32_t i = threadIdx.x; i < S.instance_count * 16u; i += CRH_BLOCK) s_inst0[i] = ((const uint32_t *)(S.instances + (i >> 4)))[i & 15u];
-		__syncthreads();
-		stk.inst0 = (const lds_u32 *)s_inst0;
-	}
-	const uint32_t lane = threadIdx.x & 63u;
-	const uint32_t wave = (blockIdx.x * CRH_BLOCK + threadIdx.x) >> 6;
-	stk.ovf = (glb_u32 *)ovfAll + (size_t)__builtin_amdgcn_readfirstlane(wave) * CRH_OVF_WORDS_PER_WAVE;
+	walkStackPoint(stk, s_stack, s_park, ovfAll);
+	stk.inst0 = INST ? stageInstLine0(S, s_inst0) : nullptr;
 	CountersT<LEVEL, false, false> cnt;
 	memset(&cnt, 0, sizeof(cnt));
 	NullPort port;                               /* (scenes with volumes — a sampler draw inside the walk — are rendered by the other kernel form) */
@@ -168,84 +162,11 @@ __global__ __launch_bounds__(CRH_BLOCK, WPS) void k_stream_walk(const DScene Sar
 	memset(&w, 0, sizeof(w));
 	w.phase = PH_IDLE;
 	uint32_t mySlot = 0;
-	uint32_t cur = 0, end = 0;                   /* wave-uniform: the slots of the unit in hand whose rays have not started */
-	bool dry = false;                            /* wave-uniform: every counter has run past its last unit */
-	uint32_t part = __builtin_amdgcn_readfirstlane(wave) & (CRH_SF_COUNTERS - 1u), partsDry = 0;          /* wave-uniform: the counter in use, and how many have been seen dry */
-	const uint32_t unitsPerCohort = CRH_SF_COHORT / CRH_SF_UNIT, nUnits = cohorts * unitsPerCohort;
-	/* retire + refill (pathtrace_roll.h: retireRefill): lanes whose walk ended leave the hit in their slot's record; they and the idle lanes take the next rays of the unit in hand */
-	auto retireRefill = [&]() __attribute__((always_inline)) {
-		if (w.phase == PH_SHADE) {
-			hits[mySlot] = f4{w.hit.t, w.hit.u, w.hit.v, asF32((uint32_t)w.hit.slot)};
-			hitInst[mySlot] = w.hit.inst;
-			w.phase = PH_IDLE;
-		}
-		const bool idle = (w.phase == PH_IDLE);
-		const unsigned long long em = __ballot(idle);
-		const uint32_t er = laneRank(em);
-		for (int tries = 0; tries < 8 && cur == end && !dry; ++tries) {          /* (a unit beyond its cohort's live slots is empty: try the next one) */
-			/* the units are dealt over CRH_SF_COUNTERS counters (unit = k * CRH_SF_COUNTERS + counter: sixteen addresses, sixteen L2 channels — one counter served an
-			 * atomic every 15 ns, a floor of 2 ms per iteration whatever the pool held); a wave starts at its own counter and moves on when one runs out */
-			uint32_t k = 0;
-			if (lane == 0) k = atomicAdd((uint32_t *)&ctl->walkCtr[part * CRH_SF_CTR_STRIDE], 1u);
-			k = __builtin_amdgcn_readfirstlane(k);
-			const uint32_t u = k * CRH_SF_COUNTERS + part;
-			if (u < nUnits) {
-				const uint32_t t = u / unitsPerCohort, off = (u % unitsPerCohort) * CRH_SF_UNIT;
-				const uint32_t n = __builtin_amdgcn_readfirstlane(count[t]);
-				if (off < n) { cur = t * CRH_SF_COHORT + off; end = t * CRH_SF_COHORT + (n < off + CRH_SF_UNIT ? n : off + CRH_SF_UNIT); }
-			} else {
-				part = (part + 1u) & (CRH_SF_COUNTERS - 1u);
-				if (++partsDry == CRH_SF_COUNTERS) dry = true;
-			}
-		}
-		const uint32_t take = min(end - cur, (uint32_t)__popcll(em));
-		if (idle && er < take) {
-			mySlot = cur + er;
-			const f4 q0 = rayO[mySlot], q1 = rayD[mySlot];
-			walkBegin(S, w, stk, v3{q0.x, q0.y, q0.z}, v3{q1.x, q1.y, q1.z}, cnt, port, (uint32_t)K.rayFlags);
-		}
-		cur += take;
-	};
-	for (;;) {
-		const uint32_t ph = w.phase;
-		const int nN = __popcll(__ballot(ph == PH_NODE)), nT = __popcll(__ballot(ph == PH_TRI)), nC = __popcll(__ballot(ph == PH_CTRL || ph == PH_NODE_SLOW));
-		const int nF = __popcll(__ballot(ph == PH_SHADE));
-		const int nE = 64 - nN - nT - nC - nF;
-		const int walkers = nN + nT + nC;
-		const bool more = !dry || cur != end;
-		if (walkers == 0 && nF == 0 && !more) break;
-		/* the round picks a mode by the megakernel's rules — 0 a node run (which serves triangle, instance-entry and retire / refill steps in place once enough lanes wait
-		 * for them), 1 a triangle run, 2 one control step, 3 retire + refill — and ONE loop body serves all four, so that the register allocator sees the largest step and not
-		 * the sum of the copies (72 VGPRs; the megakernel's fused node run needs 126) */
-		int mode = 0;
-		if (walkers == 0 || (nF + nE >= K.swapMin && (nF > 0 || more))) mode = 3;
-		else { int best = nN * K.wNode; if (nT * K.wTri > best) { best = nT * K.wTri; mode = 1; } if (nC * K.wCtrl > best) mode = 2; }
-		const int n0 = mode == 1 ? nT : nN;
-		bool again;
-		do {
-			if (mode == 0 && w.phase == PH_NODE) stepNode<true>(S, w, stk, cnt, port);
-			const int nTw = (int)__popcll(__ballot(w.phase == PH_TRI));
-			if (mode == 1 || (mode == 0 && nTw >= K.triInRun)) { if (w.phase == PH_TRI) stepTri(S, w, stk, cnt, port); }
-			const int nCw = (int)__popcll(__ballot(w.phase == PH_CTRL));
-			if (mode == 2 || (mode == 0 && nCw >= K.ctrlInRun)) {
-				if (w.phase == PH_CTRL) stepCtrl(S, w, stk, cnt, port);
-				if (mode == 2 && __ballot(w.phase == PH_NODE_SLOW)) { if (w.phase == PH_NODE_SLOW) stepNodeAny<false>(S, w, stk, cnt, port); }
-			}
-			const int nFi = (int)__popcll(__ballot(w.phase == PH_SHADE)), nEi = (int)__popcll(__ballot(w.phase == PH_IDLE));
-			if (mode == 3 || (mode == 0 && nFi + nEi >= K.swapInRun && (nFi > 0 || !dry || cur != end))) retireRefill();
-			again = mode == 0 ? (int)__popcll(__ballot(w.phase == PH_NODE)) * 8 >= n0 * K.runNum : mode == 1 ? (int)__popcll(__ballot(w.phase == PH_TRI)) * 8 >= n0 * K.runNum : false;
-		} while (again);
-	}
-	const bool lead = (lane == 0);
-	uint32_t v;
-	v = waveSum(cnt.rays); if (lead && v) atomicAdd(&counters[1], (unsigned long long)v);
-	if constexpr (LEVEL >= 2) {
-		v = waveSum(cnt.node_tests); if (lead && v) atomicAdd(&counters[2], (unsigned long long)v);
-		v = waveSum(cnt.tri_tests); if (lead && v) atomicAdd(&counters[3], (unsigned long long)v);
-		v = waveSum(cnt.inst_visits); if (lead && v) atomicAdd(&counters[4], (unsigned long long)v);
-		v = waveSum(cnt.inst_hits); if (lead && v) atomicAdd(&counters[5], (unsigned long long)v);
-		v = waveSum(cnt.sphere_tests); if (lead && v) atomicAdd(&counters[6], (unsigned long long)v);
-	}
+	StreamSource src(in, ctl, cohorts, __builtin_amdgcn_readfirstlane((blockIdx.x * CRH_BLOCK + threadIdx.x) >> 6));
+	auto retireRefill = [&]() __attribute__((always_inline)) { walkRetireRefill(S, w, stk, cnt, port, K, src, hits, hitInst, mySlot); };
+	auto moreRays = [&]() __attribute__((always_inline)) { return src.more(); };
+	walkOnlyMachine(S, w, stk, cnt, port, K, retireRefill, moreRays);
+	flushWalkCounters((threadIdx.x & 63u) == 0, cnt, counters);
 }
 
 /* SHADE + REFILL: pathtrace.c:39-57 on the walked paths of one pool, their continuations and the camera rays that take the freed slots into the other pool */
@@ -461,10 +382,8 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_STREAM_SHADE_WPS) void k_stream_shad
 			}
 		}
 	}
-	const bool lead = (lane == 0);
-	uint32_t v;
-	v = waveSum(cnt.paths); if (lead && v) atomicAdd(&counters[0], (unsigned long long)v);
-	if constexpr (LEVEL >= 2) { v = waveSum(cnt.tex_fetches); if (lead && v) atomicAdd(&counters[7], (unsigned long long)v); }
+	flushCounter(lane == 0, cnt.paths, &counters[0]);
+	if constexpr (LEVEL >= 2) flushCounter(lane == 0, cnt.tex_fetches, &counters[7]);
 }
 
 /* FOLD: the chunks that are complete and next in order go into the frame, pass by pass (renderer.c:288-291); the last workgroup through frees their ring slots, resets the

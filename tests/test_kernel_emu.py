@@ -39,6 +39,7 @@ GPU_TIER_JOBS = {     # name -> (files of the GPU tier, -k selection, number of 
     "frames": (["test_gpu_parity.py"], "test_image_parity_vs_reference", 7),
     "schedules": (["test_gpu_parity.py"], "shade_class_batches or dispatch_decompositions or split_pixels or interactive_mode or edge_cases or zero_component or srgb8_matches or error_paths or round_limit or upload_lifecycle or wide_walk_option or buffers_are_reused or every_option_set", 15),
     "stream": (["test_gpu_parity.py"], "streaming_form or wide_walk_meets", 3),          # round 6: the streaming form (walk / shade + refill / fold kernels) against the rolling kernel and the fixtures; the 4-ary walk inside the tolerance gates
+    "walk_probe": (["test_gpu_parity.py"], "test_walk_probe_equals_the_plain_walk", 2),          # k_walk_probe in every variant of the measurement (forms 0 and 1, and form 3: the walk-only machine of csrc/walk_machine.h from the probe's ray source) against the one-ray-per-lane walk, on both fixtures. Measured: 60 s alone, 159 s beside the module's other children on 8 CPUs, where `schedules`, the slowest, takes 391 s
     "rare_and_wg": (["test_nodes.py", "test_volumes.py", "test_gpu_parity.py"], "test_gpu_node_zoo or test_gpu_volumes", 3),          # (test_gpu_volumes renders with both kernel forms;
     # test_workgroup_kernel_is_bit_identical_to_the_wave_kernel passes here too, but the lock's polling takes a minute of emulation)
     "bvh": (["test_bvh_build.py"], "not cfg2_hdr and not soup_1m", 8),
@@ -142,6 +143,12 @@ def test_streaming_form_on_emulation(children):
     """CRH_KERNEL_STREAM (csrc/pathtrace_stream.h): the three kernels and the host loop that feeds them, bit-identical to the rolling kernel and to the reference's fixtures
     for pool sizes from one cohort up; the 4-ary walk at SURVEY 8(c)'s gates on two BASELINE configs."""
     run_gpu_tier_on_emulation(children, "stream")
+
+
+def test_walk_probe_on_emulation(children):
+    """k_walk_probe (csrc/walk_probe.h) on the rolling kernel's own rays of two fixtures: form 3 is the walk-only machine of csrc/walk_machine.h, the one k_stream_walk runs,
+    fed from the probe's unit queue; forms 0 and 1 call the same retire + refill from their own rounds. Every hit equals the one-ray-per-lane walk's, bit for bit."""
+    run_gpu_tier_on_emulation(children, "walk_probe")
 
 
 def test_node_programs_volumes_and_the_workgroup_kernel_on_emulation(children):
