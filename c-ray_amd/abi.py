@@ -132,6 +132,13 @@ class AdaptiveParams(C.Structure):
     _fields_ = [("min_passes", C.c_int32), ("threshold", C.c_float)]
 
 
+class AdaptiveCellsParams(C.Structure):
+    """crh_adaptive_cells_params (crh_adaptive_cells_params_default fills the defaults)."""
+    _fields_ = [("min_passes", C.c_int32), ("threshold", C.c_float), ("cell", C.c_int32), ("dilate", C.c_int32)]
+
+ADAPTIVE_CELLS_MAX = 1024          # CRH_ADAPTIVE_CELLS_MAX: cells one rectangle may hold
+
+
 # numpy dtype of crh_hit for bulk comparisons
 HIT_DTYPE = [("inst", "<i4"), ("poly", "<i4"), ("distance", "<f4"), ("uv", "<f4", (2,)), ("point", "<f4", (3,)),
              ("normal", "<f4", (3,)), ("node_tests", "<u4"), ("tri_tests", "<u4"), ("material", "<u4")]
@@ -149,6 +156,7 @@ EXPORTED_SYMBOLS = [
     "crh_denoise_params_default", "crh_denoise", "crh_denoise_time_ms", "crh_debug_denoise_launch_ms",
     "crh_denoise_variance_params_default", "crh_denoise_variance", "crh_framebuffer_copy",
     "crh_adaptive_step", "crh_adaptive_time_ms", "crh_adaptive_params_default", "crh_render_adaptive",
+    "crh_adaptive_cell_offsets", "crh_adaptive_step_cells", "crh_adaptive_cells_params_default", "crh_render_adaptive_cells",
     "crh_debug_ray_dump", "crh_debug_ray_dump_counts", "crh_debug_ray_dump_fetch", "crh_debug_walk_probe", "crh_debug_walk_probe_fetch", "crh_debug_walk_probe_compare",
 ]
 MATH_FUNCTIONS = ("sinf", "cosf", "sincosf_sin", "sincosf_cos", "logf", "log10f", "atanf", "acosf", "asinf", "tanf", "powf", "atan2f")   # enum crh_math_function

@@ -86,6 +86,12 @@ def library():
         "crh_adaptive_params_default": (None, [C.POINTER(abi.AdaptiveParams)]),
         "crh_render_adaptive": (C.c_int, [ctx, C.POINTER(abi.RenderParams), C.POINTER(abi.Tile), C.c_uint32, C.POINTER(abi.AdaptiveParams), C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
+        "crh_adaptive_cell_offsets": (C.c_int64, [C.POINTER(abi.Tile), C.c_uint32, C.c_int, C.c_void_p]),
+        "crh_adaptive_step_cells": (C.c_int, [ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(abi.Tile), C.c_uint32, C.c_int, C.c_float, C.c_int, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+        "crh_adaptive_cells_params_default": (None, [C.POINTER(abi.AdaptiveCellsParams)]),
+        "crh_render_adaptive_cells": (C.c_int, [ctx, C.POINTER(abi.RenderParams), C.POINTER(abi.Tile), C.c_uint32, C.POINTER(abi.AdaptiveCellsParams), C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
         "crh_synchronize": (C.c_int, [ctx]),
         "crh_frames_reduce": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
         "crh_frames_gather": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -134,6 +140,29 @@ def sample_count_map(width, height, tiles, passes):
     out = np.zeros((height, width), np.int32)
     for (x0, y0, x1, y1), n in zip(tiles, passes):
         out[height - y1:height - y0, x0:x1] = n
+    return out
+
+
+def adaptive_cell_offsets(tiles, cell):
+    """crh_adaptive_cell_offsets: the uint32 [n + 1] index of every rectangle's first cell in the cell-granular arrays (the last entry is the total): a rectangle
+    of tw x th pixels holds ceil(tw / cell) x ceil(th / cell) cells, rows of cells from its first stored row down, x ascending within a row."""
+    n = len(tiles)
+    arr = (abi.Tile * n)(*[abi.Tile(*t) for t in tiles]) if n else None
+    out = np.zeros(n + 1, np.uint32)
+    total = library().crh_adaptive_cell_offsets(arr, n, cell, out.ctypes.data)
+    if total < 0:
+        _check(int(total), "crh_adaptive_cell_offsets")
+    return out
+
+
+def sample_count_map_cells(width, height, tiles, cell, cell_passes):
+    """sample_count_map for Context.render_adaptive_cells' per-cell pass counts: the int32 [height, width] map, 0 where no rectangle lies."""
+    out = np.zeros((height, width), np.int32)
+    offsets = adaptive_cell_offsets(tiles, cell)
+    for (x0, y0, x1, y1), first in zip(tiles, offsets):
+        cx, cy = -(-(x1 - x0) // cell), -(-(y1 - y0) // cell)
+        counts = np.asarray(cell_passes[int(first):int(first) + cx * cy], np.int32).reshape(cy, cx)
+        out[height - y1:height - y0, x0:x1] = np.repeat(np.repeat(counts, cell, 0), cell, 1)[:y1 - y0, :x1 - x0]
     return out
 
 
@@ -372,6 +401,36 @@ class Context:
         arr = (abi.Tile * n)(*[abi.Tile(*t) for t in tiles]) if n else None
         count, errors = np.zeros(n, np.int32), np.zeros(n, np.float32)
         _check(self.L.crh_render_adaptive(self.h, C.byref(p), arr, n, C.byref(a), fb, half, count.ctypes.data, errors.ctypes.data), "crh_render_adaptive")
+        return count, errors
+
+    # ---- ... at cell granularity within each rectangle (crh_adaptive_step_cells, crh_render_adaptive_cells) ----
+    def adaptive_step_cells(self, fb, half, width, height, tiles, cell, threshold, dilate=0, live=None):
+        """One step over the cells of `tiles` (adaptive_cell_offsets gives their order): (errors float32 [cells], flags bool [cells]). A live cell goes on when its
+        error is not <= threshold or, with dilate, when that holds for one of its neighbours in the same rectangle; where it goes on, half := fb over it.
+        live: one truth value per cell (None: all). Waits for the result. threshold = inf measures only."""
+        n = len(tiles)
+        total = int(adaptive_cell_offsets(tiles, cell)[-1])
+        arr = (abi.Tile * n)(*[abi.Tile(*t) for t in tiles]) if n else None
+        errors, flags = np.zeros(total, np.float32), np.zeros(total, np.uint8)
+        mask = None
+        if live is not None:
+            mask = np.ascontiguousarray(np.asarray(live).astype(bool).astype(np.uint8))
+            if mask.shape != (total,):
+                raise ValueError(f"adaptive_step_cells(): live has shape {mask.shape}, the rectangles hold {total} cells")
+        _check(self.L.crh_adaptive_step_cells(self.h, fb, half, width, height, arr, n, cell, threshold, int(dilate), None if mask is None else mask.ctypes.data,
+                                              errors.ctypes.data, flags.ctypes.data), "crh_adaptive_step_cells")
+        return errors, flags.astype(bool)
+
+    def render_adaptive_cells(self, fb, half, width, height, max_samples, bounces, tiles, min_passes=16, threshold=0.05, cell=16, dilate=1, passes=None):
+        """crh_render_adaptive_cells: render_adaptive with the cell as the unit of decision inside every rectangle. Returns (passes per cell int32 [cells], error per
+        cell float32 [cells]) in adaptive_cell_offsets' order; fb holds each cell's mean of its passes, half the mean of the first half of them."""
+        n = len(tiles)
+        total = int(adaptive_cell_offsets(tiles, cell)[-1])
+        p = abi.RenderParams(0, 0, 0, 0, width, height, 0, max_samples if passes is None else passes, max_samples, bounces)
+        a = abi.AdaptiveCellsParams(min_passes, threshold, cell, int(dilate))
+        arr = (abi.Tile * n)(*[abi.Tile(*t) for t in tiles]) if n else None
+        count, errors = np.zeros(total, np.int32), np.zeros(total, np.float32)
+        _check(self.L.crh_render_adaptive_cells(self.h, C.byref(p), arr, n, C.byref(a), fb, half, count.ctypes.data, errors.ctypes.data), "crh_render_adaptive_cells")
         return count, errors
 
     def adaptive_time_ms(self):

@@ -96,3 +96,137 @@ __global__ __launch_bounds__(CRH_BLOCK) void k_adaptive_step(const AdaptiveArgs 
 #undef CRH_AD_LOAD
 #undef CRH_AD_STORE
 }
+
+/* ---- k_adaptive_cells: the same step at cell granularity within each rectangle (crh_adaptive_step_cells, crh_render_adaptive_cells) ----------------------
+ *
+ * The rectangle stays the unit of work and of the interface; inside it the decision is made per cell of `cell` x `cell` pixels (anchored at the rectangle's first
+ * stored row and first column; the last column and the last stored rows are ragged), optionally widened by one cell: a live cell goes on when it is hot — its
+ * error is not <= the threshold — or, with `dilate`, when one of its up to eight neighbours in the same rectangle's grid is.
+ *
+ * One 256-thread workgroup per rectangle that holds a live cell; its four waves take the cells v, v + 4, ... . Lane l sums the errors of the cell's pixels
+ * l, l + 64, ... in that order, and the 64 partials are folded by a __shfl_xor butterfly (strides 32 .. 1): float addition is commutative, so lane 0 — every
+ * lane — ends with the bits of the tree the header states, and no barrier is needed inside a cell. E and the hot flag go to LDS (6 KB for 1024 cells), one
+ * barrier; threads decide the cells t, t + 256, ... from the neighbours' flags and report; a second barrier; the waves copy their own cells that go on.
+ * No packed-float instructions, no MFMA, no scratch.
+ */
+#define CRH_AD_CELLS_MAX 1024
+#define CRH_AD_WAVE 64u
+static_assert(CRH_AD_CELLS_MAX == CRH_ADAPTIVE_CELLS_MAX, "k_adaptive_cells: the LDS arrays hold one rectangle's cells");
+
+struct AdaptiveCellsArgs {
+	const float *fb;            /* [H, W, 3], never written */
+	float *half;                /* [H, W, 3]: written over the cells that go on */
+	const crh_tile *tiles;      /* one workgroup each: the rectangles that hold a live cell */
+	const uint32_t *offsets;    /* per workgroup: the index of its rectangle's first cell in the three arrays below */
+	const uint8_t *live;        /* per cell, or NULL: every cell is live */
+	float *errors;              /* per cell */
+	uint8_t *flags;             /* per cell: 1 = goes on */
+	int W, H;
+	int cell;
+	float threshold;
+	int dilate;
+	int advanceAll;             /* crh_render_adaptive_cells' copies: no measurement, nothing reported, every live cell's half := fb */
+};
+
+__device__ __forceinline__ uint32_t adMin(uint32_t a, uint32_t b) { return a < b ? a : b; }
+
+/* half := fb over one cell, raw bits, a pixel a lane in the cell's enumeration, four pixels' loads in flight before their stores (as in k_adaptive_step: a pixel
+ * past the end reads the batch's first one again and stores nothing). */
+__device__ __forceinline__ void adCopyCell(const uint32_t *src, uint32_t *dst, size_t origin, size_t pitch, uint32_t cw, uint32_t n, uint32_t lane) {
+	const uint32_t q = CRH_AD_WAVE / cw, r = CRH_AD_WAVE % cw;
+	uint32_t row = lane / cw, x = lane % cw;
+#define CRH_ADC_STEP row += q; x += r; if (x >= cw) { x -= cw; ++row; }
+#define CRH_ADC_NEXT(at, ok, u) \
+	const bool ok = k + (u) * CRH_AD_WAVE < n; \
+	const size_t at = ok ? origin + (size_t)row * pitch + (size_t)x * 3u : at0; \
+	CRH_ADC_STEP
+#define CRH_ADC_LOAD(v, at) const uint32_t v##r = src[at], v##g = src[at + 1], v##b = src[at + 2];
+#define CRH_ADC_STORE(v, at) { dst[at] = v##r; dst[at + 1] = v##g; dst[at + 2] = v##b; }
+	for (uint32_t k = lane; k < n; k += 4u * CRH_AD_WAVE) {
+		const size_t at0 = origin + (size_t)row * pitch + (size_t)x * 3u;          /* (k < n) */
+		CRH_ADC_STEP
+		CRH_ADC_NEXT(at1, ok1, 1u)
+		CRH_ADC_NEXT(at2, ok2, 2u)
+		CRH_ADC_NEXT(at3, ok3, 3u)
+		CRH_ADC_LOAD(v0, at0) CRH_ADC_LOAD(v1, at1) CRH_ADC_LOAD(v2, at2) CRH_ADC_LOAD(v3, at3)
+		CRH_ADC_STORE(v0, at0)
+		if (ok1) CRH_ADC_STORE(v1, at1)
+		if (ok2) CRH_ADC_STORE(v2, at2)
+		if (ok3) CRH_ADC_STORE(v3, at3)
+	}
+#undef CRH_ADC_NEXT
+#undef CRH_ADC_STEP
+#undef CRH_ADC_LOAD
+#undef CRH_ADC_STORE
+}
+
+__global__ __launch_bounds__(CRH_BLOCK) void k_adaptive_cells(const AdaptiveCellsArgs A) {
+	__shared__ float s_err[CRH_AD_CELLS_MAX];
+	__shared__ uint8_t s_hot[CRH_AD_CELLS_MAX];          /* bit 0: hot, bit 1: live */
+	__shared__ uint8_t s_go[CRH_AD_CELLS_MAX];
+	const uint32_t t = threadIdx.x, wave = t / CRH_AD_WAVE, lane = t % CRH_AD_WAVE;
+	const crh_tile T = A.tiles[blockIdx.x];
+	const uint32_t first = A.offsets[blockIdx.x];
+	const uint32_t tw = (uint32_t)(T.x1 - T.x0), th = (uint32_t)(T.y1 - T.y0), c = (uint32_t)A.cell;
+	const uint32_t cx = (tw + c - 1u) / c, cy = (th + c - 1u) / c, cells = cx * cy;          /* (the host refuses rectangles of more than CRH_AD_CELLS_MAX cells) */
+	const size_t origin = ((size_t)(A.H - T.y1) * (size_t)A.W + (size_t)T.x0) * 3u;          /* the rectangle's first stored row, its first pixel */
+	const size_t pitch = (size_t)A.W * 3u;
+	if (!A.advanceAll) {
+		/* 1. the waves measure the cells wave, wave + 4, ... (everything but the lane's pixel is wave-uniform) */
+		uint32_t i = wave % cx, j = wave / cx;
+		for (uint32_t idx = wave; idx < cells; idx += CRH_BLOCK / CRH_AD_WAVE) {
+			const bool isLive = !A.live || A.live[first + idx] != 0;
+			float E = 0.0f;
+			bool hot = false;
+			if (isLive) {
+				const uint32_t cw = adMin(c, tw - i * c), ch = adMin(c, th - j * c), n = cw * ch;
+				const size_t at = origin + (size_t)(j * c) * pitch + (size_t)(i * c) * 3u;
+				const uint32_t q = CRH_AD_WAVE / cw, r = CRH_AD_WAVE % cw;
+				uint32_t row = lane / cw, x = lane % cw;
+				float p = 0.0f;
+#pragma unroll 4
+				for (uint32_t k = lane; k < n; k += CRH_AD_WAVE) {
+					p = p + adPixelError(A.fb, A.half, at + (size_t)row * pitch + (size_t)x * 3u);
+					row += q; x += r;
+					if (x >= cw) { x -= cw; ++row; }
+				}
+#pragma unroll
+				for (int stride = (int)CRH_AD_WAVE / 2; stride >= 1; stride >>= 1) p = p + __shfl_xor(p, stride);
+				E = p / (float)n;
+				hot = !(E <= A.threshold);
+			}
+			if (lane == 0) { s_err[idx] = E; s_hot[idx] = (uint8_t)((hot ? 1u : 0u) | (isLive ? 2u : 0u)); }
+			i += CRH_BLOCK / CRH_AD_WAVE;
+			while (i >= cx) { i -= cx; ++j; }
+		}
+		__syncthreads();
+		/* 2. the threads decide the cells t, t + 256, ... from the neighbours' flags, and report */
+		for (uint32_t idx = t; idx < cells; idx += CRH_BLOCK) {
+			const uint32_t ci = idx % cx, cj = idx / cx;
+			const uint32_t own = s_hot[idx];
+			bool go = (own & 1u) != 0;
+			if (A.dilate && (own & 2u) && !go) {
+				const uint32_t i0 = ci ? ci - 1u : 0u, i1 = adMin(ci + 1u, cx - 1u), j0 = cj ? cj - 1u : 0u, j1 = adMin(cj + 1u, cy - 1u);
+				for (uint32_t b = j0; b <= j1; ++b)
+					for (uint32_t a = i0; a <= i1; ++a) go = go || (s_hot[b * cx + a] & 1u);
+			}
+			s_go[idx] = go ? 1 : 0;
+			A.errors[first + idx] = s_err[idx];
+			A.flags[first + idx] = go ? 1 : 0;
+		}
+		__syncthreads();
+	}
+	/* 3. the waves copy their own cells that go on */
+	const uint32_t *src = (const uint32_t *)A.fb;
+	uint32_t *dst = (uint32_t *)A.half;
+	uint32_t i = wave % cx, j = wave / cx;
+	for (uint32_t idx = wave; idx < cells; idx += CRH_BLOCK / CRH_AD_WAVE) {
+		const bool go = A.advanceAll ? (!A.live || A.live[first + idx] != 0) : s_go[idx] != 0;
+		if (go) {
+			const uint32_t cw = adMin(c, tw - i * c), ch = adMin(c, th - j * c);
+			adCopyCell(src, dst, origin + (size_t)(j * c) * pitch + (size_t)(i * c) * 3u, pitch, cw, cw * ch, lane);
+		}
+		i += CRH_BLOCK / CRH_AD_WAVE;
+		while (i >= cx) { i -= cx; ++j; }
+	}
+}

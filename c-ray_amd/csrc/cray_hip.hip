@@ -2157,7 +2157,7 @@ int crh_adaptive_step(crh_ctx *c, const float *dev_fb, float *dev_half, int widt
 	return adLaunch(c, dev_fb, dev_half, width, height, tiles, tile_count, threshold, false, errors_host, continue_host);
 }
 
-/* The kernel of the most recent step (crh_render_adaptive's included), between two events of the library's own; 0 before the first one. */
+/* The kernel of the most recent step of either granularity (those of the two loops included), between two events of the library's own; 0 before the first one. */
 int crh_adaptive_time_ms(crh_ctx *c, float *last_ms) {
 	if (!c || !last_ms) return fail(CRH_ERR_INVALID, "crh_adaptive_time_ms: NULL argument");
 	*last_ms = c->adaptiveWatch.sum;          /* (adLaunch has read its lap) */
@@ -2222,6 +2222,199 @@ int crh_render_adaptive(crh_ctx *c, const crh_render_params *P, const crh_tile *
 		}
 		live.resize(kept); index.resize(kept);
 		if (kept && (rc = render(live, n, n))) return rc;
+	}
+	return CRH_OK;
+}
+
+/* ---- adaptive sampling at cell granularity within each rectangle (adaptive.h: k_adaptive_cells) -------------------------------------------------- */
+/* The cell grid of validated rectangles: offsets[r] = the index of rectangle r's first cell, offsets[tile_count] = the total. */
+static int adCellGrid(const char *who, const crh_tile *tiles, uint32_t tile_count, int cell, std::vector<uint32_t> *offsets, int64_t *total) {
+	if (!tiles && tile_count) return fail(CRH_ERR_INVALID, std::string(who) + ": NULL argument");
+	if (cell < 1 || cell > 1024) return fail(CRH_ERR_INVALID, std::string(who) + ": the cell size must be 1 .. 1024");
+	int64_t sum = 0;
+	if (offsets) offsets->assign((size_t)tile_count + 1, 0u);
+	for (uint32_t i = 0; i < tile_count; ++i) {
+		const crh_tile &t = tiles[i];
+		if (t.x1 <= t.x0 || t.y1 <= t.y0) return fail(CRH_ERR_INVALID, std::string(who) + ": rectangle " + std::to_string(i) + " is empty");
+		const int64_t cx = ((int64_t)t.x1 - t.x0 + cell - 1) / cell, cy = ((int64_t)t.y1 - t.y0 + cell - 1) / cell;
+		if (cx * cy > CRH_ADAPTIVE_CELLS_MAX)
+			return fail(CRH_ERR_INVALID, std::string(who) + ": rectangle " + std::to_string(i) + " holds more than " + std::to_string(CRH_ADAPTIVE_CELLS_MAX) + " cells");
+		if (offsets) (*offsets)[i] = (uint32_t)sum;
+		sum += cx * cy;
+		if (sum > 0x7fffffff) return fail(CRH_ERR_INVALID, std::string(who) + ": more than 2^31 - 1 cells");
+	}
+	if (offsets) (*offsets)[tile_count] = (uint32_t)sum;
+	*total = sum;
+	return CRH_OK;
+}
+
+int64_t crh_adaptive_cell_offsets(const crh_tile *tiles, uint32_t tile_count, int cell, uint32_t *offsets_out) {
+	std::vector<uint32_t> offsets;
+	int64_t total = 0;
+	const int rc = adCellGrid("crh_adaptive_cell_offsets", tiles, tile_count, cell, &offsets, &total);
+	if (rc) return rc;
+	if (offsets_out) memcpy(offsets_out, offsets.data(), offsets.size() * sizeof(uint32_t));
+	return total;
+}
+
+/* One launch over validated rectangles and their cell grid (offsets, total), behind whatever the stream holds; waits for it. Only the rectangles that hold a
+ * live cell get a workgroup. advanceAll: half := fb over every live cell, nothing measured or reported. */
+static int adCellsLaunch(crh_ctx *c, const float *dev_fb, float *dev_half, int width, int height, const crh_tile *tiles, uint32_t tile_count, const uint32_t *offsets,
+                         uint32_t total, int cell, float threshold, int dilate, bool advanceAll, const uint8_t *live_host, float *errors_host, uint8_t *continue_host) {
+	if (!advanceAll) {
+		if (errors_host) memset(errors_host, 0, (size_t)total * sizeof(float));
+		if (continue_host) memset(continue_host, 0, total);
+	}
+	std::vector<uint32_t> work;          /* the rectangles that hold a live cell */
+	for (uint32_t r = 0; r < tile_count; ++r) {
+		bool any = !live_host;
+		for (uint32_t k = offsets[r]; !any && k < offsets[r + 1]; ++k) any = live_host[k] != 0;
+		if (any) work.push_back(r);
+	}
+	if (work.empty()) return CRH_OK;
+	int rc = setDevice(c);
+	if (rc) return rc;
+	/* the staging block: the launched rectangles, their first cells, then per cell the errors, the flags and the live mask (zeros go up with the list, so a
+	 * cell no workgroup reports on comes back 0) */
+	const size_t groups = work.size(), tileBytes = groups * sizeof(crh_tile), offBytes = groups * sizeof(uint32_t), errBytes = (size_t)total * sizeof(float);
+	const size_t errAt = tileBytes + offBytes, flagAt = errAt + errBytes, liveAt = flagAt + total, bytes = liveAt + (live_host ? total : 0);
+	StagedBuf &sb = c->adaptive;
+	if (bytes > sb.cap) HIP_TRY(hipStreamSynchronize(c->stream));          /* (as in adLaunch: a call that failed half-way may have left its copy queued) */
+	if ((rc = sb.reserve(bytes))) return rc;
+	char *const host = (char *)sb.host, *const dev = (char *)sb.dev;
+	for (size_t g = 0; g < groups; ++g) {
+		((crh_tile *)host)[g] = tiles[work[g]];
+		((uint32_t *)(host + tileBytes))[g] = offsets[work[g]];
+	}
+	memset(host + errAt, 0, errBytes + total);
+	if (live_host) memcpy(host + liveAt, live_host, total);
+	HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, c->stream));
+	AdaptiveCellsArgs A;
+	A.fb = dev_fb; A.half = dev_half;
+	A.tiles = (const crh_tile *)dev;
+	A.offsets = (const uint32_t *)(dev + tileBytes);
+	A.errors = (float *)(dev + errAt);
+	A.flags = (uint8_t *)(dev + flagAt);
+	A.live = live_host ? (const uint8_t *)(dev + liveAt) : nullptr;
+	A.W = width; A.H = height; A.cell = cell; A.threshold = threshold; A.dilate = dilate; A.advanceAll = advanceAll ? 1 : 0;
+	if ((rc = c->adaptiveWatch.start(c->stream))) return rc;
+	hipLaunchKernelGGL(k_adaptive_cells, dim3((uint32_t)groups), dim3(CRH_BLOCK), 0, c->stream, A);
+	const hipError_t e = hipGetLastError();
+	if ((rc = c->adaptiveWatch.mark(c->stream))) return rc;
+	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string("k_adaptive_cells launch: ") + hipGetErrorString(e));
+	if (!advanceAll) HIP_TRY(hipMemcpyAsync(host + errAt, dev + errAt, errBytes + total, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	c->adaptiveWatch.stop();
+	if ((rc = c->adaptiveWatch.read())) return rc;
+	if (!advanceAll) {
+		if (errors_host) memcpy(errors_host, host + errAt, errBytes);
+		if (continue_host) for (uint32_t k = 0; k < total; ++k) continue_host[k] = host[flagAt + k] ? 1 : 0;
+	}
+	return CRH_OK;
+}
+
+/* The step's own argument rules (crh_adaptive_step's, then the cell grid's). */
+static int adCellsCheck(const char *who, crh_ctx *c, const float *dev_fb, const float *dev_half, int width, int height, const crh_tile *tiles, uint32_t tile_count, int cell,
+                        float threshold, int dilate, std::vector<uint32_t> *offsets, int64_t *total) {
+	if (!c || !dev_fb || !dev_half || (!tiles && tile_count)) return fail(CRH_ERR_INVALID, std::string(who) + ": NULL argument");
+	if (width <= 0 || height <= 0) return fail(CRH_ERR_INVALID, std::string(who) + ": bad size");
+	if (std::isnan(threshold) || std::signbit(threshold)) return fail(CRH_ERR_INVALID, std::string(who) + ": the threshold is NaN or negative");
+	if (dev_half == dev_fb) return fail(CRH_ERR_INVALID, std::string(who) + ": the half-sample frame is the frame");
+	if (dilate != 0 && dilate != 1) return fail(CRH_ERR_INVALID, std::string(who) + ": dilate must be 0 or 1");
+	const int rc = checkRects(who, tiles, tile_count, width, height, true);
+	if (rc) return rc;
+	return adCellGrid(who, tiles, tile_count, cell, offsets, total);
+}
+
+int crh_adaptive_step_cells(crh_ctx *c, const float *dev_fb, float *dev_half, int width, int height, const crh_tile *tiles, uint32_t tile_count, int cell, float threshold,
+                            int dilate, const uint8_t *live_host, float *errors_host, uint8_t *continue_host) {
+	std::vector<uint32_t> offsets;
+	int64_t total = 0;
+	const int rc = adCellsCheck("crh_adaptive_step_cells", c, dev_fb, dev_half, width, height, tiles, tile_count, cell, threshold, dilate, &offsets, &total);
+	if (rc) return rc;
+	if (tile_count == 0) return CRH_OK;
+	return adCellsLaunch(c, dev_fb, dev_half, width, height, tiles, tile_count, offsets.data(), (uint32_t)total, cell, threshold, dilate, false, live_host, errors_host,
+	                     continue_host);
+}
+
+void crh_adaptive_cells_params_default(crh_adaptive_cells_params *p) {
+	if (!p) return;
+	p->min_passes = 16; p->threshold = 0.05f; p->cell = 16; p->dilate = 1;
+}
+
+/* The loop with the cell as the unit: min_passes everywhere, then every cell doubles its pass count until it no longer goes on or the cap is reached. */
+int crh_render_adaptive_cells(crh_ctx *c, const crh_render_params *P, const crh_tile *tiles, uint32_t tile_count, const crh_adaptive_cells_params *A, float *dev_fb,
+                              float *dev_half, int32_t *passes_host, float *errors_host) {
+	const char *who = "crh_render_adaptive_cells";
+	if (!c || !P || !A || !dev_fb || !dev_half || (!tiles && tile_count)) return fail(CRH_ERR_INVALID, "crh_render_adaptive_cells: NULL argument");
+	if (!c->haveScene) return fail(CRH_ERR_INVALID, "crh_render_adaptive_cells: no scene uploaded");
+	if (P->image_width <= 0 || P->image_height <= 0 || P->first_pass != 0 || P->pass_count <= 0 || P->max_passes < P->pass_count)
+		return fail(CRH_ERR_INVALID, "crh_render_adaptive_cells: bad render parameters (first_pass must be 0, pass_count is the cap and must not exceed max_passes)");
+	const int m = A->min_passes, cap = P->pass_count;
+	if (m < 2 || (m & 1)) return fail(CRH_ERR_INVALID, "crh_render_adaptive_cells: min_passes must be even and at least 2");
+	{
+		int64_t n = m;
+		while (n < cap) n *= 2;
+		if (n != cap) return fail(CRH_ERR_INVALID, "crh_render_adaptive_cells: the cap (pass_count) must be min_passes times a power of two");
+	}
+	const int W = P->image_width, H = P->image_height, cell = A->cell;
+	std::vector<uint32_t> offsets;
+	int64_t total64 = 0;
+	int rc = adCellsCheck(who, c, dev_fb, dev_half, W, H, tiles, tile_count, cell, A->threshold, A->dilate, &offsets, &total64);
+	if (rc) return rc;
+	if (tile_count == 0) return CRH_OK;
+	const uint32_t total = (uint32_t)total64;
+	crh_render_params p = *P;
+	auto render = [&](const std::vector<crh_tile> &list, int first, int count) {
+		p.first_pass = first; p.pass_count = count;
+		return crh_render_tiles(c, &p, list.data(), (uint32_t)list.size(), dev_fb);
+	};
+	auto step = [&](float threshold, bool advanceAll, const uint8_t *live, float *err, uint8_t *go) {
+		return adCellsLaunch(c, dev_fb, dev_half, W, H, tiles, tile_count, offsets.data(), total, cell, threshold, A->dilate, advanceAll, live, err, go);
+	};
+	std::vector<crh_tile> list(tiles, tiles + tile_count);
+	if ((rc = render(list, 0, m / 2))) return rc;
+	if ((rc = step(0.0f, true, nullptr, nullptr, nullptr))) return rc;
+	if ((rc = render(list, m / 2, m - m / 2))) return rc;
+	std::vector<uint8_t> live(total, 1), go(total), still(total);
+	std::vector<float> err(total);
+	for (int n = m;; n *= 2) {
+		const bool last = n == cap;          /* measure only: nothing is left to render, so no half-sample frame moves */
+		if ((rc = step(last ? __builtin_inff() : A->threshold, false, live.data(), err.data(), go.data()))) return rc;
+		if (!last && A->threshold == 0.0f) {
+			/* threshold 0 asks for the uniform frame (crh_render_adaptive's rule and reason): a live cell that does not go on — its error is exactly 0 and no
+			 * neighbour kept it — goes on like the others, so its half-sample frame moves too */
+			bool any = false;
+			for (uint32_t k = 0; k < total; ++k) { still[k] = live[k] && !go[k]; any = any || still[k]; go[k] = live[k]; }
+			if (any && (rc = step(0.0f, true, still.data(), nullptr, nullptr))) return rc;
+		}
+		bool any = false;
+		for (uint32_t k = 0; k < total; ++k) {
+			if (!live[k]) continue;
+			if (errors_host) errors_host[k] = err[k];
+			if (go[k] && !last) { any = true; continue; }
+			live[k] = 0;
+			if (passes_host) passes_host[k] = n;
+		}
+		if (!any) break;
+		/* the live cells' pixels as maximal horizontal runs of live cells within one cell row of a rectangle: few, wide rectangles for the renderer */
+		list.clear();
+		for (uint32_t r = 0; r < tile_count; ++r) {
+			const crh_tile &t = tiles[r];
+			const int cx = (t.x1 - t.x0 + cell - 1) / cell, cy = (t.y1 - t.y0 + cell - 1) / cell;
+			for (int j = 0; j < cy; ++j) {
+				/* stored rows (H - y1) + j cell ..: in tile coordinates (y from the bottom) the cell row spans y1 - (j + 1) cell .. y1 - j cell, cut at y0 */
+				const int top = t.y1 - j * cell, bottom = std::max(t.y0, top - cell);
+				for (int i = 0; i < cx; ++i) {
+					if (!live[offsets[r] + (uint32_t)(j * cx + i)]) continue;
+					int e = i + 1;
+					while (e < cx && live[offsets[r] + (uint32_t)(j * cx + e)]) ++e;
+					list.push_back(crh_tile{t.x0 + i * cell, bottom, std::min(t.x1, t.x0 + e * cell), top});
+					i = e;
+				}
+			}
+		}
+		if ((rc = render(list, n, n))) return rc;
 	}
 	return CRH_OK;
 }

@@ -42,6 +42,9 @@
  * CRAY_HIP_ADAPTIVE=<threshold> (user-facing; CRAY_HIP_ADAPTIVE_MIN=<m>, default 16): adaptive sampling at tile granularity — every GPU thread hands its rectangles
  * (one GPU: the scene's tileWidth x tileHeight grid; several: its strips cut every tileWidth columns) to crh_render_adaptive, which gives every rectangle m passes
  * and doubles that until its error is at most the threshold or sampleCount is reached; a sampleCount that is not m 2^r: a warning and the uniform frame.
+ * CRAY_HIP_ADAPTIVE_CELL=<c> (user-facing, beside CRAY_HIP_ADAPTIVE; CRAY_HIP_ADAPTIVE_DILATE=0|1, default 1): the same rectangles, decided per c x c cell inside each
+ * (crh_render_adaptive_cells); the report line counts cells by pass count. A value that is no integer in 1 .. 1024, or a rectangle of more than 1024 cells, warns
+ * and decides per rectangle.
  * No GPU => logr(error, ...) (which exits, src/utils/logging.c:69-73): there is no CPU fallback in this file.
  */
 #include <stdlib.h>
@@ -98,6 +101,8 @@ struct gpuWorker {
 	crh_tile *adaptTiles;     /* CRAY_HIP_ADAPTIVE: this GPU's rectangles and the pass count each stopped at */
 	int32_t *adaptPasses;
 	uint32_t adaptCount;
+	uint32_t adaptUnits;      /* entries of adaptPasses: the rectangles, or with CRAY_HIP_ADAPTIVE_CELL their cells */
+	int adaptCell;            /* the cell size the frame was decided at; 0: per rectangle */
 	int device;
 	int failed;
 	char error[256];      /* crh_last_error() is per thread: the failing dispatch thread keeps its message here */
@@ -309,6 +314,20 @@ static int adaptiveSettings(const struct renderer *r, crh_adaptive_params *out) 
 	return 1;
 }
 
+/* CRAY_HIP_ADAPTIVE_CELL=<c> [CRAY_HIP_ADAPTIVE_DILATE=0|1, default 1] beside CRAY_HIP_ADAPTIVE: the decision is made per c x c cell inside every rectangle
+ * (crh_render_adaptive_cells). 1 and the two settings; 0 when the variable is unset; -1 when its value is not an integer in 1 .. 1024 (renderFrame says so once,
+ * and the frame is decided per rectangle). */
+static int adaptiveCellSettings(int *cell, int *dilate) {
+	const char *c = getenv("CRAY_HIP_ADAPTIVE_CELL"), *d = getenv("CRAY_HIP_ADAPTIVE_DILATE");
+	if (!c || !*c) return 0;
+	char *end = NULL;
+	const long v = strtol(c, &end, 10);
+	if (end == c || *end || v < 1 || v > 1024) return -1;
+	if (cell) *cell = (int)v;
+	if (dilate) *dilate = !(d && d[0] == '0' && !d[1]);
+	return 1;
+}
+
 /* The rectangles crh_render_adaptive decides on, from a GPU's share: one GPU — the whole frame — gets the scene's tile grid (tile.c:66-117 without the ordering,
  * which is a preview preference), a GPU of several gets its strips cut every tileWidth columns. */
 static uint32_t adaptiveRectangles(const struct renderer *r, const crh_tile *share, uint32_t n, int G, crh_tile **out) {
@@ -408,11 +427,22 @@ static void *gpuThread(void *arg) {
 	if (adapt && n) {
 		/* the whole frame in one call: the library's loop renders, measures and decides, rectangle by rectangle (no preview, no pause in between) */
 		w->adaptCount = adaptiveRectangles(r, share, n, G, &w->adaptTiles);
-		w->adaptPasses = calloc(w->adaptCount ? w->adaptCount : 1, sizeof(*w->adaptPasses));
+		w->adaptUnits = w->adaptCount;
+		crh_adaptive_cells_params cells;
+		crh_adaptive_cells_params_default(&cells);
+		cells.min_passes = adaptive.min_passes; cells.threshold = adaptive.threshold;
+		if (w->adaptTiles && adaptiveCellSettings(&cells.cell, &cells.dilate) > 0) {
+			const int64_t total = crh_adaptive_cell_offsets(w->adaptTiles, w->adaptCount, cells.cell, NULL);
+			if (total >= 0) { w->adaptCell = cells.cell; w->adaptUnits = (uint32_t)total; }
+			else logr(warning, "GPU %d: CRAY_HIP_ADAPTIVE_CELL=%i: %s; deciding per rectangle\n", w->device, cells.cell, crh_last_error());
+		}
+		w->adaptPasses = calloc(w->adaptUnits ? w->adaptUnits : 1, sizeof(*w->adaptPasses));
 		p.first_pass = 0; p.pass_count = r->prefs.sampleCount;
 		struct timeval tl;
 		startTimer(&tl);
-		const int rc = w->adaptTiles && w->adaptPasses ? crh_render_adaptive(w->ctx, &p, w->adaptTiles, w->adaptCount, &adaptive, w->fb, w->half, w->adaptPasses, NULL) : CRH_ERR_NOMEM;
+		const int rc = !w->adaptTiles || !w->adaptPasses ? CRH_ERR_NOMEM
+			: w->adaptCell ? crh_render_adaptive_cells(w->ctx, &p, w->adaptTiles, w->adaptCount, &cells, w->fb, w->half, w->adaptPasses, NULL)
+			: crh_render_adaptive(w->ctx, &p, w->adaptTiles, w->adaptCount, &adaptive, w->fb, w->half, w->adaptPasses, NULL);
 		w->launchUs += getUs(tl);
 		announceLaunch(w);
 		if (rc != CRH_OK || crh_synchronize(w->ctx) != CRH_OK) {
@@ -915,18 +945,25 @@ struct texture *renderFrame(struct renderer *r) {
 	if (getenv("CRAY_HIP_ADAPTIVE") && *getenv("CRAY_HIP_ADAPTIVE") && !adapt)
 		logr(warning, "c-ray-hip: CRAY_HIP_ADAPTIVE needs a threshold >= 0, an even CRAY_HIP_ADAPTIVE_MIN >= 2 (default 16) and a sample count of that times a power of two; "
 			"%i samples rendered uniformly\n", r->prefs.sampleCount);
+	if (adapt && adaptiveCellSettings(NULL, NULL) < 0)
+		logr(warning, "c-ray-hip: CRAY_HIP_ADAPTIVE_CELL needs an integer in 1 .. 1024; deciding per rectangle\n");
 	if (adapt && !failed) {
-		/* the rays spent and where: the share of the rectangles that stopped at each pass count */
+		/* the rays spent and where: the share of the rectangles (with CRAY_HIP_ADAPTIVE_CELL: of their cells) that stopped at each pass count */
 		char line[512];
 		int at = 0;
 		uint32_t all = 0;
-		for (int g = 0; g < gpus; ++g) all += workers[g].adaptCount;
+		int cell = 0;
+		for (int g = 0; g < gpus; ++g) { all += workers[g].adaptUnits; if (workers[g].adaptCell) cell = workers[g].adaptCell; }
 		for (long n = adaptive.min_passes; n <= r->prefs.sampleCount; n *= 2) {
 			uint32_t k = 0;
-			for (int g = 0; g < gpus; ++g) for (uint32_t i = 0; i < workers[g].adaptCount; ++i) k += workers[g].adaptPasses[i] == n;
+			for (int g = 0; g < gpus; ++g) for (uint32_t i = 0; i < workers[g].adaptUnits; ++i) k += workers[g].adaptPasses[i] == n;
 			if (at < (int)sizeof(line) - 32) at += snprintf(line + at, sizeof(line) - (size_t)at, "%s%ld: %.1f %%", at ? ", " : "", n, all ? 100.0 * k / all : 0.0);
 		}
-		logr(info, "Adaptive sampling (threshold %g, at least %i passes): %llu rays, %u tiles by pass count: %s.\n", (double)adaptive.threshold, adaptive.min_passes, (unsigned long long)rays, all, line);
+		if (cell)
+			logr(info, "Adaptive sampling (threshold %g, at least %i passes, cells of %i, dilate %i): %llu rays, %u cells by pass count: %s.\n", (double)adaptive.threshold,
+				adaptive.min_passes, cell, (int)!(getenv("CRAY_HIP_ADAPTIVE_DILATE") && !strcmp(getenv("CRAY_HIP_ADAPTIVE_DILATE"), "0")), (unsigned long long)rays, all, line);
+		else
+			logr(info, "Adaptive sampling (threshold %g, at least %i passes): %llu rays, %u tiles by pass count: %s.\n", (double)adaptive.threshold, adaptive.min_passes, (unsigned long long)rays, all, line);
 	}
 	if (!workers[0].failed && !r->state.renderAborted) writeAovs(r, workers[0].ctx, W, H);
 	if (!failed && !r->state.renderAborted) {          /* (a frame assembled on the host is not on GPU 0) */

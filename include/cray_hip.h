@@ -532,7 +532,8 @@ int crh_framebuffer_copy(crh_ctx *ctx, const float *dev_src, float *dev_dst, int
  * crh_last_kernel_name as they were. */
 int crh_adaptive_step(crh_ctx *ctx, const float *dev_fb, float *dev_half, int width, int height, const crh_tile *tiles, uint32_t tile_count, float threshold,
                       float *errors_host, uint8_t *continue_host);
-/* Milliseconds of the most recent step's kernel (those of crh_render_adaptive count), between two events of the library's own; 0 before the first step. */
+/* Milliseconds of the most recent step's kernel, of either granularity (those of the two loops count), between two events of the library's own; 0 before the
+ * first step. */
 int crh_adaptive_time_ms(crh_ctx *ctx, float *last_ms);
 
 /* The loop that drives it. params->pass_count is the cap, params->first_pass must be 0, params->max_passes seeds the sampler as always and must not be below the
@@ -555,6 +556,56 @@ typedef struct crh_adaptive_params {
 void crh_adaptive_params_default(crh_adaptive_params *params);          /* NULL is a no-op */
 int crh_render_adaptive(crh_ctx *ctx, const crh_render_params *params, const crh_tile *tiles, uint32_t tile_count, const crh_adaptive_params *adaptive,
                         float *dev_fb, float *dev_half, int32_t *passes_host, float *errors_host);
+
+/* The same step at cell granularity within each rectangle (additive to ABI 5). The rectangle stays the unit of work, of ownership and of the interface; inside it
+ * the decision is made per cell of cell x cell pixels, optionally widened by one cell. Every cell of the frame equals, bit for bit, the uniform render of its
+ * pixels at the pass count the cell stopped at, and its half-sample frame the uniform render at half that count.
+ * Cells. A rectangle x0, y0, x1, y1 (tw = x1 - x0, th = y1 - y0) with cell size c holds cx = ceil(tw / c) by cy = ceil(th / c) cells, anchored at its first
+ * stored row and its first column: cell (i, j) holds the columns x0 + i c .. min(x0 + (i + 1) c, x1) - 1 and the stored rows (H - y1) + j c ..
+ * min((H - y1) + (j + 1) c, H - y0) - 1, so the ragged cells are the last column and the last stored rows. Its index is offset[r] + j cx + i, offset[r] being the
+ * number of cells of the rectangles before r (crh_adaptive_cell_offsets); live_host, errors_host and continue_host have one entry per cell in that order (the
+ * latter two may be NULL). live_host == NULL means every cell is live.
+ * Error of a live cell of n = cw ch pixels, enumerated k = 0 .. n - 1, stored rows ascending, x ascending within a row: e_k is exactly crh_adaptive_step's (the
+ * guard, d, s, d / sqrt(s + 1e-4f), the clamp at 2^100 that also takes NaN), under the same rules: correctly rounded float32 + - * / sqrt, comparisons and |x|,
+ * no contraction. Sum: P_l = 0.0f, then P_l = P_l + e_k for k = l, l + 64, ... ascending, for l = 0 .. 63; then for stride = 32, 16, .., 1:
+ * P_l = P_l + P_(l + stride) for every l < stride. E = P_0 / (float)n. hot = live && !(E <= threshold). A cell that is not live reports E = 0.0f, is not hot
+ * and is never written.
+ * Decision: go = live && (hot || (dilate && one of the up to eight neighbours (i +- 1, j +- 1) inside the same rectangle's grid is hot)). Dilation never
+ * crosses a rectangle's edge: a hot cell's neighbour in the next rectangle is decided by that rectangle's cells alone. Where go, the cell's raw bits of dev_fb
+ * are copied into dev_half, all three channels, no guard. Everything else — cells that stop, cells that are not live, pixels in no rectangle, all of dev_fb —
+ * is never written.
+ * The call waits for the result like crh_adaptive_step, and crh_adaptive_time_ms reports the most recent step of either kind; crh_counters, crh_kernel_time_ms
+ * and crh_last_kernel_name stay as they were. threshold = +inf measures only. tile_count == 0, or no live cell at all, is CRH_OK: nothing is launched and the
+ * outputs are zeros. CRH_ERR_INVALID: everything crh_adaptive_step refuses, cell < 1, cell > 1024, dilate other than 0 or 1, a rectangle of more than
+ * CRH_ADAPTIVE_CELLS_MAX cells. */
+#define CRH_ADAPTIVE_CELLS_MAX 1024          /* cells one rectangle may hold */
+/* host only, no context: offsets_out[r] = index of rectangle r's first cell, offsets_out[tile_count] = total; returns the total or a negative code (CRH_ERR_INVALID:
+ * a NULL list with a nonzero count, cell outside 1 .. 1024, an empty rectangle, a rectangle of more than CRH_ADAPTIVE_CELLS_MAX cells); offsets_out may be NULL */
+int64_t crh_adaptive_cell_offsets(const crh_tile *tiles, uint32_t tile_count, int cell, uint32_t *offsets_out);
+int crh_adaptive_step_cells(crh_ctx *ctx, const float *dev_fb, float *dev_half, int width, int height, const crh_tile *tiles, uint32_t tile_count,
+                            int cell, float threshold, int dilate, const uint8_t *live_host, float *errors_host, uint8_t *continue_host);
+
+/* The loop at cell granularity: crh_render_adaptive's schedule and argument rules (plus the step's: cell, dilate, the cell count of a rectangle), with the cell
+ * as the unit.
+ *   render [0, m / 2) on every rectangle; dev_half := dev_fb over every cell; render [m / 2, m); n = m; all cells are live
+ *   while n < cap: one step over the rectangles that still hold a live cell, with the live mask; a live cell with go == 0 is done at n passes and its error is the
+ *     one just measured; live := go; render [n, 2 n) over exactly the live cells' pixels; n = 2 n
+ *   at the cap: one measure-only step over the cells that got there
+ * A cell that has stopped never comes back: dilation only ever keeps a live cell going. How the live cells are cut into rectangles for the renderer is not part of
+ * the interface (the result does not depend on the tile list). threshold == 0 asks for the uniform frame: every cell goes on to the cap, one whose error is
+ * exactly 0 included, and its half moves along. cell_passes_host[k] is the pass count cell k stopped at, cell_errors_host[k] its error at that count, in the
+ * step's cell order (either may be NULL). Afterwards every cell's dev_fb holds the mean of its n passes and dev_half the mean of its first n / 2, so
+ * crh_denoise_variance at scale 1 works on the result unchanged. The render dispatches are ordinary ones: counters, kernel time and kernel name accumulate.
+ * Every argument is checked before anything is rendered. */
+typedef struct crh_adaptive_cells_params {
+	int32_t min_passes;          /* default 16 */
+	float threshold;             /* default 0.05 */
+	int32_t cell;                /* default 16 */
+	int32_t dilate;              /* default 1 */
+} crh_adaptive_cells_params;
+void crh_adaptive_cells_params_default(crh_adaptive_cells_params *params);          /* NULL is a no-op */
+int crh_render_adaptive_cells(crh_ctx *ctx, const crh_render_params *params, const crh_tile *tiles, uint32_t tile_count, const crh_adaptive_cells_params *cells,
+                              float *dev_fb, float *dev_half, int32_t *cell_passes_host, float *cell_errors_host);
 
 /* Multi-GPU inside one process (the C host, c-ray_amd/host/renderer_hip.c: one crh_ctx + one dispatch thread per
  * GPU): sum the n per-GPU float framebuffers onto ctxs[0]'s with ONE RCCL reduce over xGMI (ncclReduce, float,
