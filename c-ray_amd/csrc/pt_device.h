@@ -814,11 +814,13 @@ CRH_DEV rgba sampleBackground(const DScene &S, ShadeRec &rec, Cnt &cnt, const Sr
 
 /* ---- intersection ------------------------------------------------------------------------------ */
 /* oct bits 0..2: signbit of d (bvh.c:368-372); bits 4..6: that slab is tested exactly (|1/d| > 1e30, incl. d == 0);
- * bit 7: some component of the ray is not finite (reference NaN semantics are then followed literally). */
+ * bit 7: some component of the ray is not finite, or the walk's closest distance is NaN (reference NaN semantics are then followed literally). */
 struct RayK { v3 o, d, inv, ss; uint32_t oct; };
 #define CRH_RAY_SLOW 0xF0u
 #define CRH_RAY_PHASE_SHIFT 16
 #define CRH_RAY_LITERAL 0x100u   /* degenerate slabs follow the reference's NaN arithmetic literally instead of being tested exactly (set by the caller of walkBegin) */
+/* what a walk's ray word gets when its closest distance becomes NaN (stepCtrl): the non-finite bit, and PH_NODE_SLOW as the phase of its node steps */
+#define CRH_RAY_NAN_DISTANCE (128u | (7u << CRH_RAY_PHASE_SHIFT))
 CRH_DEV bool finitef(float x) { return fabsf(x) <= FLT_MAX; }
 CRH_DEV RayK makeRayK(v3 o, v3 d) {                     /* bvh.c:368-376 */
 	RayK k;
@@ -854,7 +856,7 @@ CRH_DEV RayK makeRayK(v3 o, v3 d) {                     /* bvh.c:368-376 */
  *    lane with the chip waiting). Box tests only cull — the closest hit is decided by the triangle / sphere tests,
  *    which never use invDir — so such a slab is tested exactly (inside iff min <= start <= max): same hit (up to
  *    exact-tie order), after a normal number of node visits. tests: test_zero_component_rays.
- *  - non-finite rays follow the reference's select chain literally.
+ *  - non-finite rays follow the reference's select chain literally, and so does every ray once the walk's closest distance (maxDist) is NaN (stepCtrl).
  */
 /* v_min / v_max / v_max3 / v_min3 on values that are already canonical (results of fma on finite inputs): written as
  * instructions so that the compiler does not put a quieting v_max x,x in front of every operand */
@@ -1254,6 +1256,10 @@ CRH_DEV void stepCtrl(const DScene &S, Walk &w, Stack &stk, Cnt &cnt, Port &port
 		} else if (sphereTest(o, d, instRadius(inst), w.hit.t, t0, cnt)) {   /* sphere.c:20-50 */
 			w.hit.t = t0; w.hit.slot = -1; w.hit.inst = idx;
 			CRH_COUNT(cnt, inst_hits, 1);
+			/* sphere.c accepts a NaN distance (a direction near FLT_MAX — reflected + sphere * roughness — overflows its discriminant to inf - inf, and every
+			 * comparison of a NaN is false). From then on the reference's box test fails for every node: tMin <= (tMax < NaN ? tMax : NaN). The fast box test is
+			 * min / max instructions, which drop a NaN operand, so the rest of this walk takes the literal select chain (as a non-finite ray does) */
+			w.k.oct |= (t0 != t0) ? CRH_RAY_NAN_DISTANCE : 0u;          /* (a select, not a branch: measured) */
 		}
 	} else if (kind == CRH_DINST_MESH_EMPTY) {
 		if (!volume) w.hit.inst = -1;                                        /* bvh.c:362-365 via instance.c:175 (a volume walks a COPY of the record) */
@@ -1263,6 +1269,7 @@ CRH_DEV void stepCtrl(const DScene &S, Walk &w, Stack &stk, Cnt &cnt, Port &port
 	} else {
 		RayK ko = makeRayK(o, d);
 		ko.oct |= w.k.oct & CRH_RAY_LITERAL;
+		ko.oct |= (w.hit.t != w.hit.t) ? CRH_RAY_NAN_DISTANCE : 0u;          /* (the object-space ray of a walk whose closest distance is NaN: see above) */
 		bool enter = true;
 		uint32_t rootA = 0, rootAe = 0;
 		if (kind == CRH_DINST_MESH_LEAF) {                                 /* bvh.c:382-387 */

@@ -11,6 +11,9 @@
  *                           below (tests/test_nodes.py holds the expected values of the known-answer ones, which restate
  *                           /root/reference/tests/test_nodes.h), the background becomes constant white. With CRH_ZOO_TAME=1
  *                           the known-answer spheres 0..37 keep their plain material (multi-bounce frames stay in [0, ~3]).
+ *   CRH_NODE_PATCH=bsdfedges_a, bsdfedges_b   the same scene: every sphere gets one bsdf with one parameter at an edge value (roughness, IOR, mix factor,
+ *                           emission strength, colours: zeros, subnormals, infinities, NaN), constant and hit-dependent; every other material becomes plain grey, the
+ *                           background constant white (patchBsdfEdges below, tests/test_bsdf_edges.py).
  *   CRH_NODE_PATCH=volumes  sphere / mesh instances flagged in the scene become newSphereVolume / newMeshVolume instances
  *                           with an isotropic medium (instance.c:62-92, 187-216); the TLAS is rebuilt.
  *   CRH_NODE_PATCH=whitesky the background becomes constant white and nothing else changes (the JSON loader's own backgrounds are a gradient
@@ -146,6 +149,74 @@ static void patchZoo(struct renderer *r) {
 	(void)r;
 }
 
+/* ---- CRH_NODE_PATCH=bsdfedges_a / bsdfedges_b: the scatter side at its parameter edges (tests/test_bsdf_edges.py) -------------------------
+ * One bsdf per sphere with ONE edge parameter, as a constant and hit-dependent. The hit-dependent form here is x * (rayLength * 0 + 1): exact for every x —
+ * -0, subnormals, infinities and NaN included (num()'s 0 * rayLength + x turns a -0 into +0). Every material of the scene is replaced, the meshes' too, so no
+ * image texture is reachable from a shown material: the reference converts no non-finite float to an integer. tests/test_bsdf_edges.py restates these lists. */
+#define EDGE_COUNT(a) ((int)(sizeof(a) / sizeof((a)[0])))
+static V edge(float f) {
+	/* (a NaN constant cannot be built: the constructors hash-cons their nodes, and a NaN never compares equal to the candidate just inserted — they return NULL. 0 / 0 is
+	 * built instead, which the product's scene compiler folds into the constant) */
+	V c = isnan(f) ? m2(newConstantValue(W, 0.0f), newConstantValue(W, 0.0f), Divide) : newConstantValue(W, f);
+	return g_dynamic ? m2(c, m2(m2(newRayLength(W), newConstantValue(W, 0.0f), Multiply), newConstantValue(W, 1.0f), Add), Multiply) : c;
+}
+static C edgeColor(const float *c) { return g_dynamic || isnan(c[0]) || isnan(c[1]) || isnan(c[2]) ? newCombineRGB(W, edge(c[0]), edge(c[1]), edge(c[2])) : rgb(c[0], c[1], c[2]); }
+static B grey(void) { return newDiffuse(W, rgb(0.6f, 0.6f, 0.6f)); }
+
+static void patchBsdfEdges(struct renderer *r, int second) {
+	const float tiny = 1.401298464324817e-45f;      /* the smallest subnormal */
+	const float big = 3.402823466e+38f;             /* FLT_MAX */
+	const float inf = INFINITY, nan = NAN;
+	const float roughness[] = {0.0f, -0.0f, tiny, -0.5f, 0.5f, 1.0f, 8.0f, big, inf, -inf, nan};
+	const float ior[] = {1.0f, 0.0f, -0.0f, -1.0f, 0.5f, 1.45f, 1e-30f, 1e30f, inf, -inf, nan};
+	const float factor[] = {0.0f, -0.0f, 1.0f, -0.5f, 1.5f, 0.5f, inf, -inf, nan};
+	const float strength[] = {0.0f, -1.0f, 5.0f, 1e30f, inf, nan};
+	const float colors[][3] = {{0.0f, 0.0f, 0.0f}, {-0.5f, 0.25f, 0.5f}, {1.5f, 0.5f, 2.0f}, {0.5f, inf, 0.25f}, {0.5f, 0.25f, nan}};
+	const int extra[] = {2, 6, 7, 8};      /* glass roughness, constant: the four spheres left over show the smallest subnormal, 8, FLT_MAX and inf */
+	struct sphere *s = W->spheres;
+	int k = 0;
+	if (W->sphereCount < 60) { fprintf(stderr, "CRH_NODE_PATCH=bsdfedges needs the 60-sphere nodezoo scene (%d spheres)\n", W->sphereCount); exit(3); }
+	for (int i = 0; i < W->sphereCount; ++i) s[i].material.bsdf = grey();
+	for (int i = 0; i < W->meshCount; ++i)
+		for (int j = 0; j < W->meshes[i].materialCount; ++j) W->meshes[i].materials[j].bsdf = grey();
+	if (!second) {
+		for (g_dynamic = 0; g_dynamic < 2; ++g_dynamic)
+			for (int i = 0; i < EDGE_COUNT(roughness); ++i) s[k++].material.bsdf = newMetal(W, rgb(0.9f, 0.7f, 0.5f), edge(roughness[i]));
+		for (g_dynamic = 0; g_dynamic < 2; ++g_dynamic)
+			/* (newGlass() hash-conses on colour and roughness alone, glass.c:28-31: two glasses that differ in their IOR only are ONE node, the first one's. Every
+			 * sphere here gets a blue of its own) */
+			for (int i = 0; i < EDGE_COUNT(ior); ++i) s[k++].material.bsdf = newGlass(W, rgb(0.9f, 0.95f, 1.0f - 0.01f * (float)(i + g_dynamic * EDGE_COUNT(ior))), newConstantValue(W, 0.0f), edge(ior[i]));
+		g_dynamic = 0;
+		for (int i = 0; i < EDGE_COUNT(ior); ++i) {      /* plastic reads the MATERIAL's IOR (plastic.c:66-78); its coat's roughness is fixed by newPlastic() */
+			s[k].material.IOR = ior[i];
+			s[k++].material.bsdf = newPlastic(W, rgb(0.2f, 0.5f, 0.8f));
+		}
+		/* add of depth 4 over (glass, mix, plastic, emission) */
+		s[k++].material.bsdf = newAdd(W, newGlass(W, rgb(0.9f, 0.9f, 0.9f), newConstantValue(W, 0.0f), newConstantValue(W, 1.45f)),
+									  newAdd(W, newMix(W, newDiffuse(W, rgb(0.5f, 0.1f, 0.1f)), newMetal(W, rgb(0.3f, 0.3f, 0.6f), newConstantValue(W, 0.2f)), newConstantValue(W, 0.5f)),
+											 newAdd(W, newPlastic(W, rgb(0.1f, 0.4f, 0.2f)),
+													newAdd(W, newEmission(W, rgb(0.2f, 0.1f, 0.05f), newConstantValue(W, 0.5f)), newDiffuse(W, rgb(0.1f, 0.1f, 0.1f))))));
+		g_dynamic = 0;
+		for (int i = 0; i < EDGE_COUNT(extra); ++i) s[k++].material.bsdf = newGlass(W, rgb(1.0f, 0.9f, 0.8f), edge(roughness[extra[i]]), newConstantValue(W, 1.45f));
+	} else {
+		for (g_dynamic = 0; g_dynamic < 2; ++g_dynamic)
+			for (int i = 0; i < EDGE_COUNT(factor); ++i)
+				s[k++].material.bsdf = newMix(W, newDiffuse(W, rgb(0.8f, 0.2f, 0.1f)), newMetal(W, rgb(0.2f, 0.4f, 0.9f), newConstantValue(W, 0.1f)), edge(factor[i]));
+		for (g_dynamic = 0; g_dynamic < 2; ++g_dynamic)
+			for (int i = 0; i < EDGE_COUNT(strength); ++i) s[k++].material.bsdf = newEmission(W, rgb(0.9f, 0.6f, 0.3f), edge(strength[i]));
+		for (g_dynamic = 0; g_dynamic < 2; ++g_dynamic)
+			for (int i = 0; i < EDGE_COUNT(colors); ++i) s[k++].material.bsdf = newDiffuse(W, edgeColor(colors[i]));
+		for (g_dynamic = 0; g_dynamic < 2; ++g_dynamic)
+			for (int i = 0; i < EDGE_COUNT(colors); ++i) s[k++].material.bsdf = newTransparent(W, edgeColor(colors[i]));
+		for (g_dynamic = 0; g_dynamic < 2; ++g_dynamic)
+			for (int i = 0; i < EDGE_COUNT(colors); ++i) s[k++].material.bsdf = newIsotropic(W, edgeColor(colors[i]));
+	}
+	g_dynamic = 0;
+	if (k != 60) { fprintf(stderr, "CRH_NODE_PATCH=bsdfedges: %d spheres filled\n", k); exit(3); }
+	W->background = newBackground(W, newConstantTexture(W, (struct color){1.0f, 1.0f, 1.0f, 1.0f}), NULL, NULL);
+	(void)r;
+}
+
 /* Spheres whose radius is marked by a trailing ...7 in the fourth decimal (tools/gen_golden.py writes them so) and every instance of
  * the meshes whose indices are listed in CRH_VOLUME_MESHES ("0,2") become volumes. Density: CRH_VOLUME_DENSITY (default 6). */
 static void patchVolumes(struct renderer *r) {
@@ -187,6 +258,8 @@ void crh_apply_node_patch(struct renderer *r) {
 	if (!p || !*p) return;
 	W = r->scene;
 	if (!strcmp(p, "zoo")) patchZoo(r);
+	else if (!strcmp(p, "bsdfedges_a")) patchBsdfEdges(r, 0);
+	else if (!strcmp(p, "bsdfedges_b")) patchBsdfEdges(r, 1);
 	else if (!strcmp(p, "volumes")) patchVolumes(r);
 	else if (!strcmp(p, "whitesky")) W->background = newBackground(W, newConstantTexture(W, (struct color){1.0f, 1.0f, 1.0f, 1.0f}), NULL, NULL);
 	else { fprintf(stderr, "unknown CRH_NODE_PATCH=%s\n", p); exit(3); }

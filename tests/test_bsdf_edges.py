@@ -1,0 +1,474 @@
+"""The scatter side of the node library at its parameter edges: sampleBsdf, the Russian roulette and the weight update of shadeCore (c-ray_amd/csrc/pt_device.h),
+and the walk that receives the directions they produce. Every branch there decides how many sampler draws a hit consumes and so every later bounce of its path:
+`roughness > 0` (a random unit vector or none), `getDimension() > factor` (the mix branch), refract's discriminant and schlick (the reflection probability), and,
+from depth 4 on, probability = max(r, g, b), which may be 0, above 1, negative or NaN before 1 / probability goes into the weight.
+
+The parameters: metal, glass and plastic-coat roughness, glass IOR and the material IOR that plastic reads, the mix factor, the emission strength, and the colour
+of diffuse, transparent and isotropic — on zeros of both signs, the smallest subnormal, negative values, values above 1, FLT_MAX, both infinities and NaN, as a
+constant (which the scene compiler folds) and as a hit-dependent operand (tests/test_node_edges.py: Leaves — the device VM evaluates it per hit).
+
+  fixtures   bsdfedges_a, bsdfedges_b: rendered by the REAL reference (oracle/ref_node_patch.c: patchBsdfEdges builds the graphs with the reference's own
+             constructors; tools/gen_golden.py), nodezoo's sphere grid, one bsdf with one edge parameter per sphere, 160 x 96, 4 samples, 12 bounces, white sky. Two
+             fixtures hold the lists (FIXTURE_LAYOUT, checked against the decoded blobs): a — metal roughness and glass IOR in both forms, plastic on the
+             eleven material IORs, the add of depth 4, and on the four spheres left over glass roughness as a constant (smallest subnormal, 8, FLT_MAX, inf);
+             b — mix factor, emission strength and the five colours on diffuse, transparent and isotropic, all in both forms. Glass roughness beyond
+             those four spheres is in the synthesized scenes only. No image texture is reachable from a shown material or the background (asserted below), so the reference converts no
+             non-finite float to an integer, which is undefined C (tests/test_graph_edges.py: scope note).
+             Not in the fixtures, because the reference's constructors cannot build them: a NaN CONSTANT (the constructors hash-cons, a NaN never compares equal
+             to the candidate just inserted, newConstantValue / newConstantTexture return NULL and the render crashes) — NaN is built as 0 / 0 there, which the
+             scene compiler folds into the constant; and a plastic coat's roughness, which newPlastic() fixes at black. Both are in the synthesized scenes.
+  synthesized  copies of nodezoo_display's description (tests/scene_synth.py): per parameter value one scene that shows that one material on every sphere, and per
+             parameter one mixed scene whose spheres cycle through the whole list; each constant and hit-dependent. The oracle is the expectation.
+
+What is compared: the frame bit for bit — a NaN equal to a NaN of any payload (x86 and the GPU produce different default NaNs), infinities by sign — and the ray
+count; for the lane code and the device also inst_visits, inst_hits and sphere_tests. Those three pin the NaN-distance fix of stepCtrl: a ray
+whose direction is near FLT_MAX (reflected + sphere * roughness) overflows sphere.c's discriminant to inf - inf, every comparison of the NaN distance fails, and
+the reference ACCEPTS the hit with distance NaN; from then on its box test `tMin <= (tMax < NaN ? tMax : NaN)` fails for every node. The device's fast box test
+is min / max instructions, which drop a NaN operand: it went on visiting instances, and a later sphere replaced the hit (test_lane_code_equals_the_oracle, and
+test_device_equals_the_oracle on the GPU, fail without the fix in the scenes of roughness FLT_MAX and in the mixed roughness scenes, whose ray counts differ as
+well: the mixed metal scene gave 171 127 rays against the oracle's 171 112).
+
+CPU tier: oracle == reference and lane code == reference on the fixtures; lane code == oracle on every synthesized scene; coverage conditions from the oracle alone;
+a cap of 25 % on the non-finite floats of any expected frame, so that a broken comparison cannot hide behind NaN == NaN; and this file's GPU tests on the kernel
+emulation. GPU tier: crh_render_region == fixture / oracle with the default kernel, CRH_KERNEL_STREAM, CRH_OPT_RENDER_SLABS literal, and the Halton sampler on the
+mixed scenes. Every scene has run on the oracle, the lane code and the kernel emulation (the CPU tier) before it goes to a GPU."""
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from scene_synth import (ADD, COLOR_COMBINERGB, COLOR_CONSTANT, COLOR_IMAGE, DIFFUSE, EMISSION, GLASS, ISOTROPIC, MATH_ADD, MATH_DIVIDE, MATH_MULTIPLY, METAL, MIX, NONE,
+                         PLASTIC, TRANSPARENT, VALUE_CONSTANT, VALUE_MATH, VALUE_RAYLENGTH, VEC_VECMATH)
+from test_emu_parity import emu_render
+from test_graph_edges import base, ctx  # noqa: F401 (the module-scoped fixtures: nodezoo_display's scene, a device context)
+from test_graph_edges import CUBE, EMU_DIR, PLANE, REPO, ForLibrary, same_bits, scene_hits, size_of
+from test_node_edges import FLT_MAX, INF, NAN, SUB_MIN, Leaves, new_scene
+
+F = np.float32
+W, H = size_of("spheres")          # 160 x 96
+SAMPLES, BOUNCES = 4, 12
+FIXTURES = ["bsdfedges_a", "bsdfedges_b"]
+NONFINITE_CAP = 0.25
+
+# oracle/ref_node_patch.c: patchBsdfEdges holds the same lists
+ROUGHNESS = [0.0, -0.0, SUB_MIN, -0.5, 0.5, 1.0, 8.0, FLT_MAX, INF, -INF, NAN]
+IOR = [1.0, 0.0, -0.0, -1.0, 0.5, 1.45, 1e-30, 1e30, INF, -INF, NAN]
+FACTOR = [0.0, -0.0, 1.0, -0.5, 1.5, 0.5, INF, -INF, NAN]
+STRENGTH = [0.0, -1.0, 5.0, 1e30, INF, NAN]
+COLORS = [(0.0, 0.0, 0.0), (-0.5, 0.25, 0.5), (1.5, 0.5, 2.0), (0.5, INF, 0.25), (0.5, 0.25, NAN)]
+
+
+def edge_color(s, L, c):
+    return s.combine_rgb(*[L.val(x) for x in c]) if L.dynamic else s.color(*c)
+
+
+# parameter -> (values, fn(s, L, x) -> (bsdf node, material IOR), has a hit-dependent form)
+def _metal(s, L, x):
+    return s.bsdf(METAL, s.color(0.9, 0.7, 0.5), L.val(x)), 1.45
+
+
+def _glass_roughness(s, L, x):
+    return s.bsdf(GLASS, s.color(1.0, 0.9, 0.8), L.val(x), s.value(1.45)), 1.45
+
+
+def _glass_ior(s, L, x):
+    return s.bsdf(GLASS, s.color(0.9, 0.95, 1.0), s.value(0.0), L.val(x)), 1.45
+
+
+def _plastic(s, roughness, ior):
+    c = s.color(0.2, 0.5, 0.8)
+    return s.bsdf(PLASTIC, c, roughness, s.bsdf(DIFFUSE, c)), ior          # a: colour, b: the coat's roughness (a colour, plastic.c:46 reads .red), c: the diffuse layer
+
+
+def _plastic_roughness(s, L, x):
+    return _plastic(s, s.combine(L.val(x)) if L.dynamic else s.color(x, x, x), 1.45)
+
+
+def _plastic_ior(s, L, x):
+    return _plastic(s, s.color(0.0, 0.0, 0.0), x)
+
+
+def _mix(s, L, x):
+    return s.bsdf(MIX, s.bsdf(DIFFUSE, s.color(0.8, 0.2, 0.1)), s.bsdf(METAL, s.color(0.2, 0.4, 0.9), s.value(0.1)), L.val(x)), 1.45
+
+
+def _emission(s, L, x):
+    return s.bsdf(EMISSION, s.color(0.9, 0.6, 0.3), L.val(x)), 1.45
+
+
+PARAMETERS = {
+    "metal roughness": (ROUGHNESS, _metal, True),
+    "glass roughness": (ROUGHNESS, _glass_roughness, True),
+    "glass ior": (IOR, _glass_ior, True),
+    "plastic roughness": (ROUGHNESS, _plastic_roughness, True),
+    "plastic ior": (IOR, _plastic_ior, False),          # the material's field: there is no operand to make hit-dependent
+    "mix factor": (FACTOR, _mix, True),
+    "emission strength": (STRENGTH, _emission, True),
+    "diffuse colour": (COLORS, lambda s, L, c: (s.bsdf(DIFFUSE, edge_color(s, L, c)), 1.45), True),
+    "transparent colour": (COLORS, lambda s, L, c: (s.bsdf(TRANSPARENT, edge_color(s, L, c)), 1.45), True),
+    "isotropic colour": (COLORS, lambda s, L, c: (s.bsdf(ISOTROPIC, edge_color(s, L, c)), 1.45), True),
+}
+# Values that put non-finite radiance into the frame wherever they are seen, directly or by reflection: an emission of 1e30 (times a weight above 1), inf or NaN,
+# a colour with an inf or NaN channel. Shown on all 60 spheres they fill more than the cap allows of the frame (measured with the oracle: 27 % to 57 %), so
+# they are shown on every sixth sphere, the others plain grey (on every fourth, infinite emission still gives 25.1 %), and the emission strengths' mixed scene is two: the finite
+# strengths, and these on every sixth sphere.
+PRODUCERS = {"emission strength": [3, 4, 5], "diffuse colour": [3, 4], "transparent colour": [3, 4], "isotropic colour": [3, 4]}
+PRODUCER_STRIDE = 6
+MIXED, MIXED_PRODUCERS = "mixed", "mixed producers"
+
+
+def mixed_kinds(p):
+    return [MIXED, MIXED_PRODUCERS] if p == "emission strength" else [MIXED]
+
+
+# (parameter, index into its values or a mixed kind, hit-dependent)
+SCENES = [(p, k, dyn) for p, (values, _, has_dyn) in PARAMETERS.items() for dyn in ([False, True] if has_dyn else [False])
+          for k in list(range(len(values))) + mixed_kinds(p)]
+GROUPS = {f"{p} {'dynamic' if dyn else 'constant'}": [sc for sc in SCENES if sc[0] == p and sc[2] == dyn]
+          for p, (_, _, has_dyn) in PARAMETERS.items() for dyn in ([False, True] if has_dyn else [False])}
+
+
+def build(base, parameter, which, dynamic):
+    """(scene, {k: material index of value k}): one material on all spheres, or (mixed) the spheres cycle through the values. Cube and plane are plain grey, the
+    sky white."""
+    values, fn, _ = PARAMETERS[parameter]
+    s, tex = new_scene(base, "spheres")
+    L = Leaves(s, dynamic, tex)
+    producers = PRODUCERS.get(parameter, [])
+    if which == MIXED:
+        shown = [k for k in range(len(values)) if k not in producers or len(mixed_kinds(parameter)) == 1]
+    else:
+        shown = producers if which == MIXED_PRODUCERS else [which]
+    stride = PRODUCER_STRIDE if which == MIXED_PRODUCERS or which in producers else 1
+    mats = {}
+    for k in shown:
+        bsdf, ior = fn(s, L, values[k])
+        mats[k] = s.material(bsdf, ior=ior)
+    grey = s.material(s.bsdf(DIFFUSE, s.color(0.6, 0.6, 0.6)))
+    for i in range(60):
+        s.set_sphere_material(i, grey if i % stride else mats[shown[(i // stride) % len(shown)]])
+    s.set_mesh_material(CUBE, grey)
+    s.set_mesh_material(PLANE, grey)
+    s.white_sky()
+    return s, mats
+
+
+_cases = {}
+
+
+def cpu_case(oracle, base, sc, bounces=BOUNCES, halton=False):
+    """(scene, materials, the oracle's frame, its counters): rendered once, shared by the tests, left unchanged."""
+    key = sc + (bounces, halton)
+    if key not in _cases:
+        s, mats = build(base, *sc)
+        want, cnt = oracle.render(s, W, H, SAMPLES, bounces, halton=halton, threads=1 if halton else 0)
+        _cases[key] = (s, mats, want, cnt)
+    return _cases[key]
+
+
+def frames_equal(got, want):
+    """Bit for bit; a NaN equals a NaN of any payload or sign, an infinity only the infinity of its sign."""
+    return same_bits(got, want, nan_equal=True)
+
+
+def assert_frame(got, want, what):
+    bad = ~frames_equal(got, want)
+    assert not bad.any(), f"{what}: {int(bad.sum())} floats differ, first at {np.argwhere(bad)[:3].tolist()}: {got[bad][:3]} against {want[bad][:3]}"
+
+
+def nonfinite_fraction(frame):
+    return float((~np.isfinite(frame)).mean())
+
+
+WALK_COUNTERS = ("rays", "inst_visits", "inst_hits", "sphere_tests")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# CPU tier
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+def reachable_kinds(d, root):
+    """Node kinds reachable from gnode `root`: a math / vecMath node's field c is its op, every other field that names a node is a child (scene_synth.py)."""
+    seen, todo, kinds = set(), [root], set()
+    while todo:
+        j = todo.pop()
+        if j == NONE or j in seen:
+            continue
+        seen.add(j)
+        n = d.gnodes[j]
+        kinds.add(n.kind)
+        if n.kind == COLOR_IMAGE:
+            continue          # (a: texture index, b: options)
+        todo += [n.a, n.b] + ([] if n.kind in (VALUE_MATH, VEC_VECMATH) else [n.c])
+    return kinds
+
+
+def shown_roots(d):
+    roots = {d.materials[d.spheres[i].material].bsdf for i in range(d.sphere_count)}
+    for i in range(d.mesh_count):
+        m = d.meshes[i]
+        roots |= {d.materials[m.material_base + k].bsdf for k in range(m.material_count)}
+    return roots | {d.background}
+
+
+# What the fixtures' spheres show, in sphere order (oracle/ref_node_patch.c: patchBsdfEdges): (bsdf kind, where the parameter is, values, forms). "b" / "c" / "a": that
+# operand of the sphere's bsdf node — a value, for "a" a colour; "ior": the material's field.
+GLASS_ROUGHNESS_EXTRA = [SUB_MIN, 8.0, FLT_MAX, INF]
+FIXTURE_LAYOUT = {
+    "bsdfedges_a": [(METAL, "b", ROUGHNESS, (False, True)), (GLASS, "c", IOR, (False, True)), (PLASTIC, "ior", IOR, (False,)), (ADD, None, [None], (False,)),
+                    (GLASS, "b", GLASS_ROUGHNESS_EXTRA, (False,))],
+    "bsdfedges_b": [(MIX, "c", FACTOR, (False, True)), (EMISSION, "b", STRENGTH, (False, True)), (DIFFUSE, "a", COLORS, (False, True)),
+                    (TRANSPARENT, "a", COLORS, (False, True)), (ISOTROPIC, "a", COLORS, (False, True))],
+}
+
+
+def decode_value(d, j):
+    """(value, hit-dependent) of a value operand as patchBsdfEdges builds it: a constant; 0 / 0 for NaN; x * (rayLength * 0 + 1) for the hit-dependent form."""
+    n = d.gnodes[j]
+    if n.kind == VALUE_CONSTANT:
+        return n.f[0], False
+    assert n.kind == VALUE_MATH, (j, n.kind)
+    if n.c == MATH_DIVIDE:
+        assert all(d.gnodes[k].kind == VALUE_CONSTANT and d.gnodes[k].f[0] == 0 for k in (n.a, n.b))
+        return NAN, False
+    one = d.gnodes[n.b]
+    assert n.c == MATH_MULTIPLY and one.kind == VALUE_MATH and one.c == MATH_ADD and decode_value(d, one.b) == (1.0, False), j
+    zero = d.gnodes[one.a]
+    assert zero.kind == VALUE_MATH and zero.c == MATH_MULTIPLY and d.gnodes[zero.a].kind == VALUE_RAYLENGTH and decode_value(d, zero.b)[0] == 0
+    x, inner = decode_value(d, n.a)
+    assert not inner
+    return x, True
+
+
+def decode_color(d, j):
+    n = d.gnodes[j]
+    if n.kind == COLOR_CONSTANT:
+        return (n.f[0], n.f[1], n.f[2]), False
+    assert n.kind == COLOR_COMBINERGB, (j, n.kind)
+    parts = [decode_value(d, k) for k in (n.a, n.b, n.c)]
+    assert len({dyn for _, dyn in parts}) == 1
+    return tuple(x for x, _ in parts), parts[0][1]
+
+
+def same_value(a, b):
+    return F(a).tobytes() == F(b).tobytes() or bool(np.isnan(a) and np.isnan(b))
+
+
+@pytest.mark.parametrize("name", FIXTURES)
+def test_the_fixtures_hold_the_edge_lists(name, oracle, golden_blob):
+    """The committed blob, decoded: sphere by sphere the bsdf kind, the edge value — bit for bit, -0 as -0 (the reference hash-conses its constants: a -0 that came
+    back as the +0 node would show here), NaN as 0 / 0 — and the form, as FIXTURE_LAYOUT says. Every value of every list is there in both forms."""
+    scene = oracle.OracleScene(golden_blob(name))
+    d = scene.desc
+    i = 0
+    for kind, where, values, forms in FIXTURE_LAYOUT[name]:
+        for dynamic in forms:
+            for x in values:
+                mat = d.materials[d.spheres[i].material]
+                n = d.gnodes[mat.bsdf]
+                assert n.kind == kind, (name, i, n.kind, kind)
+                if where == "ior":
+                    got, dyn = (mat.ior,), False
+                elif where == "a":
+                    got, dyn = decode_color(d, n.a)
+                elif where is not None:
+                    v, dyn = decode_value(d, getattr(n, where))
+                    got = (v,)
+                if where is not None:
+                    want = x if isinstance(x, tuple) else (x,)
+                    assert dyn == dynamic and all(same_value(g, w) for g, w in zip(got, want)), (name, i, got, want, dyn, dynamic)
+                i += 1
+    assert i == d.sphere_count == 60
+    scene.close()
+
+
+@pytest.mark.parametrize("name", FIXTURES)
+def test_oracle_and_lane_code_equal_the_reference(name, emu, oracle, manifest, golden_blob, golden_ref):
+    """The reference's frame of the fixture bit for bit and its ray count, from the oracle and from the host-built lane code; no image texture is reachable from
+    any shown material or the background; every sphere shows a material of its own; the non-finite cap holds for the reference's frame."""
+    m = manifest[name]
+    assert (m["width"], m["height"], m["samples"], m["bounces"]) == (W, H, SAMPLES, BOUNCES)
+    scene = oracle.OracleScene(golden_blob(name))
+    d = scene.desc
+    for root in shown_roots(d):
+        assert COLOR_IMAGE not in reachable_kinds(d, root), (name, root)
+    assert len({d.spheres[i].material for i in range(d.sphere_count)}) == 60
+    ref = golden_ref(name)
+    print(f"{name}: {m['rays']} rays, {100 * nonfinite_fraction(ref):.1f} % of the reference's floats are not finite")
+    assert nonfinite_fraction(ref) <= NONFINITE_CAP and np.isfinite(ref).any() and (ref != 0).any()
+    got, cnt = oracle.render(scene, W, H, SAMPLES, BOUNCES)
+    assert_frame(got, ref, f"{name}: oracle against the reference")
+    assert cnt["rays"] == m["rays"], (cnt["rays"], m["rays"])
+    fb, ecnt, _ = emu_render(emu, oracle, scene, W, H, SAMPLES, BOUNCES)
+    assert_frame(fb, ref, f"{name}: lane code against the reference")
+    assert ecnt["rays"] == m["rays"], (ecnt["rays"], m["rays"])
+    assert {k: ecnt[k] for k in WALK_COUNTERS} == {k: cnt[k] for k in WALK_COUNTERS}
+    scene.close()
+
+
+@pytest.mark.parametrize("group", list(GROUPS))
+def test_lane_code_equals_the_oracle(group, emu, oracle, base):
+    """emu_render_region on every synthesized scene: the oracle's frame, and its rays, inst_visits, inst_hits and sphere_tests — equal, not merely fewer: a hit
+    with a NaN distance ends the reference's walk (module docstring), and the lane code's with it."""
+    for sc in GROUPS[group]:
+        s, _, want, cnt = cpu_case(oracle, base, sc)
+        fb, ecnt, _ = emu_render(emu, oracle, s, W, H, SAMPLES, BOUNCES)
+        assert_frame(fb, want, f"{sc}: lane code against the oracle")
+        assert {k: ecnt[k] for k in WALK_COUNTERS} == {k: cnt[k] for k in WALK_COUNTERS}, sc
+        assert ecnt["paths"] == cnt["paths"] == W * H * SAMPLES
+
+
+def test_no_expected_frame_is_mostly_not_a_number(oracle, base):
+    """At most 25 % of any scene's floats are non-finite in the oracle's frame, and every frame holds finite, non-zero pixels."""
+    worst = {}
+    for sc in SCENES:
+        want = cpu_case(oracle, base, sc)[2]
+        f = nonfinite_fraction(want)
+        worst[sc[0]] = max(worst.get(sc[0], 0.0), f)
+        assert f <= NONFINITE_CAP, (sc, f)
+        assert (np.isfinite(want) & (want != 0)).sum() >= want.size // 2, sc
+    print({k: f"{100 * v:.1f} %" for k, v in worst.items()})
+
+
+def test_every_edge_material_is_a_first_hit(oracle, base):
+    """In each mixed scene every edge material is the first hit of at least 20 pixels (the oracle's hit records of pass 0's camera rays), and a parameter's mixed
+    scenes hold all of its values."""
+    seen = {}
+    for sc in SCENES:
+        if sc[1] not in (MIXED, MIXED_PRODUCERS):
+            continue
+        s, mats, _, _ = cpu_case(oracle, base, sc)
+        hits = scene_hits(oracle, s, "spheres")[0]
+        counts = {k: int(((hits["inst"] >= 0) & (hits["material"] == m)).sum()) for k, m in mats.items()}
+        assert min(counts.values()) >= 20, (sc, counts)
+        seen.setdefault((sc[0], sc[2]), set()).update(counts)
+    for (p, dyn), ks in seen.items():
+        assert ks == set(range(len(PARAMETERS[p][0]))), (p, dyn, ks)
+
+
+def same_render(a, b):
+    return frames_equal(a[2], b[2]).all() and a[3]["rays"] == b[3]["rays"]
+
+
+@pytest.mark.parametrize("dynamic", [False, True], ids=["constant", "dynamic"])
+def test_values_the_reference_treats_alike_and_apart(dynamic, oracle, base):
+    """`roughness > 0.0f` is false for -0, a negative number, -inf and NaN: those scenes are the roughness-0 scene, frame and ray count. `getDimension() > factor`
+    is false for a NaN factor as it is for factor 1 (a draw is below 1): always b; and -0 is 0. Apart: the smallest subnormal IS > 0, so the hit draws a unit
+    vector and every later draw of the path moves; IOR 1 against 1.45."""
+    def case(p, x):
+        values = PARAMETERS[p][0]
+        k = next(i for i, v in enumerate(values) if F(v).tobytes() == F(x).tobytes() or (np.isnan(v) and np.isnan(x)))
+        return cpu_case(oracle, base, (p, k, dynamic))
+    for p in ("metal roughness", "glass roughness", "plastic roughness"):
+        zero = case(p, 0.0)
+        for x in (-0.0, -0.5, -INF, NAN):
+            assert same_render(case(p, x), zero), (p, x, case(p, x)[3]["rays"], zero[3]["rays"])
+        assert not frames_equal(case(p, SUB_MIN)[2], zero[2]).all(), p
+        print(p, "rays at roughness 0:", zero[3]["rays"], "at the smallest subnormal:", case(p, SUB_MIN)[3]["rays"])
+    assert same_render(case("mix factor", NAN), case("mix factor", 1.0))
+    assert same_render(case("mix factor", -0.0), case("mix factor", 0.0))
+    assert not frames_equal(case("mix factor", 0.5)[2], case("mix factor", 1.0)[2]).all()
+    assert not frames_equal(case("glass ior", 1.0)[2], case("glass ior", 1.45)[2]).all()
+    if not dynamic:
+        assert not frames_equal(case("plastic ior", 1.0)[2], case("plastic ior", 1.45)[2]).all()
+
+
+def test_russian_roulette_runs_in_every_mixed_scene(oracle, base):
+    """Each mixed scene renders more rays at 12 bounces than at 4: paths reach depth 4, where probability = max(r, g, b) decides."""
+    for sc in SCENES:
+        if sc[1] in (MIXED, MIXED_PRODUCERS):
+            deep, shallow = cpu_case(oracle, base, sc)[3]["rays"], cpu_case(oracle, base, sc, bounces=4)[3]["rays"]
+            assert deep > shallow, (sc, deep, shallow)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# GPU tier
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+MODES = ["default", "stream", "literal slabs"]
+
+
+class mode_of:
+    """The context's options for one mode, restored on the way out."""
+
+    def __init__(self, pkg, ctx, mode):
+        self.abi, self.ctx, self.mode = pkg.abi, ctx, mode
+
+    def __enter__(self):
+        abi = self.abi
+        if self.mode == "stream":
+            self.ctx.set_option(abi.OPT_KERNEL, abi.KERNEL_STREAM)
+        if self.mode == "literal slabs":
+            self.ctx.set_option(abi.OPT_RENDER_SLABS, abi.TRACE_SLABS_LITERAL)
+        if self.mode == "halton":
+            self.ctx.set_option(abi.OPT_SAMPLER, abi.SAMPLER_HALTON)
+        return self
+
+    def __exit__(self, *exc):
+        abi = self.abi
+        self.ctx.set_option(abi.OPT_KERNEL, abi.KERNEL_ROLL)
+        self.ctx.set_option(abi.OPT_RENDER_SLABS, abi.TRACE_SLABS_EXACT)
+        self.ctx.set_option(abi.OPT_SAMPLER, abi.SAMPLER_RANDOM)
+        return False
+
+
+def device_render(ctx, scene, fb, mode):
+    ctx.upload(scene)
+    ctx.clear(fb, W, H)
+    ctx.reset_counters()
+    ctx.render_region(fb, W, H, SAMPLES, BOUNCES)
+    if mode == "stream":
+        assert ctx.last_kernel_name().startswith("k_stream"), ctx.last_kernel_name()
+    return ctx.download(fb, W, H), ctx.counters()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("name", FIXTURES)
+def test_device_equals_the_reference(name, mode, pkg, ctx, manifest, golden_blob, golden_ref):
+    """crh_render_region on the fixture: the reference's frame and ray count."""
+    m = manifest[name]
+    fb = ctx.framebuffer(W, H)
+    with mode_of(pkg, ctx, mode):
+        got, cnt = device_render(ctx, pkg.api.Scene(golden_blob(name)), fb, mode)
+    assert_frame(got, golden_ref(name), f"{name} ({mode}): device against the reference")
+    assert cnt["rays"] == m["rays"] and cnt["paths"] == W * H * SAMPLES, (cnt, m["rays"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", MODES + ["halton"])
+@pytest.mark.parametrize("group", list(GROUPS))
+def test_device_equals_the_oracle(group, mode, pkg, ctx, oracle, base):
+    """crh_render_region on every synthesized scene of the group (with the Halton sampler: on its mixed scenes): the oracle's frame, rays, inst_visits, inst_hits
+    and sphere_tests. On the kernel emulation, where a frame takes about a second, the streaming form and the literal slabs render the mixed scenes and the
+    FLT_MAX scenes only; the default kernel renders every scene there too."""
+    fb = ctx.framebuffer(W, H)
+    halton = mode == "halton"
+    few = halton or (mode != "default" and hasattr(pkg.api.library(), "crh_emu_stats"))
+    with mode_of(pkg, ctx, mode):
+        for sc in GROUPS[group]:
+            if few and not (sc[1] in (MIXED, MIXED_PRODUCERS) or (mode != "halton" and PARAMETERS[sc[0]][0][sc[1]] == FLT_MAX)):
+                continue
+            s, _, want, ocnt = cpu_case(oracle, base, sc, halton=halton)
+            got, cnt = device_render(ctx, ForLibrary(pkg, s), fb, mode)
+            assert_frame(got, want, f"{sc} ({mode}): device against the oracle")
+            assert {k: cnt[k] for k in WALK_COUNTERS} == {k: ocnt[k] for k in WALK_COUNTERS}, (sc, mode)
+
+
+N_GPU_TESTS = len(FIXTURES) * len(MODES) + len(GROUPS) * (len(MODES) + 1)
+
+
+def test_bsdf_edges_on_the_emulation():
+    """CPU tier: this file's GPU tests run by a child pytest against the kernel emulation (tests/emu/libcray_hip_emu.so: the render kernels and the scene compiler
+    compiled unmodified on the HIP-on-CPU shim) — every one of them runs and passes there, none skipped. Measured on 8 CPUs: 248 s (about 290 frames at 12 bounces)."""
+    from conftest import locked_make
+    locked_make(["make", "-s", "-C", EMU_DIR, "libcray_hip_emu.so"])
+    env = dict(os.environ, CRH_LIB=os.path.join(EMU_DIR, "libcray_hip_emu.so"), CRH_ALLOW_EMULATION="1", HIPEMU_CUS="2", HIPEMU_THREADS="3")
+    cmd = [sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider"]
+    r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=1700)
+    tail = (r.stdout + r.stderr)[-4000:]
+    assert r.returncode == 0, tail
+    m = re.search(r"(\d+) passed", r.stdout)
+    assert m and int(m.group(1)) == N_GPU_TESTS, tail
+    assert "skipped" not in r.stdout.strip().splitlines()[-1], tail

@@ -8,7 +8,7 @@ import pytest
 
 from conftest import BIG_CASES, built_blob, camera_rays, resize_camera
 
-CASES = ["cfg1_scene", "alphanode", "fence", "glowmetal", "refraction", "uvsphere", "texwrap"]
+CASES = ["cfg1_scene", "alphanode", "fence", "glowmetal", "refraction", "uvsphere", "texwrap", "bsdfedges_a"]          # (bsdfedges_b's frame holds NaN: tests/test_bsdf_edges.py)
 
 
 def emu_render(emu, oracle, scene, w, h, s, b, region=None, shape=(8, 8), chunk=64):

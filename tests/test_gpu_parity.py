@@ -17,6 +17,9 @@ from conftest import BIG_CASES, built_blob, camera_rays, image_stats, kernel_for
 
 pytestmark = pytest.mark.gpu
 CASES = ["cfg1_scene", "alphanode", "fence", "glowmetal", "refraction", "uvsphere", "texwrap"]
+# ... and an edge scene for the frames: one bsdf parameter at an edge value per sphere (tests/test_bsdf_edges.py; its frame holds no NaN — bsdfedges_b's does, and is
+# compared there, a NaN equal to a NaN of any payload)
+IMAGE_CASES = CASES + ["bsdfedges_a"]
 
 
 @pytest.fixture(scope="module")
@@ -60,7 +63,7 @@ def test_trace_rays_bit_exact(name, pkg, ctx, oracle, golden_blob):
     assert (ho["inst"] >= 0).sum() > 500
 
 
-@pytest.mark.parametrize("name", CASES)
+@pytest.mark.parametrize("name", IMAGE_CASES)
 def test_image_parity_vs_reference(name, pkg, ctx, oracle, manifest, golden_blob, golden_ref):
     m = manifest[name]
     img, cnt, _ = gpu_render(pkg, ctx, golden_blob(name), m["width"], m["height"], m["samples"], m["bounces"])

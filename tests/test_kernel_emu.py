@@ -36,7 +36,7 @@ def emu_lib():
 
 GPU_TIER_JOBS = {     # name -> (files of the GPU tier, -k selection, number of tests that must run and pass)
     "trace_rays": (["test_gpu_parity.py"], "test_trace_rays_bit_exact and not baseline_configs", 7),
-    "frames": (["test_gpu_parity.py"], "test_image_parity_vs_reference", 7),
+    "frames": (["test_gpu_parity.py"], "test_image_parity_vs_reference", 8),
     "schedules": (["test_gpu_parity.py"], "shade_class_batches or dispatch_decompositions or split_pixels or interactive_mode or edge_cases or zero_component or srgb8_matches or error_paths or round_limit or upload_lifecycle or wide_walk_option or buffers_are_reused or every_option_set", 15),
     "stream": (["test_gpu_parity.py"], "streaming_form or wide_walk_meets", 3),          # round 6: the streaming form (walk / shade + refill / fold kernels) against the rolling kernel and the fixtures; the 4-ary walk inside the tolerance gates
     "walk_probe": (["test_gpu_parity.py"], "test_walk_probe_equals_the_plain_walk", 2),          # k_walk_probe in every variant of the measurement (forms 0 and 1, and form 3: the walk-only machine of csrc/walk_machine.h from the probe's ray source) against the one-ray-per-lane walk, on both fixtures. Measured: 60 s alone, 159 s beside the module's other children on 8 CPUs, where `schedules`, the slowest, takes 391 s

@@ -55,6 +55,11 @@ PATCHED_CASES = {
     # of two), filtered and nearest, with and without the sRGB transform, and a mix whose factor is grayscale(image); constant white sky
     "texwrap": ("texwrap.json", {"CRH_NODE_PATCH": "whitesky"}, 160, 100, 4, 4),
     "texwrap_display": ("texwrap.json", {"CRH_NODE_PATCH": "whitesky"}, 160, 100, 1, 2),    # first hit x white background: the albedo
+    # the scatter side at its parameter edges (tests/test_bsdf_edges.py): nodezoo's sphere grid, one bsdf with one edge parameter per sphere — roughness, IOR,
+    # mix factor, emission strength, colours; zeros, subnormals, infinities, NaN; constant and hit-dependent — under a constant white sky, 12 bounces so that the
+    # Russian roulette of depth >= 4 runs. Two fixtures hold the lists (oracle/ref_node_patch.c: patchBsdfEdges)
+    "bsdfedges_a": ("nodezoo.json", {"CRH_NODE_PATCH": "bsdfedges_a"}, 160, 96, 4, 12),
+    "bsdfedges_b": ("nodezoo.json", {"CRH_NODE_PATCH": "bsdfedges_b"}, 160, 96, 4, 12),
 }
 ZOO_COLS, ZOO_ROWS, ZOO_PITCH, ZOO_RADIUS = 10, 6, 0.1, 0.042
 
@@ -253,6 +258,8 @@ def main():
         gz_write(os.path.join(GOLDEN, name + ".ref.f32.gz"), buf.tobytes())
         entry.update({"ref_md5": hashlib.md5(buf.tobytes()).hexdigest(), "rays": cst["rays"], "node_tests": cst["node_tests"],
                       "tri_tests": cst["tri_tests"], "mean": float(buf.mean())})
+        if not np.isfinite(buf).all():          # (bsdfedges: the manifest stays plain JSON) the mean of the finite floats, and how many are not
+            entry.update({"mean": float(buf[np.isfinite(buf)].mean()), "nonfinite": int((~np.isfinite(buf)).sum())})
         manifest[name] = entry
         print(name, entry)
     for name, (scene, blob, w, h, spp, bounces) in BIG_CASES.items():
