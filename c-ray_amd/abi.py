@@ -7,6 +7,8 @@ import ctypes as C
 
 ABI_VERSION = 5
 AOV_CHANNELS = 8            # CRH_AOV_CHANNELS: albedo r g b, normal x y z, depth, coverage
+ID_SLOTS, ID_WORDS = 6, 16  # CRH_ID_SLOTS, CRH_ID_WORDS: id[0..5], count[0..5], lost, total, two reserved words
+IDS_MATTE_MAX = 64          # CRH_IDS_MATTE_MAX: ids one crh_ids_matte call takes
 
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED, ERR_IO, ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6
 NODE_NONE = 0xFFFFFFFF
@@ -153,6 +155,7 @@ EXPORTED_SYMBOLS = [
     "crh_blob_save", "crh_blob_load", "crh_blob_free", "crh_bvh_build_triangles", "crh_debug_eval_math", "crh_debug_plan_units", "crh_last_kernel_name", "crh_framebuffer_strips_to_srgb8",
     "crh_scene_compile", "crh_scene_upload_compiled", "crh_compiled_scene_free", "crh_debug_upload_counts",
     "crh_aov_alloc", "crh_aov_free", "crh_aov_clear", "crh_aov_download", "crh_render_aov", "crh_aov_kernel_time_ms",
+    "crh_ids_alloc", "crh_ids_free", "crh_ids_clear", "crh_ids_download", "crh_render_ids", "crh_ids_kernel_time_ms", "crh_ids_resolve", "crh_ids_matte",
     "crh_denoise_params_default", "crh_denoise", "crh_denoise_time_ms", "crh_debug_denoise_launch_ms",
     "crh_denoise_variance_params_default", "crh_denoise_variance", "crh_framebuffer_copy",
     "crh_adaptive_step", "crh_adaptive_time_ms", "crh_adaptive_params_default", "crh_render_adaptive",

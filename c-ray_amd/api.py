@@ -74,6 +74,14 @@ def library():
         "crh_aov_download": (C.c_int, [ctx, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
         "crh_render_aov": (C.c_int, [ctx, C.POINTER(abi.RenderParams), C.POINTER(abi.Tile), C.c_uint32, C.c_void_p]),
         "crh_aov_kernel_time_ms": (C.c_int, [ctx, C.POINTER(C.c_float)]),
+        "crh_ids_alloc": (C.c_int, [ctx, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+        "crh_ids_free": (C.c_int, [ctx, C.c_void_p]),
+        "crh_ids_clear": (C.c_int, [ctx, C.c_void_p, C.c_int, C.c_int]),
+        "crh_ids_download": (C.c_int, [ctx, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+        "crh_render_ids": (C.c_int, [ctx, C.POINTER(abi.RenderParams), C.POINTER(abi.Tile), C.c_uint32, C.c_void_p, C.c_void_p]),
+        "crh_ids_kernel_time_ms": (C.c_int, [ctx, C.POINTER(C.c_float)]),
+        "crh_ids_resolve": (C.c_int, [ctx, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+        "crh_ids_matte": (C.c_int, [ctx, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_uint32, C.c_void_p]),
         "crh_denoise_params_default": (None, [C.POINTER(abi.DenoiseParams)]),
         "crh_denoise": (C.c_int, [ctx, C.POINTER(abi.DenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p]),
         "crh_denoise_time_ms": (C.c_int, [ctx, C.POINTER(C.c_float)]),
@@ -242,6 +250,7 @@ class Context:
                "crh_context_create")
         self._owned_fbs = []
         self._owned_aovs = []
+        self._owned_ids = []
 
     def close(self):
         if self.h:
@@ -251,6 +260,9 @@ class Context:
             for buf in self._owned_aovs:
                 self.L.crh_aov_free(self.h, buf)
             self._owned_aovs = []
+            for buf in self._owned_ids:
+                self.L.crh_ids_free(self.h, buf)
+            self._owned_ids = []
             self.L.crh_context_destroy(self.h)
             self.h = C.c_void_p()
 
@@ -350,6 +362,50 @@ class Context:
         """Milliseconds of the most recent render_aov's kernel (waits for it)."""
         ms = C.c_float(0.0)
         _check(self.L.crh_aov_kernel_time_ms(self.h, C.byref(ms)), "crh_aov_kernel_time_ms")
+        return float(ms.value)
+
+    # ---- ID mattes: ranked instance and material coverage per pixel (include/cray_hip.h: crh_render_ids) ----
+    def ids_buffer(self, width, height):
+        """A zeroed device buffer of abi.ID_WORDS uint32 per pixel, owned by the context."""
+        p = C.c_void_p()
+        _check(self.L.crh_ids_alloc(self.h, width, height, C.byref(p)), "crh_ids_alloc")
+        self._owned_ids.append(p)
+        return p
+
+    def clear_ids(self, buf, width, height):
+        _check(self.L.crh_ids_clear(self.h, buf, width, height), "crh_ids_clear")
+
+    def render_ids(self, instance_ids, material_ids, width, height, samples, tiles=None, region=None, first_pass=0, pass_count=None):
+        """Fold the first hits of passes [first_pass, first_pass + pass_count) of `samples` into the instance-id buffer and the material-id buffer (either may be None):
+        the pixels of `tiles` (a list of x0, y0, x1, y1), or of `region`, or the whole image."""
+        x0, y0, x1, y1 = region if region else (0, 0, width, height)
+        p = abi.RenderParams(x0, y0, x1, y1, width, height, first_pass, samples - first_pass if pass_count is None else pass_count, samples, 0)
+        if tiles is None:
+            _check(self.L.crh_render_ids(self.h, C.byref(p), None, 0, instance_ids, material_ids), "crh_render_ids")
+        elif len(tiles):          # (an empty list is no work; to the C entry a count of 0 means "the region of params")
+            arr = (abi.Tile * len(tiles))(*[abi.Tile(*t) for t in tiles])
+            _check(self.L.crh_render_ids(self.h, C.byref(p), arr, len(tiles), instance_ids, material_ids), "crh_render_ids")
+
+    def download_ids(self, buf, width, height):
+        """uint32 [height, width, 16]: id[0..5], count[0..5], lost, total, two reserved words (row 0 = the top of the image, like download())."""
+        out = np.empty((height, width, abi.ID_WORDS), dtype=np.uint32)
+        _check(self.L.crh_ids_download(self.h, buf, width, height, out.ctypes.data), "crh_ids_download")
+        return out
+
+    def resolve_ids(self, buf, width, height, out):
+        """Rank the slots of every pixel of `buf` by coverage into the device float buffer `out` [height, width, 6, 2]: (id, coverage) pairs, an empty rank (-1, 0)."""
+        _check(self.L.crh_ids_resolve(self.h, buf, width, height, out), "crh_ids_resolve")
+
+    def ids_matte(self, buf, width, height, ids, out):
+        """The coverage of the ids of the list `ids` in every pixel of `buf` into the device float buffer `out` [height, width]."""
+        ids = [int(i) for i in ids]
+        arr = (C.c_uint32 * len(ids))(*ids) if ids else None
+        _check(self.L.crh_ids_matte(self.h, buf, width, height, arr, len(ids), out), "crh_ids_matte")
+
+    def ids_kernel_time_ms(self):
+        """Milliseconds of the most recent ID kernel — render_ids', resolve_ids' or ids_matte's (waits for it)."""
+        ms = C.c_float(0.0)
+        _check(self.L.crh_ids_kernel_time_ms(self.h, C.byref(ms)), "crh_ids_kernel_time_ms")
         return float(ms.value)
 
     # ---- the guided a-trous denoiser (include/cray_hip.h: crh_denoise) ----

@@ -506,6 +506,7 @@ __global__ __launch_bounds__(CRH_BLOCK) void k_trace_rays(const DScene Sarg, con
 #include "aov.h"                     /* k_aov: albedo, normal, depth and coverage of every camera ray's first hit (crh_render_aov) */
 #include "denoise.h"                 /* k_denoise_prepare / k_denoise_iter: the guided a-trous filter that consumes them (crh_denoise) */
 #include "adaptive.h"                /* k_adaptive_step: a tile's error against the half-sample frame, whether it goes on, and the half-sample frame's advance (crh_adaptive_step) */
+#include "idmatte.h"                 /* k_ids / k_ids_resolve / k_ids_matte: ranked instance and material coverage per pixel (crh_render_ids, crh_ids_resolve, crh_ids_matte) */
 
 /* bounces <= 0: pathTrace() returns black (pathtrace.c:36); only the running mean moves (renderer.c:288-291) */
 __global__ void k_fold_black(const crh_render_params P, const crh_tile *tiles, uint32_t ntiles, float *fb, unsigned long long *counters) {
@@ -679,6 +680,11 @@ struct crh_ctx {
 	 * so one of each serves), and a lap around the kernel */
 	StagedBuf adaptive;
 	Stopwatch<1> adaptiveWatch;
+	/* crh_render_ids / crh_ids_resolve / crh_ids_matte (idmatte.h): state of its own, as the AOV dispatch's — the tile list's staging buffer, the work counter, and a lap
+	 * around the most recent kernel of the three (crh_ids_kernel_time_ms) */
+	uint32_t *dIdsCounter = nullptr;
+	StagedBuf idsTiles;
+	Stopwatch<1> idsWatch;
 };
 #define CRH_WORK_SLOTS 64
 static_assert(sizeof(((crh_ctx *)nullptr)->tileSlots) / sizeof(StagedBuf) == CRH_WORK_SLOTS, "one tile slot per work counter");
@@ -976,6 +982,7 @@ int crh_context_destroy(crh_ctx *c) {
 	drop(c->dCounters); drop(c->dWork);
 	c->dStage.release(); c->dDefer.release(); c->dQueues.release(); c->dOvf.release();
 	drop(c->dAovCounter); c->aovTiles.release(); c->aovWatch.release();
+	drop(c->dIdsCounter); c->idsTiles.release(); c->idsWatch.release();
 	c->dDenoise.release(); c->denoiseWatch.release();
 	c->adaptive.release(); c->adaptiveWatch.release();
 	if (c->hErr) (void)hipHostFree(c->hErr);
@@ -1854,42 +1861,125 @@ static int checkRects(const char *who, const crh_tile *tiles, uint32_t tile_coun
 }
 
 /* ---- AOV buffers: albedo, normal, depth, coverage of the first hit (aov.h) ----------------------- */
-int crh_aov_alloc(crh_ctx *c, int width, int height, float **dev_out) {
-	if (!c || !dev_out || width <= 0 || height <= 0) return fail(CRH_ERR_INVALID, "crh_aov_alloc: bad argument");
+/* What the buffers of the entry points beside the render path share (AOV buffers: 8 floats a pixel; ID buffers: 16 words): zeroed allocation, free behind the stream,
+ * clear and download on the stream. `who` names the entry point in crh_last_error. */
+static int pixelBufAlloc(const char *who, crh_ctx *c, int width, int height, size_t pixelBytes, void **dev_out) {
+	if (!c || !dev_out || width <= 0 || height <= 0) return fail(CRH_ERR_INVALID, std::string(who) + ": bad argument");
 	int rc = setDevice(c);
 	if (rc) return rc;
 	void *p = nullptr;
-	const size_t bytes = (size_t)width * height * CRH_AOV_CHANNELS * sizeof(float);
+	const size_t bytes = (size_t)width * height * pixelBytes;
 	HIP_TRY(hipMalloc(&p, bytes));
 	HIP_TRY(hipMemsetAsync(p, 0, bytes, c->stream));
-	*dev_out = (float *)p;
+	*dev_out = p;
 	return CRH_OK;
 }
-
-int crh_aov_free(crh_ctx *c, float *dev_aov) {
-	if (!c) return fail(CRH_ERR_INVALID, "crh_aov_free: ctx is NULL");
+static int pixelBufFree(const char *who, crh_ctx *c, void *dev) {
+	if (!c) return fail(CRH_ERR_INVALID, std::string(who) + ": ctx is NULL");
 	int rc = setDevice(c);
 	if (rc) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	if (dev_aov) HIP_TRY(hipFree(dev_aov));
+	if (dev) HIP_TRY(hipFree(dev));
 	return CRH_OK;
 }
-
-int crh_aov_clear(crh_ctx *c, float *dev_aov, int width, int height) {
-	if (!c || !dev_aov || width <= 0 || height <= 0) return fail(CRH_ERR_INVALID, "crh_aov_clear: bad argument");
+static int pixelBufClear(const char *who, crh_ctx *c, void *dev, int width, int height, size_t pixelBytes) {
+	if (!c || !dev || width <= 0 || height <= 0) return fail(CRH_ERR_INVALID, std::string(who) + ": bad argument");
 	int rc = setDevice(c);
 	if (rc) return rc;
-	HIP_TRY(hipMemsetAsync(dev_aov, 0, (size_t)width * height * CRH_AOV_CHANNELS * sizeof(float), c->stream));
+	HIP_TRY(hipMemsetAsync(dev, 0, (size_t)width * height * pixelBytes, c->stream));
+	return CRH_OK;
+}
+/* (`tiles`: the caller's own list stage. The drain retires every dispatch on the stream; the flag of this one stage is cleared, any other stage still waits on its
+ * event at its next reserve(), which then returns at once) */
+static int pixelBufDownload(const char *who, crh_ctx *c, const void *dev, int width, int height, size_t pixelBytes, void *host, StagedBuf *tiles) {
+	if (!c || !dev || !host || width <= 0 || height <= 0) return fail(CRH_ERR_INVALID, std::string(who) + ": bad argument");
+	int rc = setDevice(c);
+	if (rc) return rc;
+	HIP_TRY(hipMemcpyAsync(host, dev, (size_t)width * height * pixelBytes, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	tiles->inFlight = false;
 	return CRH_OK;
 }
 
+int crh_aov_alloc(crh_ctx *c, int width, int height, float **dev_out) { return pixelBufAlloc("crh_aov_alloc", c, width, height, CRH_AOV_CHANNELS * sizeof(float), (void **)dev_out); }
+int crh_aov_free(crh_ctx *c, float *dev_aov) { return pixelBufFree("crh_aov_free", c, dev_aov); }
+int crh_aov_clear(crh_ctx *c, float *dev_aov, int width, int height) { return pixelBufClear("crh_aov_clear", c, dev_aov, width, height, CRH_AOV_CHANNELS * sizeof(float)); }
 int crh_aov_download(crh_ctx *c, const float *dev_aov, int width, int height, float *host_whc8) {
-	if (!c || !dev_aov || !host_whc8 || width <= 0 || height <= 0) return fail(CRH_ERR_INVALID, "crh_aov_download: bad argument");
-	int rc = setDevice(c);
+	return pixelBufDownload("crh_aov_download", c, dev_aov, width, height, CRH_AOV_CHANNELS * sizeof(float), host_whc8, c ? &c->aovTiles : nullptr);
+}
+
+/* The work of a crh_render_aov or crh_render_ids dispatch (aov.h: AovUnits) from its checked arguments: the rectangles that hold pixels, the first unit of each, and the
+ * sizes of a group and of a unit. total == 0: a dispatch with no work. */
+struct AovPlan {
+	std::vector<crh_tile> work;
+	std::vector<uint32_t> start;
+	uint32_t group = 0, groups = 0;
+	uint64_t total = 0;
+};
+static int planAovUnits(const char *who, const crh_ctx *c, const crh_render_params *P, const crh_tile *tiles, uint32_t tile_count, AovPlan &plan) {
+	if (P->pass_count == 0) return CRH_OK;
+	/* units of `group` consecutive pixels of a tile (aov.h) */
+	const uint32_t group = 64u / (uint32_t)std::min(P->pass_count, 64);
+	uint64_t allGroups = 0;
+	for (uint32_t i = 0; i < tile_count; ++i) {
+		const crh_tile &t = tiles[i];
+		if (t.x1 <= t.x0 || t.y1 <= t.y0) continue;
+		plan.work.push_back(t);
+		allGroups += ((uint64_t)(t.x1 - t.x0) * (uint64_t)(t.y1 - t.y0) + group - 1u) / group;
+	}
+	if (allGroups == 0) return CRH_OK;
+	if (allGroups >= (1ull << 31)) return fail(CRH_ERR_INVALID, std::string(who) + ": too many pixels in one dispatch");
+	/* a unit = `groups` consecutive groups of a tile: about eight units per wave of a full grid (every pull is an atomic on one counter), 64 groups at the most;
+	 * CRH_AOV_UNIT_GROUPS=<n> (dev / tests) fixes it */
+	const uint64_t fullWaves = (uint64_t)c->cuCount * CRH_AOV_BLOCKS_PER_CU * (CRH_BLOCK / 64);
+	uint32_t groups = (uint32_t)std::min<uint64_t>(64u, std::max<uint64_t>(1u, allGroups / (fullWaves * 8u)));
+	if (const char *env = getenv("CRH_AOV_UNIT_GROUPS")) { if (atoi(env) >= 1 && atoi(env) <= 4096) groups = (uint32_t)atoi(env); }
+	uint64_t total = 0;
+	for (const crh_tile &t : plan.work) {
+		plan.start.push_back((uint32_t)total);
+		const uint64_t tileGroups = ((uint64_t)(t.x1 - t.x0) * (uint64_t)(t.y1 - t.y0) + group - 1u) / group;
+		total += (tileGroups + groups - 1u) / groups;
+	}
+	plan.start.push_back((uint32_t)total);
+	plan.group = group; plan.groups = groups; plan.total = total;
+	return CRH_OK;
+}
+
+/* What a dispatch of k_aov's work shape does around its launch (crh_render_aov, crh_render_ids), on the caller's own counter, list staging and stopwatch. Before it:
+ * the plan, the overflow columns, the counter, the tile list on its way to the device, the stopwatch started; grid == 0: a dispatch with no work. */
+struct AovLaunch { AovUnits U; uint32_t grid = 0; };
+static int aovLaunchBegin(const char *who, crh_ctx *c, const crh_render_params *P, const crh_tile *tiles, uint32_t tile_count, uint32_t *&counter, StagedBuf &ts,
+                          Stopwatch<1> &watch, AovLaunch &L) {
+	AovPlan plan;
+	int rc = planAovUnits(who, c, P, tiles, tile_count, plan);
+	if (rc || plan.total == 0) return rc;
+	if ((rc = setDevice(c))) return rc;
+	const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)c->cuCount * CRH_AOV_BLOCKS_PER_CU, (plan.total + CRH_BLOCK / 64 - 1) / (CRH_BLOCK / 64));          /* (as many workgroups as a CU holds: aov.h) */
+	/* the render kernels' overflow columns: the same stream, one dispatch at a time */
+	if ((rc = c->dOvf.grow(c->stream, (size_t)grid * (CRH_BLOCK / 64) * CRH_OVF_WORDS_PER_WAVE))) return rc;
+	if (!counter) {
+		HIP_TRY(hipMalloc((void **)&counter, sizeof(uint32_t)));
+		HIP_TRY(hipMemsetAsync(counter, 0, sizeof(uint32_t), c->stream));
+	}
+	size_t tileBytes, listBytes;
+	if ((rc = stageTileList(ts, plan.work, plan.start, tileBytes, listBytes))) return rc;          /* (waits until the dispatch before this one has read the list) */
+	HIP_TRY(hipMemcpyAsync(ts.dev, ts.host, listBytes, hipMemcpyHostToDevice, c->stream));
+	L.U.tiles = (const crh_tile *)ts.dev;
+	L.U.start = (const uint32_t *)((const char *)ts.dev + tileBytes);
+	L.U.ntiles = (uint32_t)plan.work.size(); L.U.total = (uint32_t)plan.total; L.U.counter = counter; L.U.group = plan.group; L.U.groups = plan.groups;
+	if ((rc = watch.start(c->stream))) return rc;
+	L.grid = grid;
+	return CRH_OK;
+}
+/* ... and behind it: the lap, the counter ready for the next dispatch, the list marked in flight, the launch's error reported under the kernel's name */
+static int aovLaunchEnd(const char *kernel, crh_ctx *c, uint32_t *counter, StagedBuf &ts, Stopwatch<1> &watch) {
+	const hipError_t e = hipGetLastError();
+	int rc = watch.mark(c->stream);
 	if (rc) return rc;
-	HIP_TRY(hipMemcpyAsync(host_whc8, dev_aov, (size_t)width * height * CRH_AOV_CHANNELS * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	c->aovTiles.inFlight = false;
+	HIP_TRY(hipMemsetAsync(counter, 0, sizeof(uint32_t), c->stream));
+	if ((rc = ts.markInFlight(c->stream))) return rc;
+	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string(kernel) + " launch: " + hipGetErrorString(e));
+	watch.stop();
 	return CRH_OK;
 }
 
@@ -1905,60 +1995,12 @@ int crh_render_aov(crh_ctx *c, const crh_render_params *P, const crh_tile *tiles
 	if (rc) return rc;
 	if (c->aovDepth > CRH_AOV_STACK)
 		return fail(CRH_ERR_UNSUPPORTED, "crh_render_aov: a material nests mix / add nodes " + std::to_string(c->aovDepth) + " deep (the albedo evaluator holds " + std::to_string(CRH_AOV_STACK) + " frames)");
-	if (P->pass_count == 0) return CRH_OK;
-	/* units of `group` consecutive pixels of a tile (aov.h) */
-	const uint32_t group = 64u / (uint32_t)std::min(P->pass_count, 64);
-	std::vector<crh_tile> work;
-	std::vector<uint32_t> start;
-	uint64_t allGroups = 0;
-	for (uint32_t i = 0; i < tile_count; ++i) {
-		const crh_tile &t = tiles[i];
-		if (t.x1 <= t.x0 || t.y1 <= t.y0) continue;
-		work.push_back(t);
-		allGroups += ((uint64_t)(t.x1 - t.x0) * (uint64_t)(t.y1 - t.y0) + group - 1u) / group;
-	}
-	if (allGroups == 0) return CRH_OK;
-	if (allGroups >= (1ull << 31)) return fail(CRH_ERR_INVALID, "crh_render_aov: too many pixels in one dispatch");
-	/* a unit = `groups` consecutive groups of a tile: about eight units per wave of a full grid (every pull is an atomic on one counter), 64 groups at the most;
-	 * CRH_AOV_UNIT_GROUPS=<n> (dev / tests) fixes it */
-	const uint64_t fullWaves = (uint64_t)c->cuCount * CRH_AOV_BLOCKS_PER_CU * (CRH_BLOCK / 64);
-	uint32_t groups = (uint32_t)std::min<uint64_t>(64u, std::max<uint64_t>(1u, allGroups / (fullWaves * 8u)));
-	if (const char *env = getenv("CRH_AOV_UNIT_GROUPS")) { if (atoi(env) >= 1 && atoi(env) <= 4096) groups = (uint32_t)atoi(env); }
-	uint64_t total = 0;
-	for (const crh_tile &t : work) {
-		start.push_back((uint32_t)total);
-		const uint64_t tileGroups = ((uint64_t)(t.x1 - t.x0) * (uint64_t)(t.y1 - t.y0) + group - 1u) / group;
-		total += (tileGroups + groups - 1u) / groups;
-	}
-	start.push_back((uint32_t)total);
 	const auto *const kernel = pickRow(kAovRows, 0, c->hasPrograms, c->sampler == CRH_SAMPLER_HALTON ? 1 : 0, 0);
 	if (!kernel) return fail(CRH_ERR_HIP, std::string("k_aov launch: ") + hipGetErrorString(hipErrorInvalidDeviceFunction));
-	if ((rc = setDevice(c))) return rc;
-	const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)c->cuCount * CRH_AOV_BLOCKS_PER_CU, (total + CRH_BLOCK / 64 - 1) / (CRH_BLOCK / 64));          /* (as many workgroups as a CU holds: aov.h) */
-	/* the render kernels' overflow columns: the same stream, one dispatch at a time */
-	if ((rc = c->dOvf.grow(c->stream, (size_t)grid * (CRH_BLOCK / 64) * CRH_OVF_WORDS_PER_WAVE))) return rc;
-	if (!c->dAovCounter) {
-		HIP_TRY(hipMalloc((void **)&c->dAovCounter, sizeof(uint32_t)));
-		HIP_TRY(hipMemsetAsync(c->dAovCounter, 0, sizeof(uint32_t), c->stream));
-	}
-	StagedBuf &ts = c->aovTiles;
-	size_t tileBytes, listBytes;
-	if ((rc = stageTileList(ts, work, start, tileBytes, listBytes))) return rc;          /* (waits until the dispatch before this one has read the list) */
-	HIP_TRY(hipMemcpyAsync(ts.dev, ts.host, listBytes, hipMemcpyHostToDevice, c->stream));
-	AovUnits U;
-	U.tiles = (const crh_tile *)ts.dev;
-	U.start = (const uint32_t *)((const char *)ts.dev + tileBytes);
-	U.ntiles = (uint32_t)work.size(); U.total = (uint32_t)total; U.counter = c->dAovCounter; U.group = group; U.groups = groups;
-	const uint32_t rayFlags = (uint32_t)c->sched.rayFlags;
-	if ((rc = c->aovWatch.start(c->stream))) return rc;
-	hipLaunchKernelGGL((kernel->fn), dim3(grid), dim3(CRH_BLOCK), 0, c->stream, c->d, *P, U, dev_aov, rayFlags, c->dOvf.p);
-	const hipError_t e = hipGetLastError();
-	if ((rc = c->aovWatch.mark(c->stream))) return rc;
-	HIP_TRY(hipMemsetAsync(c->dAovCounter, 0, sizeof(uint32_t), c->stream));          /* ready for the next dispatch */
-	if ((rc = ts.markInFlight(c->stream))) return rc;
-	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string("k_aov launch: ") + hipGetErrorString(e));
-	c->aovWatch.stop();
-	return CRH_OK;
+	AovLaunch L;
+	if ((rc = aovLaunchBegin("crh_render_aov", c, P, tiles, tile_count, c->dAovCounter, c->aovTiles, c->aovWatch, L)) || !L.grid) return rc;
+	hipLaunchKernelGGL((kernel->fn), dim3(L.grid), dim3(CRH_BLOCK), 0, c->stream, c->d, *P, L.U, dev_aov, (uint32_t)c->sched.rayFlags, c->dOvf.p);
+	return aovLaunchEnd("k_aov", c, c->dAovCounter, c->aovTiles, c->aovWatch);
 }
 
 /* Duration of the most recent crh_render_aov's kernel (HIP events on the context's stream; waits for it); 0 before the first one. */
@@ -2417,6 +2459,81 @@ int crh_render_adaptive_cells(crh_ctx *c, const crh_render_params *P, const crh_
 		if ((rc = render(list, n, n))) return rc;
 	}
 	return CRH_OK;
+}
+
+/* ---- ID mattes: ranked instance and material coverage per pixel (idmatte.h) ------------------------------------------------------------------------------- */
+int crh_ids_alloc(crh_ctx *c, int width, int height, uint32_t **dev_out) { return pixelBufAlloc("crh_ids_alloc", c, width, height, CRH_ID_WORDS * sizeof(uint32_t), (void **)dev_out); }
+int crh_ids_free(crh_ctx *c, uint32_t *dev_ids) { return pixelBufFree("crh_ids_free", c, dev_ids); }
+int crh_ids_clear(crh_ctx *c, uint32_t *dev_ids, int width, int height) { return pixelBufClear("crh_ids_clear", c, dev_ids, width, height, CRH_ID_WORDS * sizeof(uint32_t)); }
+int crh_ids_download(crh_ctx *c, const uint32_t *dev_ids, int width, int height, uint32_t *host_hw16) {
+	return pixelBufDownload("crh_ids_download", c, dev_ids, width, height, CRH_ID_WORDS * sizeof(uint32_t), host_hw16, c ? &c->idsTiles : nullptr);
+}
+
+int crh_render_ids(crh_ctx *c, const crh_render_params *P, const crh_tile *tiles, uint32_t tile_count, uint32_t *dev_instance_ids, uint32_t *dev_material_ids) {
+	int rc = checkRenderParams("crh_render_ids", c, P, (dev_instance_ids || dev_material_ids) && (tiles || !tile_count));
+	if (rc) return rc;
+	if (dev_instance_ids == dev_material_ids) return fail(CRH_ERR_INVALID, "crh_render_ids: the instance buffer and the material buffer are the same");
+	const crh_tile whole{P->x0, P->y0, P->x1, P->y1};
+	if (!tiles || !tile_count) { tiles = &whole; tile_count = 1; }
+	rc = checkRects("crh_render_ids", tiles, tile_count, P->image_width, P->image_height, false);
+	if (rc) return rc;
+	AovLaunch L;          /* k_ids has k_aov's work shape: the same units, the same grid */
+	if ((rc = aovLaunchBegin("crh_render_ids", c, P, tiles, tile_count, c->dIdsCounter, c->idsTiles, c->idsWatch, L)) || !L.grid) return rc;
+	hipLaunchKernelGGL(k_ids, dim3(L.grid), dim3(CRH_BLOCK), 0, c->stream, c->d, *P, L.U, dev_instance_ids, dev_material_ids, c->sampler == CRH_SAMPLER_HALTON ? 1u : 0u,
+	                   (uint32_t)c->sched.rayFlags, c->dOvf.p);
+	return aovLaunchEnd("k_ids", c, c->dIdsCounter, c->idsTiles, c->idsWatch);
+}
+
+/* Duration of the most recent ID kernel — the dispatch's, the ranking's or the matte's (HIP events on the context's stream; waits for it); 0 before the first one. */
+int crh_ids_kernel_time_ms(crh_ctx *c, float *last_ms) {
+	if (!c || !last_ms) return fail(CRH_ERR_INVALID, "crh_ids_kernel_time_ms: NULL argument");
+	int rc = setDevice(c);
+	if (rc) return rc;
+	if ((rc = c->idsWatch.read())) return rc;
+	*last_ms = c->idsWatch.sum;
+	return CRH_OK;
+}
+
+/* What the two consumers share: one lane per pixel over the whole buffer, timed. The check and the stopwatch started ... */
+static int idsConsumeBegin(const char *who, crh_ctx *c, const uint32_t *dev_ids, int width, int height, const void *dev_out, uint64_t &pixels, dim3 &grid) {
+	if (!c || !dev_ids || !dev_out || width <= 0 || height <= 0) return fail(CRH_ERR_INVALID, std::string(who) + ": bad argument");
+	const int rc = setDevice(c);
+	if (rc) return rc;
+	pixels = (uint64_t)width * (uint64_t)height;
+	grid = dim3((uint32_t)((pixels + CRH_BLOCK - 1) / CRH_BLOCK));
+	return c->idsWatch.start(c->stream);
+}
+/* ... and, behind the launch, the lap */
+static int idsConsumeEnd(const char *who, crh_ctx *c) {
+	const hipError_t e = hipGetLastError();
+	const int rc = c->idsWatch.mark(c->stream);
+	if (rc) return rc;
+	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string(who) + " launch: " + hipGetErrorString(e));
+	c->idsWatch.stop();
+	return CRH_OK;
+}
+
+int crh_ids_resolve(crh_ctx *c, const uint32_t *dev_ids, int width, int height, float *dev_out) {
+	uint64_t pixels;
+	dim3 grid;
+	const int rc = idsConsumeBegin("crh_ids_resolve", c, dev_ids, width, height, dev_out, pixels, grid);
+	if (rc) return rc;
+	hipLaunchKernelGGL(k_ids_resolve, grid, dim3(CRH_BLOCK), 0, c->stream, dev_ids, (f4 *)dev_out, pixels);
+	return idsConsumeEnd("crh_ids_resolve", c);
+}
+
+int crh_ids_matte(crh_ctx *c, const uint32_t *dev_ids, int width, int height, const uint32_t *ids_host, uint32_t id_count, float *dev_out) {
+	if (id_count > CRH_IDS_MATTE_MAX || (!ids_host && id_count)) return fail(CRH_ERR_INVALID, "crh_ids_matte: more than CRH_IDS_MATTE_MAX ids, or a count without a list");
+	IdsMatteList L;
+	memset(&L, 0, sizeof(L));
+	L.n = id_count;
+	if (id_count) memcpy(L.ids, ids_host, id_count * sizeof(uint32_t));
+	uint64_t pixels;
+	dim3 grid;
+	const int rc = idsConsumeBegin("crh_ids_matte", c, dev_ids, width, height, dev_out, pixels, grid);
+	if (rc) return rc;
+	hipLaunchKernelGGL(k_ids_matte, grid, dim3(CRH_BLOCK), 0, c->stream, dev_ids, dev_out, pixels, L);
+	return idsConsumeEnd("crh_ids_matte", c);
 }
 
 /* ---- RCCL (loaded lazily: single-GPU users never need it) ---------------------------------------- */

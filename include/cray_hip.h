@@ -37,6 +37,8 @@ extern "C" {
  * walk-only probe —: a version-3 host is unaffected, the version stays 3.)
  * 4: the AOV entry points — crh_aov_alloc / crh_aov_free / crh_aov_clear / crh_aov_download / crh_render_aov / crh_aov_kernel_time_ms — exist.
  * 5: the denoiser — crh_denoise_params / crh_denoise_params_default / crh_denoise / crh_denoise_time_ms (and crh_debug_denoise_launch_ms) — exists.
+ * (the ID mattes — crh_ids_alloc / crh_ids_free / crh_ids_clear / crh_ids_download / crh_render_ids / crh_ids_kernel_time_ms / crh_ids_resolve / crh_ids_matte — add
+ * entry points and change no declaration: a version-5 host is unaffected, the version stays 5.)
  * A host checks crh_abi_version() == CRH_ABI_VERSION. */
 #define CRH_ABI_VERSION 5
 /* layout version of crh_scene_desc and of the scene blobs (crh_blob_save / crh_blob_load): the records have not changed since round 1 */
@@ -437,6 +439,52 @@ int crh_aov_download(crh_ctx *ctx, const float *dev_aov, int width, int height, 
 int crh_render_aov(crh_ctx *ctx, const crh_render_params *params, const crh_tile *tiles, uint32_t tile_count, float *dev_aov);
 /* Duration in milliseconds of the most recent crh_render_aov's kernel (waits for it); 0 before the first one. */
 int crh_aov_kernel_time_ms(crh_ctx *ctx, float *last_ms);
+
+/* ID mattes — the compositor's side of the above: per pixel, WHICH instances and WHICH materials the camera rays hit first, and how many of the pixel's samples each
+ * one got — a few (id, coverage) pairs per pixel, ranked by coverage (Cryptomatte's data model), from which an object or a material is isolated with correct
+ * anti-aliased edges. An ID buffer is a device buffer of CRH_ID_WORDS = 16 uint32_t per pixel (64 bytes, 16-byte aligned) in the frame buffer's pixel order, index
+ * (x + (H-1-y)*W) * 16:
+ *   0..5 id[0..5] | 6..11 count[0..5] | 12 lost | 13 total | 14, 15 reserved: crh_ids_alloc and crh_ids_clear zero them, a dispatch never writes them
+ * A slot with count == 0 is empty and has id == 0; slots fill front to back, so `used` = the number of slots with a nonzero count. An id is an index, not a name:
+ * crh_hit.inst (the instance's index in crh_scene_desc.instances) in an instance buffer, crh_hit.material in a material buffer; naming them is the host's business.
+ * The fold rule is part of the interface. For every pixel of the dispatch, the passes first_pass .. first_pass + pass_count - 1 are taken in ascending order. The ray
+ * is exactly crh_render_aov's for that (x, y, pass): initSampler(pass, max_passes, y * image_width + x), then getCameraRay, with the sampler CRH_OPT_SAMPLER names,
+ * degenerate slabs as CRH_OPT_RENDER_SLABS says, the binary walk whatever CRH_OPT_WALK says, and in a scene with volumes the free flight drawn from the path's
+ * sampler where the render draws it. Then, with s = the hit's id (a scattering event inside a volume is a hit of the volume's instance and of its material):
+ *   a miss:    total += 1, nothing else
+ *   a hit:     if some j < used has id[j] == s (the lowest such j): count[j] += 1
+ *              else if used < CRH_ID_SLOTS: id[used] = s, count[used] = 1
+ *              else: lost += 1
+ *              then total += 1
+ * Integer arithmetic modulo 2^32 only. So a buffer filled by several dispatches over consecutive pass ranges equals one dispatch over all of them bit for bit, the result
+ * does not depend on the tile list or on how the library cuts the work, and every word is predictable from the first hits. sum(count) + lost is the number of samples
+ * that hit; count[j] / total is slot j's coverage. A dispatch starts from what the buffer holds (a caller may pre-fill a record: ids it wants in fixed slots).
+ * crh_render_ids folds the instance ids into dev_instance_ids and the material ids into dev_material_ids from ONE walk; either may be NULL, and the buffer that is given
+ * gets exactly the words it gets when both are given. tiles / tile_count, the argument checks, CRH_OK for a dispatch with no work (which writes nothing), being asynchronous
+ * on the context's stream and leaving crh_counters, crh_kernel_time_ms and crh_last_kernel_name as they were: as crh_render_aov. params->bounces is ignored and there is no
+ * albedo depth limit. CRH_ERR_INVALID besides crh_render_aov's cases: both buffers NULL; the two buffers equal. Caller-owned device pointers (torch tensors) are welcome. */
+#define CRH_ID_SLOTS 6
+#define CRH_ID_WORDS 16
+int crh_ids_alloc(crh_ctx *ctx, int width, int height, uint32_t **dev_out);      /* zeroed */
+int crh_ids_free(crh_ctx *ctx, uint32_t *dev_ids);
+int crh_ids_clear(crh_ctx *ctx, uint32_t *dev_ids, int width, int height);
+int crh_ids_download(crh_ctx *ctx, const uint32_t *dev_ids, int width, int height, uint32_t *host_hw16);      /* synchronises the stream */
+int crh_render_ids(crh_ctx *ctx, const crh_render_params *params, const crh_tile *tiles, uint32_t tile_count, uint32_t *dev_instance_ids, uint32_t *dev_material_ids);
+/* Duration in milliseconds of the most recent ID kernel — crh_render_ids', crh_ids_resolve's or crh_ids_matte's, whichever was called last (waits for it); 0 before the
+ * first one. */
+int crh_ids_kernel_time_ms(crh_ctx *ctx, float *last_ms);
+/* The consumers. No scene is needed; dev_ids is any ID buffer — the instance or the material kind, the context's or the caller's —, dev_out a 16-byte aligned device
+ * float buffer in the same pixel order (row 0 = the top of the image); both asynchronous on the context's stream, both leave the render path's counters, time and
+ * kernel name as they were. Only correctly rounded uint32 -> float32 conversions and ONE correctly rounded float32 division per value: a restatement in any IEEE
+ * float32 gives the same bits. Ids of 2^24 and above, and counts and totals of 2^24 and above, round in the conversion.
+ * crh_ids_resolve: dev_out [H, W, 6, 2]. Rank r of a pixel holds the slot with the r-th largest count — equal counts: the lower slot index first; empty slots last — as
+ *   ((float)id, (float)count / (float)total); an empty rank is (-1.0f, 0.0f); a pixel with total == 0 is all empty ranks.
+ * crh_ids_matte: dev_out [H, W] = (float)n / (float)total, n = the sum (modulo 2^32) of count[j] over the non-empty slots whose id is among ids_host[0 .. id_count); 0.0f where
+ *   total == 0. A duplicate in the list counts once; id_count == 0 gives zeros. The list is read before the call returns.
+ * CRH_ERR_INVALID: a NULL context or buffer, a size <= 0; for crh_ids_matte also id_count > CRH_IDS_MATTE_MAX and a NULL list with a nonzero count. */
+int crh_ids_resolve(crh_ctx *ctx, const uint32_t *dev_ids, int width, int height, float *dev_out);
+#define CRH_IDS_MATTE_MAX 64
+int crh_ids_matte(crh_ctx *ctx, const uint32_t *dev_ids, int width, int height, const uint32_t *ids_host, uint32_t id_count, float *dev_out);
 
 /* The consumer of those buffers: an edge-avoiding a-trous wavelet filter on the albedo-demodulated frame, guided by normal and depth. No scene is needed.
  *   dev_fb   float RGB [H, W, 3]           dev_aov   [H, W, 8] as above           dev_out   float RGB [H, W, 3]; may be dev_fb, must not be dev_aov
