@@ -138,6 +138,12 @@ class AdaptiveCellsParams(C.Structure):
     """crh_adaptive_cells_params (crh_adaptive_cells_params_default fills the defaults)."""
     _fields_ = [("min_passes", C.c_int32), ("threshold", C.c_float), ("cell", C.c_int32), ("dilate", C.c_int32)]
 
+
+class PackChannel(C.Structure):
+    """crh_pack_channel: one channel of crh_pack_scanlines — a component of a device buffer [H, W, stride], optionally an id mapped through a host table."""
+    _fields_ = [("dev_src", C.c_void_p), ("stride", C.c_uint32), ("component", C.c_uint32), ("map_host", C.c_void_p), ("map_count", C.c_uint32), ("pad", C.c_uint32)]
+
+PACK_MAX_CHANNELS = 64             # CRH_PACK_MAX_CHANNELS
 ADAPTIVE_CELLS_MAX = 1024          # CRH_ADAPTIVE_CELLS_MAX: cells one rectangle may hold
 
 
@@ -156,6 +162,7 @@ EXPORTED_SYMBOLS = [
     "crh_scene_compile", "crh_scene_upload_compiled", "crh_compiled_scene_free", "crh_debug_upload_counts",
     "crh_aov_alloc", "crh_aov_free", "crh_aov_clear", "crh_aov_download", "crh_render_aov", "crh_aov_kernel_time_ms",
     "crh_ids_alloc", "crh_ids_free", "crh_ids_clear", "crh_ids_download", "crh_render_ids", "crh_ids_kernel_time_ms", "crh_ids_resolve", "crh_ids_matte",
+    "crh_pack_scanlines", "crh_pack_time_ms",
     "crh_denoise_params_default", "crh_denoise", "crh_denoise_time_ms", "crh_debug_denoise_launch_ms",
     "crh_denoise_variance_params_default", "crh_denoise_variance", "crh_framebuffer_copy",
     "crh_adaptive_step", "crh_adaptive_time_ms", "crh_adaptive_params_default", "crh_render_adaptive",

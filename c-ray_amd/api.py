@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from . import abi
+from . import abi, exr
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CRH_LIB") or os.path.join(HERE, "_lib", "libcray_hip.so")    # CRH_LIB: A/B another build (dev)
@@ -82,6 +82,8 @@ def library():
         "crh_ids_kernel_time_ms": (C.c_int, [ctx, C.POINTER(C.c_float)]),
         "crh_ids_resolve": (C.c_int, [ctx, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
         "crh_ids_matte": (C.c_int, [ctx, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_uint32, C.c_void_p]),
+        "crh_pack_scanlines": (C.c_int, [ctx, C.POINTER(abi.PackChannel), C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+        "crh_pack_time_ms": (C.c_int, [ctx, C.POINTER(C.c_float)]),
         "crh_denoise_params_default": (None, [C.POINTER(abi.DenoiseParams)]),
         "crh_denoise": (C.c_int, [ctx, C.POINTER(abi.DenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p]),
         "crh_denoise_time_ms": (C.c_int, [ctx, C.POINTER(C.c_float)]),
@@ -407,6 +409,72 @@ class Context:
         ms = C.c_float(0.0)
         _check(self.L.crh_ids_kernel_time_ms(self.h, C.byref(ms)), "crh_ids_kernel_time_ms")
         return float(ms.value)
+
+    # ---- the multi-layer OpenEXR output (include/cray_hip.h: crh_pack_scanlines; the file around the pixel data: exr.py) ----
+    def pack_scanlines(self, channels, width, height, first_row=0, row_count=None):
+        """The pixel data of stored rows [first_row, first_row + row_count) (None: to the last row) as bytes: per row int32 y, int32 4 * channels * width and one plane
+        of `width` 32-bit words per channel, in the order given. A channel is (device pointer, stride, component) or (device pointer, stride, component, map): a
+        component of a float buffer [height, width, stride]; with a map — a uint32 array — the value is an id and the word is map[id], 0 for anything that is not
+        an id below len(map)."""
+        n = len(channels)
+        arr = (abi.PackChannel * max(n, 1))()
+        keep = []          # the maps' arrays live until the call returns
+        for k, ch in zip(arr, channels):
+            src, stride, component = ch[0], ch[1], ch[2]
+            m = ch[3] if len(ch) > 3 else None
+            k.dev_src = src.value if isinstance(src, C.c_void_p) else src
+            k.stride, k.component = stride, component
+            if m is not None:
+                m = np.ascontiguousarray(m, dtype=np.uint32)
+                same = [a for a in keep if a.shape == m.shape and np.array_equal(a, m)]          # (one array per distinct map: the library uploads each once)
+                m = same[0] if same else m
+                if not same:
+                    keep.append(m)
+                k.map_host, k.map_count = m.ctypes.data, m.size
+        rows = height - first_row if row_count is None else row_count
+        out = np.empty(max(rows, 0) * (2 + n * width), np.uint32)
+        _check(self.L.crh_pack_scanlines(self.h, arr, n, width, height, first_row, rows, out.ctypes.data), "crh_pack_scanlines")
+        return out.tobytes()
+
+    def pack_time_ms(self):
+        """Milliseconds of the most recent pack_scanlines' kernel (waits for it)."""
+        ms = C.c_float(0.0)
+        _check(self.L.crh_pack_time_ms(self.h, C.byref(ms)), "crh_pack_time_ms")
+        return float(ms.value)
+
+    def write_layers_exr(self, path, width, height, fb, aov=None, denoised=None, instance_ids=None, material_ids=None, instance_names=None, material_names=None,
+                         chunk_rows=None):
+        """One multi-layer OpenEXR file (uncompressed, scanline, FLOAT channels) of the frame `fb` and whichever of the others is given: R G B; the guides of
+        an AOV buffer as albedo.R/G/B, normal.X/Y/Z, Z and A, unscaled; a denoised frame as denoised.R/G/B; the ID buffers `instance_ids` / `material_ids`
+        (render_ids) as the Cryptomatte layers CryptoObject00..02 / CryptoMaterial00..02 with their metadata. instance_names[i] / material_names[i] name id i
+        (default instance#<i> / material#<i>, for every id up to the largest one the buffer holds). The ranking runs into scratch of this call's own; the pixel data is
+        packed on the device, `chunk_rows` rows at a time (None: all at once)."""
+        ranked, maps, strings, scratch = [None, None], [None, None], {}, []
+        try:
+            for k, (ids, names, stem) in enumerate(((instance_ids, instance_names, "instance"), (material_ids, material_names, "material"))):
+                if ids is None:
+                    continue
+                if names is None:
+                    words = self.download_ids(ids, width, height)
+                    used = words[..., abi.ID_SLOTS:2 * abi.ID_SLOTS] != 0
+                    names = [f"{stem}#{i}" for i in range(int(words[..., :abi.ID_SLOTS][used].max()) + 1 if used.any() else 0)]
+                names = list(names) or [f"{stem}#0"]          # (a map has at least one entry)
+                p = C.c_void_p()          # [H, W, 6, 2] floats fit an ID buffer's 16 words a pixel
+                _check(self.L.crh_ids_alloc(self.h, width, height, C.byref(p)), "crh_ids_alloc")
+                scratch.append(p)
+                self.resolve_ids(ids, width, height, p)
+                ranked[k], maps[k] = p, exr.id_map(names)
+                strings.update(exr.crypto_attributes(exr.CRYPTO_LAYERS[k], names))
+            chans = exr.layer_channels(fb, aov, denoised, ranked[0], ranked[1], maps[0], maps[1])
+            step = height if not chunk_rows else chunk_rows
+            blocks = b"".join(self.pack_scanlines([c[1:] for c in chans], width, height, y, min(step, height - y)) for y in range(0, height, step))
+        finally:
+            for p in scratch:
+                self.L.crh_ids_free(self.h, p)
+        data = exr.file_bytes(width, height, [c[0] for c in chans], blocks, strings)
+        with open(path, "wb") as f:
+            f.write(data)
+        return [c[0] for c in chans]
 
     # ---- the guided a-trous denoiser (include/cray_hip.h: crh_denoise) ----
     def denoise(self, fb, aov, width, height, out=None, **params):

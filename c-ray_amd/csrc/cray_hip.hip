@@ -507,6 +507,7 @@ __global__ __launch_bounds__(CRH_BLOCK) void k_trace_rays(const DScene Sarg, con
 #include "denoise.h"                 /* k_denoise_prepare / k_denoise_iter: the guided a-trous filter that consumes them (crh_denoise) */
 #include "adaptive.h"                /* k_adaptive_step: a tile's error against the half-sample frame, whether it goes on, and the half-sample frame's advance (crh_adaptive_step) */
 #include "idmatte.h"                 /* k_ids / k_ids_resolve / k_ids_matte: ranked instance and material coverage per pixel (crh_render_ids, crh_ids_resolve, crh_ids_matte) */
+#include "exr_pack.h"                /* k_pack_scanlines: channels of those buffers gathered into the pixel data of a scanline OpenEXR file (crh_pack_scanlines) */
 
 /* bounces <= 0: pathTrace() returns black (pathtrace.c:36); only the running mean moves (renderer.c:288-291) */
 __global__ void k_fold_black(const crh_render_params P, const crh_tile *tiles, uint32_t ntiles, float *fb, unsigned long long *counters) {
@@ -685,12 +686,26 @@ struct crh_ctx {
 	uint32_t *dIdsCounter = nullptr;
 	StagedBuf idsTiles;
 	Stopwatch<1> idsWatch;
+	/* crh_pack_scanlines (exr_pack.h): the packed rows and, behind them, the id maps of the call; a lap around its kernel (crh_pack_time_ms) */
+	DevBuf<uint8_t> dPack;
+	Stopwatch<1> packWatch;
 };
 #define CRH_WORK_SLOTS 64
 static_assert(sizeof(((crh_ctx *)nullptr)->tileSlots) / sizeof(StagedBuf) == CRH_WORK_SLOTS, "one tile slot per work counter");
 
 static int setDevice(crh_ctx *c) {
 	HIP_TRY(hipSetDevice(c->device));
+	return CRH_OK;
+}
+
+/* What the entries that report one kernel's time share (crh_aov_kernel_time_ms, crh_ids_kernel_time_ms, crh_pack_time_ms): the stopwatch's last complete run, read once
+ * (waits for it). `who` names the entry point in crh_last_error. */
+static int watchTimeMs(const char *who, crh_ctx *c, Stopwatch<1> *watch, float *last_ms) {
+	if (!c || !last_ms) return fail(CRH_ERR_INVALID, std::string(who) + ": NULL argument");
+	int rc = setDevice(c);
+	if (rc) return rc;
+	if ((rc = watch->read())) return rc;
+	*last_ms = watch->sum;
 	return CRH_OK;
 }
 
@@ -983,6 +998,7 @@ int crh_context_destroy(crh_ctx *c) {
 	c->dStage.release(); c->dDefer.release(); c->dQueues.release(); c->dOvf.release();
 	drop(c->dAovCounter); c->aovTiles.release(); c->aovWatch.release();
 	drop(c->dIdsCounter); c->idsTiles.release(); c->idsWatch.release();
+	c->dPack.release(); c->packWatch.release();
 	c->dDenoise.release(); c->denoiseWatch.release();
 	c->adaptive.release(); c->adaptiveWatch.release();
 	if (c->hErr) (void)hipHostFree(c->hErr);
@@ -2004,14 +2020,7 @@ int crh_render_aov(crh_ctx *c, const crh_render_params *P, const crh_tile *tiles
 }
 
 /* Duration of the most recent crh_render_aov's kernel (HIP events on the context's stream; waits for it); 0 before the first one. */
-int crh_aov_kernel_time_ms(crh_ctx *c, float *last_ms) {
-	if (!c || !last_ms) return fail(CRH_ERR_INVALID, "crh_aov_kernel_time_ms: NULL argument");
-	int rc = setDevice(c);
-	if (rc) return rc;
-	if ((rc = c->aovWatch.read())) return rc;
-	*last_ms = c->aovWatch.sum;
-	return CRH_OK;
-}
+int crh_aov_kernel_time_ms(crh_ctx *c, float *last_ms) { return watchTimeMs("crh_aov_kernel_time_ms", c, c ? &c->aovWatch : nullptr, last_ms); }
 
 /* ---- the guided a-trous denoiser (denoise.h) ------------------------------------------------------ */
 void crh_denoise_params_default(crh_denoise_params *p) {
@@ -2485,14 +2494,7 @@ int crh_render_ids(crh_ctx *c, const crh_render_params *P, const crh_tile *tiles
 }
 
 /* Duration of the most recent ID kernel — the dispatch's, the ranking's or the matte's (HIP events on the context's stream; waits for it); 0 before the first one. */
-int crh_ids_kernel_time_ms(crh_ctx *c, float *last_ms) {
-	if (!c || !last_ms) return fail(CRH_ERR_INVALID, "crh_ids_kernel_time_ms: NULL argument");
-	int rc = setDevice(c);
-	if (rc) return rc;
-	if ((rc = c->idsWatch.read())) return rc;
-	*last_ms = c->idsWatch.sum;
-	return CRH_OK;
-}
+int crh_ids_kernel_time_ms(crh_ctx *c, float *last_ms) { return watchTimeMs("crh_ids_kernel_time_ms", c, c ? &c->idsWatch : nullptr, last_ms); }
 
 /* What the two consumers share: one lane per pixel over the whole buffer, timed. The check and the stopwatch started ... */
 static int idsConsumeBegin(const char *who, crh_ctx *c, const uint32_t *dev_ids, int width, int height, const void *dev_out, uint64_t &pixels, dim3 &grid) {
@@ -2535,6 +2537,58 @@ int crh_ids_matte(crh_ctx *c, const uint32_t *dev_ids, int width, int height, co
 	hipLaunchKernelGGL(k_ids_matte, grid, dim3(CRH_BLOCK), 0, c->stream, dev_ids, dev_out, pixels, L);
 	return idsConsumeEnd("crh_ids_matte", c);
 }
+
+/* ---- the pixel data of a scanline OpenEXR file, packed on the device (exr_pack.h) ------------------------------------------------------------------------------ */
+int crh_pack_scanlines(crh_ctx *c, const crh_pack_channel *ch, uint32_t n, int width, int height, int first_row, int row_count, void *host_out) {
+	/* (a row block — 8 + 4 * n * width bytes — fits the int32 that states it) */
+	bool ok = c && ch && host_out && n >= 1 && n <= CRH_PACK_MAX_CHANNELS && width > 0 && height > 0 && first_row >= 0 && row_count >= 0 && row_count <= height - first_row &&
+	          (uint64_t)n * (uint64_t)width < (1ull << 29) - 2u;
+	PackArgs A;
+	memset(&A, 0, sizeof(A));
+	size_t mapAt[CRH_PACK_MAX_CHANNELS], mapWords = 0;          /* where channel i's map starts behind the rows: channels that name the same map share it ... */
+	uint64_t first = 0;                                         /* ... and the first of them in the list (bit i) uploads it */
+	for (uint32_t i = 0; ok && i < n; ++i) {
+		const crh_pack_channel &k = ch[i];
+		ok = k.dev_src && k.stride >= 1 && k.stride <= 64 && k.component < k.stride && k.map_count <= 65536 && (!k.map_host || k.map_count);
+		A.ch[i] = PackChan{(const uint32_t *)k.dev_src, k.map_host, k.stride, k.component, k.map_count, 0};
+		uint32_t j = 0;
+		while (j < i && (ch[j].map_host != k.map_host || ch[j].map_count != k.map_count)) ++j;
+		mapAt[i] = j < i ? mapAt[j] : mapWords;
+		if (j == i && k.map_host) { first |= 1ull << i; mapWords += k.map_count; }
+	}
+	if (!ok) return fail(CRH_ERR_INVALID, "crh_pack_scanlines: bad argument");
+	if (row_count == 0) return CRH_OK;
+	int rc = setDevice(c);
+	if (rc) return rc;
+	const size_t rowWords = (size_t)row_count * (2u + (size_t)n * (size_t)width);
+	if ((rc = c->dPack.grow(c->stream, (rowWords + mapWords) * sizeof(uint32_t)))) return rc;
+	uint32_t *const rows = (uint32_t *)c->dPack.p;
+	void *const pinned = crh_internal_pinned(c, rowWords * sizeof(uint32_t));
+	hipError_t e = pinned ? hipSuccess : hipErrorOutOfMemory;          /* (one message for whatever fails first) */
+	for (uint32_t i = 0; i < n; ++i) {
+		if (!A.ch[i].map) continue;
+		uint32_t *const dev = rows + rowWords + mapAt[i];
+		if ((first >> i & 1u) && e == hipSuccess) e = hipMemcpyAsync(dev, A.ch[i].map, A.ch[i].mapCount * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+		A.ch[i].map = dev;
+	}
+	if (e == hipSuccess && (rc = c->packWatch.start(c->stream))) return rc;
+	if (e == hipSuccess) {
+		hipLaunchKernelGGL(k_pack_scanlines, dim3((uint32_t)row_count, ((uint32_t)width + CRH_BLOCK - 1u) / CRH_BLOCK), dim3(CRH_BLOCK), 0, c->stream, A, n, (uint32_t)width, (uint32_t)first_row, rows);
+		e = hipGetLastError();
+		if ((rc = c->packWatch.mark(c->stream))) return rc;
+	}
+	if (e == hipSuccess) {
+		c->packWatch.stop();
+		e = hipMemcpyAsync(pinned, rows, rowWords * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+	}
+	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string("crh_pack_scanlines: ") + hipGetErrorString(e));
+	memcpy(host_out, pinned, rowWords * sizeof(uint32_t));
+	return CRH_OK;
+}
+
+/* Duration of the most recent crh_pack_scanlines' kernel (HIP events on the context's stream; waits for it); 0 before the first one. */
+int crh_pack_time_ms(crh_ctx *c, float *last_ms) { return watchTimeMs("crh_pack_time_ms", c, c ? &c->packWatch : nullptr, last_ms); }
 
 /* ---- RCCL (loaded lazily: single-GPU users never need it) ---------------------------------------- */
 namespace {

@@ -1,0 +1,147 @@
+"""exr.py — the host side of the multi-layer OpenEXR output: an uncompressed single-part scanline file whose channels are all FLOAT, and Cryptomatte's
+naming of ids. The pixel data comes packed from the device (Context.pack_scanlines: crh_pack_scanlines, include/cray_hip.h); this module writes what
+goes around it — header, offset table — and knows which channel of which buffer carries which name. c-ray_amd/host/exr_write.c states the same in C
+for the drop-in program; both write the same bytes.
+
+File layout: magic 76 2f 31 01, version 02 00 00 00, attributes in ascending byte order of name (each `name\\0 type\\0 int32 size, value`), one \\0,
+`height` uint64 absolute offsets, then per stored row (row 0 = the top of the image = y 0, lineOrder increasing y) a block of int32 y,
+int32 4 * channels * width and one plane of `width` floats per channel, channels in ascending byte order of name.
+"""
+import json
+import struct
+
+import numpy as np
+
+MAX_NAME = 31          # attribute and channel names of a file whose version field has no long-names bit
+CRYPTO_LAYERS = ("CryptoObject", "CryptoMaterial")
+CRYPTO_RANKS = 6       # crh_ids_resolve's ranks: three RGBA layers of two (id, coverage) pairs
+
+
+def murmur3_32(data, seed=0):
+    """MurmurHash3_x86_32 of a bytes object."""
+    c1, c2, m = 0xCC9E2D51, 0x1B873593, 0xFFFFFFFF
+    h = seed & m
+    n = len(data)
+    for i in range(0, n - n % 4, 4):
+        k = struct.unpack_from("<I", data, i)[0]
+        k = (k * c1) & m
+        k = ((k << 15) | (k >> 17)) & m
+        k = (k * c2) & m
+        h ^= k
+        h = ((h << 13) | (h >> 19)) & m
+        h = (h * 5 + 0xE6546B64) & m
+    k = 0
+    tail = data[n - n % 4:]
+    for j in range(len(tail) - 1, -1, -1):
+        k = (k << 8) | tail[j]
+    if tail:
+        k = (k * c1) & m
+        k = ((k << 15) | (k >> 17)) & m
+        k = (k * c2) & m
+        h ^= k
+    h ^= n
+    h ^= h >> 16
+    h = (h * 0x85EBCA6B) & m
+    h ^= h >> 13
+    h = (h * 0xC2B2AE35) & m
+    h ^= h >> 16
+    return h
+
+
+def float_safe(h):
+    """Cryptomatte's uint32_to_float32 conversion: a word whose exponent field is 0 or 255 (a denormal, an infinity, a NaN) gets bit 23 flipped."""
+    return h ^ (1 << 23) if ((h >> 23) & 255) in (0, 255) else h
+
+
+def crypto_id(name):
+    """The 32-bit word a Cryptomatte id channel holds for the name."""
+    return float_safe(murmur3_32(name.encode("utf-8")))
+
+
+def layer_key(layer):
+    """The <k> of a layer's `cryptomatte/<k>/...` attributes: the first 7 hex digits of its name's id."""
+    return ("%08x" % crypto_id(layer))[:7]
+
+
+def id_map(names):
+    """map[i] = crypto_id(names[i]) as the uint32 array crh_pack_scanlines takes; the names must be unique (a manifest maps a name to one id)."""
+    names = list(names)
+    assert len(set(names)) == len(names), "names of a Cryptomatte layer must be unique"
+    return np.array([crypto_id(s) for s in names], dtype=np.uint32)
+
+
+def manifest(names):
+    """name -> 8 lowercase hex digits of its id, keys in id order, no whitespace."""
+    return json.dumps({s: "%08x" % crypto_id(s) for s in names}, separators=(",", ":"), ensure_ascii=False)
+
+
+def crypto_attributes(layer, names):
+    k = layer_key(layer)
+    return {f"cryptomatte/{k}/name": layer, f"cryptomatte/{k}/hash": "MurmurHash3_32", f"cryptomatte/{k}/conversion": "uint32_to_float32",
+            f"cryptomatte/{k}/manifest": manifest(names)}
+
+
+def crypto_channels(layer):
+    """The twelve channel names of a layer in rank order: (id, coverage) of rank 2k in <layer>0k.R / .G, of rank 2k + 1 in .B / .A."""
+    return [f"{layer}{r // 2:02d}.{'RGBA'[2 * (r % 2) + part]}" for r in range(CRYPTO_RANKS) for part in (0, 1)]
+
+
+def _attr(name, kind, value):
+    raw = name.encode("utf-8")
+    assert 0 < len(raw) <= MAX_NAME, f"attribute name {name!r} is longer than {MAX_NAME} bytes"
+    return raw + b"\0" + kind.encode() + b"\0" + struct.pack("<i", len(value)) + value
+
+
+def header(width, height, channel_names, strings=None):
+    """The bytes before the offset table. channel_names must be in ascending byte order; `strings` are further attributes of type string."""
+    raw = [c.encode("utf-8") for c in channel_names]
+    assert raw == sorted(raw) and len(set(raw)) == len(raw), "channels must be unique and in ascending byte order of name"
+    chlist = b""
+    for c in raw:
+        assert 0 < len(c) <= MAX_NAME, f"channel name {c!r} is longer than {MAX_NAME} bytes"
+        chlist += c + b"\0" + struct.pack("<iB3xii", 2, 0, 1, 1)          # FLOAT, pLinear 0, xSampling 1, ySampling 1
+    chlist += b"\0"
+    window = struct.pack("<4i", 0, 0, width - 1, height - 1)
+    attrs = {"channels": ("chlist", chlist), "compression": ("compression", b"\0"), "dataWindow": ("box2i", window), "displayWindow": ("box2i", window),
+             "lineOrder": ("lineOrder", b"\0"), "pixelAspectRatio": ("float", struct.pack("<f", 1.0)), "screenWindowCenter": ("v2f", struct.pack("<2f", 0.0, 0.0)),
+             "screenWindowWidth": ("float", struct.pack("<f", 1.0))}
+    for k, v in (strings or {}).items():
+        assert k not in attrs
+        attrs[k] = ("string", v.encode("utf-8"))
+    out = bytes([0x76, 0x2F, 0x31, 0x01, 2, 0, 0, 0])
+    for k in sorted(attrs, key=lambda s: s.encode("utf-8")):
+        out += _attr(k, *attrs[k])
+    return out + b"\0"
+
+
+def file_bytes(width, height, channel_names, blocks, strings=None):
+    """The whole file: `blocks` is the packed pixel data of all `height` rows, as crh_pack_scanlines lays it out."""
+    block = 8 + 4 * len(channel_names) * width
+    assert len(blocks) == block * height, "the pixel data is not height blocks of 8 + 4 * channels * width bytes"
+    head = header(width, height, channel_names, strings)
+    first = len(head) + 8 * height
+    return head + struct.pack(f"<{height}Q", *[first + block * y for y in range(height)]) + bytes(blocks)
+
+
+def pack_host(planes, width, height):
+    """The pixel data from host arrays — planes: [height, width] arrays of 32-bit words in channel order —, for files that never were on a device."""
+    rows = np.stack([np.ascontiguousarray(p).view(np.uint32).reshape(height, width) for p in planes], axis=1)          # [H, C, W]
+    out = np.empty((height, 2 + len(planes) * width), np.uint32)
+    out[:, 0] = np.arange(height, dtype=np.uint32)
+    out[:, 1] = 4 * len(planes) * width
+    out[:, 2:] = rows.reshape(height, -1)
+    return out.astype("<u4").tobytes()
+
+
+def layer_channels(fb, aov=None, denoised=None, instance_ranked=None, material_ranked=None, instance_map=None, material_map=None):
+    """(name, device pointer, stride, component, map) of every channel of the layers whose buffer is given, in ascending byte order of name — the order of the
+    file's channel list and of the pack. fb / denoised: float [H, W, 3]; aov: [H, W, 8] (crh_render_aov); *_ranked: crh_ids_resolve's [H, W, 6, 2]."""
+    ch = [(n, fb, 3, i, None) for i, n in enumerate("RGB")]
+    if aov is not None:
+        ch += [(n, aov, 8, i, None) for i, n in enumerate(("albedo.R", "albedo.G", "albedo.B", "normal.X", "normal.Y", "normal.Z", "Z", "A"))]
+    if denoised is not None:
+        ch += [(f"denoised.{n}", denoised, 3, i, None) for i, n in enumerate("RGB")]
+    for layer, ranked, m in ((CRYPTO_LAYERS[0], instance_ranked, instance_map), (CRYPTO_LAYERS[1], material_ranked, material_map)):
+        if ranked is not None:
+            ch += [(n, ranked, 2 * CRYPTO_RANKS, i, m if i % 2 == 0 else None) for i, n in enumerate(crypto_channels(layer))]
+    return sorted(ch, key=lambda c: c[0].encode("utf-8"))

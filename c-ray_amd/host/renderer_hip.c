@@ -45,6 +45,10 @@
  * CRAY_HIP_ADAPTIVE_CELL=<c> (user-facing, beside CRAY_HIP_ADAPTIVE; CRAY_HIP_ADAPTIVE_DILATE=0|1, default 1): the same rectangles, decided per c x c cell inside each
  * (crh_render_adaptive_cells); the report line counts cells by pass count. A value that is no integer in 1 .. 1024, or a rectangle of more than 1024 cells, warns
  * and decides per rectangle.
+ * CRAY_HIP_EXR=1 (user-facing): one multi-layer OpenEXR file <imgFileName>_layers beside the frame — the frame's floats, and whatever CRAY_HIP_AOV and CRAY_HIP_DENOISE
+ * produced, unscaled: the buffers stay on GPU 0 until writeLayers below has packed them (crh_pack_scanlines) —; CRAY_HIP_IDS=<n> beside it: GPU 0 also renders n passes
+ * of the instance and material ID buffers (crh_render_ids), which go into the file as Cryptomatte layers named after the scene's meshes. The frame, its image and the
+ * other side files are those of a run without the two.
  * No GPU => logr(error, ...) (which exits, src/utils/logging.c:69-73): there is no CPU fallback in this file.
  */
 #include <stdlib.h>
@@ -61,6 +65,7 @@
 #include "datatypes/image/texture.h"
 #include "datatypes/color.h"
 #include "datatypes/scene.h"
+#include "datatypes/mesh.h"
 #include "datatypes/tile.h"
 #include "datatypes/vertexbuffer.h"
 #include "utils/ui.h"
@@ -73,6 +78,7 @@
 
 #include "cray_hip.h"
 #include "flatten.h"
+#include "exr_write.h"
 #include "share.h"
 
 #define MAX_GPUS 16
@@ -680,7 +686,8 @@ static int assembleOnHost(struct renderer *r, struct gpuWorker *workers, int gpu
 /* CRAY_HIP_AOV=<n>: min(n, sampleCount) passes of the first-hit buffers of the whole image, on GPU 0 (primary rays only: nothing to gather), written as 8-bit
  * images <imgFileName>_albedo, _normal (0.5 n + 0.5) and _depth (divided by the frame's largest depth) beside the frame, by the reference's own newImageFile /
  * writeImage; CRH_DUMP_AOV_F32=<path> dumps the raw [H, W, 8] floats the way CRH_DUMP_F32 dumps the frame. The scene is still resident in ctx. */
-static void writeAovs(struct renderer *r, crh_ctx *ctx, int W, int H) {
+/* `keep` (CRAY_HIP_EXR): where the device buffer goes instead of being freed — it is the caller's then. */
+static void writeAovs(struct renderer *r, crh_ctx *ctx, int W, int H, float **keep) {
 	const char *e = getenv("CRAY_HIP_AOV");
 	int n = e ? atoi(e) : 0;
 	if (n <= 0 || !ctx) return;
@@ -697,7 +704,8 @@ static void writeAovs(struct renderer *r, crh_ctx *ctx, int W, int H) {
 		free(host);
 		return;
 	}
-	crh_aov_free(ctx, dev);
+	if (keep) *keep = dev;
+	else crh_aov_free(ctx, dev);
 	const char *dump = getenv("CRH_DUMP_AOV_F32");
 	if (dump) {
 		FILE *f = fopen(dump, "wb");
@@ -734,7 +742,8 @@ static void writeAovs(struct renderer *r, crh_ctx *ctx, int W, int H) {
  * crh_denoise_variance (CRAY_HIP_DENOISE_VARIANCE=1) — into a second buffer with guides rendered here — CRAY_HIP_AOV's n passes if that
  * is set, min(16, sampleCount) otherwise —, written as <imgFileName>_denoised beside the frame (8-bit exactly as the frame's: crh_framebuffer_to_srgb8, then the
  * reference's newImageFile / writeImage); CRH_DUMP_DENOISED_F32=<path> dumps the [H, W, 3] floats. Unset: nothing is allocated, nothing is written. */
-static void writeDenoised(struct renderer *r, crh_ctx *ctx, const float *fb, const float *half, int halfPasses, int W, int H) {
+/* `keep` (CRAY_HIP_EXR): where the denoised device buffer goes instead of being freed — it is the caller's then. */
+static void writeDenoised(struct renderer *r, crh_ctx *ctx, const float *fb, const float *half, int halfPasses, int W, int H, float **keep) {
 	const char *e = getenv("CRAY_HIP_DENOISE");
 	const int iterations = e ? atoi(e) : 0;
 	if (iterations <= 0 || !ctx || !fb) return;
@@ -763,7 +772,8 @@ static void writeDenoised(struct renderer *r, crh_ctx *ctx, const float *fb, con
 		&& crh_framebuffer_download(ctx, out, W, H, host) == CRH_OK;
 	if (!ok) logr(warning, "c-ray-hip: the frame could not be denoised: %s\n", host ? crh_last_error() : "out of memory");
 	if (aov) crh_aov_free(ctx, aov);
-	if (out) crh_framebuffer_free(ctx, out);
+	if (out && ok && keep) *keep = out;
+	else if (out) crh_framebuffer_free(ctx, out);
 	const char *base = r->prefs.imgFileName ? r->prefs.imgFileName : "rendered";
 	char *name = ok ? malloc(strlen(base) + strlen("_denoised") + 1) : NULL;
 	if (name) {
@@ -780,6 +790,91 @@ static void writeDenoised(struct renderer *r, crh_ctx *ctx, const float *fb, con
 		logr(info, "Denoised frame written (%s%i iteration%s, %i guide pass%s, %.3f ms).\n", half ? "variance-guided, " : "", iterations, iterations == 1 ? "" : "s", n, n == 1 ? "" : "es", (double)ms);
 	} else destroyTexture(t);
 	free(host);
+}
+
+/* CRAY_HIP_EXR=1: the names of the scene's ids, taken while the flattened scene is there (a long frame gives it back early): instance i is <mesh name>#<i> for a mesh
+ * instance and sphere#<i> otherwise, material i is material#<i>. */
+struct layerNames { char **instances, **materials; uint32_t instanceCount, materialCount; };
+static char *numberedName(const char *stem, uint32_t i) {
+	char *s = malloc(strlen(stem) + 16);
+	if (s) sprintf(s, "%s#%u", stem, i);
+	return s;
+}
+static void layerNamesCollect(const struct renderer *r, const crh_scene_desc *scene, struct layerNames *out) {
+	out->instanceCount = (uint32_t)scene->instance_count;
+	out->materialCount = (uint32_t)scene->material_count;
+	out->instances = calloc(out->instanceCount ? out->instanceCount : 1, sizeof(char *));
+	out->materials = calloc(out->materialCount ? out->materialCount : 1, sizeof(char *));
+	for (uint32_t i = 0; out->instances && i < out->instanceCount; ++i) {
+		const crh_instance *fi = &scene->instances[i];
+		const bool mesh = fi->kind == CRH_INSTANCE_MESH || fi->kind == CRH_INSTANCE_MESH_VOLUME;
+		const char *name = mesh ? r->scene->meshes[fi->object].name : "sphere";
+		out->instances[i] = numberedName(name ? name : "mesh", i);
+	}
+	for (uint32_t i = 0; out->materials && i < out->materialCount; ++i) out->materials[i] = numberedName("material", i);
+}
+static void layerNamesFree(struct layerNames *n) {
+	for (uint32_t i = 0; n->instances && i < n->instanceCount; ++i) free(n->instances[i]);
+	for (uint32_t i = 0; n->materials && i < n->materialCount; ++i) free(n->materials[i]);
+	free(n->instances); free(n->materials);
+	memset(n, 0, sizeof(*n));
+}
+
+/* CRAY_HIP_EXR=1: <imgFilePath><imgFileName>_layers_<imgCount, four digits>.exr — the name the frame's own file would get for <imgFileName>_layers — holds the frame
+ * `fb`, the guide buffers `aov` and the denoised frame `denoised` where CRAY_HIP_AOV / CRAY_HIP_DENOISE left them on GPU 0, and with CRAY_HIP_IDS=<n> the ranked ids of
+ * min(n, sampleCount) passes of both ID buffers rendered here, as Cryptomatte layers. The channels are packed on the device (crh_pack_scanlines), at most 32 MB a call. */
+static void writeLayers(struct renderer *r, crh_ctx *ctx, const float *fb, const float *aov, const float *denoised, const struct layerNames *names, int W, int H) {
+	const char *e = getenv("CRAY_HIP_IDS");
+	int n = e ? atoi(e) : 0;
+	if (n > r->prefs.sampleCount) n = r->prefs.sampleCount;
+	const bool ids = n > 0 && names->instances && names->materials && names->instanceCount && names->materialCount && names->instanceCount <= 65536 && names->materialCount <= 65536;
+	if (n > 0 && !ids) logr(warning, "c-ray-hip: CRAY_HIP_IDS needs 1 .. 65536 instances and materials; the layers file gets no id layers\n");
+	uint32_t *buf[2] = {NULL, NULL}, *map[2] = {NULL, NULL};
+	float *ranked[2] = {NULL, NULL};          /* [H, W, 6, 2] floats in an ID buffer's 16 words a pixel */
+	struct exr_attr strings[8];
+	int stringCount = 0;
+	bool ok = true;
+	if (ids) {
+		crh_render_params p;
+		memset(&p, 0, sizeof(p));
+		p.x1 = W; p.y1 = H; p.image_width = W; p.image_height = H; p.pass_count = n; p.max_passes = r->prefs.sampleCount;
+		for (int k = 0; k < 2; ++k) ok = ok && crh_ids_alloc(ctx, W, H, &buf[k]) == CRH_OK && crh_ids_alloc(ctx, W, H, (uint32_t **)&ranked[k]) == CRH_OK;
+		ok = ok && crh_render_ids(ctx, &p, NULL, 0, buf[0], buf[1]) == CRH_OK;
+		for (int k = 0; k < 2 && ok; ++k) {
+			char **list = k ? names->materials : names->instances;
+			const uint32_t count = k ? names->materialCount : names->instanceCount;
+			ok = crh_ids_resolve(ctx, buf[k], W, H, ranked[k]) == CRH_OK && (map[k] = malloc(count * sizeof(uint32_t))) != NULL;
+			for (uint32_t i = 0; ok && i < count; ++i) ok = list[i] != NULL;
+			for (uint32_t i = 0; ok && i < count; ++i) map[k][i] = exr_crypto_id(list[i]);
+			if (ok && exr_crypto_attrs(k ? "CryptoMaterial" : "CryptoObject", (const char *const *)list, count, strings + stringCount) == 0) stringCount += 4;
+			else ok = false;
+		}
+	}
+	crh_pack_channel channels[CRH_PACK_MAX_CHANNELS];
+	const char *channelNames[CRH_PACK_MAX_CHANNELS];
+	const int count = exr_layer_channels(fb, aov, denoised, ids ? ranked[0] : NULL, ids ? ranked[1] : NULL, map[0], names->instanceCount, map[1], names->materialCount, channels, channelNames);
+	const size_t block = 8u + 4u * (size_t)count * (size_t)W;
+	char *blocks = ok ? malloc(block * (size_t)H) : NULL;
+	int chunk = (int)(((size_t)32 << 20) / block);
+	if (chunk < 1) chunk = 1;
+	ok = ok && blocks;
+	for (int y = 0; ok && y < H; y += chunk)
+		ok = crh_pack_scanlines(ctx, channels, (uint32_t)count, W, H, y, H - y < chunk ? H - y : chunk, blocks + block * (size_t)y) == CRH_OK;
+	const char *base = r->prefs.imgFileName ? r->prefs.imgFileName : "rendered";
+	const char *dir = r->prefs.imgFilePath ? r->prefs.imgFilePath : "";
+	char *path = malloc(strlen(dir) + strlen(base) + 32);
+	if (ok && path) {
+		sprintf(path, "%s%s_layers_%04d.exr", dir, base, r->prefs.imgCount);
+		if (exr_write_file(path, W, H, channelNames, count, strings, stringCount, blocks) == 0) logr(info, "Layers written to %s (%i channels%s).\n", path, count, ids ? ", Cryptomatte ids" : "");
+		else logr(warning, "c-ray-hip: the layers file %s could not be written\n", path);
+	} else logr(warning, "c-ray-hip: the layers file could not be made: %s\n", blocks && path ? crh_last_error() : "out of memory");
+	free(path); free(blocks);
+	exr_free_attrs(strings, stringCount);
+	for (int k = 0; k < 2; ++k) {
+		if (buf[k]) crh_ids_free(ctx, buf[k]);
+		if (ranked[k]) crh_ids_free(ctx, (uint32_t *)ranked[k]);
+		free(map[k]);
+	}
 }
 
 struct texture *renderFrame(struct renderer *r) {
@@ -851,6 +946,10 @@ struct texture *renderFrame(struct renderer *r) {
 	startTimer(&phase);
 	int frc = crh_flatten_world(r, &scene);
 	const long flattenUs = getUs(phase);
+	const bool layers = getenv("CRAY_HIP_EXR") && atoi(getenv("CRAY_HIP_EXR")) > 0;
+	struct layerNames layerNames;
+	memset(&layerNames, 0, sizeof(layerNames));
+	if (layers && frc == CRH_OK) layerNamesCollect(r, &scene, &layerNames);
 	/* several GPUs: ONE layout compile, here, behind the flattener; the GPU threads only copy (the reference builds its scene once and every worker reads it:
 	 * src/datatypes/scene.c:111-213). One GPU: its crh_scene_upload compiles with the texels' copy beside it */
 	crh_compiled_scene *compiled = NULL;
@@ -965,7 +1064,8 @@ struct texture *renderFrame(struct renderer *r) {
 		else
 			logr(info, "Adaptive sampling (threshold %g, at least %i passes): %llu rays, %u tiles by pass count: %s.\n", (double)adaptive.threshold, adaptive.min_passes, (unsigned long long)rays, all, line);
 	}
-	if (!workers[0].failed && !r->state.renderAborted) writeAovs(r, workers[0].ctx, W, H);
+	float *keptAov = NULL, *keptDenoised = NULL;          /* CRAY_HIP_EXR: the guides and the denoised frame stay on GPU 0 for the layers file */
+	if (!workers[0].failed && !r->state.renderAborted) writeAovs(r, workers[0].ctx, W, H, layers && !failed ? &keptAov : NULL);
 	if (!failed && !r->state.renderAborted) {          /* (a frame assembled on the host is not on GPU 0) */
 		const int halfAt = varianceHalfPasses(r);          /* (sampleCount / 2 also describes an adaptive frame: every rectangle's half holds the first half of its passes, scale 1) */
 		if (halfAt && gpus > 1) {          /* the half-sample frame: the same strips, the same way to GPU 0 */
@@ -974,8 +1074,13 @@ struct texture *renderFrame(struct renderer *r) {
 			for (int g = 0; g < gpus; ++g) { ctxs[g] = workers[g].ctx; halves[g] = workers[g].half; }
 			assembleFrame(ctxs, halves, gpus, W, H);
 		}
-		writeDenoised(r, workers[0].ctx, workers[0].fb, halfAt ? workers[0].half : NULL, halfAt, W, H);
-	}
+		writeDenoised(r, workers[0].ctx, workers[0].fb, halfAt ? workers[0].half : NULL, halfAt, W, H, layers ? &keptDenoised : NULL);
+		if (layers) writeLayers(r, workers[0].ctx, workers[0].fb, keptAov, keptDenoised, &layerNames, W, H);
+	} else if (layers) logr(warning, "c-ray-hip: CRAY_HIP_EXR needs the frame on GPU 0; no layers file\n");
+	if (keptAov) crh_aov_free(workers[0].ctx, keptAov);
+	if (keptDenoised) crh_framebuffer_free(workers[0].ctx, keptDenoised);
+	layerNamesFree(&layerNames);
+	if (!layers && getenv("CRAY_HIP_IDS") && atoi(getenv("CRAY_HIP_IDS")) > 0) logr(warning, "c-ray-hip: CRAY_HIP_IDS has no output without CRAY_HIP_EXR=1\n");
 
 	for (int g = 0; g < gpus; ++g) {
 		if (workers[g].ctx && workers[g].fb) crh_framebuffer_free(workers[g].ctx, workers[g].fb);

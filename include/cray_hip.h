@@ -39,6 +39,7 @@ extern "C" {
  * 5: the denoiser — crh_denoise_params / crh_denoise_params_default / crh_denoise / crh_denoise_time_ms (and crh_debug_denoise_launch_ms) — exists.
  * (the ID mattes — crh_ids_alloc / crh_ids_free / crh_ids_clear / crh_ids_download / crh_render_ids / crh_ids_kernel_time_ms / crh_ids_resolve / crh_ids_matte — add
  * entry points and change no declaration: a version-5 host is unaffected, the version stays 5.)
+ * (crh_pack_scanlines / crh_pack_time_ms — the pixel data of a multi-layer OpenEXR file, packed on the device — likewise: additive, the version stays 5.)
  * A host checks crh_abi_version() == CRH_ABI_VERSION. */
 #define CRH_ABI_VERSION 5
 /* layout version of crh_scene_desc and of the scene blobs (crh_blob_save / crh_blob_load): the records have not changed since round 1 */
@@ -485,6 +486,36 @@ int crh_ids_kernel_time_ms(crh_ctx *ctx, float *last_ms);
 int crh_ids_resolve(crh_ctx *ctx, const uint32_t *dev_ids, int width, int height, float *dev_out);
 #define CRH_IDS_MATTE_MAX 64
 int crh_ids_matte(crh_ctx *ctx, const uint32_t *dev_ids, int width, int height, const uint32_t *ids_host, uint32_t id_count, float *dev_out);
+
+/* The way out of the library for all of the above: the pixel-data section of an uncompressed scanline OpenEXR file whose channels are all FLOAT, gathered on the device
+ * from the buffers named by a channel list and fetched with one copy. The file around it — header, offset table, Cryptomatte metadata — is the host's business
+ * (c-ray_amd/host/exr_write.c, c-ray_amd/exr.py). No scene is needed.
+ * A channel is one component of a device buffer of 32-bit words [H, W, stride] in the frame buffer's stored order (row 0 = the top of the image), the context's or the
+ * caller's: the frame (stride 3), an AOV buffer (8), crh_ids_resolve's output (12), anything else of that shape.
+ * host_out receives row_count blocks of 8 + 4 * channel_count * width bytes each. The block of stored row y = first_row + r holds, in order: int32 y, int32
+ * 4 * channel_count * width, and for channel c = 0 .. channel_count - 1 in the order given the `width` words of that channel for x = 0 .. width - 1. In a file the
+ * channel list is in ascending byte order of name: that is the order to hand in.
+ *   map_host == NULL: the word is the bits of dev_src[(y * W + x) * stride + component], copied: NaNs, infinities and -0 pass unchanged.
+ *   map_host != NULL: the source value v is an id as crh_ids_resolve writes it — (float)id, an empty rank -1. If v >= 0 && v < (float)map_count &&
+ *     (float)(uint32_t)v == v the word is map_host[(uint32_t)v], otherwise 0x00000000. The maps are read before the call returns and uploaded into scratch the
+ *     context owns (channels that name the same map and count share one copy).
+ * The call launches behind whatever is queued on the context's stream, copies the result through the context's pinned scratch and waits for it. first_row / row_count
+ * let a caller bound that scratch: the blocks of consecutive chunks concatenate to those of one call. row_count == 0 is CRH_OK and writes nothing. Like a denoise the
+ * call leaves crh_counters, crh_kernel_time_ms and crh_last_kernel_name as they were; crh_pack_time_ms reports the last call's kernel time between two of the
+ * library's own events (waits for it; 0 before the first one).
+ * CRH_ERR_INVALID: a NULL context, list, source or output; channel_count outside 1 .. CRH_PACK_MAX_CHANNELS; a size <= 0; rows outside the image (first_row < 0,
+ * row_count < 0, first_row + row_count > height); a row block of 2^31 bytes or more; stride outside 1 .. 64; component >= stride; map_count > 65536; a map with count 0. */
+#define CRH_PACK_MAX_CHANNELS 64
+typedef struct crh_pack_channel {
+	const float    *dev_src;    /* float [H, W, stride], stored order (row 0 = top), the context's or the caller's */
+	uint32_t        stride;     /* floats per pixel, 1 .. 64 */
+	uint32_t        component;  /* < stride */
+	const uint32_t *map_host;   /* NULL: the source word's bits are copied. Otherwise the value is an id, see above */
+	uint32_t        map_count;  /* <= 65536 */
+	uint32_t        pad;
+} crh_pack_channel;
+int crh_pack_scanlines(crh_ctx *ctx, const crh_pack_channel *channels, uint32_t channel_count, int width, int height, int first_row, int row_count, void *host_out);
+int crh_pack_time_ms(crh_ctx *ctx, float *last_ms);
 
 /* The consumer of those buffers: an edge-avoiding a-trous wavelet filter on the albedo-demodulated frame, guided by normal and depth. No scene is needed.
  *   dev_fb   float RGB [H, W, 3]           dev_aov   [H, W, 8] as above           dev_out   float RGB [H, W, 3]; may be dev_fb, must not be dev_aov

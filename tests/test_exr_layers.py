@@ -1,0 +1,625 @@
+"""The multi-layer OpenEXR output: crh_pack_scanlines (c-ray_amd/csrc/exr_pack.h) gathers channels of the frame, the guide buffers, a denoised frame and
+ranked ids into the pixel data of an uncompressed scanline file on the device; c-ray_amd/exr.py and c-ray_amd/host/exr_write.c write the file around it,
+with Cryptomatte's metadata on the id layers.
+
+The reader below is this file's own, written from the format's description (magic, version, attributes, chlist, offset table, blocks), and is anchored
+by a file spelled out field by field. CPU tier: the format, the hash, C against Python, the struct; the GPU tests again on the kernel emulation. GPU tier:
+the packed bytes bit for bit against a NumPy restatement of the header's contract, row chunks, refused arguments, a rendered file read back, and the
+drop-in program's file."""
+import ctypes as C
+import json
+import os
+import re
+import struct
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from test_idmatte import DeviceWords, resolve_expected
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EMU_DIR = os.path.join(REPO, "tests", "emu")
+GUIDES = ("albedo.R", "albedo.G", "albedo.B", "normal.X", "normal.Y", "normal.Z", "Z", "A")
+
+
+def crypto_names(layer):
+    """rank r: id in <layer>0k.R (r = 2k) or .B (r = 2k + 1), coverage in .G or .A"""
+    return [(f"{layer}{r // 2:02d}.{'RB'[r % 2]}", f"{layer}{r // 2:02d}.{'GA'[r % 2]}") for r in range(6)]
+
+
+ALL_38 = ["R", "G", "B"] + list(GUIDES) + ["denoised.R", "denoised.G", "denoised.B"] + [n for layer in ("CryptoObject", "CryptoMaterial") for pair in crypto_names(layer) for n in pair]
+assert len(ALL_38) == 38
+
+
+@pytest.fixture(scope="module")
+def ctx(pkg):
+    if pkg.api.device_count() < 1:
+        pytest.fail("GPU tier needs a HIP device; libcray_hip has no CPU fallback")
+    c = pkg.api.Context(0)
+    yield c
+    c.close()
+
+
+# ---- the reader ---------------------------------------------------------------------------------------------------------------------------
+def _cstr(data, pos):
+    end = data.index(b"\0", pos)
+    return data[pos:end], end + 1
+
+
+def read_exr(data):
+    """An uncompressed single-part scanline OpenEXR file whose channels are all FLOAT -> width, height, attributes {name: (type, value bytes)} and their order,
+    channel names in file order, planes {name: uint32 [H, W]}, the offset table, the y of every block in file order, where the first block starts and the last ends."""
+    assert data[0:4] == bytes([0x76, 0x2F, 0x31, 0x01]), "magic"
+    assert data[4:8] == bytes([2, 0, 0, 0]), "version 2, no flags: single part, scanline, short names"
+    pos, attrs, order = 8, {}, []
+    while data[pos] != 0:
+        name, pos = _cstr(data, pos)
+        kind, pos = _cstr(data, pos)
+        size, = struct.unpack_from("<i", data, pos)
+        assert 1 <= len(name) <= 31 and size >= 0
+        attrs[name.decode()] = (kind.decode(), data[pos + 4:pos + 4 + size])
+        order.append(name)
+        pos += 4 + size
+    pos += 1
+    kind, chl = attrs["channels"]
+    assert kind == "chlist" and chl[-1] == 0
+    names, at = [], 0
+    while chl[at] != 0:
+        name, at = _cstr(chl, at)
+        pixel_type, p_linear, z0, z1, z2, xs, ys = struct.unpack_from("<iBBBBii", chl, at)
+        assert (pixel_type, p_linear, z0, z1, z2, xs, ys) == (2, 0, 0, 0, 0, 1, 1), name
+        assert 1 <= len(name) <= 31
+        names.append(name.decode())
+        at += 16
+    assert at == len(chl) - 1
+    assert attrs["compression"] == ("compression", b"\0") and attrs["lineOrder"] == ("lineOrder", b"\0")
+    assert attrs["dataWindow"][0] == "box2i" and attrs["displayWindow"] == attrs["dataWindow"]
+    x0, y0, x1, y1 = struct.unpack("<4i", attrs["dataWindow"][1])
+    assert (x0, y0) == (0, 0)
+    w, h = x1 + 1, y1 + 1
+    assert attrs["pixelAspectRatio"] == ("float", struct.pack("<f", 1.0)) and attrs["screenWindowWidth"] == ("float", struct.pack("<f", 1.0))
+    assert attrs["screenWindowCenter"] == ("v2f", struct.pack("<2f", 0.0, 0.0))
+    offsets = list(struct.unpack_from(f"<{h}Q", data, pos))
+    pos += 8 * h
+    first = pos
+    planes = np.empty((len(names), h, w), np.uint32)
+    ys = []
+    for y in range(h):          # (in file order)
+        yy, size = struct.unpack_from("<ii", data, pos)
+        assert size == 4 * len(names) * w, "a block's byte count"
+        ys.append(yy)
+        planes[:, yy, :] = np.frombuffer(data, "<u4", len(names) * w, pos + 8).reshape(len(names), w)
+        pos += 8 + size
+    return {"width": w, "height": h, "attrs": attrs, "attr_order": order, "names": names, "planes": dict(zip(names, planes)), "offsets": offsets, "ys": ys,
+            "first": first, "end": pos}
+
+
+def check_structure(f, data):
+    """What every file of this writer holds: offsets at their blocks, blocks in row order and back to back, sorted attributes and channels, nothing behind."""
+    block = 8 + 4 * len(f["names"]) * f["width"]
+    assert f["offsets"] == [f["first"] + block * y for y in range(f["height"])], "every offset is the position of its block"
+    assert f["ys"] == list(range(f["height"])), "blocks in row order"
+    assert f["end"] == len(data)
+    raw = [n.encode() for n in f["names"]]
+    assert raw == sorted(raw) and len(set(raw)) == len(raw), "channels in ascending byte order of name"
+    assert f["attr_order"] == sorted(f["attr_order"]), "attributes in ascending byte order of name"
+
+
+def attr_string(f, name):
+    kind, value = f["attrs"][name]
+    assert kind == "string"
+    return value.decode("utf-8")
+
+
+# ---- CPU tier: the format ----------------------------------------------------------------------------------------------------------------
+def hand_built_2x1():
+    """A 2 x 1 image with the channels B and R: B = (0.25, -0.0), R = (1.5, NaN 0x7fc00123)."""
+    def attr(name, kind, value):
+        return name + b"\0" + kind + b"\0" + struct.pack("<i", len(value)) + value
+
+    def channel(name):
+        return name + b"\0" + struct.pack("<i", 2) + struct.pack("<B", 0) + b"\0\0\0" + struct.pack("<i", 1) + struct.pack("<i", 1)
+    head = bytes([0x76, 0x2F, 0x31, 0x01]) + bytes([0x02, 0x00, 0x00, 0x00])
+    head += attr(b"channels", b"chlist", channel(b"B") + channel(b"R") + b"\0")
+    head += attr(b"compression", b"compression", struct.pack("<B", 0))
+    head += attr(b"dataWindow", b"box2i", struct.pack("<i", 0) + struct.pack("<i", 0) + struct.pack("<i", 1) + struct.pack("<i", 0))
+    head += attr(b"displayWindow", b"box2i", struct.pack("<i", 0) + struct.pack("<i", 0) + struct.pack("<i", 1) + struct.pack("<i", 0))
+    head += attr(b"lineOrder", b"lineOrder", struct.pack("<B", 0))
+    head += attr(b"pixelAspectRatio", b"float", struct.pack("<f", 1.0))
+    head += attr(b"screenWindowCenter", b"v2f", struct.pack("<f", 0.0) + struct.pack("<f", 0.0))
+    head += attr(b"screenWindowWidth", b"float", struct.pack("<f", 1.0))
+    head += b"\0"
+    table = struct.pack("<Q", len(head) + 8)          # one row: its block follows the one-entry table
+    block = struct.pack("<i", 0) + struct.pack("<i", 4 * 2 * 2)
+    block += struct.pack("<I", 0x3E800000) + struct.pack("<I", 0x80000000)          # B: 0.25, -0.0
+    block += struct.pack("<I", 0x3FC00000) + struct.pack("<I", 0x7FC00123)          # R: 1.5, a NaN with a payload
+    return head + table + block
+
+
+def test_reader_parses_hand_built_bytes_and_exr_py_writes_them(pkg):
+    data = hand_built_2x1()
+    f = read_exr(data)
+    assert (f["width"], f["height"], f["names"]) == (2, 1, ["B", "R"])
+    assert f["planes"]["B"].tolist() == [[0x3E800000, 0x80000000]] and f["planes"]["R"].tolist() == [[0x3FC00000, 0x7FC00123]]
+    check_structure(f, data)
+    exr = pkg.exr
+    b = np.array([[0x3E800000, 0x80000000]], np.uint32)
+    r = np.array([[0x3FC00000, 0x7FC00123]], np.uint32)
+    assert exr.file_bytes(2, 1, ["B", "R"], exr.pack_host([b, r], 2, 1)) == data
+    with pytest.raises(AssertionError):
+        exr.header(2, 1, ["R", "B"])          # not in ascending byte order
+    with pytest.raises(AssertionError):
+        exr.header(2, 1, ["B" * 32])           # longer than 31 bytes
+
+
+@pytest.mark.parametrize("w,h,nch", [(1, 1, 1), (3, 2, 7), (161, 75, 38)])
+def test_round_trip(w, h, nch, pkg):
+    exr = pkg.exr
+    rng = np.random.default_rng(w * 1000 + nch)
+    names = sorted((ALL_38[i] for i in rng.permutation(38)[:nch]), key=lambda s: s.encode())
+    planes = [rng.integers(0, 2 ** 32, (h, w), dtype=np.uint32) for _ in names]          # any bit pattern: NaNs, infinities, subnormals
+    strings = {"cryptomatte/3ae39a5/name": "CryptoObject", "aaa": "", "zzz": "ä \"quoted\""} if nch > 1 else None
+    data = exr.file_bytes(w, h, names, exr.pack_host(planes, w, h), strings)
+    f = read_exr(data)
+    check_structure(f, data)
+    assert (f["width"], f["height"], f["names"]) == (w, h, names)
+    for n, p in zip(names, planes):
+        assert np.array_equal(f["planes"][n], p), n
+    if strings:
+        for k, v in strings.items():
+            assert attr_string(f, k) == v
+        assert f["attr_order"][0] == b"aaa" and f["attr_order"][-1] == b"zzz"
+    if nch == 38:          # the channel order handed to the pack is the file's
+        chans = exr.layer_channels(1, 2, 3, 4, 5, "im", "mm")
+        assert [c[0] for c in chans] == names == sorted(ALL_38, key=lambda s: s.encode())
+        by = {c[0]: c[1:] for c in chans}
+        assert by["G"] == (1, 3, 1, None) and by["Z"] == (2, 8, 6, None) and by["A"] == (2, 8, 7, None) and by["normal.Y"] == (2, 8, 4, None) and by["denoised.B"] == (3, 3, 2, None)
+        for layer, src, m in (("CryptoObject", 4, "im"), ("CryptoMaterial", 5, "mm")):
+            for r, (idn, covn) in enumerate(crypto_names(layer)):
+                assert by[idn] == (src, 12, 2 * r, m) and by[covn] == (src, 12, 2 * r + 1, None), (idn, covn)
+
+
+def test_cryptomatte_hash_and_keys(pkg):
+    exr = pkg.exr
+    assert exr.murmur3_32(b"") == 0x00000000 and exr.crypto_id("") == 0x00800000
+    assert exr.murmur3_32(b"hello") == 0x248BFA47 == exr.crypto_id("hello")
+    assert exr.murmur3_32(b"foo") == 0xF6A5C420 == exr.crypto_id("foo")
+    assert exr.float_safe(0x7F812345) == 0x7F012345 and exr.float_safe(0xFFFFFFFF) == 0xFF7FFFFF          # exponent 255: bit 23 flips, a finite normal number
+    assert exr.float_safe(0x00000001) == 0x00800001 and exr.float_safe(0x3F800000) == 0x3F800000
+    for word in (exr.float_safe(0x7F812345), exr.float_safe(0xFFFFFFFF), exr.float_safe(1)):
+        v = np.array([word], np.uint32).view(np.float32)[0]
+        assert np.isfinite(v) and abs(v) >= np.finfo(np.float32).tiny
+    assert exr.layer_key("CryptoObject") == "3ae39a5" and exr.layer_key("CryptoMaterial") == "be359d6"
+    attrs = exr.crypto_attributes("CryptoObject", ["b", "a"])
+    assert attrs["cryptomatte/3ae39a5/name"] == "CryptoObject" and attrs["cryptomatte/3ae39a5/hash"] == "MurmurHash3_32"
+    assert attrs["cryptomatte/3ae39a5/conversion"] == "uint32_to_float32"
+    assert attrs["cryptomatte/3ae39a5/manifest"] == '{"b":"%08x","a":"%08x"}' % (exr.crypto_id("b"), exr.crypto_id("a"))
+    with pytest.raises(AssertionError):
+        exr.id_map(["same", "same"])
+
+
+C_PROGRAM = r"""
+#include <stdio.h>
+#include <string.h>
+#include "exr_write.h"
+/* 3 x 2, all 38 channels of the layer list; the word of channel c at (x, y) is 0x3f000000 + 4096 * c + 16 * y + x */
+int main(int argc, char **argv) {
+	static const char *inst[3] = {"sphere#0", "a \"quoted\\\" mesh\n#1", "m\303\244sh#2"};
+	static const char *mat[2] = {"material#0", "material#1"};
+	crh_pack_channel ch[CRH_PACK_MAX_CHANNELS];
+	const char *names[CRH_PACK_MAX_CHANNELS];
+	static float a, b, c, d, e;
+	const int n = exr_layer_channels(&a, &b, &c, &d, &e, NULL, 0, NULL, 0, ch, names);
+	uint32_t blocks[2][2 + 38 * 3];
+	struct exr_attr strings[8];
+	if (argc < 2 || n != 38 || exr_crypto_attrs("CryptoObject", inst, 3, strings) || exr_crypto_attrs("CryptoMaterial", mat, 2, strings + 4)) return 1;
+	for (int y = 0; y < 2; ++y) {
+		blocks[y][0] = (uint32_t)y; blocks[y][1] = 4u * 38u * 3u;
+		for (int k = 0; k < n; ++k) for (int x = 0; x < 3; ++x) blocks[y][2 + k * 3 + x] = 0x3f000000u + 4096u * (uint32_t)k + 16u * (uint32_t)y + (uint32_t)x;
+	}
+	for (int k = 0; k < n; ++k) printf("%s %u %u %d\n", names[k], ch[k].stride, ch[k].component, (int)(ch[k].dev_src == &a ? 0 : ch[k].dev_src == &b ? 1 : ch[k].dev_src == &c ? 2 : ch[k].dev_src == &d ? 3 : 4));
+	printf("hash %08x %08x %08x %08x\n", exr_murmur3_32("", 0, 0), exr_crypto_id(""), exr_crypto_id("hello"), exr_crypto_id("foo"));
+	const int rc = exr_write_file(argv[1], 3, 2, names, n, strings, 8, blocks);
+	exr_free_attrs(strings, 8);
+	return rc ? 2 : 0;
+}
+"""
+
+
+def test_c_writer_writes_the_bytes_of_exr_py(pkg, tmp_path):
+    """c-ray_amd/host/exr_write.c in a program of its own (built with AddressSanitizer and UBSan) against exr.py: the 3 x 2 file with every layer, names that need
+    JSON escapes and UTF-8, byte for byte; its channel list and hashes."""
+    exr = pkg.exr
+    host = os.path.join(REPO, "c-ray_amd", "host")
+    src, exe, out = tmp_path / "exr_c.c", tmp_path / "exr_c", tmp_path / "c.exr"
+    src.write_text(C_PROGRAM)
+    subprocess.check_call(["gcc", "-std=gnu99", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
+                           "-I" + os.path.join(REPO, "include"), "-I" + host, str(src), os.path.join(host, "exr_write.c"), "-o", str(exe)])
+    r = subprocess.run([str(exe), str(out)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    lines = r.stdout.splitlines()
+    assert lines[-1] == "hash 00000000 00800000 248bfa47 f6a5c420"
+    chans = exr.layer_channels(0, 1, 2, 3, 4, "m", "m")
+    assert [ln.split(" ") for ln in lines[:-1]] == [[c[0], str(c[2]), str(c[3]), str(c[1])] for c in chans]
+    inst, mat = ["sphere#0", "a \"quoted\\\" mesh\n#1", "mäsh#2"], ["material#0", "material#1"]
+    strings = dict(exr.crypto_attributes("CryptoObject", inst), **exr.crypto_attributes("CryptoMaterial", mat))
+    planes = [np.array([[0x3F000000 + 4096 * k + 16 * y + x for x in range(3)] for y in range(2)], np.uint32) for k in range(38)]
+    want = exr.file_bytes(3, 2, [c[0] for c in chans], exr.pack_host(planes, 3, 2), strings)
+    got = out.read_bytes()
+    assert got == want
+    f = read_exr(got)
+    check_structure(f, got)
+    assert list(json.loads(attr_string(f, "cryptomatte/3ae39a5/manifest"))) == inst
+
+
+def test_pack_channel_struct_matches_header(pkg, tmp_path):
+    src, exe = tmp_path / "size.c", tmp_path / "size"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "cray_hip.h"\nint main(void){printf("%zu %zu %zu %zu %zu %d\\n", sizeof(crh_pack_channel), '
+                   'offsetof(crh_pack_channel, stride), offsetof(crh_pack_channel, component), offsetof(crh_pack_channel, map_host), offsetof(crh_pack_channel, map_count), '
+                   'CRH_PACK_MAX_CHANNELS);return 0;}\n')
+    subprocess.check_call(["gcc", "-I" + os.path.join(REPO, "include"), str(src), "-o", str(exe)])
+    size, stride, component, map_host, map_count, most = (int(v) for v in subprocess.check_output([str(exe)]).split())
+    P = pkg.abi.PackChannel
+    assert (C.sizeof(P), P.stride.offset, P.component.offset, P.map_host.offset, P.map_count.offset) == (size, stride, component, map_host, map_count) and size == 32
+    assert most == pkg.abi.PACK_MAX_CHANNELS == 64
+
+
+# ---- the NumPy restatement of crh_pack_scanlines' contract ------------------------------------------------------------------------------
+def pack_expected(chans, w, h, first=0, rows=None):
+    """chans: (uint32 [h, w, stride] array, stride, component, map or None) in order -> the bytes of stored rows [first, first + rows)."""
+    rows = h - first if rows is None else rows
+    out = np.zeros((rows, 2 + len(chans) * w), np.uint32)
+    out[:, 0] = np.arange(first, first + rows, dtype=np.uint32)
+    out[:, 1] = 4 * len(chans) * w
+    for c, (src, stride, comp, m) in enumerate(chans):
+        assert src.shape == (h, w, stride)
+        words = src[first:first + rows, :, comp]
+        if m is not None:
+            v = words.view(np.float32)
+            with np.errstate(invalid="ignore"):
+                ok = (v >= 0) & (v < np.float32(len(m)))
+                u = np.where(ok, v, np.float32(0)).astype(np.uint32)
+                ok &= u.astype(np.float32) == v
+            words = np.where(ok, m[u], np.uint32(0))
+        out[:, 2 + c * w:2 + (c + 1) * w] = words
+    return out.tobytes()
+
+
+SPECIAL = np.array([0x7FC00000, 0xFFC12345, 0x7F800001, 0x7F800000, 0xFF800000, 0x80000000, 0x00000001, 0x807FFFFF, 0x00000000, 0x3F800000], np.uint32)
+
+
+def source(rng, w, h, stride):
+    """uint32 [h, w, stride]: random bit patterns with NaNs (quiet, signalling, negative), both infinities, -0.0 and subnormals planted"""
+    a = rng.integers(0, 2 ** 32, (h, w, stride), dtype=np.uint32)
+    flat = a.reshape(-1)
+    at = np.arange(0, flat.size, 3)
+    flat[at] = SPECIAL[np.arange(at.size) % SPECIAL.size]
+    return a
+
+
+def plant_ids(rng, a, comp, count):
+    """component `comp` of `a` becomes ids against a map of `count` entries: the edge values first, valid ids behind them"""
+    edge = np.array([-1.0, 0.0, count - 1, count, 2.5, np.nan, 16777216.0, -0.0, 0.5, count - 0.5, 1e30, np.inf, -np.inf, 1e-45, -2.0, 4294967296.0], np.float32)
+    vals = rng.integers(0, count, a.shape[0] * a.shape[1]).astype(np.float32)
+    vals[:min(edge.size, vals.size)] = edge[:vals.size]
+    a[:, :, comp] = vals.view(np.uint32).reshape(a.shape[:2])
+
+
+def pack_case(name):
+    """(w, h, sources {key: uint32 array}, channels [(key, stride, component, map key or None)], maps {key: uint32 array})"""
+    rng = np.random.default_rng(sum(name.encode()))
+    maps = {"big": rng.integers(0, 2 ** 32, 65536, dtype=np.uint32), "five": rng.integers(1, 2 ** 32, 5, dtype=np.uint32), "one": np.array([0xDEADBEEF], np.uint32)}
+    if name == "1x1":
+        w, h = 1, 1
+        src = {"a": np.array([[[0x7FC00123]]], np.uint32)}
+        chans = [("a", 1, 0, None)]
+    elif name == "3x2":
+        w, h = 3, 2
+        src = {"fb": source(rng, w, h, 3), "aov": source(rng, w, h, 8)}
+        chans = [("aov", 8, 7, None), ("fb", 3, 2, None), ("aov", 8, 0, None), ("fb", 3, 0, None), ("aov", 8, 3, None), ("fb", 3, 1, None), ("aov", 8, 6, None), ("aov", 8, 5, "five")]
+        plant_ids(rng, src["aov"], 5, 5)
+    elif name == "67x5":          # more columns than a wave, the channel maximum, the stride maximum, one source word read twice, three maps
+        w, h = 67, 5
+        src = {"s64": source(rng, w, h, 64), "s1": source(rng, w, h, 1), "s12": source(rng, w, h, 12), "s3": source(rng, w, h, 3)}
+        chans = [("s64", 64, 63, None), ("s1", 1, 0, None), ("s12", 12, 0, "big"), ("s12", 12, 1, None), ("s12", 12, 2, "big"), ("s12", 12, 4, "five"), ("s12", 12, 6, "one"),
+                 ("s12", 12, 6, None)]
+        chans += [("s64", 64, k, None) for k in range(50)] + [("s3", 3, k % 3, None) for k in range(6)]
+        for comp, count in ((0, 65536), (2, 65536), (4, 5), (6, 1)):
+            plant_ids(rng, src["s12"], comp, count)
+        assert len(chans) == 64
+    else:          # the layout of a whole file: strides 3, 8 and 12, ids through two maps
+        assert name == "161x75"
+        w, h = 161, 75
+        src = {"fb": source(rng, w, h, 3), "aov": source(rng, w, h, 8), "dn": source(rng, w, h, 3), "io": source(rng, w, h, 12), "im": source(rng, w, h, 12)}
+        for comp in range(0, 12, 2):
+            plant_ids(rng, src["io"], comp, 65536)
+            plant_ids(rng, src["im"], comp, 5)
+        chans = [("io", 12, k, "big" if k % 2 == 0 else None) for k in range(12)] + [("im", 12, k, "five" if k % 2 == 0 else None) for k in range(12)]
+        chans += [("fb", 3, k, None) for k in range(3)] + [("aov", 8, k, None) for k in range(8)] + [("dn", 3, k, None) for k in range(3)]
+        assert len(chans) == 38
+    return w, h, src, chans, maps
+
+
+def run_pack(pkg, ctx, case, **rows):
+    """(the bytes the library packs, the bytes of the restatement)"""
+    w, h, src, chans, maps = case
+    dev = {k: DeviceWords(pkg, v) for k, v in src.items()}
+    got = ctx.pack_scanlines([(dev[k].ptr, stride, comp, None if m is None else maps[m]) for k, stride, comp, m in chans], w, h, **rows)
+    want = pack_expected([(src[k], stride, comp, None if m is None else maps[m]) for k, stride, comp, m in chans], w, h, rows.get("first_row", 0), rows.get("row_count"))
+    for k, d in dev.items():
+        assert np.array_equal(d.read(ctx), src[k]), "a source was written"
+    return got, want
+
+
+def words_differ(got, want):
+    if len(got) != len(want):
+        return f"{len(got)} bytes, want {len(want)}"
+    g, x = np.frombuffer(got, np.uint32), np.frombuffer(want, np.uint32)
+    bad = np.flatnonzero(g != x)
+    return f"{bad.size} of {g.size} words differ, first at word {bad[0]}: {g[bad[0]]:#x} != {x[bad[0]]:#x}" if bad.size else "equal"
+
+
+# ---- the GPU tier -------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["1x1", "3x2", "67x5", "161x75"])
+def test_pack_equals_the_numpy_restatement(name, pkg, ctx):
+    """Bit for bit: NaNs with payloads, infinities, -0.0 and subnormals pass through unmapped channels; mapped channels take -1, 0, map_count - 1, map_count, 2.5,
+    NaN, 16 777 216 against a 65 536-entry map, -0.0, a subnormal, 2^32 and the infinities."""
+    case = pack_case(name)
+    got, want = run_pack(pkg, ctx, case)
+    assert len(want) == case[1] * (8 + 4 * len(case[3]) * case[0])
+    if name == "161x75":          # the restatement itself: the edge ids of the first mapped channel (channel 0, row 0), one by one
+        big = case[4]["big"]
+        row0 = np.frombuffer(want, np.uint32)[2:2 + 16]
+        assert row0.tolist() == [0, big[0], big[65535], 0, 0, 0, 0, big[0], 0, 0, 0, 0, 0, 0, 0, 0]
+    assert got == want, words_differ(got, want)
+    assert ctx.pack_time_ms() > 0.0
+
+
+@pytest.mark.gpu
+def test_row_chunks_concatenate(pkg, ctx):
+    case = pack_case("67x5")
+    w, h = case[0], case[1]
+    whole, want = run_pack(pkg, ctx, case)
+    assert whole == want
+    parts = [run_pack(pkg, ctx, case, first_row=f, row_count=n) for f, n in ((0, 1), (1, h - 2), (h - 1, 1))]
+    for got, want_part in parts:
+        assert got == want_part, words_differ(got, want_part)
+    assert b"".join(p[0] for p in parts) == whole
+    # row_count == 0: CRH_OK, nothing written
+    dev = DeviceWords(pkg, case[2]["s3"])
+    ch = pkg.abi.PackChannel(dev.ptr, 3, 0, None, 0, 0)
+    out = np.full(64, 0xA5A5A5A5, np.uint32)
+    for first in (0, 2, h):
+        assert ctx.L.crh_pack_scanlines(ctx.h, C.byref(ch), 1, w, h, first, 0, out.ctypes.data) == pkg.abi.OK
+    assert (out == 0xA5A5A5A5).all()
+    assert ctx.pack_scanlines([(dev.ptr, 3, 0)], w, h, first_row=h, row_count=0) == b""
+
+
+@pytest.mark.gpu
+def test_refused_arguments_leave_everything_untouched(pkg, ctx, golden_blob, manifest):
+    """CRH_ERR_INVALID for every refused argument; the output is not written, a valid call behind them works, the frame, the guides and the ids are as they were,
+    and so are crh_counters and crh_last_kernel_name."""
+    abi = pkg.abi
+    w, h = 40, 25
+    ctx.upload(pkg.api.Scene(golden_blob("glowmetal")))
+    fb, aov, ids = ctx.framebuffer(w, h), ctx.aov_buffer(w, h), ctx.ids_buffer(w, h)
+    ctx.reset_counters()
+    ctx.render_region(fb, w, h, 2, 3)
+    ctx.render_aov(aov, w, h, 2)
+    ctx.render_ids(ids, None, w, h, 2)
+    before = ctx.download(fb, w, h), ctx.download_aov(aov, w, h), ctx.download_ids(ids, w, h)
+    counters, kernel = ctx.counters(), ctx.L.crh_last_kernel_name(ctx.h)
+    assert before[0].any() and counters["rays"] > 0 and kernel
+    m = np.arange(7, dtype=np.uint32)
+    out = np.full(h * (2 + 2 * w), 0xA5A5A5A5, np.uint32)
+    good = [(fb.value, 3, 1, None, 0), (aov.value, 8, 7, m.ctypes.data, 7)]
+
+    def call(chans, count=None, width=w, height=h, first=0, rows=h, handle=ctx.h, dst=out.ctypes.data, null_list=False):
+        arr = (abi.PackChannel * 66)()
+        for k, c in zip(arr, chans):
+            k.dev_src, k.stride, k.component, k.map_host, k.map_count = c
+        return ctx.L.crh_pack_scanlines(handle, None if null_list else arr, len(chans) if count is None else count, width, height, first, rows, dst)
+    refused = {
+        "NULL context": dict(handle=None), "NULL list": dict(null_list=True), "NULL output": dict(dst=None),
+        "NULL source": dict(chans=[good[0], (None, 3, 0, None, 0)]),
+        "no channels": dict(count=0), "65 channels": dict(chans=[good[0]] * 65),
+        "width 0": dict(width=0), "height 0": dict(height=0), "width < 0": dict(width=-w), "height < 0": dict(height=-h),
+        "first_row < 0": dict(first=-1, rows=1), "row_count < 0": dict(rows=-1), "rows past the image": dict(first=1, rows=h), "first_row == height": dict(first=h, rows=1),
+        "component == stride": dict(chans=[(fb.value, 3, 3, None, 0)]), "stride 0": dict(chans=[(fb.value, 0, 0, None, 0)]), "stride 65": dict(chans=[(fb.value, 65, 0, None, 0)]),
+        "map_count 65537": dict(chans=[good[0], (aov.value, 8, 7, m.ctypes.data, 65537)]), "a map with count 0": dict(chans=[(aov.value, 8, 7, m.ctypes.data, 0)]),
+    }
+    for what, kw in refused.items():
+        kw.setdefault("chans", good)
+        assert call(**kw) == abi.ERR_INVALID, what
+        assert b"crh_pack_scanlines" in ctx.L.crh_last_error(), what
+        assert (out == 0xA5A5A5A5).all(), what
+    assert call(good) == abi.OK
+    want = pack_expected([(before[0].view(np.uint32), 3, 1, None), (before[1].view(np.uint32), 8, 7, m)], w, h)
+    assert out.tobytes() == want, words_differ(out.tobytes(), want)
+    after = ctx.download(fb, w, h), ctx.download_aov(aov, w, h), ctx.download_ids(ids, w, h)
+    for a, b in zip(before, after):
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    assert ctx.counters() == counters and ctx.L.crh_last_kernel_name(ctx.h) == kernel
+
+
+def matte_from_file(f, layer, name_id):
+    """The coverage where a Crypto id channel of the layer holds the id, else 0."""
+    out = np.zeros((f["height"], f["width"]), np.float32)
+    for idn, covn in crypto_names(layer):
+        out += np.where(f["planes"][idn] == np.uint32(name_id), f["planes"][covn].view(np.float32), np.float32(0.0))
+    return out
+
+
+def check_crypto_layer(pkg, f, layer, ranked, names):
+    """The id channels hold the names' converted hashes (0.0f where the rank is empty), the coverage channels the ranked coverages; the manifest inverts."""
+    exr = pkg.exr
+    manifest = json.loads(attr_string(f, f"cryptomatte/{exr.layer_key(layer)}/manifest"))
+    assert list(manifest) == list(names), "keys in id order"
+    assert [int(v, 16) for v in manifest.values()] == [exr.crypto_id(s) for s in names] and all(re.fullmatch(r"[0-9a-f]{8}", v) for v in manifest.values())
+    index = {int(v, 16): i for i, v in enumerate(manifest.values())}
+    assert len(index) == len(names), "the manifest inverts to the indices"
+    assert attr_string(f, f"cryptomatte/{exr.layer_key(layer)}/name") == layer
+    assert attr_string(f, f"cryptomatte/{exr.layer_key(layer)}/hash") == "MurmurHash3_32"
+    assert attr_string(f, f"cryptomatte/{exr.layer_key(layer)}/conversion") == "uint32_to_float32"
+    table = np.array([exr.crypto_id(s) for s in names], np.uint32)
+    for r, (idn, covn) in enumerate(crypto_names(layer)):
+        ids = ranked[..., r, 0]
+        empty = ids < 0
+        assert (ids[~empty] < len(names)).all()
+        want = np.where(empty, np.uint32(0), table[np.where(empty, 0, ids).astype(np.int64)])
+        assert np.array_equal(f["planes"][idn], want), idn
+        assert np.array_equal(f["planes"][covn], ranked[..., r, 1].view(np.uint32)), covn
+        back = np.array([index[int(v)] for v in f["planes"][idn][~empty]], np.float32)
+        assert np.array_equal(back, ids[~empty]), "the file's ids invert to the indices through the manifest"
+
+
+@pytest.mark.gpu
+def test_rendered_layers_file(pkg, ctx, golden_blob, tmp_path):
+    """glowmetal at 160 x 100: 4 passes, guides and ids at 4 passes, one denoise. write_layers_exr writes, this file's reader reads: every layer bit for bit."""
+    w, h, n = 160, 100, 4
+    ctx.upload(pkg.api.Scene(golden_blob("glowmetal")))
+    fb, dn, aov = ctx.framebuffer(w, h), ctx.framebuffer(w, h), ctx.aov_buffer(w, h)
+    bi, bm = ctx.ids_buffer(w, h), ctx.ids_buffer(w, h)
+    ctx.render_region(fb, w, h, n, 4)
+    ctx.render_aov(aov, w, h, n)
+    ctx.render_ids(bi, bm, w, h, n)
+    ctx.denoise(fb, aov, w, h, out=dn, iterations=2)
+    path = str(tmp_path / "layers.exr")
+    names = ctx.write_layers_exr(path, w, h, fb, aov=aov, denoised=dn, instance_ids=bi, material_ids=bm, chunk_rows=37)
+    data = open(path, "rb").read()
+    f = read_exr(data)
+    check_structure(f, data)
+    assert f["names"] == names == sorted(ALL_38, key=lambda s: s.encode()) and (f["width"], f["height"]) == (w, h)
+    frame, guides, denoised = ctx.download(fb, w, h), ctx.download_aov(aov, w, h), ctx.download(dn, w, h)
+    assert frame.any() and (frame.view(np.uint32) != denoised.view(np.uint32)).any() and guides[..., 7].any()
+    for k, c in enumerate("RGB"):
+        assert np.array_equal(f["planes"][c], frame[..., k].view(np.uint32)), c
+        assert np.array_equal(f["planes"]["denoised." + c], denoised[..., k].view(np.uint32)), "denoised." + c
+    for k, c in enumerate(GUIDES):
+        assert np.array_equal(f["planes"][c], guides[..., k].view(np.uint32)), c
+    words_i, words_m = ctx.download_ids(bi, w, h), ctx.download_ids(bm, w, h)
+    for layer, words, stem in (("CryptoObject", words_i, "instance"), ("CryptoMaterial", words_m, "material")):
+        ranked = resolve_expected(words)          # (held bit for bit to crh_ids_resolve by tests/test_idmatte.py)
+        top = int(words[..., 0:6][words[..., 6:12] != 0].max())
+        assert top >= 1
+        check_crypto_layer(pkg, f, layer, ranked, [f"{stem}#{i}" for i in range(top + 1)])
+    # for every single instance id, the matte rebuilt from the file is crh_ids_matte's
+    present = np.unique(words_i[..., 0:6][words_i[..., 6:12] != 0])
+    assert present.size >= 2
+    out = DeviceWords(pkg, np.zeros((h, w), np.float32))
+    for i in present:
+        ctx.ids_matte(bi, w, h, [int(i)], out.ptr)
+        want = out.read(ctx)
+        got = matte_from_file(f, "CryptoObject", pkg.exr.crypto_id(f"instance#{int(i)}"))
+        assert want.any() and np.array_equal(got.view(np.uint32), want.view(np.uint32)), f"instance {int(i)}"
+    # one call and chunks of 37 rows write the same file; without the optional buffers the file holds the frame alone
+    again = str(tmp_path / "again.exr")
+    ctx.write_layers_exr(again, w, h, fb, aov=aov, denoised=dn, instance_ids=bi, material_ids=bm)
+    assert open(again, "rb").read() == data
+    assert ctx.write_layers_exr(again, w, h, fb) == ["B", "G", "R"]
+    g = read_exr(open(again, "rb").read())
+    assert g["names"] == ["B", "G", "R"] and not [a for a in g["attrs"] if a.startswith("cryptomatte")] and np.array_equal(g["planes"]["G"], f["planes"]["G"])
+
+
+# ---- the drop-in program ------------------------------------------------------------------------------------------------------------------
+def dropin_paths():
+    exe = os.path.join(REPO, "c-ray_amd", "_lib", "c-ray-hip")
+    overlay = os.path.join(REPO, "oracle", "_ref", "input")
+    return exe, overlay, os.path.exists(exe) and os.path.exists(os.path.join(overlay, "scene.json"))
+
+
+def run_dropin(manifest, out_dir, extra_env):
+    """c-ray-hip on cfg1_scene with CRAY_HIP_AOV=4 CRAY_HIP_DENOISE=2 and `extra_env`: the float dumps of the frame, the guides and the denoised frame, and every
+    file it wrote beside them."""
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    import refrun
+    exe, overlay, _ = dropin_paths()
+    m = manifest["cfg1_scene"]
+    w, h, s, b = m["width"], m["height"], m["samples"], m["bounces"]
+    os.makedirs(out_dir, exist_ok=True)
+    scene = refrun.rewrite_scene("scene.json", w, h, s, b, out_dir=str(out_dir))
+    dumps = {k: os.path.join(out_dir, k + ".f32") for k in ("frame", "aov", "denoised")}
+    env = dict(os.environ, CRH_DUMP_F32=dumps["frame"], CRH_DUMP_AOV_F32=dumps["aov"], CRH_DUMP_DENOISED_F32=dumps["denoised"], CRAY_HIP_DEVICES="1", CRAY_HIP_AOV="4",
+               CRAY_HIP_DENOISE="2")
+    for k in ("CRAY_HIP_DENOISE_VARIANCE", "CRAY_HIP_ADAPTIVE", "CRAY_HIP_EXR", "CRAY_HIP_IDS", "CRH_DENOISE_FORM", "CRH_DROPIN_PASSES"):
+        env.pop(k, None)
+    env.update(extra_env)
+    proc = subprocess.run([exe], input=json.dumps(scene).encode(), cwd=overlay, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+    text = proc.stdout.decode(errors="replace")
+    assert proc.returncode == 0, text[-2000:]
+    files = {f: open(os.path.join(out_dir, f), "rb").read() for f in sorted(os.listdir(out_dir))}
+    return files, text
+
+
+@pytest.mark.gpu
+def test_dropin_program_writes_the_layers_file(pkg, ctx, manifest, golden_blob, tmp_path):
+    """c-ray-hip on cfg1_scene with CRAY_HIP_AOV=4 CRAY_HIP_IDS=4 CRAY_HIP_DENOISE=2 CRAY_HIP_EXR=1: every file of the run without the last two variables is there
+    byte for byte, one .exr more; it parses, holds the dumped floats, and its bytes are those Context.write_layers_exr writes from the same buffers and names."""
+    from test_gpu_parity import dropin_env
+    if not dropin_paths()[2]:
+        pytest.skip("c-ray-hip or the asset overlay is not built (needs the reference's sources at build time)")
+    m = manifest["cfg1_scene"]
+    w, h, s = m["width"], m["height"], m["samples"]
+    plain, _ = run_dropin(manifest, str(tmp_path / "plain"), dropin_env())
+    files, text = run_dropin(manifest, str(tmp_path / "layers"), dict(dropin_env(), CRAY_HIP_IDS="4", CRAY_HIP_EXR="1"))
+    extra = sorted(set(files) - set(plain))
+    assert extra == ["refrun_layers_0000.exr"] and sorted(set(plain) - set(files)) == [], (sorted(files), sorted(plain))
+    assert len(plain) == 3 + 5 and "frame.f32" in plain, sorted(plain)          # three dumps; the frame, three guide images, the denoised image
+    for name, data in plain.items():
+        assert files[name] == data, f"{name} changed"
+    assert "refrun_layers_0000.exr" in text
+    data = files[extra[0]]
+    f = read_exr(data)
+    check_structure(f, data)
+    assert (f["width"], f["height"]) == (w, h) and f["names"] == sorted(ALL_38, key=lambda x: x.encode())
+    frame = np.frombuffer(files["frame.f32"], np.uint32).reshape(h, w, 3)
+    guides = np.frombuffer(files["aov.f32"], np.uint32).reshape(h, w, 8)
+    denoised = np.frombuffer(files["denoised.f32"], np.uint32).reshape(h, w, 3)
+    for k, c in enumerate("RGB"):
+        assert np.array_equal(f["planes"][c], frame[..., k]), c
+        assert np.array_equal(f["planes"]["denoised." + c], denoised[..., k]), "denoised." + c
+    for k, c in enumerate(GUIDES):
+        assert np.array_equal(f["planes"][c], guides[..., k]), c
+    inst = list(json.loads(attr_string(f, "cryptomatte/3ae39a5/manifest")))
+    mat = list(json.loads(attr_string(f, "cryptomatte/be359d6/manifest")))
+    scene = pkg.api.Scene(golden_blob("cfg1_scene"))
+    assert len(inst) == scene.desc.instance_count == 19 and len(mat) == scene.desc.material_count
+    assert all(re.fullmatch(rf".+#{i}", s) for i, s in enumerate(inst)) and any(s.startswith("sphere#") for s in inst) and any(not s.startswith("sphere#") for s in inst)
+    assert mat == [f"material#{i}" for i in range(len(mat))]
+    # the same buffers through the API: the dumps uploaded, the ids rendered (min(4, samples) passes of `samples`)
+    ctx.upload(scene)
+    bi, bm = ctx.ids_buffer(w, h), ctx.ids_buffer(w, h)
+    ctx.render_ids(bi, bm, w, h, s, pass_count=min(4, s))
+    dev = [DeviceWords(pkg, a) for a in (frame, guides, denoised)]
+    path = str(tmp_path / "api.exr")
+    ctx.write_layers_exr(path, w, h, dev[0].ptr, aov=dev[1].ptr, denoised=dev[2].ptr, instance_ids=bi, material_ids=bm, instance_names=inst, material_names=mat)
+    assert open(path, "rb").read() == data
+    for layer, buf, names in (("CryptoObject", bi, inst), ("CryptoMaterial", bm, mat)):
+        check_crypto_layer(pkg, f, layer, resolve_expected(ctx.download_ids(buf, w, h)), names)
+
+
+# ---- the CPU tier's run of the above ------------------------------------------------------------------------------------------------------
+def test_pack_kernel_on_the_emulation():
+    """CPU tier: this file's GPU tests run by a child pytest against the kernel emulation (tests/emu/libcray_hip_emu.so: k_pack_scanlines and its entry point
+    compiled unmodified on the HIP-on-CPU shim) — every one of them runs and passes there, none skipped (the drop-in test where the drop-in program is built)."""
+    from conftest import locked_make
+    # csrc/exr_pack.h is not among the prerequisites the emulation's build rule lists for its kernel object: an object older than the header is rebuilt here
+    # (-W: make takes cray_hip.hip, which includes the header and which the rule does list, as just modified)
+    csrc = os.path.join(REPO, "c-ray_amd", "csrc")
+    obj = os.path.join(EMU_DIR, "_obj", "kernel_emu.o")
+    stale = os.path.exists(obj) and os.path.getmtime(os.path.join(csrc, "exr_pack.h")) > os.path.getmtime(obj)
+    locked_make(["make", "-s", "-C", EMU_DIR] + (["-W", os.path.join(csrc, "cray_hip.hip")] if stale else []) + ["libcray_hip_emu.so"])
+    assert os.path.getmtime(os.path.join(csrc, "exr_pack.h")) <= os.path.getmtime(obj), "the emulation's kernel object is older than csrc/exr_pack.h"
+    libdir = os.path.join(EMU_DIR, "_dropin_libs")
+    dropin = dropin_paths()[2] and os.path.isdir(libdir)
+    env = dict(os.environ, CRH_LIB=os.path.join(EMU_DIR, "libcray_hip_emu.so"), CRH_ALLOW_EMULATION="1", CRH_DROPIN_LIBDIR=libdir, HIPEMU_CUS="2", HIPEMU_THREADS="3")
+    cmd = [sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider"] + ([] if dropin else ["-k", "not dropin"])
+    r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=1700)
+    tail = (r.stdout + r.stderr)[-4000:]
+    assert r.returncode == 0, tail
+    m = re.search(r"(\d+) passed", r.stdout)
+    assert m and int(m.group(1)) == (8 if dropin else 7), tail
+    assert "skipped" not in r.stdout.strip().splitlines()[-1], tail
