@@ -253,8 +253,19 @@ class Context:
         self._owned_fbs = []
         self._owned_aovs = []
         self._owned_ids = []
+        self._device, self._stream, self._zip = int(device), stream, None
+
+    def _zip_context(self):
+        """The companion library's context of write_layers_exr(compression=...): on this context's device, on the caller's stream if one was given; made on first use."""
+        if self._zip is None:
+            from . import exrzip
+            self._zip = exrzip.ZipContext(self._device, self._stream)
+        return self._zip
 
     def close(self):
+        if getattr(self, "_zip", None) is not None:
+            self._zip.close()
+            self._zip = None
         if self.h:
             for fb in self._owned_fbs:
                 self.L.crh_framebuffer_free(self.h, fb)
@@ -443,12 +454,16 @@ class Context:
         return float(ms.value)
 
     def write_layers_exr(self, path, width, height, fb, aov=None, denoised=None, instance_ids=None, material_ids=None, instance_names=None, material_names=None,
-                         chunk_rows=None):
-        """One multi-layer OpenEXR file (uncompressed, scanline, FLOAT channels) of the frame `fb` and whichever of the others is given: R G B; the guides of
+                         chunk_rows=None, compression="none"):
+        """One multi-layer OpenEXR file (scanline, FLOAT channels) of the frame `fb` and whichever of the others is given: R G B; the guides of
         an AOV buffer as albedo.R/G/B, normal.X/Y/Z, Z and A, unscaled; a denoised frame as denoised.R/G/B; the ID buffers `instance_ids` / `material_ids`
         (render_ids) as the Cryptomatte layers CryptoObject00..02 / CryptoMaterial00..02 with their metadata. instance_names[i] / material_names[i] name id i
         (default instance#<i> / material#<i>, for every id up to the largest one the buffer holds). The ranking runs into scratch of this call's own; the pixel data is
-        packed on the device, `chunk_rows` rows at a time (None: all at once)."""
+        packed on the device, `chunk_rows` rows at a time (None: all at once). compression: "none", or "zips" / "zip" — a chunk a row / every 16 rows, deflated on the
+        device by the companion library (exrzip.py: loaded on first use; `chunk_rows` is rounded up to a multiple of 16 for "zip")."""
+        from . import exrzip          # (binds the companion library on first use)
+        if compression not in exrzip.COMPRESSION:
+            raise ValueError(f"compression {compression!r}: one of {sorted(exrzip.COMPRESSION)}")
         ranked, maps, strings, scratch = [None, None], [None, None], {}, []
         try:
             for k, (ids, names, stem) in enumerate(((instance_ids, instance_names, "instance"), (material_ids, material_names, "material"))):
@@ -467,11 +482,20 @@ class Context:
                 strings.update(exr.crypto_attributes(exr.CRYPTO_LAYERS[k], names))
             chans = exr.layer_channels(fb, aov, denoised, ranked[0], ranked[1], maps[0], maps[1])
             step = height if not chunk_rows else chunk_rows
-            blocks = b"".join(self.pack_scanlines([c[1:] for c in chans], width, height, y, min(step, height - y)) for y in range(0, height, step))
+            if compression == "none":
+                blocks = b"".join(self.pack_scanlines([c[1:] for c in chans], width, height, y, min(step, height - y)) for y in range(0, height, step))
+            else:
+                kind, lines = exrzip.COMPRESSION[compression]
+                step = -(-step // lines) * lines
+                self.synchronize()          # the companion's stream may be another: its sources must be complete
+                parts = [self._zip_context().pack_zip([c[1:] for c in chans], width, height, lines, y, min(step, height - y)) for y in range(0, height, step)]
         finally:
             for p in scratch:
                 self.L.crh_ids_free(self.h, p)
-        data = exr.file_bytes(width, height, [c[0] for c in chans], blocks, strings)
+        if compression == "none":
+            data = exr.file_bytes(width, height, [c[0] for c in chans], blocks, strings)
+        else:
+            data = exr.file_bytes_chunked(width, height, [c[0] for c in chans], b"".join(p[0] for p in parts), np.concatenate([p[1] for p in parts]), strings, kind)
         with open(path, "wb") as f:
             f.write(data)
         return [c[0] for c in chans]

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""build.py — compile libcray_hip.so (the product) for gfx950 with hipcc, in-tree.
+"""build.py — compile libcray_hip.so (the product) and libcray_hip_exr.so (its companion of output codecs) for gfx950 with hipcc, in-tree.
 
     python c-ray_amd/build.py [--force]
 
@@ -16,6 +16,8 @@ and three that matter for speed (-O2 rather than -O3: +0.4..1.7 %, two rounds in
 and one for the link: -Wl,-s leaves the local symbol table out (51 KB of a library whose exported names are all in .dynsym; the kernels' own symbol tables, inside
 the code objects, are untouched) — tests/test_abi.py holds the library under 3 MiB, and the denoise kernels would have taken it 16 KB over.
 The library has no CPU path: without a HIP device every entry point returns CRH_ERR_NO_DEVICE.
+libcray_hip_exr.so (include/cray_hip_exr.h: the ZIP / ZIPS deflate of the layers file) is built behind it from a translation unit of its own, csrc/exr_zip.hip, with the
+same compiler and flags: the product library is at its size limit and needs none of it to render. It has no CPU path either.
 """
 import os
 import subprocess
@@ -26,6 +28,10 @@ REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "_lib")
 LIB = os.path.join(OUT_DIR, "libcray_hip.so")
+EXR_LIB = os.path.join(OUT_DIR, "libcray_hip_exr.so")
+EXR_SOURCES = [os.path.join(CSRC, "exr_zip.hip")]
+EXR_DEPS = EXR_SOURCES + [os.path.join(CSRC, "exr_zip.h"), os.path.join(CSRC, "ctx_buffers.h"), os.path.join(REPO, "include", "cray_hip_exr.h"),
+                          os.path.join(REPO, "include", "cray_hip.h")]
 
 SOURCES = [os.path.join(CSRC, "cray_hip.hip"), os.path.join(CSRC, "bvh_build.hip")]
 CXX_SOURCES = [os.path.join(CSRC, "scene_compile.cpp")]      # host-only C++ (g++, -ffp-contract=off: prepared triangles)
@@ -51,7 +57,26 @@ def up_to_date():
     return all(os.path.getmtime(d) <= t for d in deps())
 
 
+def build_exr(force=False, verbose=True, extra=()):
+    """libcray_hip_exr.so: one hipcc call, the product's flags."""
+    if not force and os.path.exists(EXR_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(EXR_LIB) for d in EXR_DEPS + [os.path.abspath(__file__)]):
+        return EXR_LIB
+    os.makedirs(OUT_DIR, exist_ok=True)
+    cmd = [HIPCC] + FLAGS + list(extra) + ["-x", "hip"] + EXR_SOURCES + ["-shared", "-Wl,-s", "-o", EXR_LIB + ".tmp"]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    os.replace(EXR_LIB + ".tmp", EXR_LIB)
+    return EXR_LIB
+
+
 def build(force=False, verbose=True, extra=()):
+    build_product(force, verbose, extra)
+    build_exr(force, verbose, extra)
+    return LIB
+
+
+def build_product(force=False, verbose=True, extra=()):
     if not force and up_to_date():
         return LIB
     os.makedirs(OUT_DIR, exist_ok=True)

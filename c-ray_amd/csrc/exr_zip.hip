@@ -1,0 +1,179 @@
+/*
+ * exr_zip.hip — libcray_hip_exr.so: the C-ABI of include/cray_hip_exr.h around the kernels of exr_zip.h. A translation unit of its own: it shares no state with
+ * libcray_hip.so and includes of it only what is plain HIP runtime bookkeeping (ctx_buffers.h: DevBuf, Stopwatch) and the channel descriptor (cray_hip.h).
+ */
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstring>
+#include <string>
+
+#include "cray_hip_exr.h"
+
+namespace {
+thread_local std::string g_error;
+int fail(int code, const std::string &what) { g_error = what; return code; }
+}  // namespace
+#define HIP_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(CRH_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(e_)); } while (0)
+#include "ctx_buffers.h"
+#include "exr_zip.h"
+
+struct crx_ctx {
+	int device = 0;
+	hipStream_t stream = nullptr;
+	bool ownStream = false;
+	DevBuf<uint32_t> dT, dSegOut, dMeta, dMaps;          /* T' of every chunk; the segments' outputs; segMeta + segOff + chunkInfo; the id maps of the call */
+	DevBuf<uint64_t> dPos;                               /* chunkPos */
+	DevBuf<uint8_t> dOut;                                /* the compacted result */
+	void *pinned = nullptr;
+	size_t pinnedBytes = 0;
+	Stopwatch<CRX_ZIP_PHASES> watch;
+};
+
+namespace {
+int growPinned(crx_ctx *c, size_t bytes) {
+	if (bytes <= c->pinnedBytes) return 0;
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	void *const old = c->pinned;
+	c->pinned = nullptr; c->pinnedBytes = 0;
+	if (old) HIP_TRY(hipHostFree(old));
+	HIP_TRY(hipHostMalloc(&c->pinned, bytes, hipHostMallocDefault));
+	c->pinnedBytes = bytes;
+	return 0;
+}
+}  // namespace
+
+extern "C" {
+
+const char *crx_last_error(void) { return g_error.c_str(); }
+uint32_t crx_zip_segment_bytes(void) { return CRX_SEG; }
+
+int crx_context_create(int device, void *stream, crx_ctx **out) {
+	if (!out) return fail(CRH_ERR_INVALID, "crx_context_create: out is NULL");
+	*out = nullptr;
+	int count = 0;
+	if (hipGetDeviceCount(&count) != hipSuccess || count < 1) { (void)hipGetLastError(); return fail(CRH_ERR_NO_DEVICE, "crx_context_create: no HIP device (there is no CPU path)"); }
+	if (device < 0 || device >= count) return fail(CRH_ERR_INVALID, "crx_context_create: no such device");
+	HIP_TRY(hipSetDevice(device));
+	crx_ctx *const c = new crx_ctx;
+	c->device = device;
+	if (stream) c->stream = (hipStream_t)stream;
+	else {
+		const hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+		if (e != hipSuccess) { delete c; return fail(CRH_ERR_HIP, std::string("crx_context_create: ") + hipGetErrorString(e)); }
+		c->ownStream = true;
+	}
+	*out = c;
+	return CRH_OK;
+}
+
+int crx_context_destroy(crx_ctx *c) {
+	if (!c) return CRH_OK;
+	(void)hipSetDevice(c->device);
+	(void)hipStreamSynchronize(c->stream);
+	c->dT.release(); c->dSegOut.release(); c->dMeta.release(); c->dMaps.release(); c->dPos.release(); c->dOut.release();
+	if (c->pinned) (void)hipHostFree(c->pinned);
+	c->watch.release();
+	if (c->ownStream) (void)hipStreamDestroy(c->stream);
+	delete c;
+	return CRH_OK;
+}
+
+int crx_pack_zip(crx_ctx *c, const crh_pack_channel *ch, uint32_t nch, int width, int height, int first_row, int row_count, int lines_per_chunk, void *host_out,
+                 uint64_t *chunk_bytes_host, uint64_t *total_bytes) {
+	bool ok = c && ch && host_out && chunk_bytes_host && total_bytes && nch >= 1 && nch <= CRH_PACK_MAX_CHANNELS && width > 0 && height > 0 && first_row >= 0 &&
+	          row_count >= 0 && row_count <= height - first_row && (uint64_t)nch * (uint64_t)width < (1ull << 29) - 2u && (lines_per_chunk == 1 || lines_per_chunk == 16);
+	ok = ok && first_row % lines_per_chunk == 0 && (first_row + row_count == height || (first_row + row_count) % lines_per_chunk == 0) &&
+	     4ull * nch * (uint64_t)width * (uint64_t)lines_per_chunk < (1ull << 31);
+	ZipArgs A;
+	memset(&A, 0, sizeof(A));
+	size_t mapAt[CRH_PACK_MAX_CHANNELS], mapWords = 0;          /* channels that name the same map share its copy; the first of them in the list (bit i) uploads it */
+	uint64_t first = 0;
+	for (uint32_t i = 0; ok && i < nch; ++i) {
+		const crh_pack_channel &k = ch[i];
+		ok = k.dev_src && k.stride >= 1 && k.stride <= 64 && k.component < k.stride && k.map_count <= 65536 && (!k.map_host || k.map_count);
+		A.ch[i] = ZipChan{(const uint32_t *)k.dev_src, k.map_host, k.stride, k.component, k.map_count, 0};
+		uint32_t j = 0;
+		while (j < i && (ch[j].map_host != k.map_host || ch[j].map_count != k.map_count)) ++j;
+		mapAt[i] = j < i ? mapAt[j] : mapWords;
+		if (j == i && k.map_host) { first |= 1ull << i; mapWords += k.map_count; }
+	}
+	if (!ok) return fail(CRH_ERR_INVALID, "crx_pack_zip: bad argument");
+	if (row_count == 0) { *total_bytes = 0; return CRH_OK; }
+
+	ZipGeom G;
+	G.nch = nch; G.width = (uint32_t)width; G.firstRow = (uint32_t)first_row; G.rowCount = (uint32_t)row_count; G.lpc = (uint32_t)lines_per_chunk;
+	G.nchunks = (G.rowCount + G.lpc - 1u) / G.lpc;
+	G.fullBytes = 4u * nch * G.width * G.lpc;
+	G.segsPerChunk = (G.fullBytes + CRX_SEG - 1u) / CRX_SEG;
+	const uint32_t blocksPerChunk = (G.fullBytes / 4u + 255u) / 256u;
+	const uint64_t segs = (uint64_t)G.nchunks * G.segsPerChunk, blocks = (uint64_t)G.nchunks * blocksPerChunk;
+	if (segs >= (1ull << 31) || blocks >= (1ull << 31)) return fail(CRH_ERR_NOMEM, "crx_pack_zip: too many rows for one call (pass fewer rows at a time)");
+	const size_t rawBytes = 4u * (size_t)nch * (size_t)width * (size_t)row_count, outBytes = 8u * (size_t)G.nchunks + rawBytes;
+	const size_t sizeWords = 2u * (size_t)G.nchunks + 1u;          /* chunkPos */
+
+	HIP_TRY(hipSetDevice(c->device));
+	int rc;
+	if ((rc = c->dT.grow(c->stream, (size_t)G.nchunks * (G.fullBytes / 4u)))) return rc;
+	if ((rc = c->dSegOut.grow(c->stream, (size_t)segs * (CRX_SEG_OUT / 4u)))) return rc;
+	if ((rc = c->dMeta.grow(c->stream, 5u * (size_t)segs + 4u * (size_t)G.nchunks))) return rc;
+	if ((rc = c->dMaps.grow(c->stream, mapWords ? mapWords : 1u))) return rc;
+	if ((rc = c->dPos.grow(c->stream, sizeWords))) return rc;
+	if ((rc = c->dOut.grow(c->stream, outBytes))) return rc;
+	if ((rc = growPinned(c, outBytes > sizeWords * 8u ? outBytes : sizeWords * 8u))) return rc;
+	uint32_t *const segMeta = c->dMeta.p, *const segOff = segMeta + 4u * (size_t)segs, *const chunkInfo = segOff + (size_t)segs;
+
+	for (uint32_t i = 0; i < nch; ++i) {
+		if (!A.ch[i].map) continue;
+		uint32_t *const dev = c->dMaps.p + mapAt[i];
+		if (first >> i & 1u) HIP_TRY(hipMemcpyAsync(dev, A.ch[i].map, A.ch[i].mapCount * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+		A.ch[i].map = dev;
+	}
+	if ((rc = c->watch.start(c->stream))) return rc;
+	hipLaunchKernelGGL(k_zip_transform, dim3((uint32_t)blocks), dim3(256), 0, c->stream, A, G, blocksPerChunk, c->dT.p);
+	HIP_TRY(hipGetLastError());
+	if ((rc = c->watch.mark(c->stream))) return rc;
+	hipLaunchKernelGGL(k_zip_deflate, dim3((uint32_t)segs), dim3(64), 0, c->stream, G, c->dT.p, c->dSegOut.p, segMeta);
+	HIP_TRY(hipGetLastError());
+	if ((rc = c->watch.mark(c->stream))) return rc;
+	hipLaunchKernelGGL(k_zip_scan, dim3(1), dim3(256), 0, c->stream, G, segMeta, segOff, chunkInfo, c->dPos.p);
+	HIP_TRY(hipGetLastError());
+	if ((rc = c->watch.mark(c->stream))) return rc;
+	hipLaunchKernelGGL(k_zip_emit, dim3((uint32_t)segs), dim3(256), 0, c->stream, A, G, c->dSegOut.p, segMeta, segOff, chunkInfo, c->dPos.p, c->dOut.p);
+	HIP_TRY(hipGetLastError());
+	if ((rc = c->watch.mark(c->stream))) return rc;
+	c->watch.stop();
+
+	/* the sizes first: they say how many bytes to fetch */
+	uint64_t *const sizes = (uint64_t *)c->pinned;
+	HIP_TRY(hipMemcpyAsync(sizes, c->dPos.p, sizeWords * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	const uint64_t total = sizes[2u * (size_t)G.nchunks];
+	if (total > outBytes || total < 8u * (uint64_t)G.nchunks) return fail(CRH_ERR_HIP, "crx_pack_zip: the device reported an impossible size");
+	memcpy(chunk_bytes_host, sizes + G.nchunks, G.nchunks * sizeof(uint64_t));
+	*total_bytes = total;
+	HIP_TRY(hipMemcpyAsync(c->pinned, c->dOut.p, total, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	memcpy(host_out, c->pinned, total);
+	return CRH_OK;
+}
+
+int crx_pack_zip_phases_ms(crx_ctx *c, float phases_ms[CRX_ZIP_PHASES]) {
+	if (!c || !phases_ms) return fail(CRH_ERR_INVALID, "crx_pack_zip_phases_ms: NULL argument");
+	HIP_TRY(hipSetDevice(c->device));
+	const int rc = c->watch.read();
+	if (rc) return rc;
+	for (int i = 0; i < CRX_ZIP_PHASES; ++i) phases_ms[i] = i < c->watch.laps ? c->watch.ms[i] : 0.0f;
+	return CRH_OK;
+}
+
+int crx_pack_zip_time_ms(crx_ctx *c, float *ms) {
+	float phases[CRX_ZIP_PHASES];
+	if (!ms) return fail(CRH_ERR_INVALID, "crx_pack_zip_time_ms: NULL argument");
+	const int rc = crx_pack_zip_phases_ms(c, phases);
+	if (rc) return rc;
+	*ms = c->watch.sum;
+	return CRH_OK;
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
-"""exr.py — the host side of the multi-layer OpenEXR output: an uncompressed single-part scanline file whose channels are all FLOAT, and Cryptomatte's
-naming of ids. The pixel data comes packed from the device (Context.pack_scanlines: crh_pack_scanlines, include/cray_hip.h); this module writes what
-goes around it — header, offset table — and knows which channel of which buffer carries which name. c-ray_amd/host/exr_write.c states the same in C
+"""exr.py — the host side of the multi-layer OpenEXR output: a single-part scanline file whose channels are all FLOAT — uncompressed, or ZIP / ZIPS
+compressed from chunks deflated on the device (file_bytes_chunked; Context.write_layers_exr(compression=...), exrzip.py) —, and Cryptomatte's naming of ids.
+The pixel data comes packed from the device (Context.pack_scanlines: crh_pack_scanlines, include/cray_hip.h); this module writes what goes around it — header, offset table — and knows which channel of which buffer carries which name. c-ray_amd/host/exr_write.c states the same in C
 for the drop-in program; both write the same bytes.
 
 File layout: magic 76 2f 31 01, version 02 00 00 00, attributes in ascending byte order of name (each `name\\0 type\\0 int32 size, value`), one \\0,
@@ -92,8 +92,10 @@ def _attr(name, kind, value):
     return raw + b"\0" + kind.encode() + b"\0" + struct.pack("<i", len(value)) + value
 
 
-def header(width, height, channel_names, strings=None):
-    """The bytes before the offset table. channel_names must be in ascending byte order; `strings` are further attributes of type string."""
+def header(width, height, channel_names, strings=None, compression=0):
+    """The bytes before the offset table. channel_names must be in ascending byte order; `strings` are further attributes of type string; `compression` is the
+    value of the attribute of that name: 0 none, 2 ZIPS (a chunk a row), 3 ZIP (a chunk every 16 rows)."""
+    assert compression in (0, 2, 3)
     raw = [c.encode("utf-8") for c in channel_names]
     assert raw == sorted(raw) and len(set(raw)) == len(raw), "channels must be unique and in ascending byte order of name"
     chlist = b""
@@ -102,7 +104,7 @@ def header(width, height, channel_names, strings=None):
         chlist += c + b"\0" + struct.pack("<iB3xii", 2, 0, 1, 1)          # FLOAT, pLinear 0, xSampling 1, ySampling 1
     chlist += b"\0"
     window = struct.pack("<4i", 0, 0, width - 1, height - 1)
-    attrs = {"channels": ("chlist", chlist), "compression": ("compression", b"\0"), "dataWindow": ("box2i", window), "displayWindow": ("box2i", window),
+    attrs = {"channels": ("chlist", chlist), "compression": ("compression", bytes([compression])), "dataWindow": ("box2i", window), "displayWindow": ("box2i", window),
              "lineOrder": ("lineOrder", b"\0"), "pixelAspectRatio": ("float", struct.pack("<f", 1.0)), "screenWindowCenter": ("v2f", struct.pack("<2f", 0.0, 0.0)),
              "screenWindowWidth": ("float", struct.pack("<f", 1.0))}
     for k, v in (strings or {}).items():
@@ -121,6 +123,24 @@ def file_bytes(width, height, channel_names, blocks, strings=None):
     head = header(width, height, channel_names, strings)
     first = len(head) + 8 * height
     return head + struct.pack(f"<{height}Q", *[first + block * y for y in range(height)]) + bytes(blocks)
+
+
+LINES_PER_CHUNK = {0: 1, 2: 1, 3: 16}          # by the compression attribute
+
+
+def file_bytes_chunked(width, height, channel_names, chunk_data, chunk_sizes, strings=None, compression=3):
+    """The whole file of compression 2 (ZIPS) or 3 (ZIP): `chunk_data` is the chunks back to back in row order as crx_pack_zip writes them (include/cray_hip_exr.h:
+    int32 y, int32 size, `size` bytes), `chunk_sizes` their byte counts (8 + size). The offset table has one entry per chunk; the chunks follow verbatim."""
+    assert compression in (2, 3)
+    sizes = [int(v) for v in chunk_sizes]
+    assert len(sizes) == -(-height // LINES_PER_CHUNK[compression]), "one chunk for every LINES_PER_CHUNK rows"
+    assert sum(sizes) == len(chunk_data) and all(v >= 8 for v in sizes), "the chunk sizes do not add up to the chunk data"
+    head = header(width, height, channel_names, strings, compression)
+    at, offsets = len(head) + 8 * len(sizes), []
+    for v in sizes:
+        offsets.append(at)
+        at += v
+    return head + struct.pack(f"<{len(sizes)}Q", *offsets) + bytes(chunk_data)
 
 
 def pack_host(planes, width, height):

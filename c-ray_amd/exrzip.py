@@ -1,0 +1,125 @@
+"""exrzip.py — thin ctypes binding of libcray_hip_exr.so (include/cray_hip_exr.h), the companion library of output codecs: the pixel data of a ZIP / ZIPS
+compressed scanline OpenEXR file, deflated on the device. Plumbing: the work is in c-ray_amd/csrc/exr_zip.h. The library loads on first use; there is no CPU
+fallback: `library()` raises if it has not been built, every call raises `CrhError` on a non-zero return code.
+"""
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import abi
+from .api import CrhError
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.environ.get("CRX_LIB") or os.path.join(HERE, "_lib", "libcray_hip_exr.so")    # CRX_LIB: another build (dev, the emulation tier)
+COMPRESSION = {"none": (0, 1), "zips": (2, 1), "zip": (3, 16)}          # name -> (the file's compression attribute, lines per chunk)
+
+_lib = None
+
+
+def library():
+    """Load libcray_hip_exr.so (built by c-ray_amd/build.py). Raises loudly if it is missing."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise FileNotFoundError(f"{LIB_PATH} is missing: run `python c-ray_amd/build.py` (or __graft_entry__.build()); there is no CPU fallback")
+    try:          # (as api.library(): torch's copy of the HIP runtime first, where there is one)
+        import torch  # noqa: F401
+    except Exception:
+        pass
+    L = C.CDLL(LIB_PATH)
+    if hasattr(L, "crx_emu_stats") and os.environ.get("CRH_ALLOW_EMULATION") != "1":
+        raise RuntimeError(f"{LIB_PATH} is the CPU emulation of the kernels (test infrastructure): the product has no CPU path "
+                           "(set CRH_ALLOW_EMULATION=1 only in tests / tools that mean it)")
+    ctx = C.c_void_p
+    sig = {
+        "crx_context_create": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(ctx)]),
+        "crx_context_destroy": (C.c_int, [ctx]),
+        "crx_last_error": (C.c_char_p, []),
+        "crx_pack_zip": (C.c_int, [ctx, C.POINTER(abi.PackChannel), C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+        "crx_pack_zip_time_ms": (C.c_int, [ctx, C.POINTER(C.c_float)]),
+        "crx_pack_zip_phases_ms": (C.c_int, [ctx, C.POINTER(C.c_float)]),
+        "crx_zip_segment_bytes": (C.c_uint32, []),
+    }
+    for name, (res, args) in sig.items():
+        fn = getattr(L, name)
+        fn.restype = res
+        fn.argtypes = args
+    _lib = L
+    return L
+
+
+def _check(rc, where):
+    if rc != 0:
+        raise CrhError(rc, where, (library().crx_last_error() or b"").decode(errors="replace"))
+
+
+def segment_bytes():
+    return int(library().crx_zip_segment_bytes())
+
+
+def pack_channels(channels):
+    """(the crh_pack_channel array of a list of (device pointer, stride, component[, map]), the arrays that must outlive the call)"""
+    n = len(channels)
+    arr = (abi.PackChannel * max(n, 1))()
+    keep = []
+    for k, ch in zip(arr, channels):
+        src, stride, component = ch[0], ch[1], ch[2]
+        m = ch[3] if len(ch) > 3 else None
+        k.dev_src = src.value if isinstance(src, C.c_void_p) else src
+        k.stride, k.component = stride, component
+        if m is not None:
+            m = np.ascontiguousarray(m, dtype=np.uint32)
+            same = [a for a in keep if a.shape == m.shape and np.array_equal(a, m)]          # (one array per distinct map: the library uploads each once)
+            m = same[0] if same else m
+            if not same:
+                keep.append(m)
+            k.map_host, k.map_count = m.ctypes.data, m.size
+    return arr, keep
+
+
+class ZipContext:
+    """One crx_ctx: a device, a stream (a raw hipStream_t, or None for one of the library's own) and the scratch of its calls."""
+
+    def __init__(self, device=0, stream=None):
+        self.L = library()
+        self.h = C.c_void_p()
+        _check(self.L.crx_context_create(int(device), C.c_void_p(stream) if stream else None, C.byref(self.h)), "crx_context_create")
+
+    def close(self):
+        if self.h:
+            self.L.crx_context_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def pack_zip(self, channels, width, height, lines_per_chunk, first_row=0, row_count=None):
+        """(the chunks of stored rows [first_row, first_row + row_count) as bytes — per chunk int32 y, int32 size, the data —, the uint64 array of their byte
+        counts). Channels as Context.pack_scanlines takes them; lines_per_chunk 1 (ZIPS) or 16 (ZIP). The sources must be complete."""
+        arr, keep = pack_channels(channels)
+        n = len(channels)
+        rows = height - first_row if row_count is None else row_count
+        chunks = max(-(-max(rows, 0) // max(lines_per_chunk, 1)), 0)
+        out = np.empty(8 * chunks + 4 * n * max(width, 0) * max(rows, 0), np.uint8)
+        sizes = np.zeros(max(chunks, 1), np.uint64)
+        total = C.c_uint64(0)
+        _check(self.L.crx_pack_zip(self.h, arr, n, width, height, first_row, rows, lines_per_chunk, out.ctypes.data, sizes.ctypes.data, C.byref(total)), "crx_pack_zip")
+        del keep
+        return out[:total.value].tobytes(), sizes[:chunks if total.value else 0]
+
+    def time_ms(self):
+        """Milliseconds of the most recent pack_zip's kernels, summed (waits for them)."""
+        ms = C.c_float(0.0)
+        _check(self.L.crx_pack_zip_time_ms(self.h, C.byref(ms)), "crx_pack_zip_time_ms")
+        return float(ms.value)
+
+    def phases_ms(self):
+        """Milliseconds per launch of the most recent pack_zip: gather + transform, deflate, sizes and offsets, compaction."""
+        ms = (C.c_float * 4)()
+        _check(self.L.crx_pack_zip_phases_ms(self.h, ms), "crx_pack_zip_phases_ms")
+        return [float(v) for v in ms]

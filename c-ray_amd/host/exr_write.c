@@ -1,10 +1,11 @@
 /* exr_write.c — see exr_write.h. The layout, for a reader of this file alone:
  *   magic 76 2f 31 01, version 02 00 00 00 (single part, scanline, short names);
  *   attributes in ascending byte order of name, each `name\0 type\0 int32 size, value`: channels (chlist: per channel name\0, int32 pixelType 2 = FLOAT, uint8 pLinear 0,
- *   three zero bytes, int32 xSampling 1, int32 ySampling 1; one \0 ends the list), compression (one byte 0), dataWindow and displayWindow (box2i 0, 0, W - 1, H - 1),
+ *   three zero bytes, int32 xSampling 1, int32 ySampling 1; one \0 ends the list), compression (one byte: 0, or 2 ZIPS / 3 ZIP in a chunked file), dataWindow and displayWindow (box2i 0, 0, W - 1, H - 1),
  *   lineOrder (one byte 0: increasing y, stored row 0 is y 0), pixelAspectRatio (float 1), screenWindowCenter (v2f 0, 0), screenWindowWidth (float 1), the string
  *   attributes (size = length, no terminator); one \0 ends the header;
- *   H uint64 absolute offsets; the packed blocks.
+ *   H uint64 absolute offsets; the packed blocks. A chunked file (exr_write_file_chunked): one offset per chunk of 1 (ZIPS) or 16 (ZIP) rows, the chunks as
+ *   crx_pack_zip writes them (include/cray_hip_exr.h: int32 y, int32 size, the data).
  * Little-endian throughout, written byte by byte. */
 #include "exr_write.h"
 
@@ -157,9 +158,11 @@ int exr_layer_channels(const float *fb, const float *aov, const float *denoised,
 struct attr { const char *name, *type; const void *value; size_t size; };
 static int attr_by_name(const void *a, const void *b) { return strcmp(((const struct attr *)a)->name, ((const struct attr *)b)->name); }
 
-int exr_write_file(const char *path, int width, int height, const char *const *channel_names, int channel_count, const struct exr_attr *strings, int string_count,
-                   const void *blocks) {
+/* both files: compression 0 with `height` blocks of one size (sizes NULL), or 2 / 3 with chunk_count chunks of the sizes given */
+static int write_file(const char *path, int width, int height, const char *const *channel_names, int channel_count, const struct exr_attr *strings, int string_count,
+                      int compression, const void *blocks, const uint64_t *sizes, int chunk_count) {
 	if (width <= 0 || height <= 0 || channel_count <= 0 || string_count < 0) return -1;
+	const unsigned char kind = (unsigned char)compression;
 	struct bytes chlist = {0}, window = {0}, one = {0}, zero2 = {0}, head = {0};
 	for (int c = 0; c < channel_count; ++c) {
 		const size_t len = strlen(channel_names[c]);
@@ -179,7 +182,7 @@ int exr_write_file(const char *path, int width, int height, const char *const *c
 	int rc = attrs && !chlist.failed && !window.failed && !one.failed && !zero2.failed ? 0 : -1;
 	if (!rc) {
 		attrs[0] = (struct attr){"channels", "chlist", chlist.p, chlist.n};
-		attrs[1] = (struct attr){"compression", "compression", "", 1};
+		attrs[1] = (struct attr){"compression", "compression", &kind, 1};
 		attrs[2] = (struct attr){"dataWindow", "box2i", window.p, window.n};
 		attrs[3] = (struct attr){"displayWindow", "box2i", window.p, window.n};
 		attrs[4] = (struct attr){"lineOrder", "lineOrder", "", 1};
@@ -198,16 +201,34 @@ int exr_write_file(const char *path, int width, int height, const char *const *c
 		}
 		put(&head, "", 1);
 		const uint64_t block = 8u + 4u * (uint64_t)channel_count * (uint64_t)width;
-		const uint64_t first = head.n + 8u * (uint64_t)height;
-		for (int y = 0; y < height; ++y) put_u64(&head, first + block * (uint64_t)y);
+		uint64_t at = head.n + 8u * (uint64_t)chunk_count, total = 0;
+		for (int k = 0; k < chunk_count; ++k) {
+			const uint64_t size = sizes ? sizes[k] : block;
+			if (size < 8u) rc = -1;
+			put_u64(&head, at + total);
+			total += size;
+		}
 		if (head.failed) rc = -1;
 		FILE *f = rc ? NULL : fopen(path, "wb");
 		if (!f) rc = -1;
 		else {
-			if (fwrite(head.p, 1, head.n, f) != head.n || fwrite(blocks, 1, (size_t)(block * (uint64_t)height), f) != (size_t)(block * (uint64_t)height)) rc = -1;
+			if (fwrite(head.p, 1, head.n, f) != head.n || fwrite(blocks, 1, (size_t)total, f) != (size_t)total) rc = -1;
 			if (fclose(f) != 0) rc = -1;
 		}
 	}
 	free(attrs); free(chlist.p); free(window.p); free(one.p); free(zero2.p); free(head.p);
 	return rc;
+}
+
+int exr_write_file(const char *path, int width, int height, const char *const *channel_names, int channel_count, const struct exr_attr *strings, int string_count,
+                   const void *blocks) {
+	return write_file(path, width, height, channel_names, channel_count, strings, string_count, 0, blocks, NULL, height);
+}
+
+int exr_write_file_chunked(const char *path, int width, int height, const char *const *channel_names, int channel_count, const struct exr_attr *strings,
+                           int string_count, int compression, const void *chunk_data, const uint64_t *chunk_sizes, int chunk_count) {
+	if ((compression != 2 && compression != 3) || height <= 0 || !chunk_data || !chunk_sizes) return -1;
+	const int lines = compression == 3 ? 16 : 1;
+	if (chunk_count != (height + lines - 1) / lines) return -1;
+	return write_file(path, width, height, channel_names, channel_count, strings, string_count, compression, chunk_data, chunk_sizes, chunk_count);
 }

@@ -1,5 +1,5 @@
-/* exr_write.h — the host side of the multi-layer OpenEXR output, in C for the drop-in program: an uncompressed single-part scanline file whose channels are all
- * FLOAT, and Cryptomatte's naming of ids. The pixel data comes packed from the library (crh_pack_scanlines, include/cray_hip.h); this file knows which channel of
+/* exr_write.h — the host side of the multi-layer OpenEXR output, in C for the drop-in program: a single-part scanline file whose channels are all
+ * FLOAT — uncompressed, or ZIP / ZIPS from chunks deflated on the device —, and Cryptomatte's naming of ids. The pixel data comes packed from the library (crh_pack_scanlines, include/cray_hip.h); this file knows which channel of
  * which buffer carries which name and writes what goes around the data. c-ray_amd/exr.py states the same in Python; both write the same bytes. Not part of the
  * library. */
 #pragma once
@@ -32,3 +32,9 @@ int exr_layer_channels(const float *fb, const float *aov, const float *denoised,
  * 8 + 4 * channel_count * width bytes as crh_pack_scanlines lays them out — verbatim. 0, or -1 (a name too long or out of order, out of memory, the file). */
 int exr_write_file(const char *path, int width, int height, const char *const *channel_names, int channel_count, const struct exr_attr *strings, int string_count,
                    const void *blocks);
+
+/* The same file with compression 2 (ZIPS: a chunk a row) or 3 (ZIP: a chunk every 16 rows): the offset table has chunk_count = ceil(height / 1 or 16) entries and
+ * `chunk_data` — the chunks back to back as crx_pack_zip writes them (include/cray_hip_exr.h), chunk k of chunk_sizes[k] bytes — follows verbatim. 0, or -1 (also:
+ * another compression, a chunk count that does not fit the height, a chunk of less than 8 bytes). Same bytes as exr.file_bytes_chunked. */
+int exr_write_file_chunked(const char *path, int width, int height, const char *const *channel_names, int channel_count, const struct exr_attr *strings,
+                           int string_count, int compression, const void *chunk_data, const uint64_t *chunk_sizes, int chunk_count);

@@ -77,6 +77,7 @@
 #include "utils/encoders/encoder.h"
 
 #include "cray_hip.h"
+#include "cray_hip_exr.h"
 #include "flatten.h"
 #include "exr_write.h"
 #include "share.h"
@@ -822,7 +823,8 @@ static void layerNamesFree(struct layerNames *n) {
 
 /* CRAY_HIP_EXR=1: <imgFilePath><imgFileName>_layers_<imgCount, four digits>.exr — the name the frame's own file would get for <imgFileName>_layers — holds the frame
  * `fb`, the guide buffers `aov` and the denoised frame `denoised` where CRAY_HIP_AOV / CRAY_HIP_DENOISE left them on GPU 0, and with CRAY_HIP_IDS=<n> the ranked ids of
- * min(n, sampleCount) passes of both ID buffers rendered here, as Cryptomatte layers. The channels are packed on the device (crh_pack_scanlines), at most 32 MB a call. */
+ * min(n, sampleCount) passes of both ID buffers rendered here, as Cryptomatte layers. The channels are packed on the device (crh_pack_scanlines), at most 32 MB a call;
+ * with CRAY_HIP_EXR_COMPRESSION=zip|zips beside it they are deflated there as well (crx_pack_zip of libcray_hip_exr.so) and the file is a ZIP / ZIPS one. */
 static void writeLayers(struct renderer *r, crh_ctx *ctx, const float *fb, const float *aov, const float *denoised, const struct layerNames *names, int W, int H) {
 	const char *e = getenv("CRAY_HIP_IDS");
 	int n = e ? atoi(e) : 0;
@@ -853,21 +855,47 @@ static void writeLayers(struct renderer *r, crh_ctx *ctx, const float *fb, const
 	crh_pack_channel channels[CRH_PACK_MAX_CHANNELS];
 	const char *channelNames[CRH_PACK_MAX_CHANNELS];
 	const int count = exr_layer_channels(fb, aov, denoised, ids ? ranked[0] : NULL, ids ? ranked[1] : NULL, map[0], names->instanceCount, map[1], names->materialCount, channels, channelNames);
+	/* CRAY_HIP_EXR_COMPRESSION=zip|zips: the chunks deflated on the device by the companion library (crx_pack_zip, include/cray_hip_exr.h), 16 rows or one a chunk */
+	const char *how = getenv("CRAY_HIP_EXR_COMPRESSION");
+	int kind = 0;
+	if (how && !strcmp(how, "zip")) kind = 3;
+	else if (how && !strcmp(how, "zips")) kind = 2;
+	else if (how && *how && strcmp(how, "none")) logr(warning, "c-ray-hip: CRAY_HIP_EXR_COMPRESSION=%s is not zip, zips or none; the layers file stays uncompressed\n", how);
+	const int lines = kind == 3 ? 16 : 1, chunks = (H + lines - 1) / lines;
 	const size_t block = 8u + 4u * (size_t)count * (size_t)W;
-	char *blocks = ok ? malloc(block * (size_t)H) : NULL;
+	char *blocks = ok ? malloc(kind ? 8u * (size_t)chunks + (block - 8u) * (size_t)H : block * (size_t)H) : NULL;
+	uint64_t *sizes = kind ? malloc((size_t)chunks * sizeof(*sizes)) : NULL;
 	int chunk = (int)(((size_t)32 << 20) / block);
 	if (chunk < 1) chunk = 1;
-	ok = ok && blocks;
-	for (int y = 0; ok && y < H; y += chunk)
+	chunk = (chunk + lines - 1) / lines * lines;
+	ok = ok && blocks && (!kind || sizes);
+	const char *why = NULL;
+	if (kind && ok) {
+		crx_ctx *zip = NULL;
+		size_t at = 0;
+		ok = crh_synchronize(ctx) == CRH_OK;          /* the companion's stream is its own: the sources must be complete */
+		if (ok && crx_context_create(0, NULL, &zip) != CRH_OK) { ok = false; why = crx_last_error(); }
+		for (int y = 0; ok && y < H; y += chunk) {
+			uint64_t total = 0;
+			if (crx_pack_zip(zip, channels, (uint32_t)count, W, H, y, H - y < chunk ? H - y : chunk, lines, blocks + at, sizes + y / lines, &total) != CRH_OK) { ok = false; why = crx_last_error(); }
+			at += (size_t)total;
+		}
+		if (why) logr(warning, "c-ray-hip: %s\n", why);
+		crx_context_destroy(zip);
+	}
+	for (int y = 0; !kind && ok && y < H; y += chunk)
 		ok = crh_pack_scanlines(ctx, channels, (uint32_t)count, W, H, y, H - y < chunk ? H - y : chunk, blocks + block * (size_t)y) == CRH_OK;
 	const char *base = r->prefs.imgFileName ? r->prefs.imgFileName : "rendered";
 	const char *dir = r->prefs.imgFilePath ? r->prefs.imgFilePath : "";
 	char *path = malloc(strlen(dir) + strlen(base) + 32);
 	if (ok && path) {
 		sprintf(path, "%s%s_layers_%04d.exr", dir, base, r->prefs.imgCount);
-		if (exr_write_file(path, W, H, channelNames, count, strings, stringCount, blocks) == 0) logr(info, "Layers written to %s (%i channels%s).\n", path, count, ids ? ", Cryptomatte ids" : "");
+		const int rc = kind ? exr_write_file_chunked(path, W, H, channelNames, count, strings, stringCount, kind, blocks, sizes, chunks)
+		                    : exr_write_file(path, W, H, channelNames, count, strings, stringCount, blocks);
+		if (rc == 0) logr(info, "Layers written to %s (%i channels%s).\n", path, count, ids ? ", Cryptomatte ids" : "");
 		else logr(warning, "c-ray-hip: the layers file %s could not be written\n", path);
-	} else logr(warning, "c-ray-hip: the layers file could not be made: %s\n", blocks && path ? crh_last_error() : "out of memory");
+	} else logr(warning, "c-ray-hip: the layers file could not be made: %s\n", blocks && path && (!kind || sizes) ? crh_last_error() : "out of memory");
+	free(sizes);
 	free(path); free(blocks);
 	exr_free_attrs(strings, stringCount);
 	for (int k = 0; k < 2; ++k) {

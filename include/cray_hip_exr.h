@@ -1,0 +1,68 @@
+/*
+ * cray_hip_exr.h — the C-ABI of libcray_hip_exr.so, the companion library of the output codecs: what leaves the product as a file and needs no scene, no path
+ * state and nothing of the render path. Its first and so far only codec: the pixel data of a ZIP- or ZIPS-compressed scanline OpenEXR file, deflated on the device
+ * from the buffers libcray_hip.so already makes (c-ray_amd/csrc/exr_zip.h). Plain C, int return codes: 0 (CRH_OK) is ok, the negative CRH_ERR_* values of cray_hip.h
+ * are reused, crx_last_error() holds the text of the calling thread's last failure. There is NO CPU path: without a HIP device crx_context_create answers
+ * CRH_ERR_NO_DEVICE. A context belongs to one device and one stream and is used by one thread at a time.
+ *
+ * Why a library of its own: libcray_hip.so is held under 3 MiB (tests/test_abi.py) and is full; nothing in here is needed to render.
+ */
+#ifndef CRAY_HIP_EXR_H
+#define CRAY_HIP_EXR_H
+
+#include <stdint.h>
+
+#include "cray_hip.h"          /* crh_pack_channel, CRH_PACK_MAX_CHANNELS, CRH_OK, CRH_ERR_* */
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct crx_ctx crx_ctx;
+
+/* `stream` is a raw hipStream_t (the launches and copies of every call queue behind whatever is on it) or NULL for a stream of the library's own. The scratch of
+ * the calls — transformed chunks, segment outputs, the compacted result, the id maps, pinned memory for the copy out — belongs to the context: grown on demand,
+ * freed by crx_context_destroy. CRH_ERR_INVALID: out == NULL, device < 0 or not below the device count. */
+int crx_context_create(int device, void *stream, crx_ctx **out);
+int crx_context_destroy(crx_ctx *ctx);
+const char *crx_last_error(void);
+
+/* crh_pack_scanlines' pixel data (cray_hip.h), compressed: the chunks of a scanline OpenEXR file of compression 2 (ZIPS, lines_per_chunk 1) or 3 (ZIP, 16).
+ *
+ * Channels mean exactly what they mean to crh_pack_scanlines: one component of a device buffer of 32-bit words [H, W, stride], copied bit for bit; with a map the
+ * value is an id and the word is map_host[id], 0x00000000 for -1, a fraction, a NaN, or an id at or past map_count. The maps are read before the call returns. The
+ * caller guarantees that the sources are complete (after work of another context or stream: synchronise that first).
+ *
+ * Chunks. A chunk is lines_per_chunk consecutive stored rows starting at a multiple of lines_per_chunk; the image's last chunk may be shorter. first_row must be a
+ * multiple of lines_per_chunk, first_row + row_count must be `height` or a multiple of lines_per_chunk.
+ * Raw bytes. A chunk's raw bytes R are its rows' planes exactly as crh_pack_scanlines lays them out, without the per-row 8-byte headers:
+ * n = 4 * channel_count * width * lines of them.
+ * Transform (OpenEXR's ZIP rule). T[i / 2] = R[i] for even i, T[(n + 1) / 2 + i / 2] = R[i] for odd i; then T'[0] = T[0] and T'[j] = (T[j] - T[j - 1] + 128) mod 256
+ * for j >= 1, computed on the un-predicted T.
+ * The chunk in host_out: int32 y (its first stored row), int32 size, `size` bytes of data. The data is a zlib stream of T' — header 0x78 0x01, deflate blocks any
+ * inflate accepts (fixed Huffman codes, matches within segments of the chunk), Adler-32 of T' big-endian — if that stream is shorter than n; otherwise the n raw
+ * bytes R. size == n means raw. Chunks stand back to back in row order; chunk_bytes_host[k] = 8 + size of chunk k, *total_bytes their sum. host_out must hold
+ * 8 * chunks + 4 * channel_count * width * row_count bytes, chunk_bytes_host one entry per chunk; the output is never larger.
+ * Determinism. The bytes are a function of the arguments and the sources only — not of scheduling, of the number of CUs, or of earlier calls: two calls give equal
+ * bytes, and the chunks of consecutive calls over first_row ranges concatenate to those of one call.
+ * CRH_ERR_INVALID: everything crh_pack_scanlines refuses (a NULL context, list, source or output; channel_count outside 1 .. CRH_PACK_MAX_CHANNELS; a size <= 0; rows
+ * outside the image; stride outside 1 .. 64; component >= stride; map_count > 65536; a map with count 0), lines_per_chunk not 1 or 16, misaligned rows, a NULL
+ * chunk_bytes_host or total_bytes, a chunk of 2^31 bytes or more. row_count == 0 is CRH_OK, writes nothing and sets *total_bytes to 0. A refused call writes
+ * nothing anywhere.
+ * The call launches behind whatever is queued on the context's stream, copies the sizes and then `total` bytes through the context's pinned scratch and waits. */
+int crx_pack_zip(crx_ctx *ctx, const crh_pack_channel *channels, uint32_t channel_count, int width, int height, int first_row, int row_count, int lines_per_chunk,
+                 void *host_out, uint64_t *chunk_bytes_host, uint64_t *total_bytes);
+
+/* The last complete crx_pack_zip's kernel time between the library's own events (waits for it): the sum of its launches, and per launch in phases_ms —
+ * [0] gather + transform, [1] deflate, [2] sizes and offsets, [3] compaction. 0 before the first call. */
+#define CRX_ZIP_PHASES 4
+int crx_pack_zip_time_ms(crx_ctx *ctx, float *ms);
+int crx_pack_zip_phases_ms(crx_ctx *ctx, float phases_ms[CRX_ZIP_PHASES]);
+
+/* The bytes of T' one deflate segment covers (matches do not cross segments; a chunk of at most this many bytes is one deflate block). */
+uint32_t crx_zip_segment_bytes(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -1,0 +1,138 @@
+#!/usr/bin/env python3
+"""exr_zip_rate.py — what the ZIP / ZIPS compressed layers file costs and saves on the frame of tools/exr_rate.py: the bench scene (the cfg2 blob bench.py uses) at
+1280 x 720 with all 38 channels — the frame, the guides, a denoised frame and both ranked ID buffers.
+
+    python tools/exr_zip_rate.py [--out profiles/exr_zip_rate.log]
+
+One process, behind warm-up rounds, medians of interleaved rounds of
+  zip, zips     crx_pack_zip over the whole frame in one call (lines_per_chunk 16 and 1): the kernels per phase by crx_pack_zip_phases_ms (the companion library's
+                events around its four launches), the wall time of the whole call (map upload, kernels, sizes, copy through pinned memory, copy out), and the
+                wall time of exr.file_bytes_chunked + the file's write to a temporary directory;
+  none          the wall time of Context.pack_scanlines on the same buffers and of exr.file_bytes + the file's write.
+Then, once, the yardstick: host zlib, level 1, fixed codes (Z_FIXED), per chunk on the same transformed bytes, raw where not shorter, on one thread.
+Two expectations are marked met or refuted: the compressed call + write is no slower end to end than the uncompressed one, and the device's size is within a few
+percent (5 %) of the yardstick's. Without a GPU nothing is measured and the log says so."""
+import os
+import statistics
+import sys
+import tempfile
+import time
+import zlib
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+W, H, PASSES, BOUNCES, GUIDE_PASSES, ROUNDS, WARM = 1280, 720, 16, 8, 16, 7, 2
+PHASES = ("gather + transform", "deflate", "sizes and offsets", "compaction")
+
+
+def zip_forward(raw):
+    r = np.frombuffer(raw, np.uint8)
+    t = np.concatenate([r[0::2], r[1::2]])
+    p = t.copy()
+    p[1:] = t[1:] - t[:-1] + np.uint8(128)
+    return p.tobytes()
+
+
+def measure():
+    sys.path.insert(0, REPO)
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    from __graft_entry__ import load_package
+    from denoise_rate import blob_path
+    pkg = load_package()
+    api, exr = pkg.api, pkg.exr
+    import cray_amd.exrzip as exrzip
+    ctx = api.Context(0)
+    scene = api.Scene(blob_path())
+    ctx.upload(scene)
+    fb, dn, aov = ctx.framebuffer(W, H), ctx.framebuffer(W, H), ctx.aov_buffer(W, H)
+    bi, bm, ri, rm = (ctx.ids_buffer(W, H) for _ in range(4))
+    ctx.render_region(fb, W, H, PASSES, BOUNCES)
+    ctx.render_aov(aov, W, H, PASSES, pass_count=GUIDE_PASSES)
+    ctx.render_ids(bi, bm, W, H, PASSES, pass_count=GUIDE_PASSES)
+    ctx.denoise(fb, aov, W, H, out=dn)
+    ctx.resolve_ids(bi, W, H, ri)
+    ctx.resolve_ids(bm, W, H, rm)
+    inst = [f"instance#{i}" for i in range(int(scene.desc.instance_count))]
+    mat = [f"material#{i}" for i in range(int(scene.desc.material_count))]
+    chans = exr.layer_channels(fb, aov, dn, ri, rm, exr.id_map(inst), exr.id_map(mat))
+    names = [c[0] for c in chans]
+    strings = dict(exr.crypto_attributes("CryptoObject", inst), **exr.crypto_attributes("CryptoMaterial", mat))
+    n = len(chans)
+    ctx.synchronize()
+    zctx = exrzip.ZipContext(0)
+    t = {k: {"call": [], "write": [], "phases": []} for k in ("zip", "zips", "none")}
+    size, device = {}, {}          # the files' bytes; the bytes of the device's chunks
+    with tempfile.TemporaryDirectory() as tmp:
+        for r in range(WARM + ROUNDS):
+            for kind in ("zip", "zips", "none"):
+                t0 = time.perf_counter()
+                if kind == "none":
+                    blocks = ctx.pack_scanlines([c[1:] for c in chans], W, H)
+                else:
+                    data, sizes = zctx.pack_zip([c[1:] for c in chans], W, H, exrzip.COMPRESSION[kind][1])
+                t1 = time.perf_counter()
+                whole = exr.file_bytes(W, H, names, blocks, strings) if kind == "none" else exr.file_bytes_chunked(W, H, names, data, sizes, strings, exrzip.COMPRESSION[kind][0])
+                with open(os.path.join(tmp, "layers.exr"), "wb") as f:
+                    f.write(whole)
+                t2 = time.perf_counter()
+                size[kind] = len(whole)
+                if kind != "none":
+                    device[kind] = len(data)
+                if r >= WARM:
+                    t[kind]["call"].append((t1 - t0) * 1e3)
+                    t[kind]["write"].append((t2 - t1) * 1e3)
+                    if kind != "none":
+                        t[kind]["phases"].append(zctx.phases_ms())
+    raw = np.frombuffer(blocks, np.uint8).reshape(H, 8 + 4 * n * W)[:, 8:].tobytes()
+    lines = [f"{os.path.basename(blob_path())} {W}x{H}, {n} channels, {len(raw)} raw bytes; segment {exrzip.segment_bytes()} bytes; {ROUNDS} interleaved rounds behind {WARM} warm-up "
+             f"rounds, one process, one device"]
+    med = statistics.median
+    for kind in ("zip", "zips"):
+        ph = np.median(np.array(t[kind]["phases"]), axis=0)
+        lines.append(f"{kind:5s} kernels (crx_pack_zip_phases_ms): " + ", ".join(f"{name} {v:.3f} ms" for name, v in zip(PHASES, ph)) + f"; sum {ph.sum():.3f} ms")
+    for kind in ("zip", "zips", "none"):
+        c, w = med(t[kind]["call"]), med(t[kind]["write"])
+        lines.append(f"{kind:5s} whole call (wall) median {c:9.3f} ms (min {min(t[kind]['call']):.3f}, max {max(t[kind]['call']):.3f});  file bytes + write median {w:9.3f} ms;  "
+                     f"together {c + w:9.3f} ms;  file {size[kind]} bytes = {size[kind] / size['none']:.4f} of the uncompressed file")
+    yard = {}
+    for kind in ("zip", "zips"):
+        per = 4 * n * W * exrzip.COMPRESSION[kind][1]
+        t0 = time.perf_counter()
+        got = 0
+        for at in range(0, len(raw), per):
+            chunk = raw[at:at + per]
+            c = zlib.compressobj(1, zlib.DEFLATED, 15, 8, zlib.Z_FIXED)
+            got += 8 + min(len(c.compress(zip_forward(chunk)) + c.flush()), len(chunk))
+        yard[kind] = got
+        lines.append(f"{kind:5s} yardstick (host zlib level 1, Z_FIXED, one thread, transform included): {got} bytes of chunks in {(time.perf_counter() - t0) * 1e3:.0f} ms; "
+                     f"the device's chunks: {device[kind]} bytes = {device[kind] / got:.4f} of the yardstick's")
+    none_ms = med(t["none"]["call"]) + med(t["none"]["write"])
+    for kind in ("zip", "zips"):
+        ms = med(t[kind]["call"]) + med(t[kind]["write"])
+        lines.append(f"expectation: the compressed output ({kind}) is no slower end to end than the uncompressed one: {ms:.1f} ms against {none_ms:.1f} ms: {'met' if ms <= none_ms else 'REFUTED'}")
+    for kind in ("zip", "zips"):
+        chunks = device[kind]
+        lines.append(f"expectation: the device's size ({kind}) is within 5 % of the yardstick's: {chunks / yard[kind]:.4f} at segment {exrzip.segment_bytes()}: "
+                     f"{'met' if chunks <= 1.05 * yard[kind] else 'REFUTED'}")
+    zctx.close()
+    ctx.close()
+    return lines
+
+
+def main():
+    args = sys.argv[1:]
+    out = args[args.index("--out") + 1] if "--out" in args else os.path.join(REPO, "profiles", "exr_zip_rate.log")
+    sys.path.insert(0, REPO)
+    from __graft_entry__ import load_package
+    gpu = load_package().api.device_count() > 0
+    lines = measure() if gpu else ["no HIP device here: nothing is measured"]
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        f.write(text)
+
+
+if __name__ == "__main__":
+    main()
