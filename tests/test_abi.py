@@ -7,7 +7,8 @@ import subprocess
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import REPO, header_values
+
 STRUCTS = {"crh_bvh_node": "BvhNode", "crh_poly": "Poly", "crh_instance": "Instance", "crh_mesh": "Mesh", "crh_sphere": "Sphere",
            "crh_material": "Material", "crh_gnode": "GNode", "crh_texture": "Texture", "crh_camera": "Camera",
            "crh_scene_desc": "SceneDesc", "crh_render_params": "RenderParams", "crh_counters": "Counters", "crh_hit": "Hit",
@@ -15,15 +16,10 @@ STRUCTS = {"crh_bvh_node": "BvhNode", "crh_poly": "Poly", "crh_instance": "Insta
 
 
 def test_struct_sizes_match_header(pkg, tmp_path):
-    src = tmp_path / "sizes.c"
-    body = "\n".join(f'printf("{c} %zu\\n", sizeof({c}));' for c in STRUCTS)
-    src.write_text('#include <stdio.h>\n#include "cray_hip.h"\nint main(void){' + body + "return 0;}\n")
-    exe = tmp_path / "sizes"
-    subprocess.check_call(["gcc", "-I" + os.path.join(REPO, "include"), str(src), "-o", str(exe)])
-    out = subprocess.check_output([str(exe)]).decode()
-    for line in out.splitlines():
-        cname, size = line.split()
-        assert C.sizeof(getattr(pkg.abi, STRUCTS[cname])) == int(size), cname
+    sizes = header_values(tmp_path, *[f"sizeof({c})" for c in STRUCTS])
+    assert len(sizes) == len(STRUCTS)
+    for cname, size in zip(STRUCTS, sizes):
+        assert C.sizeof(getattr(pkg.abi, STRUCTS[cname])) == size, cname
     assert C.sizeof(pkg.abi.Instance) == 128 and C.sizeof(pkg.abi.BvhNode) == 32 and C.sizeof(pkg.abi.Poly) == 40
 
 

@@ -2,98 +2,23 @@
 |frame - half| / sqrt(frame), `half` being the mean of the first half of the frame's passes; a tile whose error is at most the threshold stops, the others double
 their pass count, and k_adaptive_step moves their half-sample frame along.
 
-The step's arithmetic is part of the interface (include/cray_hip.h). `restatement` below is that arithmetic in NumPy float32 — the same enumeration of a tile's
+The step's arithmetic is part of the interface (include/cray_hip.h). tests/adaptive_spec.py's `restatement` is that arithmetic in NumPy float32 — the same enumeration of a tile's
 pixels, the same 256 strided partial sums, the same tree — and the GPU tier holds the kernel to it bit for bit: errors, flags and the half-sample frame afterwards.
 On a rendered scene every tile of an adaptive frame is, bit for bit, the uniform render at the pass count the tile stopped at, and its half-sample frame the
 uniform render at half of that, so crh_denoise_variance works on it with scale 1. Without the renderer: passes go where the noise is. The CPU tier runs this
 file's GPU tests on the kernel emulation (tests/emu)."""
 import ctypes as C
-import json
-import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from test_denoise import DeviceArray, assert_bit_equal, bits, f32, poisoned, synthetic
-from test_denoise_variance import dropin_paths, poisoned_half, restatement_v
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(REPO, "tests", "emu")
-EMAX = f32(2.0 ** 100)
-INF = float("inf")
-
-
-# ---- the restatement (include/cray_hip.h: crh_adaptive_step) ---------------------------------------------------------------------------------
-def guard(a):
-    return np.where(np.isfinite(a) & (a > 0), a, f32(0)).astype(f32)
-
-
-def pixel_errors(fb, half):
-    """e of every pixel, [H, W] in stored order."""
-    F, A = guard(fb), guard(half)
-    with np.errstate(all="ignore"):
-        d = (np.abs(F[..., 0] - A[..., 0]) + np.abs(F[..., 1] - A[..., 1])) + np.abs(F[..., 2] - A[..., 2])
-        s = (F[..., 0] + F[..., 1]) + F[..., 2]
-        e = d / np.sqrt(s + f32(1e-4))
-        e = np.where(e < EMAX, e, EMAX).astype(f32)
-    assert e.dtype == np.float32
-    return e
-
-
-def tile_error(e, H, tile):
-    """E of one tile: thread t adds e_k for k = t, t + 256, ... in ascending order, then the tree over the 256 partials."""
-    x0, y0, x1, y1 = tile
-    ek = e[H - y1:H - y0, x0:x1].ravel()          # stored rows H - y1 .. H - 1 - y0 ascending, x ascending within a row
-    n = ek.size
-    P = np.zeros(256, f32)
-    for first in range(0, n, 256):
-        m = min(256, n - first)
-        P[:m] = P[:m] + ek[first:first + m]
-    stride = 128
-    while stride >= 1:
-        P[:stride] = P[:stride] + P[stride:2 * stride]
-        stride //= 2
-    E = P[0] / f32(n)
-    assert E.dtype == np.float32
-    return E
-
-
-def restatement(fb, half, tiles, threshold):
-    """errors float32 [n], flags bool [n], and the half-sample frame afterwards."""
-    H = fb.shape[0]
-    e = pixel_errors(fb, half)
-    errors = np.array([tile_error(e, H, t) for t in tiles], f32)
-    flags = ~(errors <= f32(threshold))
-    after = half.copy()
-    for (x0, y0, x1, y1), go in zip(tiles, flags):
-        if go:
-            after[H - y1:H - y0, x0:x1] = fb[H - y1:H - y0, x0:x1]
-    return errors, flags, after
-
-
-def same_bits(got, want, what):
-    diff = int((bits(got) != bits(want)).sum())
-    print(f"{what}: {diff} of {want.size} floats differ")
-    assert got.shape == want.shape and diff == 0, f"{what}: {diff} floats differ"
-
-
-def grid(pkg, w, h, tw, th):
-    return pkg.tiles.quantize_image(w, h, tw, th, pkg.tiles.ORDER_NORMAL)
+from adaptive_spec import (CAP, EMAX, H2, INF, TILE, W2, api_threshold_and_frame, frames, grid, pixel_errors, restatement, run_dropin, strip_cut_rectangles, tile_lists,
+                           two_noise_levels)
+from denoise_spec import restatement_v
+from support import DeviceArray, assert_bit_equal, bits, ctx, dropin_env, dropin_paths, emulated_dropin, f32, header_values, run_gpu_tests_on_emulation, same_bits  # noqa: F401 (ctx: the fixture)
 
 
 # ---- plumbing -----------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def ctx(pkg):
-    if pkg.api.device_count() < 1:
-        pytest.fail("GPU tier needs a HIP device; libcray_hip has no CPU fallback")
-    c = pkg.api.Context(0)
-    yield c
-    c.close()
-
-
 def gpu_step(pkg, ctx, fb, half, tiles, threshold):
     """Context.adaptive_step on copies of fb and half: errors, flags, the half-sample frame afterwards; the frame must come back untouched."""
     h, w = fb.shape[:2]
@@ -104,30 +29,6 @@ def gpu_step(pkg, ctx, fb, half, tiles, threshold):
 
 
 # ---- 1. the step equals the restatement bit for bit --------------------------------------------------------------------------------------------
-def tile_lists(pkg):
-    whole = lambda w, h: [(0, 0, w, h)]
-    cut = grid(pkg, 161, 75, 64, 64)                                 # 3 x 2 tiles, ragged on the right (33 wide) and at the top (11 high: y counts from the bottom)
-    sparse = [t for i, t in enumerate(cut) if i not in (1, 3)] + [(70, 5, 99, 31)]          # two tiles left out, a rectangle inside one of the holes
-    corners = [(0, 0, 1, 1), (160, 0, 161, 1), (0, 74, 1, 75), (160, 74, 161, 75)]
-    return {"1x1": (1, 1, whole(1, 1)), "3x2": (3, 2, whole(3, 2)), "37x29": (37, 29, whole(37, 29)), "300x5": (300, 5, whole(300, 5)),
-            "161x75-64x64": (161, 75, cut), "161x75-sparse": (161, 75, sparse), "161x75-corners": (161, 75, corners)}
-
-
-_frames = {}
-
-
-def frames(w, h):
-    """The poisoned synthetic frame of a shape and a poisoned second realisation of it as the half-sample frame (made once, never modified)."""
-    if (w, h) not in _frames:
-        fb, half = poisoned(synthetic(w, h)[0]), poisoned_half(synthetic(w, h, seed=11)[0])
-        if w > 2 and h > 2:          # a pixel whose sum overflows: d and sqrt(s) are both inf, e is a NaN and takes the clamp's second branch
-            fb[1, 1, 0:2] = 3.0e38
-        for a in (fb, half):
-            a.setflags(write=False)
-        _frames[(w, h)] = (fb, half)
-    return _frames[(w, h)]
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["1x1", "3x2", "37x29", "300x5", "161x75-64x64", "161x75-sparse", "161x75-corners"])
 def test_step_equals_the_restatement_bit_for_bit(name, pkg, ctx):
@@ -170,9 +71,6 @@ def test_step_equals_the_restatement_bit_for_bit(name, pkg, ctx):
 
 
 # ---- 2. every tile of an adaptive frame is a uniform frame --------------------------------------------------------------------------------------
-W2, H2, CAP = 160, 100, 16
-
-
 @pytest.fixture(scope="module")
 def rendered(pkg, ctx, manifest, golden_blob):
     """glowmetal at 160 x 100, tiles 32 x 20, min_passes 2, cap 16 of max_passes 16: the uniform frames at 1, 2, 4, 8 and 16 passes (once each), the errors of a
@@ -259,15 +157,6 @@ def test_threshold_extremes(pkg, ctx, rendered):
 
 
 # ---- 3. it spends passes where the noise is (no renderer) ----------------------------------------------------------------------------------------
-def two_noise_levels(w, h, n, seed=7):
-    """test_denoise_variance.sampled with a relative sigma of 0.6 on the left half of the image and 0.05 on the right: the mean of n samples and of the first n / 2."""
-    clean = synthetic(w, h)[2]
-    rs = np.where(np.mgrid[0:h, 0:w][1] < w // 2, 0.6, 0.05)[..., None]
-    rng = np.random.default_rng(seed)
-    samples = [np.maximum(clean * (1 + rs * rng.standard_normal(clean.shape)), 0) for _ in range(n)]
-    return np.mean(samples, 0).astype(f32), np.mean(samples[:n // 2], 0).astype(f32)
-
-
 @pytest.mark.gpu
 def test_passes_go_where_the_noise_is(pkg, ctx):
     w, h = 128, 100
@@ -313,11 +202,8 @@ def test_entry_point_behaviour(pkg, manifest, golden_blob, tmp_path):
     if api.device_count() < 1:
         pytest.fail("GPU tier needs a HIP device; libcray_hip has no CPU fallback")
     assert abi.ABI_VERSION == 5 and L.crh_abi_version() == 5, "the entry points are additive to ABI 5"
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include "cray_hip.h"\nint main(void){printf("%zu %i\\n", sizeof(crh_adaptive_params), CRH_ABI_VERSION);return 0;}\n')
-    subprocess.check_call(["gcc", "-I" + os.path.join(REPO, "include"), str(src), "-o", str(tmp_path / "size")])
-    size, version = subprocess.check_output([str(tmp_path / "size")]).decode().split()
-    assert int(size) == C.sizeof(abi.AdaptiveParams) == 8 and int(version) == 5
+    size, version = header_values(tmp_path, "sizeof(crh_adaptive_params)", "CRH_ABI_VERSION")
+    assert size == C.sizeof(abi.AdaptiveParams) == 8 and version == 5
     p = abi.AdaptiveParams(-1, -1.0)
     L.crh_adaptive_params_default(C.byref(p))
     assert (p.min_passes, p.threshold) == (16, f32(0.05))
@@ -395,55 +281,10 @@ def test_entry_point_behaviour(pkg, manifest, golden_blob, tmp_path):
 
 
 # ---- 6. the drop-in program ------------------------------------------------------------------------------------------------------------------------
-TILE = (64, 40)          # cfg1_scene at 320 x 200: 5 x 5 tiles
-
-
-def run_dropin(manifest, out_dir, extra_env):
-    """c-ray-hip on cfg1_scene with 64 x 40 tiles and `extra_env`, its images in out_dir: the frame's floats, the image files written, the output."""
-    sys.path.insert(0, os.path.join(REPO, "tools"))
-    import refrun
-    exe, overlay, _ = dropin_paths()
-    m = manifest["cfg1_scene"]
-    w, h, s, b = m["width"], m["height"], m["samples"], m["bounces"]
-    os.makedirs(out_dir, exist_ok=True)
-    scene = refrun.rewrite_scene("scene.json", w, h, s, b, tile=TILE, out_dir=str(out_dir))
-    frame = os.path.join(out_dir, "frame.f32")
-    env = dict(os.environ, CRH_DUMP_F32=frame, CRAY_HIP_DEVICES="1")
-    for k in ("CRAY_HIP_AOV", "CRAY_HIP_DENOISE", "CRAY_HIP_DENOISE_VARIANCE", "CRAY_HIP_ADAPTIVE", "CRAY_HIP_ADAPTIVE_MIN", "CRH_DROPIN_PASSES"):
-        env.pop(k, None)
-    env.update(extra_env)
-    proc = subprocess.run([exe], input=json.dumps(scene).encode(), cwd=overlay, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    text = proc.stdout.decode(errors="replace")
-    assert proc.returncode == 0, text[-2000:]
-    files = {f: open(os.path.join(out_dir, f), "rb").read() for f in sorted(os.listdir(out_dir)) if f.endswith(".bmp")}
-    return np.fromfile(frame, dtype=np.float32).reshape(h, w, 3), files, text
-
-
-def api_threshold_and_frame(pkg, ctx, manifest, golden_blob, tiles):
-    """cfg1_scene through the API over `tiles`, min_passes 2 of its 4 samples: the median error of a measure-only step at 2 passes, and render_adaptive's frame
-    and pass counts at that threshold."""
-    m = manifest["cfg1_scene"]
-    w, h, s, b = m["width"], m["height"], m["samples"], m["bounces"]
-    assert s == 4
-    ctx.upload(pkg.api.Scene(golden_blob("cfg1_scene")))
-    fb, half = ctx.framebuffer(w, h), ctx.framebuffer(w, h)
-    ctx.render_tiles(fb, w, h, s, b, tiles, first_pass=0, pass_count=1)
-    ctx.copy_framebuffer(fb, half, w, h)
-    ctx.render_tiles(fb, w, h, s, b, tiles, first_pass=1, pass_count=1)
-    first, _ = ctx.adaptive_step(fb, half, w, h, tiles, INF)
-    threshold = float(np.median(first))
-    ctx.clear(fb, w, h)
-    ctx.clear(half, w, h)
-    passes, _ = ctx.render_adaptive(fb, half, w, h, s, b, tiles, min_passes=2, threshold=threshold)
-    assert (passes == 2).any() and (passes == 4).any()
-    return threshold, ctx.download(fb, w, h), passes
-
-
 @pytest.mark.gpu
 def test_dropin_program_renders_adaptively(pkg, ctx, manifest, golden_blob, tmp_path):
     """c-ray-hip: CRAY_HIP_ADAPTIVE=0 (every tile goes to the cap) writes the frame and the image of a run without it; a finite threshold writes the frame
     Context.render_adaptive gives over the scene's tile grid, and says where the passes went; a sample count that is not min 2^r warns and renders uniformly."""
-    from test_gpu_parity import dropin_env
     if not dropin_paths()[2]:
         pytest.skip("c-ray-hip or the asset overlay is not built (needs the reference's sources at build time)")
     m = manifest["cfg1_scene"]
@@ -477,28 +318,11 @@ def test_dropin_program_renders_adaptively(pkg, ctx, manifest, golden_blob, tmp_
         assert f"{len(tiles)} tiles" in text, text[-1500:]
 
 
-def strip_cut_rectangles(w, h, devices):
-    """What the program's GPU threads decide on when there are several: GPU g's 4-row strips (every devices-th one), cut every tileWidth columns."""
-    return [(x, y, min(x + TILE[0], w), min(y + 4, h)) for g in range(devices) for i, y in enumerate(range(0, h, 4)) if i % devices == g for x in range(0, w, TILE[0])]
-
-
 # ---- 7. the CPU tier ---------------------------------------------------------------------------------------------------------------------------------
 def test_adaptive_kernel_on_the_emulation():
     """CPU tier: this file's GPU tests run by a child pytest against the kernel emulation (tests/emu/libcray_hip_emu.so: k_adaptive_step and the two entry points
     compiled unmodified on the HIP-on-CPU shim, two emulated devices) — every one of them runs and passes there, none skipped (the drop-in tests where the drop-in
     program is built)."""
-    from conftest import locked_make
-    locked_make(["make", "-s", "-C", EMU_DIR, "libcray_hip_emu.so"])
-    libdir = os.path.join(EMU_DIR, "_dropin_libs")
-    dropin = dropin_paths()[2] and os.path.isdir(libdir)
-    env = dict(os.environ, CRH_LIB=os.path.join(EMU_DIR, "libcray_hip_emu.so"), CRH_ALLOW_EMULATION="1", CRH_DROPIN_LIBDIR=libdir, HIPEMU_CUS="2", HIPEMU_THREADS="3",
-               HIPEMU_DEVICES="2")
-    cmd = [sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-s", "-p", "no:cacheprovider"] + ([] if dropin else ["-k", "not dropin"])
-    r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=1700)
-    tail = (r.stdout + r.stderr)[-4000:]
-    assert r.returncode == 0, tail
-    m = re.search(r"(\d+) passed", r.stdout)
-    assert m and int(m.group(1)) == (13 if dropin else 12), tail
-    assert "skipped" not in r.stdout.strip().splitlines()[-1], tail
-    if dropin:
-        assert "two devices against Context.render_adaptive" in r.stdout, tail
+    out = run_gpu_tests_on_emulation(__file__, 13, passed_without_dropin=12, extra_env={"HIPEMU_DEVICES": "2"}, show_output=True)
+    if emulated_dropin():
+        assert "two devices against Context.render_adaptive" in out, out[-4000:]

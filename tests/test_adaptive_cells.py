@@ -9,20 +9,14 @@ half-sample frame the uniform render at half of that, and the whole loop is repl
 on the kernel emulation (tests/emu)."""
 import ctypes as C
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from test_adaptive import (CAP, EMAX, H2, INF, TILE, W2, frames, grid, pixel_errors, restatement, run_dropin, same_bits, strip_cut_rectangles, tile_lists,
+from adaptive_spec import (CAP, EMAX, H2, INF, TILE, W2, api_threshold_and_frame, frames, grid, pixel_errors, restatement, run_dropin, strip_cut_rectangles, tile_lists,
                            two_noise_levels)
-from test_denoise import DeviceArray, assert_bit_equal, bits, f32
-from test_denoise_variance import dropin_paths, restatement_v
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(REPO, "tests", "emu")
+from denoise_spec import restatement_v
+from support import DeviceArray, assert_bit_equal, bits, ctx, dropin_env, dropin_paths, emulated_dropin, f32, header_values, run_gpu_tests_on_emulation, same_bits  # noqa: F401 (ctx: the fixture)
 
 
 # ---- the restatement (include/cray_hip.h: crh_adaptive_step_cells) ----------------------------------------------------------------------------
@@ -115,15 +109,6 @@ def restatement_cells(fb, half, tiles, c, threshold, dilate, live=None, all_erro
 
 
 # ---- plumbing -----------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def ctx(pkg):
-    if pkg.api.device_count() < 1:
-        pytest.fail("GPU tier needs a HIP device; libcray_hip has no CPU fallback")
-    c = pkg.api.Context(0)
-    yield c
-    c.close()
-
-
 def gpu_step_cells(pkg, ctx, fb, half, tiles, c, threshold, dilate, live=None):
     """Context.adaptive_step_cells on copies of fb and half: errors, flags, the half-sample frame afterwards; the frame must come back untouched."""
     h, w = fb.shape[:2]
@@ -423,11 +408,8 @@ def test_cell_entry_point_behaviour(pkg, manifest, golden_blob, tmp_path):
     if api.device_count() < 1:
         pytest.fail("GPU tier needs a HIP device; libcray_hip has no CPU fallback")
     assert abi.ABI_VERSION == 5 and L.crh_abi_version() == 5, "the entry points are additive to ABI 5"
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include "cray_hip.h"\nint main(void){printf("%zu %i %i\\n", sizeof(crh_adaptive_cells_params), CRH_ADAPTIVE_CELLS_MAX, CRH_ABI_VERSION);return 0;}\n')
-    subprocess.check_call(["gcc", "-I" + os.path.join(REPO, "include"), str(src), "-o", str(tmp_path / "size")])
-    size, most, version = subprocess.check_output([str(tmp_path / "size")]).decode().split()
-    assert int(size) == C.sizeof(abi.AdaptiveCellsParams) == 16 and int(most) == abi.ADAPTIVE_CELLS_MAX == 1024 and int(version) == 5
+    size, most, version = header_values(tmp_path, "sizeof(crh_adaptive_cells_params)", "CRH_ADAPTIVE_CELLS_MAX", "CRH_ABI_VERSION")
+    assert size == C.sizeof(abi.AdaptiveCellsParams) == 16 and most == abi.ADAPTIVE_CELLS_MAX == 1024 and version == 5
     p = abi.AdaptiveCellsParams(-1, -1.0, -1, -1)
     L.crh_adaptive_cells_params_default(C.byref(p))
     assert (p.min_passes, p.threshold, p.cell, p.dilate) == (16, f32(0.05), 16, 1)
@@ -598,7 +580,6 @@ def test_dropin_program_renders_adaptively_by_cells(pkg, ctx, manifest, golden_b
     """c-ray-hip: CRAY_HIP_ADAPTIVE_CELL=16 beside CRAY_HIP_ADAPTIVE writes the frame Context.render_adaptive_cells gives over the scene's tile grid and counts
     cells by pass count; with the variable unset the frame and the image are those of the rectangle-granular loop byte for byte; a value that is no cell size, or a
     rectangle of more than 1024 cells, warns and decides per rectangle."""
-    from test_gpu_parity import dropin_env
     if not dropin_paths()[2]:
         pytest.skip("c-ray-hip or the asset overlay is not built (needs the reference's sources at build time)")
     m = manifest["cfg1_scene"]
@@ -619,7 +600,6 @@ def test_dropin_program_renders_adaptively_by_cells(pkg, ctx, manifest, golden_b
     share = 100.0 * float((passes == 2).sum()) / len(passes)
     assert f"2: {share:.1f} %" in line[0] and f"4: {100 - share:.1f} %" in line[0], line
     # unset: the rectangle-granular loop, byte for byte (the frame Context.render_adaptive gives, and the same image whatever CRAY_HIP_ADAPTIVE_DILATE says)
-    from test_adaptive import api_threshold_and_frame
     threshold, want, _ = api_threshold_and_frame(pkg, ctx, manifest, golden_blob, tiles)
     env = dict(base, CRAY_HIP_ADAPTIVE=repr(threshold), CRAY_HIP_ADAPTIVE_MIN="2")
     plain, plain_files, plain_text = run_dropin(manifest, str(tmp_path / "unset"), env)
@@ -648,19 +628,7 @@ def test_adaptive_cells_kernel_on_the_emulation():
     """CPU tier: this file's GPU tests run by a child pytest against the kernel emulation (tests/emu/libcray_hip_emu.so: k_adaptive_cells and the entry points
     compiled unmodified on the HIP-on-CPU shim, two emulated devices) — every one of them runs and passes there, none skipped (the drop-in test where the drop-in
     program is built)."""
-    from conftest import locked_make
-    locked_make(["make", "-s", "-C", EMU_DIR, "libcray_hip_emu.so"])
-    libdir = os.path.join(EMU_DIR, "_dropin_libs")
-    dropin = dropin_paths()[2] and os.path.isdir(libdir)
-    env = dict(os.environ, CRH_LIB=os.path.join(EMU_DIR, "libcray_hip_emu.so"), CRH_ALLOW_EMULATION="1", CRH_DROPIN_LIBDIR=libdir, HIPEMU_CUS="2", HIPEMU_THREADS="3",
-               HIPEMU_DEVICES="2")
-    cmd = [sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-s", "-p", "no:cacheprovider"] + ([] if dropin else ["-k", "not dropin"])
-    r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=1700)
-    tail = (r.stdout + r.stderr)[-4000:]
-    assert r.returncode == 0, tail
-    m = re.search(r"(\d+) passed", r.stdout)
     cases = len(CASES) + 2 + 1 + 3 + 1 + 1          # the step, the uniform-frame test with and without dilation, the extremes, the noise test at three cell sizes, ...
-    assert m and int(m.group(1)) == (cases + 1 if dropin else cases), tail
-    assert "skipped" not in r.stdout.strip().splitlines()[-1], tail
-    if dropin:
-        assert "two devices against Context.render_adaptive_cells" in r.stdout, tail
+    out = run_gpu_tests_on_emulation(__file__, cases + 1, passed_without_dropin=cases, extra_env={"HIPEMU_DEVICES": "2"}, show_output=True)
+    if emulated_dropin():
+        assert "two devices against Context.render_adaptive_cells" in out, out[-4000:]

@@ -7,62 +7,21 @@ background) and against a restatement of the albedo rule on constant graphs, the
 every surface emits white under a black sky (volumes and both samplers included), and every decomposition of a dispatch against one
 dispatch. The CPU tier runs this file's GPU tests on the kernel emulation (tests/emu: the same kernel source on a HIP shim)."""
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from conftest import resize_camera
+from firsthit_spec import first_hits, geometry_expected, ragged_tiles
+from reference_checks import check_known_answers
+from support import DeviceArray, ctx, dropin_env, dropin_paths, run_dropin, run_gpu_tests_on_emulation  # noqa: F401 (ctx: the fixture)
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(REPO, "tests", "emu")
 NONE = 0xFFFFFFFF
 # enum crh_node_kind (include/cray_hip.h)
 DIFFUSE, METAL, GLASS, PLASTIC, MIX, ADD, TRANSPARENT, EMISSION, ISOTROPIC = range(1, 10)
 COLOR_CONSTANT, VALUE_CONSTANT = 32, 64
 KIND_NAMES = {DIFFUSE: "diffuse", METAL: "metal", GLASS: "glass", PLASTIC: "plastic", MIX: "mix", ADD: "add", TRANSPARENT: "transparent",
               EMISSION: "emission", ISOTROPIC: "isotropic"}
-
-
-@pytest.fixture(scope="module")
-def ctx(pkg):
-    if pkg.api.device_count() < 1:
-        pytest.fail("GPU tier needs a HIP device; libcray_hip has no CPU fallback")
-    c = pkg.api.Context(0)
-    yield c
-    c.close()
-
-
-def fold(mean, sample, completed):
-    """renderer.c:288-291 in float32, the operations in the reference's order."""
-    n1, t = np.float32(completed - 1), np.float32(1.0) / np.float32(completed)
-    return ((mean * n1) + sample) * t
-
-
-def first_hits(oracle, oscene, w, h, passes, max_passes, region=None):
-    """oracle.camera_ray -> oracle.trace_rays for every pixel of the region and every pass: hits[pass][row, col] (stored rows run top-down)."""
-    x0, y0, x1, y1 = region or (0, 0, w, h)
-    rays = np.zeros((len(passes), y1 - y0, x1 - x0, 6), np.float32)
-    for k, p in enumerate(passes):
-        for y in range(y0, y1):
-            for x in range(x0, x1):
-                rays[k, y1 - 1 - y, x - x0] = oracle.camera_ray(oscene, x, y, p, max_passes)
-    return oracle.trace_rays(oscene, rays.reshape(-1, 6)).reshape(len(passes), y1 - y0, x1 - x0)
-
-
-def geometry_expected(hits, passes):
-    """Channels 3..7 of the samples (a miss: zeros; a hit: the record's normal and distance, coverage 1), folded in pass order."""
-    mean = np.zeros(hits.shape[1:] + (5,), np.float32)
-    for k, p in enumerate(passes):
-        hit = hits[k]["inst"] >= 0
-        s = np.zeros_like(mean)
-        s[..., 0:3] = np.where(hit[..., None], hits[k]["normal"], np.float32(0))
-        s[..., 3] = np.where(hit, hits[k]["distance"], np.float32(0))
-        s[..., 4] = hit.astype(np.float32)
-        mean = fold(mean, s, p + 1)
-    return mean
 
 
 def gpu_aov(pkg, ctx, blob, w, h, samples, resize=False, **kw):
@@ -99,7 +58,6 @@ def test_geometry_channels_equal_the_oracles_first_hits(name, w, h, passes, resi
 def test_albedo_equals_the_references_render_on_diffuse_materials(pkg, ctx, oracle, golden_blob, golden_ref):
     """nodezoo_display, 1 pass of 1: where the first hit lands on a material whose root is a diffuse bsdf and which does not emit, and the path's second ray
     reached the white background (the golden pixel is not black), the reference's pixel IS the albedo: image, checker, blackbody, combineRGB, vecToColor graphs."""
-    from test_nodes import check_known_answers
     w, h = 320, 192
     blob = golden_blob("nodezoo_display")
     oscene = oracle.OracleScene(blob)
@@ -199,37 +157,6 @@ def test_coverage_equals_the_oracles_render_of_white_emitters(name, w, h, passes
     print(f"{name} {'halton' if halton else 'random'}: {partial} partial pixels")
     assert partial >= 100
     assert np.array_equal(got.view(np.uint32), np.ascontiguousarray(want).view(np.uint32)), f"{(got != want).sum()} pixels differ"
-
-
-def ragged_tiles(w, h):
-    """Rectangles that cover the frame: columns of widths 1, 7, 13, 67, ... cut into rows of heights 3, 37, rest."""
-    tiles, x, k = [], 0, 0
-    while x < w:
-        x1 = min(w, x + (1, 7, 13, 67)[k % 4])
-        for y0, y1 in ((0, 3), (3, 40), (40, h)):
-            tiles.append((x, y0, x1, y1))
-        x, k = x1, k + 1
-    return tiles
-
-
-class DeviceArray:
-    """A caller-owned AOV buffer filled by the caller (crh_render_aov takes any device pointer): a torch tensor on the GPU; under the kernel
-    emulation, whose device memory is the host heap, a numpy array."""
-
-    def __init__(self, pkg, values):
-        self.emulated = hasattr(pkg.api.library(), "crh_emu_stats")
-        if self.emulated:
-            self.a = np.ascontiguousarray(values, np.float32).copy()
-            self.ptr = self.a.ctypes.data
-        else:
-            import torch
-            self.a = torch.from_numpy(np.ascontiguousarray(values, np.float32)).to("cuda:0")
-            torch.cuda.synchronize()
-            self.ptr = self.a.data_ptr()
-
-    def read(self, ctx):
-        ctx.synchronize()
-        return self.a.copy() if self.emulated else self.a.cpu().numpy()
 
 
 @pytest.mark.gpu
@@ -353,28 +280,15 @@ def test_entry_point_behaviour(pkg, oracle, golden_blob):
 @pytest.mark.gpu
 def test_dropin_program_writes_the_buffers(pkg, ctx, manifest, golden_blob, tmp_path):
     """c-ray-hip with CRAY_HIP_AOV=2: the dump equals Context.render_aov's two passes, three images stand beside the frame; unset, nothing more is written."""
-    import json
-    from test_gpu_parity import dropin_env
-    exe = os.path.join(REPO, "c-ray_amd", "_lib", "c-ray-hip")
-    overlay = os.path.join(REPO, "oracle", "_ref", "input")
-    if not (os.path.exists(exe) and os.path.exists(os.path.join(overlay, "scene.json"))):
-        pytest.skip("c-ray-hip or the asset overlay is not built (needs /root/reference at build time)")
-    sys.path.insert(0, os.path.join(REPO, "tools"))
-    import refrun
+    if not dropin_paths()[2]:
+        pytest.skip("c-ray-hip or the asset overlay is not built (needs the reference's sources at build time)")
     m = manifest["cfg1_scene"]
-    w, h, s, b = m["width"], m["height"], m["samples"], m["bounces"]
-    scene = refrun.rewrite_scene("scene.json", w, h, s, b, out_dir=str(tmp_path))
-    dump, frame = str(tmp_path / "aov.f32"), str(tmp_path / "frame.f32")
-    env = dict(os.environ, CRH_DUMP_F32=frame, CRAY_HIP_DEVICES="1", **dropin_env())
-    env.pop("CRAY_HIP_AOV", None)
-    proc = subprocess.run([exe], input=json.dumps(scene).encode(), cwd=overlay, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    assert proc.returncode == 0, proc.stdout.decode(errors="replace")[-2000:]
-    plain = sorted(f for f in os.listdir(tmp_path) if f.endswith(".bmp"))
+    w, h, s = m["width"], m["height"], m["samples"]
+    env = dict(dropin_env(), CRH_DUMP_F32=str(tmp_path / "frame.f32"))
+    plain = sorted(f for f in run_dropin(manifest, tmp_path, env)[0] if f.endswith(".bmp"))
     assert len(plain) == 1, plain
-    proc = subprocess.run([exe], input=json.dumps(scene).encode(), cwd=overlay, env=dict(env, CRAY_HIP_AOV="2", CRH_DUMP_AOV_F32=dump), stdout=subprocess.PIPE,
-                          stderr=subprocess.STDOUT, timeout=600)
-    assert proc.returncode == 0, proc.stdout.decode(errors="replace")[-2000:]
-    got = np.fromfile(dump, dtype=np.float32).reshape(h, w, 8)
+    dumped = run_dropin(manifest, tmp_path, dict(env, CRAY_HIP_AOV="2", CRH_DUMP_AOV_F32=str(tmp_path / "aov.f32")))[0]["aov.f32"]
+    got = np.frombuffer(dumped, np.float32).reshape(h, w, 8)
     want = gpu_aov(pkg, ctx, golden_blob("cfg1_scene"), w, h, s, pass_count=2)
     assert want[..., 7].any()
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
@@ -389,16 +303,4 @@ def test_dropin_program_writes_the_buffers(pkg, ctx, manifest, golden_blob, tmp_
 def test_aov_kernel_on_the_emulation():
     """CPU tier: this file's GPU tests run by a child pytest against the kernel emulation (tests/emu/libcray_hip_emu.so: k_aov and crh_render_aov compiled
     unmodified on the HIP-on-CPU shim) — every one of them runs and passes there, none skipped (the drop-in test where the drop-in program is built)."""
-    from conftest import locked_make
-    locked_make(["make", "-s", "-C", EMU_DIR, "libcray_hip_emu.so"])
-    dropin = os.path.exists(os.path.join(REPO, "c-ray_amd", "_lib", "c-ray-hip")) and os.path.exists(os.path.join(REPO, "oracle", "_ref", "input", "scene.json")) \
-        and os.path.isdir(os.path.join(EMU_DIR, "_dropin_libs"))
-    env = dict(os.environ, CRH_LIB=os.path.join(EMU_DIR, "libcray_hip_emu.so"), CRH_ALLOW_EMULATION="1", CRH_DROPIN_LIBDIR=os.path.join(EMU_DIR, "_dropin_libs"),
-               HIPEMU_CUS="2", HIPEMU_THREADS="3")
-    cmd = [sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider"] + ([] if dropin else ["-k", "not dropin"])
-    r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=1700)
-    tail = (r.stdout + r.stderr)[-4000:]
-    assert r.returncode == 0, tail
-    m = re.search(r"(\d+) passed", r.stdout)
-    assert m and int(m.group(1)) == (12 if dropin else 11), tail
-    assert "skipped" not in r.stdout.strip().splitlines()[-1], tail
+    run_gpu_tests_on_emulation(__file__, 12, passed_without_dropin=11)

@@ -5,7 +5,7 @@ from depth 4 on, probability = max(r, g, b), which may be 0, above 1, negative o
 
 The parameters: metal, glass and plastic-coat roughness, glass IOR and the material IOR that plastic reads, the mix factor, the emission strength, and the colour
 of diffuse, transparent and isotropic — on zeros of both signs, the smallest subnormal, negative values, values above 1, FLT_MAX, both infinities and NaN, as a
-constant (which the scene compiler folds) and as a hit-dependent operand (tests/test_node_edges.py: Leaves — the device VM evaluates it per hit).
+constant (which the scene compiler folds) and as a hit-dependent operand (tests/graph_spec.py: Leaves— the device VM evaluates it per hit).
 
   fixtures   bsdfedges_a, bsdfedges_b: rendered by the REAL reference (oracle/ref_node_patch.c: patchBsdfEdges builds the graphs with the reference's own
              constructors; tools/gen_golden.py), nodezoo's sphere grid, one bsdf with one edge parameter per sphere, 160 x 96, 4 samples, 12 bounces, white sky. Two
@@ -13,7 +13,7 @@ constant (which the scene compiler folds) and as a hit-dependent operand (tests/
              eleven material IORs, the add of depth 4, and on the four spheres left over glass roughness as a constant (smallest subnormal, 8, FLT_MAX, inf);
              b — mix factor, emission strength and the five colours on diffuse, transparent and isotropic, all in both forms. Glass roughness beyond
              those four spheres is in the synthesized scenes only. No image texture is reachable from a shown material or the background (asserted below), so the reference converts no
-             non-finite float to an integer, which is undefined C (tests/test_graph_edges.py: scope note).
+             non-finite float to an integer, which is undefined C (tests/graph_spec.py: Restatement.image asserts it).
              Not in the fixtures, because the reference's constructors cannot build them: a NaN CONSTANT (the constructors hash-cons, a NaN never compares equal
              to the candidate just inserted, newConstantValue / newConstantTexture return NULL and the render crashes) — NaN is built as 0 / 0 there, which the
              scene compiler folds into the constant; and a plastic coat's roughness, which newPlastic() fixes at black. Both are in the synthesized scenes.
@@ -32,20 +32,14 @@ CPU tier: oracle == reference and lane code == reference on the fixtures; lane c
 a cap of 25 % on the non-finite floats of any expected frame, so that a broken comparison cannot hide behind NaN == NaN; and this file's GPU tests on the kernel
 emulation. GPU tier: crh_render_region == fixture / oracle with the default kernel, CRH_KERNEL_STREAM, CRH_OPT_RENDER_SLABS literal, and the Halton sampler on the
 mixed scenes. Every scene has run on the oracle, the lane code and the kernel emulation (the CPU tier) before it goes to a GPU."""
-import os
-import re
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
+from graph_spec import base  # noqa: F401 (the module-scoped fixture: nodezoo_display's scene)
+from graph_spec import CUBE, FLT_MAX, INF, NAN, PLANE, SUB_MIN, ForLibrary, Leaves, new_scene, same_bits, scene_hits, size_of
 from scene_synth import (ADD, COLOR_COMBINERGB, COLOR_CONSTANT, COLOR_IMAGE, DIFFUSE, EMISSION, GLASS, ISOTROPIC, MATH_ADD, MATH_DIVIDE, MATH_MULTIPLY, METAL, MIX, NONE,
                          PLASTIC, TRANSPARENT, VALUE_CONSTANT, VALUE_MATH, VALUE_RAYLENGTH, VEC_VECMATH)
-from test_emu_parity import emu_render
-from test_graph_edges import base, ctx  # noqa: F401 (the module-scoped fixtures: nodezoo_display's scene, a device context)
-from test_graph_edges import CUBE, EMU_DIR, PLANE, REPO, ForLibrary, same_bits, scene_hits, size_of
-from test_node_edges import FLT_MAX, INF, NAN, SUB_MIN, Leaves, new_scene
+from support import ctx, emu_render, run_gpu_tests_on_emulation  # noqa: F401 (ctx: the fixture)
 
 F = np.float32
 W, H = size_of("spheres")          # 160 x 96
@@ -462,13 +456,4 @@ N_GPU_TESTS = len(FIXTURES) * len(MODES) + len(GROUPS) * (len(MODES) + 1)
 def test_bsdf_edges_on_the_emulation():
     """CPU tier: this file's GPU tests run by a child pytest against the kernel emulation (tests/emu/libcray_hip_emu.so: the render kernels and the scene compiler
     compiled unmodified on the HIP-on-CPU shim) — every one of them runs and passes there, none skipped. Measured on 8 CPUs: 248 s (about 290 frames at 12 bounces)."""
-    from conftest import locked_make
-    locked_make(["make", "-s", "-C", EMU_DIR, "libcray_hip_emu.so"])
-    env = dict(os.environ, CRH_LIB=os.path.join(EMU_DIR, "libcray_hip_emu.so"), CRH_ALLOW_EMULATION="1", HIPEMU_CUS="2", HIPEMU_THREADS="3")
-    cmd = [sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider"]
-    r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=1700)
-    tail = (r.stdout + r.stderr)[-4000:]
-    assert r.returncode == 0, tail
-    m = re.search(r"(\d+) passed", r.stdout)
-    assert m and int(m.group(1)) == N_GPU_TESTS, tail
-    assert "skipped" not in r.stdout.strip().splitlines()[-1], tail
+    run_gpu_tests_on_emulation(__file__, N_GPU_TESTS)

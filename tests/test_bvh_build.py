@@ -13,27 +13,10 @@ import os
 import numpy as np
 import pytest
 
-CASES = ["cfg1_scene", "alphanode", "fence", "glowmetal", "refraction", "uvsphere"]
+from reference_checks import assert_same_bvh, mesh_views
+
+CASES =["cfg1_scene", "alphanode", "fence", "glowmetal", "refraction", "uvsphere"]
 BIG = ["cfg2_hdr", "soup_1m"]        # scenes/_built (present where __graft_entry__.build() ran with the reference tree)
-
-
-def mesh_views(desc, m):
-    """(reference nodes uint32[n, 8], reference prim order int32[count], polys pointer, count) of mesh m."""
-    mesh = desc.meshes[m]
-    nodes = np.ctypeslib.as_array(C.cast(desc.nodes, C.POINTER(C.c_uint32)), shape=(int(desc.node_count), 8))
-    prims = np.ctypeslib.as_array(C.cast(desc.prim_indices, C.POINTER(C.c_int32)), shape=(int(desc.prim_index_count),))
-    polys = C.cast(desc.polys, C.c_void_p).value + 40 * mesh.poly_base
-    n, count = mesh.node_count, mesh.poly_count
-    return nodes[mesh.node_base:mesh.node_base + n], prims[mesh.prim_base:mesh.prim_base + (count if n else 0)], polys, count
-
-
-def assert_same_bvh(nodes, prims, ref_nodes, ref_prims, what):
-    assert nodes.shape == ref_nodes.shape, (what, nodes.shape, ref_nodes.shape)
-    leaf = ((ref_nodes[:, 7] >> 30) & 1) == 1
-    assert np.array_equal(((nodes[:, 7] >> 30) & 1) == 1, leaf), what
-    assert np.array_equal(nodes[:, :7], ref_nodes[:, :7]), what           # bounds (bit patterns) + first child / first prim
-    assert np.array_equal(nodes[leaf, 7] & 0x7FFFFFFF, ref_nodes[leaf, 7] & 0x7FFFFFFF), what
-    assert np.array_equal(prims, ref_prims), what
 
 
 def blob_path(name, golden_blob):

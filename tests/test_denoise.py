@@ -1,117 +1,21 @@
 """The guided à-trous denoiser (crh_denoise, c-ray_amd/csrc/denoise.h): the frame, demodulated by the first-hit albedo, filtered with the 5 x 5 B3-spline taps
 at steps 1, 2, 4, ... under normal, depth and luminance weights.
 
-The filter's arithmetic is part of the interface (include/cray_hip.h): correctly rounded float32 + - * / sqrt in a fixed order. `restatement` below is that
-arithmetic in NumPy float32, and the GPU tier holds the kernels to it bit for bit — on a synthetic scene at shapes that leave every tiling path (single pixel,
+The filter's arithmetic is part of the interface (include/cray_hip.h): correctly rounded float32 + - * / sqrt in a fixed order. tests/denoise_spec.py's
+`restatement` is that arithmetic in NumPy float32, and the GPU tier holds the kernels to it bit for bit — on a synthetic scene at shapes that leave every tiling path (single pixel,
 smaller than the footprint, ragged tiles, steps larger than the image) and on a rendered frame with its own guides. Two properties are checked without the
 restatement: nothing leaks across a normal edge, and the noise goes down by the factor a five-level wavelet filter must reach. The CPU tier runs this file's GPU
 tests on the kernel emulation (tests/emu: the same kernel source on a HIP shim)."""
 import ctypes as C
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(REPO, "tests", "emu")
-f32 = np.float32
-K = [f32(3 / 8), f32(1 / 4), f32(1 / 16)]
+from denoise_spec import poisoned, restatement, synthetic
+from support import DeviceArray, assert_bit_equal, bits, ctx, dropin_env, dropin_paths, f32, header_values, run_dropin, run_gpu_tests_on_emulation  # noqa: F401 (ctx: the fixture)
+
 DEFAULTS = dict(iterations=5, sigma_normal=1.0, sigma_depth=0.05, sigma_color=1.0)
-
-
-# ---- the restatement (include/cray_hip.h: crh_denoise) --------------------------------------------------------------------------------
-def lum(I):
-    return (f32(0.2126) * I[..., 0] + f32(0.7152) * I[..., 1]) + f32(0.0722) * I[..., 2]
-
-
-def prepare(fb, aov):
-    alb, n, d, cov = aov[..., 0:3], aov[..., 3:6], aov[..., 6], aov[..., 7]
-    a = np.maximum(alb + (f32(1) - cov)[..., None], f32(2.0 ** -8))
-    c = np.where(np.isfinite(fb) & (fb > 0), fb, f32(0))
-    I = c / a
-    nn = (n[..., 0] * n[..., 0] + n[..., 1] * n[..., 1]) + n[..., 2] * n[..., 2]
-    with np.errstate(all="ignore"):
-        nh = np.where((nn > 0)[..., None], n / np.sqrt(nn)[..., None], f32(0))
-        z = np.where(cov > 0, d / cov, f32(0))
-    Crec = np.concatenate([I, lum(I)[..., None]], -1).astype(f32)
-    Grec = np.concatenate([nh, z[..., None]], -1).astype(f32)
-    return Crec, Grec, a.astype(f32)
-
-
-def iteration(Crec, Grec, s, sn, sz, sc):
-    H, W, _ = Crec.shape
-    acc, ws = np.zeros((H, W, 3), f32), np.zeros((H, W), f32)
-    one = f32(1)
-    for dy in range(-2, 3):
-        for dx in range(-2, 3):
-            oy, ox = dy * s, dx * s
-            y0, y1, x0, x1 = max(0, -oy), min(H, H - oy), max(0, -ox), min(W, W - ox)
-            if y0 >= y1 or x0 >= x1:
-                continue
-            P, Q = np.s_[y0:y1, x0:x1], np.s_[y0 + oy:y1 + oy, x0 + ox:x1 + ox]
-            h = K[abs(dx)] * K[abs(dy)]
-            dn = Grec[P][..., 0:3] - Grec[Q][..., 0:3]
-            d2 = (dn[..., 0] * dn[..., 0] + dn[..., 1] * dn[..., 1]) + dn[..., 2] * dn[..., 2]
-            t = np.maximum(one - sn * d2, f32(0))
-            t2 = t * t
-            wn = t2 * t2
-            zp, zq = Grec[P][..., 3], Grec[Q][..., 3]
-            r = (np.abs(zp - zq) / (np.maximum(zp, zq) + f32(1e-6))) / sz
-            wz = one / (one + r * r)
-            lp, lq = Crec[P][..., 3], Crec[Q][..., 3]
-            e = (lp - lq) / (sc * ((lp + lq) + f32(1e-4)))
-            wc = one / (one + e * e)
-            w = ((h * wn) * wz) * wc
-            acc[P] = acc[P] + w[..., None] * Crec[Q][..., 0:3]
-            ws[P] = ws[P] + w
-    I = acc / ws[..., None]
-    return np.concatenate([I, lum(I)[..., None]], -1).astype(f32)
-
-
-def restatement(fb, aov, iterations=5, sigma_normal=1.0, sigma_depth=0.05, sigma_color=1.0):
-    Crec, Grec, a = prepare(fb, aov)
-    for i in range(iterations):
-        Crec = iteration(Crec, Grec, 1 << i, f32(sigma_normal), f32(sigma_depth), f32(f32(sigma_color) * f32(2.0 ** -i)))
-    out = Crec[..., 0:3] * a
-    assert out.dtype == np.float32
-    return out
-
-
-# ---- the synthetic scene ----------------------------------------------------------------------------------------------------------------
-def synthetic(W, H, seed=7):
-    """A left wall (normal (1, 0, 0), depth 4 + 0.01 row) and a right plane (normal (0, 0.6, 0.8), depth 7 + 0.02 col) under a top strip of misses; the row
-    below the strip is half covered, its albedo, normal and depth pre-multiplied by the coverage as a folded AOV is; a 5-pixel checker albedo; irradiance
-    constant per region; multiplicative Gaussian noise of relative sigma 0.2, clamped at 0. Returns noisy, aov, clean, left mask, the half-covered row."""
-    rng = np.random.default_rng(seed)
-    yy, xx = np.mgrid[0:H, 0:W]
-    top = (12 * H) // 70
-    left, bg = xx < (45 * W) // 100, yy < top
-    aov = np.zeros((H, W, 8), f32)
-    nrm = np.where(left[..., None], np.array([1, 0, 0], f32), np.array([0, 0.6, 0.8], f32)).astype(f32)
-    depth = np.where(left, f32(4) + f32(0.01) * yy, f32(7) + f32(0.02) * xx).astype(f32)
-    alb = ((0.2 + 0.6 * (((xx // 5) + (yy // 5)) % 2))[..., None] * np.array([1, 0.8, 0.6])).astype(f32)
-    cov = np.ones((H, W), f32)
-    cov[bg] = 0
-    cov[top] = 0.5
-    aov[..., 0:3], aov[..., 3:6], aov[..., 6], aov[..., 7] = alb * cov[..., None], nrm * cov[..., None], depth * cov, cov
-    irr = np.where(left[..., None], np.array([1.5, 1.2, 1.0], f32), np.array([0.3, 0.5, 0.9], f32)).astype(f32)
-    clean = (irr * (aov[..., 0:3] + (1 - cov)[..., None])).astype(f32)
-    clean[bg] = np.array([0.7, 0.8, 1.0], f32)
-    noisy = np.maximum((clean * (1 + 0.2 * rng.standard_normal((H, W, 3)))).astype(f32), f32(0))
-    return noisy, aov, clean, left, top
-
-
-def poisoned(noisy):
-    """One NaN, one +inf and one negative channel: the filter's guard maps them to 0."""
-    fb = noisy.copy()
-    H, W, _ = fb.shape
-    fb[H // 2, W // 3, 0] = np.nan
-    fb[H // 3, W // 2, 1] = np.inf
-    fb[H - 1, W - 1, 2] = -1.0
-    return fb
 
 
 _cache = {}
@@ -131,39 +35,6 @@ def case(W, H, **params):
 
 
 # ---- plumbing -----------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def ctx(pkg):
-    if pkg.api.device_count() < 1:
-        pytest.fail("GPU tier needs a HIP device; libcray_hip has no CPU fallback")
-    c = pkg.api.Context(0)
-    yield c
-    c.close()
-
-
-class DeviceArray:
-    """A caller-owned device buffer (crh_denoise takes any device pointer): a torch tensor on the GPU; under the kernel emulation, whose device memory is
-    the host heap, a numpy array."""
-
-    def __init__(self, pkg, values):
-        self.emulated = hasattr(pkg.api.library(), "crh_emu_stats")
-        if self.emulated:
-            self.a = np.ascontiguousarray(values, np.float32).copy()
-            self.ptr = self.a.ctypes.data
-        else:
-            import torch
-            self.a = torch.from_numpy(np.ascontiguousarray(values, np.float32).copy()).to("cuda:0")
-            torch.cuda.synchronize()
-            self.ptr = self.a.data_ptr()
-
-    def read(self, ctx):
-        ctx.synchronize()
-        return self.a.copy() if self.emulated else self.a.cpu().numpy()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def gpu_denoise(pkg, ctx, fb, aov, in_place=False, **params):
     """Context.denoise on copies of fb and aov: the output; out of place, the inputs must come back untouched."""
     h, w = fb.shape[:2]
@@ -178,13 +49,6 @@ def gpu_denoise(pkg, ctx, fb, aov, in_place=False, **params):
         assert np.array_equal(bits(dfb.read(ctx)), bits(fb)), "the frame was written"
     assert np.array_equal(bits(daov.read(ctx)), bits(aov)), "the guides were written"
     return out
-
-
-def assert_bit_equal(got, want, what):
-    diff = int((bits(got) != bits(want)).sum())
-    print(f"{what}: {diff} of {want.size} floats differ")
-    assert got.shape == want.shape and diff == 0, f"{what}: {diff} floats differ"
-    assert np.isfinite(got).all(), what
 
 
 # ---- 1. bit equality with the restatement ----------------------------------------------------------------------------------------------------
@@ -290,11 +154,8 @@ def test_entry_point_behaviour(pkg, manifest, golden_blob, tmp_path):
         pytest.fail("GPU tier needs a HIP device; libcray_hip has no CPU fallback")
     assert abi.ABI_VERSION == 5 and L.crh_abi_version() == 5
     # the struct as the header lays it out, and its defaults
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include "cray_hip.h"\nint main(void){printf("%zu %i\\n", sizeof(crh_denoise_params), CRH_ABI_VERSION);return 0;}\n')
-    subprocess.check_call(["gcc", "-I" + os.path.join(REPO, "include"), str(src), "-o", str(tmp_path / "size")])
-    size, version = subprocess.check_output([str(tmp_path / "size")]).decode().split()
-    assert int(size) == C.sizeof(abi.DenoiseParams) == 24 and int(version) == 5
+    size, version = header_values(tmp_path, "sizeof(crh_denoise_params)", "CRH_ABI_VERSION")
+    assert size == C.sizeof(abi.DenoiseParams) == 24 and version == 5
     p = abi.DenoiseParams(-1, -1, -1, -1.0, -1.0, -1.0)
     L.crh_denoise_params_default(C.byref(p))
     assert (p.iterations, p.sigma_normal, p.sigma_depth, p.sigma_color) == (5, 1.0, f32(0.05), 1.0)
@@ -351,34 +212,19 @@ def test_entry_point_behaviour(pkg, manifest, golden_blob, tmp_path):
 def test_dropin_program_writes_the_denoised_frame(pkg, ctx, manifest, golden_blob, tmp_path):
     """c-ray-hip with CRAY_HIP_DENOISE=3: the dump equals Context.denoise of the same frame and guides, exactly one more image stands beside the frame, and
     the frame's own image is the one of the run without the variable."""
-    import json
-    from test_gpu_parity import dropin_env
-    exe = os.path.join(REPO, "c-ray_amd", "_lib", "c-ray-hip")
-    overlay = os.path.join(REPO, "oracle", "_ref", "input")
-    if not (os.path.exists(exe) and os.path.exists(os.path.join(overlay, "scene.json"))):
+    if not dropin_paths()[2]:
         pytest.skip("c-ray-hip or the asset overlay is not built (needs the reference's sources at build time)")
-    sys.path.insert(0, os.path.join(REPO, "tools"))
-    import refrun
     m = manifest["cfg1_scene"]
-    w, h, s, b = m["width"], m["height"], m["samples"], m["bounces"]
-    scene = refrun.rewrite_scene("scene.json", w, h, s, b, out_dir=str(tmp_path))
-    dump, frame_path = str(tmp_path / "denoised.f32"), str(tmp_path / "frame.f32")
-    env = dict(os.environ, CRH_DUMP_F32=frame_path, CRAY_HIP_DEVICES="1", **dropin_env())
-    for k in ("CRAY_HIP_AOV", "CRAY_HIP_DENOISE", "CRH_DENOISE_FORM"):
-        env.pop(k, None)
-    proc = subprocess.run([exe], input=json.dumps(scene).encode(), cwd=overlay, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    assert proc.returncode == 0, proc.stdout.decode(errors="replace")[-2000:]
-    plain = sorted(f for f in os.listdir(tmp_path) if f.endswith(".bmp"))
+    w, h, s = m["width"], m["height"], m["samples"]
+    env = dict(dropin_env(), CRH_DUMP_F32=str(tmp_path / "frame.f32"))
+    plain_files, _ = run_dropin(manifest, tmp_path, env)
+    plain = sorted(f for f in plain_files if f.endswith(".bmp"))
     assert len(plain) == 1, plain
-    plain_bmp = open(tmp_path / plain[0], "rb").read()
-    plain_frame = np.fromfile(frame_path, dtype=np.float32)
-    proc = subprocess.run([exe], input=json.dumps(scene).encode(), cwd=overlay, env=dict(env, CRAY_HIP_DENOISE="3", CRH_DUMP_DENOISED_F32=dump),
-                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    assert proc.returncode == 0, proc.stdout.decode(errors="replace")[-2000:]
-    frame = np.fromfile(frame_path, dtype=np.float32)
-    assert np.array_equal(frame.view(np.uint32), plain_frame.view(np.uint32)), "the frame itself is untouched"
-    frame = frame.reshape(h, w, 3)
-    got = np.fromfile(dump, dtype=np.float32).reshape(h, w, 3)
+    plain_bmp = plain_files[plain[0]]
+    all_files, _ = run_dropin(manifest, tmp_path, dict(env, CRAY_HIP_DENOISE="3", CRH_DUMP_DENOISED_F32=str(tmp_path / "denoised.f32")))
+    assert all_files["frame.f32"] == plain_files["frame.f32"], "the frame itself is untouched"
+    frame = np.frombuffer(all_files["frame.f32"], np.float32).reshape(h, w, 3)
+    got = np.frombuffer(all_files["denoised.f32"], np.float32).reshape(h, w, 3)
     # the guides the program renders: min(16, sampleCount) passes of sampleCount
     ctx.upload(pkg.api.Scene(golden_blob("cfg1_scene")))
     buf = ctx.aov_buffer(w, h)
@@ -388,11 +234,11 @@ def test_dropin_program_writes_the_denoised_frame(pkg, ctx, manifest, golden_blo
     want = gpu_denoise(pkg, ctx, frame, aov, iterations=3)
     assert_bit_equal(got, want, "drop-in")
     assert (bits(got) != bits(frame)).any()
-    files = sorted(f for f in os.listdir(tmp_path) if f.endswith(".bmp"))
+    files = sorted(f for f in all_files if f.endswith(".bmp"))
     stem = plain[0][:-len("_0000.bmp")]
     assert files == sorted(plain + [f"{stem}_denoised_0000.bmp"]), files
-    assert open(tmp_path / plain[0], "rb").read() == plain_bmp, "the frame's image changed"
-    data = open(tmp_path / f"{stem}_denoised_0000.bmp", "rb").read()
+    assert all_files[plain[0]] == plain_bmp, "the frame's image changed"
+    data = all_files[f"{stem}_denoised_0000.bmp"]
     assert data[:2] == b"BM" and int.from_bytes(data[18:22], "little") == w and abs(int.from_bytes(data[22:26], "little", signed=True)) == h
     assert data != plain_bmp
 
@@ -401,16 +247,4 @@ def test_dropin_program_writes_the_denoised_frame(pkg, ctx, manifest, golden_blo
 def test_denoise_kernels_on_the_emulation():
     """CPU tier: this file's GPU tests run by a child pytest against the kernel emulation (tests/emu/libcray_hip_emu.so: the denoise kernels and crh_denoise
     compiled unmodified on the HIP-on-CPU shim) — every one of them runs and passes there, none skipped (the drop-in test where the drop-in program is built)."""
-    from conftest import locked_make
-    locked_make(["make", "-s", "-C", EMU_DIR, "libcray_hip_emu.so"])
-    dropin = os.path.exists(os.path.join(REPO, "c-ray_amd", "_lib", "c-ray-hip")) and os.path.exists(os.path.join(REPO, "oracle", "_ref", "input", "scene.json")) \
-        and os.path.isdir(os.path.join(EMU_DIR, "_dropin_libs"))
-    env = dict(os.environ, CRH_LIB=os.path.join(EMU_DIR, "libcray_hip_emu.so"), CRH_ALLOW_EMULATION="1", CRH_DROPIN_LIBDIR=os.path.join(EMU_DIR, "_dropin_libs"),
-               HIPEMU_CUS="2", HIPEMU_THREADS="3")
-    cmd = [sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider"] + ([] if dropin else ["-k", "not dropin"])
-    r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=1700)
-    tail = (r.stdout + r.stderr)[-4000:]
-    assert r.returncode == 0, tail
-    m = re.search(r"(\d+) passed", r.stdout)
-    assert m and int(m.group(1)) == (16 if dropin else 15), tail
-    assert "skipped" not in r.stdout.strip().splitlines()[-1], tail
+    run_gpu_tests_on_emulation(__file__, 16, passed_without_dropin=15)

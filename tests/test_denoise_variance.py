@@ -1,118 +1,20 @@
 """The variance-guided denoiser (crh_denoise_variance, c-ray_amd/csrc/denoise.h): crh_denoise's filter with the colour weight in units of each pixel's own standard
 deviation, the variance estimated from a second frame buffer that holds the mean of the first h of the frame's n passes.
 
-Like crh_denoise's, the arithmetic is part of the interface (include/cray_hip.h). `restatement_v` below is that arithmetic in NumPy float32 — prepare, lum and K are
-tests/test_denoise.py's — and the GPU tier holds the kernels to it bit for bit, on the synthetic scene and on a rendered frame whose half-sample buffer is taken with
+Like crh_denoise's, the arithmetic is part of the interface (include/cray_hip.h). tests/denoise_spec.py's `restatement_v` is that arithmetic in NumPy float32 —
+on crh_denoise's prepare, lum and K — and the GPU tier holds the kernels to it bit for bit, on the synthetic scene and on a rendered frame whose half-sample buffer is taken with
 copy_framebuffer between two dispatches. Without the restatement: nothing leaks across a normal edge; on a scene with shadow edges that neither normal nor depth
 marks — where the plain filter returns a frame worse than its input — the error falls well below the input's, and it keeps falling as samples are added. The CPU
 tier runs this file's GPU tests on the kernel emulation (tests/emu)."""
 import ctypes as C
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from test_denoise import DeviceArray, K, assert_bit_equal, bits, f32, lum, poisoned, prepare, restatement, synthetic
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(REPO, "tests", "emu")
-VMAX = f32(2.0 ** 100)
-
-
-# ---- the restatement (include/cray_hip.h: crh_denoise_variance) ------------------------------------------------------------------------
-def windows(H, W, oy, ox):
-    """The pixels p whose tap q = p + (ox, oy) is inside the image, and those taps; None when there are none."""
-    y0, y1, x0, x1 = max(0, -oy), min(H, H - oy), max(0, -ox), min(W, W - ox)
-    if y0 >= y1 or x0 >= x1:
-        return None
-    return np.s_[y0:y1, x0:x1], np.s_[y0 + oy:y1 + oy, x0 + ox:x1 + ox]
-
-
-def gw(G, P, Q, sn, sz):
-    """wn, wz as in test_denoise.iteration()"""
-    one = f32(1)
-    dn = G[P][..., 0:3] - G[Q][..., 0:3]
-    d2 = (dn[..., 0] * dn[..., 0] + dn[..., 1] * dn[..., 1]) + dn[..., 2] * dn[..., 2]
-    t = np.maximum(one - sn * d2, f32(0))
-    t2 = t * t
-    wn = t2 * t2
-    zp, zq = G[P][..., 3], G[Q][..., 3]
-    r = (np.abs(zp - zq) / (np.maximum(zp, zq) + f32(1e-6))) / sz
-    return wn, one / (one + r * r)
-
-
-def prefilter(V, G, sn, sz):
-    H, W = V.shape
-    acc, ws = np.zeros((H, W), f32), np.zeros((H, W), f32)
-    for dy in range(-2, 3):
-        for dx in range(-2, 3):
-            PQ = windows(H, W, dy, dx)
-            if PQ is None:
-                continue
-            P, Q = PQ
-            wn, wz = gw(G, P, Q, sn, sz)
-            wg = wn * wz
-            acc[P] = acc[P] + wg * V[Q]
-            ws[P] = ws[P] + wg
-    return acc / ws
-
-
-def iteration_v(I, V, G, s, sn, sz, sc):
-    H, W, _ = I.shape
-    one = f32(1)
-    L = lum(I)
-    den = sc * np.sqrt(V) + f32(1e-4)
-    acc, ws, va = np.zeros((H, W, 3), f32), np.zeros((H, W), f32), np.zeros((H, W), f32)
-    for dy in range(-2, 3):
-        for dx in range(-2, 3):
-            PQ = windows(H, W, dy * s, dx * s)
-            if PQ is None:
-                continue
-            P, Q = PQ
-            h = K[abs(dx)] * K[abs(dy)]
-            wn, wz = gw(G, P, Q, sn, sz)
-            e = (L[P] - L[Q]) / den[P]
-            wc = one / (one + e * e)
-            w = ((h * wn) * wz) * wc
-            acc[P] = acc[P] + w[..., None] * I[Q]
-            ws[P] = ws[P] + w
-            va[P] = va[P] + (w * w) * V[Q]
-    return acc / ws[..., None], va / (ws * ws)
-
-
-def restatement_v(fb, half, aov, scale, iterations=5, sigma_normal=1.0, sigma_depth=0.05, sigma_color=3.0):
-    Crec, G, a = prepare(fb, aov)
-    I = Crec[..., 0:3]
-    with np.errstate(all="ignore"):
-        Chalf, _, _ = prepare(half, aov)
-        d = Chalf[..., 3] - Crec[..., 3]
-        v = f32(scale) * (d * d)
-    V = np.where(v < VMAX, v, VMAX).astype(f32)          # NaN and inf -> 2^100
-    sn, sz, sc = f32(sigma_normal), f32(sigma_depth), f32(sigma_color)
-    if iterations:
-        V = prefilter(V, G, sn, sz)
-    for i in range(iterations):
-        I, V = iteration_v(I, V, G, 1 << i, sn, sz, sc)
-        assert I.dtype == np.float32 and V.dtype == np.float32
-    out = I * a
-    assert out.dtype == np.float32
-    return out
-
-
-# ---- inputs -------------------------------------------------------------------------------------------------------------------------------
-def poisoned_half(noisy):
-    """The half-sample frame's own NaN, inf and negative channel, away from the frame's, and one finite value whose irradiance overflows: variance 2^100."""
-    half = noisy.copy()
-    H, W, _ = half.shape
-    half[H // 4, W // 2, 1] = np.nan
-    half[(2 * H) // 3, W // 5, 2] = np.inf
-    half[0, W - 1, 0] = -2.0
-    if W > 1:          # (a single pixel has no channel left)
-        half[H - 1, 0, 1] = 3.0e38
-    return half
+import support
+from denoise_spec import poisoned, poisoned_half, restatement, restatement_v, synthetic
+from support import DROPIN_LIBDIR, DeviceArray, assert_bit_equal, bits, ctx, dropin_env, dropin_paths, emulated_dropin, f32, header_values, run_gpu_tests_on_emulation  # noqa: F401 (ctx: the fixture)
 
 
 _cache = {}
@@ -133,7 +35,7 @@ def case(W, H, half_passes, passes, **params):
 
 
 def shadowed(W, H):
-    """test_denoise.synthetic's scene under a shadow pattern that neither normal nor depth marks: diagonal stripes 20 pixels wide, every other one at a quarter of
+    """denoise_spec.synthetic's scene under a shadow pattern that neither normal nor depth marks: diagonal stripes 20 pixels wide, every other one at a quarter of
     the irradiance, over both surfaces (not over the misses). Returns the clean frame and the guides."""
     _, aov, clean, _, _ = synthetic(W, H)
     yy, xx = np.mgrid[0:H, 0:W]
@@ -153,15 +55,6 @@ def rmse(a, b):
 
 
 # ---- plumbing -----------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def ctx(pkg):
-    if pkg.api.device_count() < 1:
-        pytest.fail("GPU tier needs a HIP device; libcray_hip has no CPU fallback")
-    c = pkg.api.Context(0)
-    yield c
-    c.close()
-
-
 def gpu_denoise_v(pkg, ctx, fb, half, aov, half_passes, passes, in_place=False, **params):
     """Context.denoise_variance on copies of fb, half and aov: the output; the half-sample frame and the guides, and out of place the frame, come back untouched."""
     h, w = fb.shape[:2]
@@ -294,12 +187,8 @@ def test_entry_point_behaviour(pkg, tmp_path):
     if api.device_count() < 1:
         pytest.fail("GPU tier needs a HIP device; libcray_hip has no CPU fallback")
     assert abi.ABI_VERSION == 5 and L.crh_abi_version() == 5, "the entry points are additive to ABI 5"
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include "cray_hip.h"\nint main(void){printf("%zu %zu %i\\n", sizeof(crh_denoise_variance_params), sizeof(crh_denoise_params), '
-                   'CRH_ABI_VERSION);return 0;}\n')
-    subprocess.check_call(["gcc", "-I" + os.path.join(REPO, "include"), str(src), "-o", str(tmp_path / "size")])
-    size, plain_size, version = subprocess.check_output([str(tmp_path / "size")]).decode().split()
-    assert int(size) == C.sizeof(abi.DenoiseVarianceParams) == 28 and int(plain_size) == C.sizeof(abi.DenoiseParams) == 24 and int(version) == 5
+    size, plain_size, version = header_values(tmp_path, "sizeof(crh_denoise_variance_params)", "sizeof(crh_denoise_params)", "CRH_ABI_VERSION")
+    assert size == C.sizeof(abi.DenoiseVarianceParams) == 28 and plain_size == C.sizeof(abi.DenoiseParams) == 24 and version == 5
     # the defaults and the scale
     p = abi.DenoiseVarianceParams(-1, -1, -1, -1.0, -1.0, -1.0, -1.0)
     L.crh_denoise_variance_params_default(C.byref(p), 4, 8)
@@ -382,32 +271,13 @@ def test_the_two_filters_share_a_context_and_the_copy_keeps_bits(pkg, ctx):
 
 
 # ---- 7. the drop-in program ----------------------------------------------------------------------------------------------------------------------
-def dropin_paths():
-    exe = os.path.join(REPO, "c-ray_amd", "_lib", "c-ray-hip")
-    overlay = os.path.join(REPO, "oracle", "_ref", "input")
-    return exe, overlay, os.path.exists(exe) and os.path.exists(os.path.join(overlay, "scene.json"))
-
-
 def run_dropin(manifest, out_dir, extra_env):
-    """c-ray-hip on cfg1_scene with CRAY_HIP_DENOISE=3 and `extra_env`, its images in out_dir: the frame's floats, the denoised floats, the files written."""
-    import json
-    sys.path.insert(0, os.path.join(REPO, "tools"))
-    import refrun
-    exe, overlay, _ = dropin_paths()
+    """c-ray-hip on cfg1_scene with CRAY_HIP_DENOISE=3 and `extra_env`, its images in out_dir: the frame's floats, the denoised floats, the images written, the output."""
     m = manifest["cfg1_scene"]
-    w, h, s, b = m["width"], m["height"], m["samples"], m["bounces"]
-    os.makedirs(out_dir, exist_ok=True)
-    scene = refrun.rewrite_scene("scene.json", w, h, s, b, out_dir=str(out_dir))
-    frame, dump = os.path.join(out_dir, "frame.f32"), os.path.join(out_dir, "denoised.f32")
-    env = dict(os.environ, CRH_DUMP_F32=frame, CRH_DUMP_DENOISED_F32=dump, CRAY_HIP_DEVICES="1", CRAY_HIP_DENOISE="3")
-    for k in ("CRAY_HIP_AOV", "CRAY_HIP_DENOISE_VARIANCE", "CRH_DENOISE_FORM", "CRH_DROPIN_PASSES"):
-        env.pop(k, None)
-    env.update(extra_env)
-    proc = subprocess.run([exe], input=json.dumps(scene).encode(), cwd=overlay, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    text = proc.stdout.decode(errors="replace")
-    assert proc.returncode == 0, text[-2000:]
-    files = {f: open(os.path.join(out_dir, f), "rb").read() for f in sorted(os.listdir(out_dir)) if f.endswith(".bmp")}
-    return np.fromfile(frame, dtype=np.float32).reshape(h, w, 3), np.fromfile(dump, dtype=np.float32).reshape(h, w, 3), files, text
+    dumps = dict(CRH_DUMP_F32=os.path.join(out_dir, "frame.f32"), CRH_DUMP_DENOISED_F32=os.path.join(out_dir, "denoised.f32"))
+    files, text = support.run_dropin(manifest, out_dir, dict(dumps, CRAY_HIP_DENOISE="3", **extra_env))
+    frame, denoised = (np.frombuffer(files[f], np.float32).reshape(m["height"], m["width"], 3) for f in ("frame.f32", "denoised.f32"))
+    return frame, denoised, {f: data for f, data in files.items() if f.endswith(".bmp")}, text
 
 
 @pytest.mark.gpu
@@ -415,7 +285,6 @@ def test_dropin_program_splits_the_frame_and_writes_the_variance_guided_image(pk
     """c-ray-hip with CRAY_HIP_DENOISE=3 CRAY_HIP_DENOISE_VARIANCE=1: the frame, its dump and its image are those of the run without the second variable (the two
     dispatches compose), the same files are written, and the denoised dump equals Context.denoise_variance of that frame with a half-sample frame rendered through
     the API — passes [0, s / 2) of s — and the program's guides."""
-    from test_gpu_parity import dropin_env
     if not dropin_paths()[2]:
         pytest.skip("c-ray-hip or the asset overlay is not built (needs the reference's sources at build time)")
     m = manifest["cfg1_scene"]
@@ -444,20 +313,9 @@ def test_variance_kernels_on_the_emulation(manifest, tmp_path):
     crh_denoise_variance compiled unmodified on the HIP-on-CPU shim) — every one of them runs and passes there, none skipped (the drop-in test where the drop-in
     program is built). Where it is, the drop-in program also runs on two emulated devices: the half-sample frames are gathered like the frame, and the denoised
     image is the one a single device writes."""
-    from conftest import locked_make
-    locked_make(["make", "-s", "-C", EMU_DIR, "libcray_hip_emu.so"])
-    libdir = os.path.join(EMU_DIR, "_dropin_libs")
-    dropin = dropin_paths()[2] and os.path.isdir(libdir)
-    env = dict(os.environ, CRH_LIB=os.path.join(EMU_DIR, "libcray_hip_emu.so"), CRH_ALLOW_EMULATION="1", CRH_DROPIN_LIBDIR=libdir, HIPEMU_CUS="2", HIPEMU_THREADS="3")
-    cmd = [sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider"] + ([] if dropin else ["-k", "not dropin"])
-    r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=1700)
-    tail = (r.stdout + r.stderr)[-4000:]
-    assert r.returncode == 0, tail
-    m = re.search(r"(\d+) passed", r.stdout)
-    assert m and int(m.group(1)) == (15 if dropin else 14), tail
-    assert "skipped" not in r.stdout.strip().splitlines()[-1], tail
-    if dropin:
-        emu = dict(HIPEMU_CUS="2", HIPEMU_THREADS="3", CRAY_HIP_DENOISE_VARIANCE="1", LD_LIBRARY_PATH=libdir + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
+    run_gpu_tests_on_emulation(__file__, 15, passed_without_dropin=14)
+    if emulated_dropin():
+        emu = dict(HIPEMU_CUS="2", HIPEMU_THREADS="3", CRAY_HIP_DENOISE_VARIANCE="1", LD_LIBRARY_PATH=DROPIN_LIBDIR + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
         one_frame, one, one_files, _ = run_dropin(manifest, str(tmp_path / "one"), dict(emu, HIPEMU_DEVICES="1"))
         two_frame, two, two_files, _ = run_dropin(manifest, str(tmp_path / "two"), dict(emu, HIPEMU_DEVICES="2", CRAY_HIP_DEVICES="2"))
         assert np.array_equal(bits(one_frame), bits(two_frame))

@@ -7,19 +7,9 @@ import numpy as np
 import pytest
 
 from conftest import BIG_CASES, built_blob, camera_rays, resize_camera
+from support import emu_render
 
 CASES = ["cfg1_scene", "alphanode", "fence", "glowmetal", "refraction", "uvsphere", "texwrap", "bsdfedges_a"]          # (bsdfedges_b's frame holds NaN: tests/test_bsdf_edges.py)
-
-
-def emu_render(emu, oracle, scene, w, h, s, b, region=None, shape=(8, 8), chunk=64):
-    abi = oracle.abi
-    x0, y0, x1, y1 = region or (0, 0, w, h)
-    fb = np.zeros((h, w, 3), np.float32)
-    cnt, hi = abi.Counters(), C.c_uint32()
-    p = abi.RenderParams(x0, y0, x1, y1, w, h, 0, s, s, b)
-    rc = emu.emu_render_region(scene.ptr, C.byref(p), fb.ctypes.data, C.byref(cnt), C.byref(hi), shape[0], shape[1], chunk)
-    assert rc == 0, emu.emu_last_error()
-    return fb, cnt.as_dict(), hi.value
 
 
 @pytest.mark.parametrize("name", CASES)

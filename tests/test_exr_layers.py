@@ -2,98 +2,22 @@
 ranked ids into the pixel data of an uncompressed scanline file on the device; c-ray_amd/exr.py and c-ray_amd/host/exr_write.c write the file around it,
 with Cryptomatte's metadata on the id layers.
 
-The reader below is this file's own, written from the format's description (magic, version, attributes, chlist, offset table, blocks), and is anchored
-by a file spelled out field by field. CPU tier: the format, the hash, C against Python, the struct; the GPU tests again on the kernel emulation. GPU tier:
+The reader (tests/exr_reader.py) is the tests' own, written from the format's description (magic, version, attributes, chlist, offset table, blocks), and is
+anchored by a file spelled out field by field. CPU tier: the format, the hash, C against Python, the struct; the GPU tests again on the kernel emulation. GPU tier:
 the packed bytes bit for bit against a NumPy restatement of the header's contract, row chunks, refused arguments, a rendered file read back, and the
 drop-in program's file."""
 import ctypes as C
 import json
 import os
 import re
-import struct
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from test_idmatte import DeviceWords, resolve_expected
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(REPO, "tests", "emu")
-GUIDES = ("albedo.R", "albedo.G", "albedo.B", "normal.X", "normal.Y", "normal.Z", "Z", "A")
-
-
-def crypto_names(layer):
-    """rank r: id in <layer>0k.R (r = 2k) or .B (r = 2k + 1), coverage in .G or .A"""
-    return [(f"{layer}{r // 2:02d}.{'RB'[r % 2]}", f"{layer}{r // 2:02d}.{'GA'[r % 2]}") for r in range(6)]
-
-
-ALL_38 = ["R", "G", "B"] + list(GUIDES) + ["denoised.R", "denoised.G", "denoised.B"] + [n for layer in ("CryptoObject", "CryptoMaterial") for pair in crypto_names(layer) for n in pair]
-assert len(ALL_38) == 38
-
-
-@pytest.fixture(scope="module")
-def ctx(pkg):
-    if pkg.api.device_count() < 1:
-        pytest.fail("GPU tier needs a HIP device; libcray_hip has no CPU fallback")
-    c = pkg.api.Context(0)
-    yield c
-    c.close()
-
-
-# ---- the reader ---------------------------------------------------------------------------------------------------------------------------
-def _cstr(data, pos):
-    end = data.index(b"\0", pos)
-    return data[pos:end], end + 1
-
-
-def read_exr(data):
-    """An uncompressed single-part scanline OpenEXR file whose channels are all FLOAT -> width, height, attributes {name: (type, value bytes)} and their order,
-    channel names in file order, planes {name: uint32 [H, W]}, the offset table, the y of every block in file order, where the first block starts and the last ends."""
-    assert data[0:4] == bytes([0x76, 0x2F, 0x31, 0x01]), "magic"
-    assert data[4:8] == bytes([2, 0, 0, 0]), "version 2, no flags: single part, scanline, short names"
-    pos, attrs, order = 8, {}, []
-    while data[pos] != 0:
-        name, pos = _cstr(data, pos)
-        kind, pos = _cstr(data, pos)
-        size, = struct.unpack_from("<i", data, pos)
-        assert 1 <= len(name) <= 31 and size >= 0
-        attrs[name.decode()] = (kind.decode(), data[pos + 4:pos + 4 + size])
-        order.append(name)
-        pos += 4 + size
-    pos += 1
-    kind, chl = attrs["channels"]
-    assert kind == "chlist" and chl[-1] == 0
-    names, at = [], 0
-    while chl[at] != 0:
-        name, at = _cstr(chl, at)
-        pixel_type, p_linear, z0, z1, z2, xs, ys = struct.unpack_from("<iBBBBii", chl, at)
-        assert (pixel_type, p_linear, z0, z1, z2, xs, ys) == (2, 0, 0, 0, 0, 1, 1), name
-        assert 1 <= len(name) <= 31
-        names.append(name.decode())
-        at += 16
-    assert at == len(chl) - 1
-    assert attrs["compression"] == ("compression", b"\0") and attrs["lineOrder"] == ("lineOrder", b"\0")
-    assert attrs["dataWindow"][0] == "box2i" and attrs["displayWindow"] == attrs["dataWindow"]
-    x0, y0, x1, y1 = struct.unpack("<4i", attrs["dataWindow"][1])
-    assert (x0, y0) == (0, 0)
-    w, h = x1 + 1, y1 + 1
-    assert attrs["pixelAspectRatio"] == ("float", struct.pack("<f", 1.0)) and attrs["screenWindowWidth"] == ("float", struct.pack("<f", 1.0))
-    assert attrs["screenWindowCenter"] == ("v2f", struct.pack("<2f", 0.0, 0.0))
-    offsets = list(struct.unpack_from(f"<{h}Q", data, pos))
-    pos += 8 * h
-    first = pos
-    planes = np.empty((len(names), h, w), np.uint32)
-    ys = []
-    for y in range(h):          # (in file order)
-        yy, size = struct.unpack_from("<ii", data, pos)
-        assert size == 4 * len(names) * w, "a block's byte count"
-        ys.append(yy)
-        planes[:, yy, :] = np.frombuffer(data, "<u4", len(names) * w, pos + 8).reshape(len(names), w)
-        pos += 8 + size
-    return {"width": w, "height": h, "attrs": attrs, "attr_order": order, "names": names, "planes": dict(zip(names, planes)), "offsets": offsets, "ys": ys,
-            "first": first, "end": pos}
+from exr_reader import ALL_38, GUIDES, SPECIAL, attr_string, check_crypto_layer, crypto_names, hand_built_2x1, plant_ids, read_exr, run_dropin
+from firsthit_spec import resolve_expected
+from support import EMU_DIR, REPO, DeviceArray, ctx, dropin_env, dropin_paths, header_values, run_gpu_tests_on_emulation  # noqa: F401 (ctx: the fixture)
 
 
 def check_structure(f, data):
@@ -107,37 +31,7 @@ def check_structure(f, data):
     assert f["attr_order"] == sorted(f["attr_order"]), "attributes in ascending byte order of name"
 
 
-def attr_string(f, name):
-    kind, value = f["attrs"][name]
-    assert kind == "string"
-    return value.decode("utf-8")
-
-
 # ---- CPU tier: the format ----------------------------------------------------------------------------------------------------------------
-def hand_built_2x1():
-    """A 2 x 1 image with the channels B and R: B = (0.25, -0.0), R = (1.5, NaN 0x7fc00123)."""
-    def attr(name, kind, value):
-        return name + b"\0" + kind + b"\0" + struct.pack("<i", len(value)) + value
-
-    def channel(name):
-        return name + b"\0" + struct.pack("<i", 2) + struct.pack("<B", 0) + b"\0\0\0" + struct.pack("<i", 1) + struct.pack("<i", 1)
-    head = bytes([0x76, 0x2F, 0x31, 0x01]) + bytes([0x02, 0x00, 0x00, 0x00])
-    head += attr(b"channels", b"chlist", channel(b"B") + channel(b"R") + b"\0")
-    head += attr(b"compression", b"compression", struct.pack("<B", 0))
-    head += attr(b"dataWindow", b"box2i", struct.pack("<i", 0) + struct.pack("<i", 0) + struct.pack("<i", 1) + struct.pack("<i", 0))
-    head += attr(b"displayWindow", b"box2i", struct.pack("<i", 0) + struct.pack("<i", 0) + struct.pack("<i", 1) + struct.pack("<i", 0))
-    head += attr(b"lineOrder", b"lineOrder", struct.pack("<B", 0))
-    head += attr(b"pixelAspectRatio", b"float", struct.pack("<f", 1.0))
-    head += attr(b"screenWindowCenter", b"v2f", struct.pack("<f", 0.0) + struct.pack("<f", 0.0))
-    head += attr(b"screenWindowWidth", b"float", struct.pack("<f", 1.0))
-    head += b"\0"
-    table = struct.pack("<Q", len(head) + 8)          # one row: its block follows the one-entry table
-    block = struct.pack("<i", 0) + struct.pack("<i", 4 * 2 * 2)
-    block += struct.pack("<I", 0x3E800000) + struct.pack("<I", 0x80000000)          # B: 0.25, -0.0
-    block += struct.pack("<I", 0x3FC00000) + struct.pack("<I", 0x7FC00123)          # R: 1.5, a NaN with a payload
-    return head + table + block
-
-
 def test_reader_parses_hand_built_bytes_and_exr_py_writes_them(pkg):
     data = hand_built_2x1()
     f = read_exr(data)
@@ -255,12 +149,9 @@ def test_c_writer_writes_the_bytes_of_exr_py(pkg, tmp_path):
 
 
 def test_pack_channel_struct_matches_header(pkg, tmp_path):
-    src, exe = tmp_path / "size.c", tmp_path / "size"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "cray_hip.h"\nint main(void){printf("%zu %zu %zu %zu %zu %d\\n", sizeof(crh_pack_channel), '
-                   'offsetof(crh_pack_channel, stride), offsetof(crh_pack_channel, component), offsetof(crh_pack_channel, map_host), offsetof(crh_pack_channel, map_count), '
-                   'CRH_PACK_MAX_CHANNELS);return 0;}\n')
-    subprocess.check_call(["gcc", "-I" + os.path.join(REPO, "include"), str(src), "-o", str(exe)])
-    size, stride, component, map_host, map_count, most = (int(v) for v in subprocess.check_output([str(exe)]).split())
+    size, stride, component, map_host, map_count, most = header_values(
+        tmp_path, "sizeof(crh_pack_channel)", "offsetof(crh_pack_channel, stride)", "offsetof(crh_pack_channel, component)", "offsetof(crh_pack_channel, map_host)",
+        "offsetof(crh_pack_channel, map_count)", "CRH_PACK_MAX_CHANNELS")
     P = pkg.abi.PackChannel
     assert (C.sizeof(P), P.stride.offset, P.component.offset, P.map_host.offset, P.map_count.offset) == (size, stride, component, map_host, map_count) and size == 32
     assert most == pkg.abi.PACK_MAX_CHANNELS == 64
@@ -287,9 +178,6 @@ def pack_expected(chans, w, h, first=0, rows=None):
     return out.tobytes()
 
 
-SPECIAL = np.array([0x7FC00000, 0xFFC12345, 0x7F800001, 0x7F800000, 0xFF800000, 0x80000000, 0x00000001, 0x807FFFFF, 0x00000000, 0x3F800000], np.uint32)
-
-
 def source(rng, w, h, stride):
     """uint32 [h, w, stride]: random bit patterns with NaNs (quiet, signalling, negative), both infinities, -0.0 and subnormals planted"""
     a = rng.integers(0, 2 ** 32, (h, w, stride), dtype=np.uint32)
@@ -297,14 +185,6 @@ def source(rng, w, h, stride):
     at = np.arange(0, flat.size, 3)
     flat[at] = SPECIAL[np.arange(at.size) % SPECIAL.size]
     return a
-
-
-def plant_ids(rng, a, comp, count):
-    """component `comp` of `a` becomes ids against a map of `count` entries: the edge values first, valid ids behind them"""
-    edge = np.array([-1.0, 0.0, count - 1, count, 2.5, np.nan, 16777216.0, -0.0, 0.5, count - 0.5, 1e30, np.inf, -np.inf, 1e-45, -2.0, 4294967296.0], np.float32)
-    vals = rng.integers(0, count, a.shape[0] * a.shape[1]).astype(np.float32)
-    vals[:min(edge.size, vals.size)] = edge[:vals.size]
-    a[:, :, comp] = vals.view(np.uint32).reshape(a.shape[:2])
 
 
 def pack_case(name):
@@ -345,7 +225,7 @@ def pack_case(name):
 def run_pack(pkg, ctx, case, **rows):
     """(the bytes the library packs, the bytes of the restatement)"""
     w, h, src, chans, maps = case
-    dev = {k: DeviceWords(pkg, v) for k, v in src.items()}
+    dev = {k: DeviceArray(pkg, v, np.uint32) for k, v in src.items()}
     got = ctx.pack_scanlines([(dev[k].ptr, stride, comp, None if m is None else maps[m]) for k, stride, comp, m in chans], w, h, **rows)
     want = pack_expected([(src[k], stride, comp, None if m is None else maps[m]) for k, stride, comp, m in chans], w, h, rows.get("first_row", 0), rows.get("row_count"))
     for k, d in dev.items():
@@ -389,7 +269,7 @@ def test_row_chunks_concatenate(pkg, ctx):
         assert got == want_part, words_differ(got, want_part)
     assert b"".join(p[0] for p in parts) == whole
     # row_count == 0: CRH_OK, nothing written
-    dev = DeviceWords(pkg, case[2]["s3"])
+    dev = DeviceArray(pkg, case[2]["s3"], np.uint32)
     ch = pkg.abi.PackChannel(dev.ptr, 3, 0, None, 0, 0)
     out = np.full(64, 0xA5A5A5A5, np.uint32)
     for first in (0, 2, h):
@@ -453,29 +333,6 @@ def matte_from_file(f, layer, name_id):
     return out
 
 
-def check_crypto_layer(pkg, f, layer, ranked, names):
-    """The id channels hold the names' converted hashes (0.0f where the rank is empty), the coverage channels the ranked coverages; the manifest inverts."""
-    exr = pkg.exr
-    manifest = json.loads(attr_string(f, f"cryptomatte/{exr.layer_key(layer)}/manifest"))
-    assert list(manifest) == list(names), "keys in id order"
-    assert [int(v, 16) for v in manifest.values()] == [exr.crypto_id(s) for s in names] and all(re.fullmatch(r"[0-9a-f]{8}", v) for v in manifest.values())
-    index = {int(v, 16): i for i, v in enumerate(manifest.values())}
-    assert len(index) == len(names), "the manifest inverts to the indices"
-    assert attr_string(f, f"cryptomatte/{exr.layer_key(layer)}/name") == layer
-    assert attr_string(f, f"cryptomatte/{exr.layer_key(layer)}/hash") == "MurmurHash3_32"
-    assert attr_string(f, f"cryptomatte/{exr.layer_key(layer)}/conversion") == "uint32_to_float32"
-    table = np.array([exr.crypto_id(s) for s in names], np.uint32)
-    for r, (idn, covn) in enumerate(crypto_names(layer)):
-        ids = ranked[..., r, 0]
-        empty = ids < 0
-        assert (ids[~empty] < len(names)).all()
-        want = np.where(empty, np.uint32(0), table[np.where(empty, 0, ids).astype(np.int64)])
-        assert np.array_equal(f["planes"][idn], want), idn
-        assert np.array_equal(f["planes"][covn], ranked[..., r, 1].view(np.uint32)), covn
-        back = np.array([index[int(v)] for v in f["planes"][idn][~empty]], np.float32)
-        assert np.array_equal(back, ids[~empty]), "the file's ids invert to the indices through the manifest"
-
-
 @pytest.mark.gpu
 def test_rendered_layers_file(pkg, ctx, golden_blob, tmp_path):
     """glowmetal at 160 x 100: 4 passes, guides and ids at 4 passes, one denoise. write_layers_exr writes, this file's reader reads: every layer bit for bit."""
@@ -509,7 +366,7 @@ def test_rendered_layers_file(pkg, ctx, golden_blob, tmp_path):
     # for every single instance id, the matte rebuilt from the file is crh_ids_matte's
     present = np.unique(words_i[..., 0:6][words_i[..., 6:12] != 0])
     assert present.size >= 2
-    out = DeviceWords(pkg, np.zeros((h, w), np.float32))
+    out = DeviceArray(pkg, np.zeros((h, w), np.float32))
     for i in present:
         ctx.ids_matte(bi, w, h, [int(i)], out.ptr)
         want = out.read(ctx)
@@ -525,40 +382,10 @@ def test_rendered_layers_file(pkg, ctx, golden_blob, tmp_path):
 
 
 # ---- the drop-in program ------------------------------------------------------------------------------------------------------------------
-def dropin_paths():
-    exe = os.path.join(REPO, "c-ray_amd", "_lib", "c-ray-hip")
-    overlay = os.path.join(REPO, "oracle", "_ref", "input")
-    return exe, overlay, os.path.exists(exe) and os.path.exists(os.path.join(overlay, "scene.json"))
-
-
-def run_dropin(manifest, out_dir, extra_env):
-    """c-ray-hip on cfg1_scene with CRAY_HIP_AOV=4 CRAY_HIP_DENOISE=2 and `extra_env`: the float dumps of the frame, the guides and the denoised frame, and every
-    file it wrote beside them."""
-    sys.path.insert(0, os.path.join(REPO, "tools"))
-    import refrun
-    exe, overlay, _ = dropin_paths()
-    m = manifest["cfg1_scene"]
-    w, h, s, b = m["width"], m["height"], m["samples"], m["bounces"]
-    os.makedirs(out_dir, exist_ok=True)
-    scene = refrun.rewrite_scene("scene.json", w, h, s, b, out_dir=str(out_dir))
-    dumps = {k: os.path.join(out_dir, k + ".f32") for k in ("frame", "aov", "denoised")}
-    env = dict(os.environ, CRH_DUMP_F32=dumps["frame"], CRH_DUMP_AOV_F32=dumps["aov"], CRH_DUMP_DENOISED_F32=dumps["denoised"], CRAY_HIP_DEVICES="1", CRAY_HIP_AOV="4",
-               CRAY_HIP_DENOISE="2")
-    for k in ("CRAY_HIP_DENOISE_VARIANCE", "CRAY_HIP_ADAPTIVE", "CRAY_HIP_EXR", "CRAY_HIP_IDS", "CRH_DENOISE_FORM", "CRH_DROPIN_PASSES"):
-        env.pop(k, None)
-    env.update(extra_env)
-    proc = subprocess.run([exe], input=json.dumps(scene).encode(), cwd=overlay, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    text = proc.stdout.decode(errors="replace")
-    assert proc.returncode == 0, text[-2000:]
-    files = {f: open(os.path.join(out_dir, f), "rb").read() for f in sorted(os.listdir(out_dir))}
-    return files, text
-
-
 @pytest.mark.gpu
 def test_dropin_program_writes_the_layers_file(pkg, ctx, manifest, golden_blob, tmp_path):
     """c-ray-hip on cfg1_scene with CRAY_HIP_AOV=4 CRAY_HIP_IDS=4 CRAY_HIP_DENOISE=2 CRAY_HIP_EXR=1: every file of the run without the last two variables is there
     byte for byte, one .exr more; it parses, holds the dumped floats, and its bytes are those Context.write_layers_exr writes from the same buffers and names."""
-    from test_gpu_parity import dropin_env
     if not dropin_paths()[2]:
         pytest.skip("c-ray-hip or the asset overlay is not built (needs the reference's sources at build time)")
     m = manifest["cfg1_scene"]
@@ -593,7 +420,7 @@ def test_dropin_program_writes_the_layers_file(pkg, ctx, manifest, golden_blob, 
     ctx.upload(scene)
     bi, bm = ctx.ids_buffer(w, h), ctx.ids_buffer(w, h)
     ctx.render_ids(bi, bm, w, h, s, pass_count=min(4, s))
-    dev = [DeviceWords(pkg, a) for a in (frame, guides, denoised)]
+    dev = [DeviceArray(pkg, a, np.uint32) for a in (frame, guides, denoised)]
     path = str(tmp_path / "api.exr")
     ctx.write_layers_exr(path, w, h, dev[0].ptr, aov=dev[1].ptr, denoised=dev[2].ptr, instance_ids=bi, material_ids=bm, instance_names=inst, material_names=mat)
     assert open(path, "rb").read() == data
@@ -605,21 +432,6 @@ def test_dropin_program_writes_the_layers_file(pkg, ctx, manifest, golden_blob, 
 def test_pack_kernel_on_the_emulation():
     """CPU tier: this file's GPU tests run by a child pytest against the kernel emulation (tests/emu/libcray_hip_emu.so: k_pack_scanlines and its entry point
     compiled unmodified on the HIP-on-CPU shim) — every one of them runs and passes there, none skipped (the drop-in test where the drop-in program is built)."""
-    from conftest import locked_make
-    # csrc/exr_pack.h is not among the prerequisites the emulation's build rule lists for its kernel object: an object older than the header is rebuilt here
-    # (-W: make takes cray_hip.hip, which includes the header and which the rule does list, as just modified)
-    csrc = os.path.join(REPO, "c-ray_amd", "csrc")
-    obj = os.path.join(EMU_DIR, "_obj", "kernel_emu.o")
-    stale = os.path.exists(obj) and os.path.getmtime(os.path.join(csrc, "exr_pack.h")) > os.path.getmtime(obj)
-    locked_make(["make", "-s", "-C", EMU_DIR] + (["-W", os.path.join(csrc, "cray_hip.hip")] if stale else []) + ["libcray_hip_emu.so"])
-    assert os.path.getmtime(os.path.join(csrc, "exr_pack.h")) <= os.path.getmtime(obj), "the emulation's kernel object is older than csrc/exr_pack.h"
-    libdir = os.path.join(EMU_DIR, "_dropin_libs")
-    dropin = dropin_paths()[2] and os.path.isdir(libdir)
-    env = dict(os.environ, CRH_LIB=os.path.join(EMU_DIR, "libcray_hip_emu.so"), CRH_ALLOW_EMULATION="1", CRH_DROPIN_LIBDIR=libdir, HIPEMU_CUS="2", HIPEMU_THREADS="3")
-    cmd = [sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider"] + ([] if dropin else ["-k", "not dropin"])
-    r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=1700)
-    tail = (r.stdout + r.stderr)[-4000:]
-    assert r.returncode == 0, tail
-    m = re.search(r"(\d+) passed", r.stdout)
-    assert m and int(m.group(1)) == (8 if dropin else 7), tail
-    assert "skipped" not in r.stdout.strip().splitlines()[-1], tail
+    run_gpu_tests_on_emulation(__file__, 8, passed_without_dropin=7)
+    header, obj = os.path.join(REPO, "c-ray_amd", "csrc", "exr_pack.h"), os.path.join(EMU_DIR, "_obj", "kernel_emu.o")
+    assert os.path.getmtime(header) <= os.path.getmtime(obj), "the emulation's kernel object is older than csrc/exr_pack.h"

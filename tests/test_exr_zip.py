@@ -8,21 +8,18 @@ GPU tests run by a child pytest on the emulation (tests/emu/Makefile.exr). GPU t
 planes, chunked calls, refused arguments, size conditions against host zlib with fixed codes, a rendered file, the drop-in program."""
 import ctypes as C
 import os
-import re
 import struct
 import subprocess
-import sys
 import zlib
 
 import numpy as np
 import pytest
 
-from test_exr_layers import ALL_38, SPECIAL, check_crypto_layer, dropin_paths, plant_ids, run_dropin
-from test_exr_layers import read_exr as read_exr_plain
-from test_idmatte import DeviceWords, resolve_expected
+import exr_reader
+from exr_reader import ALL_38, SPECIAL, check_crypto_layer, hand_built_2x1, plant_ids, run_dropin
+from firsthit_spec import resolve_expected
+from support import EMU_DIR, REPO, DeviceArray, ctx, dropin_env, dropin_paths, run_gpu_tests_on_emulation  # noqa: F401 (ctx: the fixture)
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(REPO, "tests", "emu")
 LINES = {0: 1, 2: 1, 3: 16}
 
 
@@ -96,11 +93,11 @@ def yardstick(raw, n_per_chunk):
 
 # ---- the reader: compression 0, 2 and 3 -------------------------------------------------------------------------------------------------
 def read_exr(data):
-    """A single-part scanline OpenEXR file whose channels are all FLOAT, uncompressed, ZIPS or ZIP -> what test_exr_layers.read_exr returns, and `compression`,
+    """A single-part scanline OpenEXR file whose channels are all FLOAT, uncompressed, ZIPS or ZIP -> what exr_reader.read_exr returns, and `compression`,
     `chunks` [(y, size, n)]. Every offset is checked against the position of its chunk."""
     kind = data[data.index(b"compression\0compression\0") + 28]
     if kind == 0:
-        f = read_exr_plain(data)
+        f = exr_reader.read_exr(data)
         f["compression"] = 0
         return f
     assert kind in (2, 3)
@@ -163,7 +160,7 @@ def host_chunks(planes, w, h, lines):
 
 # ---- CPU tier: the format ---------------------------------------------------------------------------------------------------------------
 def hand_built_2x1_zips():
-    """The 2 x 1 image of test_exr_layers.hand_built_2x1 — B = (0.25, -0.0), R = (1.5, NaN 0x7fc00123) — as a ZIPS file: one chunk, raw (16 bytes do not deflate)."""
+    """The 2 x 1 image of exr_reader.hand_built_2x1— B = (0.25, -0.0), R = (1.5, NaN 0x7fc00123) — as a ZIPS file: one chunk, raw (16 bytes do not deflate)."""
     def attr(name, kind, value):
         return name + b"\0" + kind + b"\0" + struct.pack("<i", len(value)) + value
 
@@ -202,7 +199,6 @@ def test_reader_is_anchored_and_exr_py_writes_the_chunked_file(pkg):
     assert sizes == [24]
     assert exr.file_bytes_chunked(2, 1, ["B", "R"], chunks, sizes, compression=2) == data
     # compression 0 keeps its bytes: header() and file_bytes() as before
-    from test_exr_layers import hand_built_2x1
     assert exr.file_bytes(2, 1, ["B", "R"], exr.pack_host([b, r], 2, 1)) == hand_built_2x1()
     assert exr.header(2, 1, ["B", "R"]) == exr.header(2, 1, ["B", "R"], compression=0) == hand_built_2x1()[:-8 - 24]
     # a compressible image of two ZIP chunks (17 rows) and of 17 ZIPS chunks: deflated chunks, a short last chunk, strings
@@ -280,15 +276,6 @@ def test_c_chunked_writer_writes_the_bytes_of_exr_py(pkg, tmp_path):
 
 # ---- the GPU tier -----------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def ctx(pkg):
-    if pkg.api.device_count() < 1:
-        pytest.fail("GPU tier needs a HIP device; libcray_hip has no CPU fallback")
-    c = pkg.api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
 def zctx(pkg, ctx):
     import cray_amd.exrzip as exrzip
     z = exrzip.ZipContext(0)
@@ -333,7 +320,7 @@ def zip_case(name):
 def run_zip(pkg, ctx, zctx, case, lines, **rows):
     """(crx_pack_zip's bytes, its sizes, the raw bytes Context.pack_scanlines gives for the same rows with the row headers stripped)"""
     w, h, src, chans, maps = case
-    dev = {k: DeviceWords(pkg, v) for k, v in src.items()}
+    dev = {k: DeviceArray(pkg, v, np.uint32) for k, v in src.items()}
     ch = [(dev[k].ptr, stride, comp, None if m is None else maps[m]) for k, stride, comp, m in chans]
     ctx.synchronize()
     data, sizes = zctx.pack_zip(ch, w, h, lines, **rows)
@@ -423,7 +410,7 @@ def test_crafted_planes(pkg, ctx, zctx):
     tps.append(bytes([128]) * n); what.append("constant")
     planes = crafted(tps)
     h, w = planes.shape
-    dev = DeviceWords(pkg, planes.reshape(h, w, 1))
+    dev = DeviceArray(pkg, planes.reshape(h, w, 1), np.uint32)
     ctx.synchronize()
     data, sizes = zctx.pack_zip([(dev.ptr, 1, 0)], w, h, 1)
     chunks = split_chunks(data, sizes, 1, w, 0, h, 1)
@@ -466,7 +453,7 @@ def test_refused_arguments_leave_everything_untouched(pkg, ctx, zctx):
     abi = pkg.abi
     w, h = 40, 35
     rng = np.random.default_rng(3)
-    a, b = DeviceWords(pkg, flat_source(rng, w, h, 3)), DeviceWords(pkg, flat_source(rng, w, h, 8))
+    a, b = DeviceArray(pkg, flat_source(rng, w, h, 3), np.uint32), DeviceArray(pkg, flat_source(rng, w, h, 8), np.uint32)
     m = np.arange(7, dtype=np.uint32)
     good = [(a.ptr, 3, 1, None, 0), (b.ptr, 8, 7, m.ctypes.data, 7)]
     out = np.full(8 * h + 4 * 2 * w * h, 0xA5, np.uint8)
@@ -532,7 +519,7 @@ def test_size_conditions(name, pkg, ctx, zctx):
     planes = [np.ascontiguousarray(p).view(np.uint32) for p in size_sets()[name]]
     w, h, nch = 160, 96, len(planes)
     words = np.ascontiguousarray(np.stack(planes, axis=2))          # [h, w, nch]
-    dev = DeviceWords(pkg, words)
+    dev = DeviceArray(pkg, words, np.uint32)
     ch = [(dev.ptr, nch, c) for c in range(nch)]
     ctx.synchronize()
     raw = strip_headers(ctx.pack_scanlines(ch, w, h), nch, w)
@@ -603,7 +590,6 @@ def test_rendered_layers_file_compressed(pkg, ctx, golden_blob, manifest, tmp_pa
 def test_dropin_program_writes_the_compressed_layers_file(pkg, ctx, manifest, golden_blob, tmp_path):
     """c-ray-hip with CRAY_HIP_EXR=1 CRAY_HIP_EXR_COMPRESSION=zip: the layers file is, byte for byte, what Context.write_layers_exr(compression="zip") writes from
     the same buffers and names; every other file of the run equals the run without the variable."""
-    from test_gpu_parity import dropin_env
     import json
     if not dropin_paths()[2]:
         pytest.skip("c-ray-hip or the asset overlay is not built (needs the reference's sources at build time)")
@@ -628,7 +614,7 @@ def test_dropin_program_writes_the_compressed_layers_file(pkg, ctx, manifest, go
     ctx.upload(pkg.api.Scene(golden_blob("cfg1_scene")))
     bi, bm = ctx.ids_buffer(w, h), ctx.ids_buffer(w, h)
     ctx.render_ids(bi, bm, w, h, s, pass_count=min(4, s))
-    dev = [DeviceWords(pkg, a) for a in (frame, guides, denoised)]
+    dev = [DeviceArray(pkg, a, np.uint32) for a in (frame, guides, denoised)]
     path = str(tmp_path / "api.exr")
     ctx.write_layers_exr(path, w, h, dev[0].ptr, aov=dev[1].ptr, denoised=dev[2].ptr, instance_ids=bi, material_ids=bm, instance_names=inst, material_names=mat,
                          compression="zip")
@@ -640,17 +626,5 @@ def test_zip_kernels_on_the_emulation():
     """CPU tier: this file's GPU tests run by a child pytest against the emulation builds — tests/emu/libcray_hip_exr_emu.so (Makefile.exr: exr_zip.hip unmodified
     on the HIP-on-CPU shim) beside tests/emu/libcray_hip_emu.so, both in one process — every one of them runs and passes there, none skipped (the drop-in test
     where the drop-in program is built)."""
-    from conftest import locked_make
-    locked_make(["make", "-s", "-C", EMU_DIR, "libcray_hip_emu.so"])
-    locked_make(["make", "-s", "-C", EMU_DIR, "-f", "Makefile.exr"])
-    libdir = os.path.join(EMU_DIR, "_dropin_libs")
-    dropin = dropin_paths()[2] and os.path.isdir(libdir) and os.path.exists(os.path.join(libdir, "libcray_hip_exr.so"))
-    env = dict(os.environ, CRH_LIB=os.path.join(EMU_DIR, "libcray_hip_emu.so"), CRX_LIB=os.path.join(EMU_DIR, "libcray_hip_exr_emu.so"), CRH_ALLOW_EMULATION="1",
-               CRH_DROPIN_LIBDIR=libdir, HIPEMU_CUS="2", HIPEMU_THREADS="3")
-    cmd = [sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider"] + ([] if dropin else ["-k", "not dropin"])
-    r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=1700)
-    tail = (r.stdout + r.stderr)[-4000:]
-    assert r.returncode == 0, tail
-    m = re.search(r"(\d+) passed", r.stdout)
-    assert m and int(m.group(1)) == (10 if dropin else 9), tail
-    assert "skipped" not in r.stdout.strip().splitlines()[-1], tail
+    run_gpu_tests_on_emulation(__file__, 10, passed_without_dropin=9, extra_env={"CRX_LIB": os.path.join(EMU_DIR, "libcray_hip_exr_emu.so")},
+                               make_targets=("libcray_hip_emu.so", "-f Makefile.exr"), dropin_libs=("libcray_hip_exr.so",))

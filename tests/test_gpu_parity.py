@@ -14,30 +14,13 @@ import numpy as np
 import pytest
 
 from conftest import BIG_CASES, built_blob, camera_rays, image_stats, kernel_forms, resize_camera
+from support import ctx, dropin_env, dropin_paths  # noqa: F401 (ctx: the module-scoped device context)
 
 pytestmark = pytest.mark.gpu
 CASES = ["cfg1_scene", "alphanode", "fence", "glowmetal", "refraction", "uvsphere", "texwrap"]
 # ... and an edge scene for the frames: one bsdf parameter at an edge value per sphere (tests/test_bsdf_edges.py; its frame holds no NaN — bsdfedges_b's does, and is
 # compared there, a NaN equal to a NaN of any payload)
 IMAGE_CASES = CASES + ["bsdfedges_a"]
-
-
-@pytest.fixture(scope="module")
-def ctx(pkg):
-    if pkg.api.device_count() < 1:
-        pytest.fail("GPU tier needs a HIP device; libcray_hip has no CPU fallback")
-    c = pkg.api.Context(0)
-    yield c
-    c.close()
-
-
-def dropin_env():
-    """Extra environment of the c-ray-hip child processes. Empty on a GPU box. The CPU tier (tests/test_kernel_emu.py) runs these tests
-    against the kernel emulation: CRH_DROPIN_LIBDIR names a directory whose libcray_hip.so IS the emulation library, and the program's
-    loader finds it there before its RUNPATH."""
-    import os
-    libdir = os.environ.get("CRH_DROPIN_LIBDIR")
-    return {"LD_LIBRARY_PATH": libdir + ":" + os.environ.get("LD_LIBRARY_PATH", "")} if libdir else {}
 
 
 def gpu_render(pkg, ctx, blob, w, h, s, b, **kw):
@@ -1037,12 +1020,10 @@ def test_dropin_binary_renders_through_the_reference_program(pkg, ctx, manifest,
     import os
     import subprocess
     import sys
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(repo, "c-ray_amd", "_lib", "c-ray-hip")
-    overlay = os.path.join(repo, "oracle", "_ref", "input")
-    if not (os.path.exists(exe) and os.path.exists(os.path.join(overlay, "scene.json"))):
-        pytest.skip("c-ray-hip or the asset overlay is not built (needs /root/reference at build time)")
-    sys.path.insert(0, os.path.join(repo, "tools"))
+    exe, overlay, built = dropin_paths()
+    if not built:
+        pytest.skip("c-ray-hip or the asset overlay is not built (needs the reference's sources at build time)")
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
     import refrun
     m = manifest["cfg1_scene"]
     w, h, s, b = m["width"], m["height"], m["samples"], m["bounces"]
@@ -1205,12 +1186,10 @@ def test_cluster_worker_renders_its_tiles_on_the_gpu(float_tiles, pkg, oracle, m
     import subprocess
     import sys
     import time
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    gpu_worker = os.path.join(repo, "c-ray_amd", "_lib", "c-ray-hip")
-    overlay = os.path.join(repo, "oracle", "_ref", "input")
-    if not (os.path.exists(gpu_worker) and os.path.exists(os.path.join(overlay, "scene.json"))):
-        pytest.skip("c-ray-hip / the asset overlay are not built (needs /root/reference at build time)")
-    sys.path.insert(0, os.path.join(repo, "tools"))
+    gpu_worker, overlay, built = dropin_paths()
+    if not built:
+        pytest.skip("c-ray-hip / the asset overlay are not built (needs the reference's sources at build time)")
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
     import refrun
     m = manifest["cfg1_scene"]
     w, h = m["width"], m["height"]

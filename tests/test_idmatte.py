@@ -8,29 +8,15 @@ coverage pass by pass. The two consumers are held bit for bit to numpy float32 r
 emulation (tests/emu: the same kernel source on a HIP shim)."""
 import ctypes as C
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from conftest import resize_camera
-from test_aov import first_hits, ragged_tiles
+from firsthit_spec import LOST, SLOTS, TOTAL, WORDS, first_hits, ragged_tiles, resolve_expected
+from support import EMU_DIR, REPO, DeviceArray, ctx, run_gpu_tests_on_emulation  # noqa: F401 (ctx: the fixture)
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(REPO, "tests", "emu")
-SLOTS, WORDS, LOST, TOTAL = 6, 16, 12, 13
 SLOT = np.arange(SLOTS)
-
-
-@pytest.fixture(scope="module")
-def ctx(pkg):
-    if pkg.api.device_count() < 1:
-        pytest.fail("GPU tier needs a HIP device; libcray_hip has no CPU fallback")
-    c = pkg.api.Context(0)
-    yield c
-    c.close()
 
 
 # ---- the restatements -------------------------------------------------------------------------------------------------------------------
@@ -59,20 +45,6 @@ def expected_ids(hits, start=None):
     return inst, mat
 
 
-def resolve_expected(buf):
-    """crh_ids_resolve in numpy float32: [..., 6, 2]."""
-    ids, cnt, total = buf[..., 0:SLOTS], buf[..., SLOTS:2 * SLOTS], buf[..., TOTAL]
-    order = np.argsort(-cnt.astype(np.int64), axis=-1, kind="stable")          # count descending; equal counts: the lower slot first
-    ids, cnt = np.take_along_axis(ids, order, -1), np.take_along_axis(cnt, order, -1)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        cov = cnt.astype(np.float32) / total.astype(np.float32)[..., None]
-    empty = (cnt == 0) | (total == 0)[..., None]
-    out = np.empty(buf.shape[:-1] + (SLOTS, 2), np.float32)
-    out[..., 0] = np.where(empty, np.float32(-1.0), ids.astype(np.float32))
-    out[..., 1] = np.where(empty, np.float32(0.0), cov)
-    return out
-
-
 def matte_expected(buf, ids):
     """crh_ids_matte in numpy float32: [...]."""
     idw, cnt, total = buf[..., 0:SLOTS], buf[..., SLOTS:2 * SLOTS], buf[..., TOTAL]
@@ -87,29 +59,6 @@ def used_slots(buf):
 
 
 # ---- what the tests share ---------------------------------------------------------------------------------------------------------------
-class DeviceWords:
-    """A caller-owned device buffer filled by the caller (the ID entry points take any device pointer): a torch tensor on the GPU; under the
-    kernel emulation, whose device memory is the host heap, a numpy array. uint32 words travel as int32 bits (torch's everyday dtype)."""
-
-    def __init__(self, pkg, values):
-        values = np.ascontiguousarray(values)
-        self.dtype, self.shape = values.dtype, values.shape
-        self.emulated = hasattr(pkg.api.library(), "crh_emu_stats")
-        if self.emulated:
-            self.a = values.copy()
-            self.ptr = self.a.ctypes.data
-        else:
-            import torch
-            self.a = torch.from_numpy(values.view(np.int32 if values.dtype == np.uint32 else values.dtype).copy()).to("cuda:0")
-            torch.cuda.synchronize()
-            self.ptr = self.a.data_ptr()
-        assert self.ptr % 16 == 0
-
-    def read(self, ctx):
-        ctx.synchronize()
-        return self.a.copy() if self.emulated else self.a.cpu().numpy().view(self.dtype).reshape(self.shape)
-
-
 _CASES = {"glowmetal": (160, 100, 5, False), "cfg1_scene": (160, 100, 4, True), "cfg1_tiny": (8, 5, 130, True)}
 _cache = {}
 
@@ -214,7 +163,7 @@ def test_caller_owned_prefilled_buffers(pkg, ctx, oracle, golden_blob):
             assert (want_i[..., 5][some] == first_inst[some].astype(np.uint32)).all() and (want_i[..., 0:5] == rec[0:5]).all()
             assert want_i[..., LOST].sum() > 0 and want_m[..., LOST].sum() > 0, "the rectangle shows pixels with two ids"
             assert np.array_equal(want_i[..., 11] + want_i[..., LOST], hit_passes) and (want_i[..., TOTAL] == 20).all()
-        di, dm = DeviceWords(pkg, start), DeviceWords(pkg, start)
+        di, dm = DeviceArray(pkg, start, np.uint32), DeviceArray(pkg, start, np.uint32)
         ctx.render_ids(di.ptr, dm.ptr, w, h, passes, region=region)
         for name, dev, want in (("instance", di, want_i), ("material", dm, want_m)):
             got = dev.read(ctx)
@@ -347,15 +296,15 @@ def test_resolve_and_matte_equal_their_restatements(pkg, ctx, oracle, golden_blo
     ties = 0
     for name, buf, hits in inputs:
         h, w = buf.shape[:2]
-        dev = DeviceWords(pkg, buf)
-        out = DeviceWords(pkg, np.full((h, w, SLOTS, 2), 7.0, np.float32))
+        dev = DeviceArray(pkg, buf, np.uint32)
+        out = DeviceArray(pkg, np.full((h, w, SLOTS, 2), 7.0, np.float32))
         ctx.resolve_ids(dev.ptr, w, h, out.ptr)
         got, want = out.read(ctx), resolve_expected(buf)
         assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), f"{name}: {int((got.view(np.uint32) != want.view(np.uint32)).sum())} floats of the ranking differ"
         cnt = buf[..., SLOTS:2 * SLOTS]
         ties += int(((cnt[..., :-1] == cnt[..., 1:]) & (cnt[..., 1:] != 0)).any(axis=-1).sum())
         present = np.unique(buf[..., 0:SLOTS][cnt != 0])
-        mout = DeviceWords(pkg, np.full((h, w), 7.0, np.float32))
+        mout = DeviceArray(pkg, np.full((h, w), 7.0, np.float32))
         lists = [[], [int(present[0])], [int(present[0])] * 3, [int(i) for i in present[:2]] + [int(present[0])], [int(i) for i in present[-64:]], [4000000000]]
         mattes = []
         for ids in lists:
@@ -392,8 +341,8 @@ def test_entry_point_behaviour(pkg, golden_blob):
         assert c.ids_kernel_time_ms() == 0.0
         assert L.crh_render_ids(c.h, C.byref(p), None, 0, bi, bm) == abi.ERR_INVALID          # no scene
         # the consumers need none
-        out = DeviceWords(pkg, np.full((h, w, SLOTS, 2), 7.0, np.float32))
-        mout = DeviceWords(pkg, np.full((h, w), 7.0, np.float32))
+        out = DeviceArray(pkg, np.full((h, w, SLOTS, 2), 7.0, np.float32))
+        mout = DeviceArray(pkg, np.full((h, w), 7.0, np.float32))
         c.resolve_ids(bi, w, h, out.ptr)
         c.ids_matte(bi, w, h, [0, 1], mout.ptr)
         got = out.read(c)
@@ -464,19 +413,6 @@ def test_entry_point_behaviour(pkg, golden_blob):
 def test_id_kernels_on_the_emulation():
     """CPU tier: this file's GPU tests run by a child pytest against the kernel emulation (tests/emu/libcray_hip_emu.so: k_ids, the two consumers and their
     entry points compiled unmodified on the HIP-on-CPU shim) — every one of them runs and passes there, none skipped."""
-    from conftest import locked_make
-    # csrc/idmatte.h is not among the prerequisites the emulation's build rule lists for its kernel object: an object older than the header is rebuilt here
-    # (-W: make takes cray_hip.hip, which includes the header and which the rule does list, as just modified)
-    csrc = os.path.join(REPO, "c-ray_amd", "csrc")
-    obj = os.path.join(EMU_DIR, "_obj", "kernel_emu.o")
-    stale = os.path.exists(obj) and os.path.getmtime(os.path.join(csrc, "idmatte.h")) > os.path.getmtime(obj)
-    locked_make(["make", "-s", "-C", EMU_DIR] + (["-W", os.path.join(csrc, "cray_hip.hip")] if stale else []) + ["libcray_hip_emu.so"])
-    assert os.path.getmtime(os.path.join(csrc, "idmatte.h")) <= os.path.getmtime(obj), "the emulation's kernel object is older than csrc/idmatte.h"
-    env = dict(os.environ, CRH_LIB=os.path.join(EMU_DIR, "libcray_hip_emu.so"), CRH_ALLOW_EMULATION="1", HIPEMU_CUS="2", HIPEMU_THREADS="3")
-    cmd = [sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider"]
-    r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=1700)
-    tail = (r.stdout + r.stderr)[-4000:]
-    assert r.returncode == 0, tail
-    m = re.search(r"(\d+) passed", r.stdout)
-    assert m and int(m.group(1)) == 9, tail
-    assert "skipped" not in r.stdout.strip().splitlines()[-1], tail
+    run_gpu_tests_on_emulation(__file__, 9)
+    header, obj = os.path.join(REPO, "c-ray_amd", "csrc", "idmatte.h"), os.path.join(EMU_DIR, "_obj", "kernel_emu.o")
+    assert os.path.getmtime(header) <= os.path.getmtime(obj), "the emulation's kernel object is older than csrc/idmatte.h"

@@ -22,9 +22,7 @@ import sys
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(REPO, "tests", "emu")
-EMU_LIB = os.path.join(EMU_DIR, "libcray_hip_emu.so")
+from support import DROPIN_LIBDIR, EMU_DIR, EMU_LIB, REPO, dropin_paths, emulation_env
 
 
 @pytest.fixture(scope="module")
@@ -55,7 +53,7 @@ def children(emu_lib):
     """Every child process of this module, started at once (they are independent; each runs the emulation on two OS threads): the module
     takes as long as its slowest child instead of the sum."""
     import tempfile
-    env = dict(os.environ, CRH_LIB=emu_lib, CRH_ALLOW_EMULATION="1", CRH_DROPIN_LIBDIR=os.path.join(EMU_DIR, "_dropin_libs"), HIPEMU_CUS="2", HIPEMU_THREADS="3")
+    env = emulation_env(CRH_DROPIN_LIBDIR=DROPIN_LIBDIR)
     procs = {}
 
     def start(name, cmd, **more_env):
@@ -272,8 +270,8 @@ def test_dropin_program_and_cluster_worker_on_emulation(children):
     config 1 through renderFrame() -> flatten -> C-ABI -> kernels (emulated) -> BMP encoder, normal and --iterative, and its `--worker` serves
     the reference's wire protocol to a test master: the reference's frame bit for bit, its tiles byte for byte. Needs the drop-in program and
     the asset overlay (built where /root/reference exists)."""
-    if not (os.path.exists(os.path.join(REPO, "c-ray_amd", "_lib", "c-ray-hip")) and os.path.exists(os.path.join(REPO, "oracle", "_ref", "input", "scene.json"))):
-        pytest.skip("c-ray-hip or the asset overlay is not built (needs /root/reference at build time)")
+    if not dropin_paths()[2]:
+        pytest.skip("c-ray-hip or the asset overlay is not built (needs the reference's sources at build time)")
     run_gpu_tier_on_emulation(children, "dropin")
 
 
@@ -286,13 +284,12 @@ def test_dropin_program_on_several_emulated_gpus(emu_lib, manifest, golden_ref, 
     import hashlib
     import json
     import numpy as np
-    exe = os.path.join(REPO, "c-ray_amd", "_lib", "c-ray-hip")
-    overlay = os.path.join(REPO, "oracle", "_ref", "input")
-    if not (os.path.exists(exe) and os.path.exists(os.path.join(overlay, "scene.json"))):
-        pytest.skip("c-ray-hip or the asset overlay is not built (needs /root/reference at build time)")
+    exe, overlay, built = dropin_paths()
+    if not built:
+        pytest.skip("c-ray-hip or the asset overlay is not built (needs the reference's sources at build time)")
     sys.path.insert(0, os.path.join(REPO, "tools"))
     import refrun
-    libdir = os.path.join(EMU_DIR, "_dropin_libs")
+    libdir = DROPIN_LIBDIR
     for mode, key, gpu_counts in (((), "cfg1_scene", (2, 5, 8)), (("--iterative",), "cfg1_scene_iterative", (3, 8))):
         m = manifest[key]
         w, h = manifest["cfg1_scene"]["width"], manifest["cfg1_scene"]["height"]

@@ -1,7 +1,7 @@
 """The node programs at their numeric edges: every pure node kind (checker, gradient — as a bsdf's operand, which the device evaluates outside the VM, and
 inside a program —, blackbody, combine, combineRGB, vecToColor, alpha, grayscale, the 15 math ops, fresnel, rayLength, normal, the 10 vecMath ops) on operands that no fixture holds — zero divisors, negative bases, subnormals, infinities, NaN, signed
 zeros, the clamps' boundaries — evaluated by the device VM per hit ("dynamic") and once on the host by the scene compiler ("folded"), and held to a restatement of
-the reference's sources (tests/test_graph_edges.py: Restatement) bit for bit, a NaN equal to a NaN of any payload.
+the reference's sources (tests/graph_spec.py: Restatement) bit for bit, a NaN equal to a NaN of any payload.
 
 Scenes are copies of nodezoo_display's description (tests/scene_synth.py); every graph is shown as diffuse(colour), so the albedo channel of crh_render_aov reads
 it out. A value operand that depends on the hit but is exact is alpha(image(T, NO_BILINEAR)) of a float RGBA texture:
@@ -14,36 +14,21 @@ CPU tier: coverage conditions from the oracle's hits, the special classes among 
 sky, the compiler's folding and its slot limit, and this file's GPU tests on the kernel emulation. GPU tier: albedo == restatement on every scene, dynamic ==
 folded directly, a full-path frame == the oracle's, and the refusal of a program that needs nine operand slots."""
 import ctypes as C
-import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import resize_camera
-from scene_synth import (COLOR_IMAGE, DIFFUSE, EMISSION, GLASS, IMAGE_NO_BILINEAR, IMAGE_SRGB_TRANSFORM, METAL, MIX, MATH_ABS, MATH_ADD, MATH_COS, MATH_DIVIDE, MATH_LOG, MATH_MAX, MATH_MIN,
-                         MATH_MULTIPLY, MATH_POWER, MATH_SIN, MATH_SQRT, MATH_SUBTRACT, MATH_TAN, MATH_TO_DEGREES, MATH_TO_RADIANS, VEC_ABS, VEC_ADD, VEC_CROSS,
-                         VEC_MULTIPLY, VEC_NORMALIZE, VEC_REFLECT, SynthScene)
-from test_aov import fold
-from test_graph_edges import base, ctx  # noqa: F401 (the module-scoped fixtures: nodezoo_display's scene, a device context)
-from test_graph_edges import (CUBE, EMU_DIR, MESH_CAMERA_A, PLANE, REPO, ForLibrary, Restatement, assert_aov, gpu_aov, same_bits, scene_hits, size_of,
-                              white_sky_selection)
+from firsthit_spec import fold
+from graph_spec import base  # noqa: F401 (the module-scoped fixture: nodezoo_display's scene)
+from graph_spec import (CUBE, FLT_MAX, FLT_MIN, INF, NAN, NB, PLANE, SUB_MAX, SUB_MIN, F, ForLibrary, Leaves, Restatement, S, assert_aov, bits, f32, gpu_aov, new_scene, same_bits,
+                        scene_hits, size_of, white_sky_selection)
+from scene_synth import (COLOR_IMAGE, DIFFUSE, EMISSION, GLASS, METAL, MIX, MATH_ABS, MATH_ADD, MATH_COS, MATH_DIVIDE, MATH_LOG, MATH_MAX, MATH_MIN, MATH_MULTIPLY, MATH_POWER,
+                         MATH_SIN, MATH_SQRT, MATH_SUBTRACT, MATH_TAN, MATH_TO_DEGREES, MATH_TO_RADIANS, VEC_ABS, VEC_CROSS, VEC_NORMALIZE, VEC_REFLECT)
+from support import ctx, run_gpu_tests_on_emulation  # noqa: F401 (ctx: the fixture)
 
-F = np.float32
-NB, S = IMAGE_NO_BILINEAR, IMAGE_SRGB_TRANSFORM
 SLOTS = 8          # CRH_PROG_SLOTS (c-ray_amd/csrc/pt_device.h)
 
 
-def f32(x):
-    return float(F(x))
-
-
-FLT_MAX, FLT_MIN = f32(np.finfo(F).max), f32(np.finfo(F).tiny)
-SUB_MIN = f32(np.finfo(F).smallest_subnormal)          # 1.4e-45
-SUB_MAX = f32(np.nextafter(F(FLT_MIN), F(0)))          # the largest subnormal
-INF, NAN = float("inf"), float("nan")
 PI = f32(np.pi)
 HALF_PI = f32(np.pi / 2)
 
@@ -85,36 +70,6 @@ VEC_PAIRS = [(ZERO, (1.0, 2.0, 3.0)),                                           
              ((FLT_MAX, -FLT_MAX, 1.0), (FLT_MAX, FLT_MAX, -2.0))]                # sums and products overflow to both infinities
 VEC_OP_NAMES = ["add", "subtract", "multiply", "average", "dot", "cross", "normalize", "reflect", "length", "abs"]
 WHITE = (1.0, 1.0, 1.0)
-
-
-def bits(x):
-    return int(F(x).view(np.uint32))
-
-
-# ---------------------------------------------------------------------------------------------------------------------------------------------------
-# Leaves: how a graph gets its operands
-# ---------------------------------------------------------------------------------------------------------------------------------------------------
-class Leaves:
-    """dynamic: a value is alpha(image(1 x 1 float RGBA texture, NO_BILINEAR)), a vector is add(C, multiply(normal, 0)); otherwise constants."""
-
-    def __init__(self, s, dynamic, textures=None):
-        self.s, self.dynamic, self.textures = s, dynamic, textures          # textures: the scene's shared image textures (new_scene), for the checkers' colours
-        self._tex = {}
-
-    def val(self, x):
-        s = self.s
-        if not self.dynamic:
-            return s.value(x)
-        if bits(x) not in self._tex:
-            self._tex[bits(x)] = s.texture(np.array([[[0.25, 0.5, 0.75, x]]], F))
-        return s.alpha(s.image(self._tex[bits(x)], NB))
-
-    def vec(self, x, y, z):
-        s = self.s
-        assert not any(bits(v) == bits(-0.0) for v in (x, y, z))
-        if not self.dynamic:
-            return s.vec(x, y, z)
-        return s.vecmath(VEC_ADD, s.vec(x, y, z), s.vecmath(VEC_MULTIPLY, s.normal(), s.vec(0.0, 0.0, 0.0)))
 
 
 def right_deep(s, L, ops, xs):
@@ -217,30 +172,6 @@ POOL = GRAPHS + CONST_LEAF
 MESH_CHECKERS = [(sc, images) for images in (False, True) for sc in CHECKER_SCALES]
 N_DYNAMIC = len(MESH_CHECKERS)
 N_SPHERE_SCENES = -(-len(POOL) // 60)
-
-
-def shared_textures(s):
-    """Two image textures for the checkers' colours, and as many more as the fixture's own (unshown) image nodes need to stay valid."""
-    rng = np.random.default_rng(20261018)
-    a = rng.integers(0, 256, (6, 7, 4), dtype=np.uint8)
-    tex = {"rgba7x6": s.texture(a), "rgbaf2x2": s.texture(rng.random((2, 2, 4), dtype=F))}
-    while s.texture_total() < s.base.desc.texture_count:
-        s.texture(np.zeros((1, 1, 3), np.uint8))
-    return tex
-
-
-def new_scene(base, view):
-    s = SynthScene(base)
-    s.drop_textures()
-    tex = shared_textures(s)
-    cam = s.desc.camera
-    if view == "spheres":
-        resize_camera(s, *size_of("spheres"))
-    else:
-        for k in range(12):
-            cam.A[k] = MESH_CAMERA_A[k]
-        resize_camera(s, *size_of(view))
-    return s, tex
 
 
 def show(s, labels, entries):
@@ -745,13 +676,4 @@ N_GPU_TESTS = len(GROUPS) + 1 + 2 + 2
 def test_node_edges_on_the_emulation():
     """CPU tier: this file's GPU tests run by a child pytest against the kernel emulation (tests/emu/libcray_hip_emu.so: k_aov, the render kernels and the scene
     compiler compiled unmodified on the HIP-on-CPU shim) — every one of them runs and passes there, none skipped."""
-    from conftest import locked_make
-    locked_make(["make", "-s", "-C", EMU_DIR, "libcray_hip_emu.so"])
-    env = dict(os.environ, CRH_LIB=os.path.join(EMU_DIR, "libcray_hip_emu.so"), CRH_ALLOW_EMULATION="1", HIPEMU_CUS="2", HIPEMU_THREADS="3")
-    cmd = [sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider"]
-    r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=1700)
-    tail = (r.stdout + r.stderr)[-4000:]
-    assert r.returncode == 0, tail
-    m = re.search(r"(\d+) passed", r.stdout)
-    assert m and int(m.group(1)) == N_GPU_TESTS, tail
-    assert "skipped" not in r.stdout.strip().splitlines()[-1], tail
+    run_gpu_tests_on_emulation(__file__, N_GPU_TESTS)

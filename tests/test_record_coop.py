@@ -13,16 +13,13 @@ GPU tier (-m gpu): the smallest shapes at which the exchange can go wrong, again
 single path slot in use (one partial quad, lanes 1..63 idle), batches whose size is no multiple of four with continuing and ending paths mixed inside a
 quad, tiles one, two and three pixels wide, and a scene with emission (non-zero radiance words through the exchange).
 
-Run as a script (`python tests/test_record_coop.py NAME ...` with CRH_LIB set) it is the child that renders and prints one JSON line per fixture.
+The variant builds and the child that renders the fixtures are tests/emu_variants.py's.
 """
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-from test_path_record_layout import EMU_DIR, EMU_FLAGS, EMU_LIB, FIXTURES, REPO, render
+from emu_variants import build_variants, render_with_each
+from support import ctx  # noqa: F401 (the module-scoped device context)
 
 SWITCHES = ("CRH_REC_COOP_LOAD", "CRH_REC_COOP_STORE", "CRH_MISS_SKIP_HIT")
 
@@ -30,28 +27,11 @@ SWITCHES = ("CRH_REC_COOP_LOAD", "CRH_REC_COOP_STORE", "CRH_MISS_SKIP_HIT")
 @pytest.fixture(scope="module")
 def libs(tmp_path_factory):
     """(the emulation library as built, the same source with the three switches at 0, ... and at 1)"""
-    from conftest import locked_make
-    locked_make(["make", "-s", "-C", EMU_DIR, "libcray_hip_emu.so"])
-    d = tmp_path_factory.mktemp("coop")
-    others = [os.path.join(EMU_DIR, "_obj", o) for o in ("bvh_emu.o", "hipemu.o", "scene_compile.o", "scene_blob.o")]
-    built = [(v, str(d / f"kernel_emu_{v}.o"), str(d / f"libcray_hip_emu_coop{v}.so")) for v in (0, 1)]
-    compiles = [subprocess.Popen(["g++"] + EMU_FLAGS + [f"-D{s}={v}" for s in SWITCHES] + ["-c", os.path.join(EMU_DIR, "kernel_emu.cpp"), "-o", obj]) for v, obj, _ in built]
-    assert [c.wait() for c in compiles] == [0, 0]
-    for _, obj, lib in built:
-        subprocess.check_call(["g++", "-shared", "-pthread", obj] + others + ["-ldl", "-o", lib])
-    return (EMU_LIB,) + tuple(lib for _, _, lib in built)
+    return build_variants(tmp_path_factory.mktemp("coop"), {f"coop{v}": [f"-D{s}={v}" for s in SWITCHES] for v in (0, 1)})
 
 
 def test_cooperative_record_access_is_bit_identical_to_the_plain_access(libs):
-    import json
-    env = dict(os.environ, CRH_ALLOW_EMULATION="1", HIPEMU_CUS="2", HIPEMU_THREADS="3")
-    procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__)] + FIXTURES, env=dict(env, CRH_LIB=lib), cwd=REPO,
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for lib in libs]
-    outs = [p.communicate(timeout=1700)[0] for p in procs]
-    for p, out in zip(procs, outs):
-        assert p.returncode == 0, out[-4000:]
-    coop, plain, all_on = ([json.loads(l) for l in out.splitlines() if l.startswith("{")] for out in outs)
-    assert [r["name"] for r in coop] == FIXTURES and [r["name"] for r in plain] == FIXTURES and [r["name"] for r in all_on] == FIXTURES, outs
+    coop, plain, all_on = render_with_each(libs)
     for a, b, c in zip(coop, plain, all_on):
         assert a["kernel"].startswith("k_pathtrace_roll<2,4,"), a
         assert a == b and a == c, (a, b, c)          # frame md5, level-2 counters, u_node / u_shade / u_swap lane sums
@@ -61,16 +41,6 @@ def test_cooperative_record_access_is_bit_identical_to_the_plain_access(libs):
 
 
 # ---- GPU tier ------------------------------------------------------------------------------------------------------------------------
-
-@pytest.fixture(scope="module")
-def ctx(pkg):
-    if pkg.api.device_count() < 1:
-        pytest.fail("GPU tier needs a HIP device; libcray_hip has no CPU fallback")
-    c = pkg.api.Context(0)
-    yield c
-    c.close()
-
-
 def against_oracle(pkg, ctx, oracle, blob, w, h, spp, bounces, tiles, lean=True):
     """Render the tiles on the GPU (one dispatch) and with the oracle; the frames must be equal bit for bit, the ray counts equal, nothing outside the tiles touched.
     lean: the scene must have run a lean instantiation — the one with the cooperative access."""
@@ -134,7 +104,3 @@ def test_emission_goes_through_the_exchange(pkg, ctx, oracle, manifest, golden_b
     x0, y0 = (w - 64) // 2, (h - 64) // 2
     img = against_oracle(pkg, ctx, oracle, golden_blob("glowmetal"), w, h, 4, m["bounces"], [(x0, y0, x0 + 64, y0 + 64)], lean=False)
     assert img.any()
-
-
-if __name__ == "__main__":
-    render(sys.argv[1:])

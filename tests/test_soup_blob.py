@@ -11,7 +11,9 @@ import sys
 import numpy as np
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from reference_checks import assert_same_bvh, mesh_views
+
+REPO =os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "tools"))
 
 
@@ -100,7 +102,6 @@ def test_soup_10m(pkg, oracle, tmp_path):
     # the GPU-built tree IS the reference's (round 5: until then only tests/test_bvh_build.py's meshes of up to 1 M triangles held the builder to that; here the same blob
     # went to the GPU and to the oracle, and a wrong-but-valid tree would have passed): the restated reference builder (oracle/bvh_oracle.c, pinned against the
     # reference's own trees inside every fixture blob) on the same 10 M polygons — 13 s of one core — node for node, bit for bit, prim order included
-    from test_bvh_build import assert_same_bvh, mesh_views
     d = scene.desc
     gpu_nodes, gpu_prims, polys, count = mesh_views(d, 0)
     assert count == n

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import camera_rays, image_stats, kernel_forms
+from support import emu_render
 
 
 def test_oracle_bit_exact_on_volumes(oracle, manifest, golden_blob, golden_ref):
@@ -28,7 +29,6 @@ def test_oracle_bit_exact_on_volumes(oracle, manifest, golden_blob, golden_ref):
 @pytest.mark.parametrize("shape,chunk", [((8, 8), 64), ((2, 2), 3)])
 def test_emulated_kernel_bit_exact_on_volumes(shape, chunk, emu, oracle, manifest, golden_blob, golden_ref):
     """The device lane code (walk state machine with the two volume phases, sampler draw through the path port) built for the host."""
-    from test_emu_parity import emu_render
     m = manifest["volumes"]
     scene = oracle.OracleScene(golden_blob("volumes"))
     fb, cnt, _ = emu_render(emu, oracle, scene, m["width"], m["height"], m["samples"], m["bounces"], shape=shape, chunk=chunk)
