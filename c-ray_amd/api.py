@@ -454,13 +454,17 @@ class Context:
         return float(ms.value)
 
     def write_layers_exr(self, path, width, height, fb, aov=None, denoised=None, instance_ids=None, material_ids=None, instance_names=None, material_names=None,
-                         chunk_rows=None, compression="none"):
-        """One multi-layer OpenEXR file (scanline, FLOAT channels) of the frame `fb` and whichever of the others is given: R G B; the guides of
+                         chunk_rows=None, compression="none", half=False):
+        """One multi-layer OpenEXR file (scanline, FLOAT channels; HALF ones with `half`) of the frame `fb` and whichever of the others is given: R G B; the guides of
         an AOV buffer as albedo.R/G/B, normal.X/Y/Z, Z and A, unscaled; a denoised frame as denoised.R/G/B; the ID buffers `instance_ids` / `material_ids`
         (render_ids) as the Cryptomatte layers CryptoObject00..02 / CryptoMaterial00..02 with their metadata. instance_names[i] / material_names[i] name id i
         (default instance#<i> / material#<i>, for every id up to the largest one the buffer holds). The ranking runs into scratch of this call's own; the pixel data is
         packed on the device, `chunk_rows` rows at a time (None: all at once). compression: "none", or "zips" / "zip" — a chunk a row / every 16 rows, deflated on the
-        device by the companion library (exrzip.py: loaded on first use; `chunk_rows` is rounded up to a multiple of 16 for "zip")."""
+        device by the companion library (exrzip.py: loaded on first use; `chunk_rows` is rounded up to a multiple of 16 for "zip").
+        half: True stores the colour layers that are present — R G B, albedo.R/G/B, normal.X/Y/Z, denoised.R/G/B — as 16-bit HALF channels, as compositors expect
+        them; Z, A and the Cryptomatte channels stay FLOAT. An iterable of channel names stores exactly those as HALF; a name the file does not have, or a
+        Cryptomatte channel, raises ValueError. The conversion rounds to nearest even (include/cray_hip_exr.h); values above 65504 become infinity — that is
+        the format, not a fault. With `half` every compression, "none" too, is packed by the companion library (crx_pack); falsy: today's paths and bytes."""
         from . import exrzip          # (binds the companion library on first use)
         if compression not in exrzip.COMPRESSION:
             raise ValueError(f"compression {compression!r}: one of {sorted(exrzip.COMPRESSION)}")
@@ -482,7 +486,13 @@ class Context:
                 strings.update(exr.crypto_attributes(exr.CRYPTO_LAYERS[k], names))
             chans = exr.layer_channels(fb, aov, denoised, ranked[0], ranked[1], maps[0], maps[1])
             step = height if not chunk_rows else chunk_rows
-            if compression == "none":
+            types = exr.half_types([c[0] for c in chans], half) if half else None
+            if types is not None:
+                kind, lines = exrzip.COMPRESSION[compression]
+                step = -(-step // lines) * lines
+                self.synchronize()          # the companion's stream may be another: its sources must be complete
+                parts = [self._zip_context().pack([c[1:] for c in chans], width, height, kind, types, y, min(step, height - y)) for y in range(0, height, step)]
+            elif compression == "none":
                 blocks = b"".join(self.pack_scanlines([c[1:] for c in chans], width, height, y, min(step, height - y)) for y in range(0, height, step))
             else:
                 kind, lines = exrzip.COMPRESSION[compression]
@@ -492,10 +502,10 @@ class Context:
         finally:
             for p in scratch:
                 self.L.crh_ids_free(self.h, p)
-        if compression == "none":
+        if types is None and compression == "none":
             data = exr.file_bytes(width, height, [c[0] for c in chans], blocks, strings)
         else:
-            data = exr.file_bytes_chunked(width, height, [c[0] for c in chans], b"".join(p[0] for p in parts), np.concatenate([p[1] for p in parts]), strings, kind)
+            data = exr.file_bytes_chunked(width, height, [c[0] for c in chans], b"".join(p[0] for p in parts), np.concatenate([p[1] for p in parts]), strings, kind, types)
         with open(path, "wb") as f:
             f.write(data)
         return [c[0] for c in chans]

@@ -1,6 +1,6 @@
 /*
- * exr_zip.h — the kernels of crx_pack_zip (include/cray_hip_exr.h): the chunks of a ZIP / ZIPS compressed scanline OpenEXR file, deflated on the device. Part of
- * libcray_hip_exr.so (exr_zip.hip); nothing of libcray_hip.so includes this file.
+ * exr_zip.h — the kernels of crx_pack_zip and crx_pack (include/cray_hip_exr.h): the chunks of a ZIP / ZIPS compressed scanline OpenEXR file, deflated on the device,
+ * with FLOAT or — crx_pack — per channel HALF pixels. Part of libcray_hip_exr.so (exr_zip.hip); nothing of libcray_hip.so includes this file.
  *
  * Four launches on one stream, ordered by launch order alone — no workgroup waits for another, every loop's trip count follows from CRX_SEG or the chunk size:
  *   k_zip_transform  gather + byte split + predictor in one pass: a lane makes four consecutive bytes of T' from the (at most three) raw words they come from,
@@ -18,10 +18,34 @@
  *                    shorter than n); then the chunks' positions in the output, their byte counts and the total.
  *   k_zip_emit       one workgroup per segment copies it behind the chunk's 8-byte header and the zlib header — or, in a raw chunk, gathers that stretch of
  *                    raw bytes from the sources; the first writes the headers and the Adler-32 trailer.
+ * A call whose channels are all FLOAT runs exactly these. A call with a HALF channel (crx_pack) runs k_zip_transform_mixed and k_zip_emit_mixed in their places:
+ * a row is no longer nch * width words but one plane of 2- or 4-byte pixels per channel, so byte i of a chunk is found as line i / rowBytes, the channel whose
+ * stretch of the row holds the rest (a binary search in the prefix table of the channels' byte offsets, at most 65 words, in LDS), pixel and byte within the
+ * pixel; a lane still makes four consecutive bytes of T' and stores one word. n is even but not always a multiple of 4: the T' pitch is whole words, the two
+ * bytes behind an n = 2 (mod 4) are stored as zero, k_zip_deflate takes no position at or beyond len into a match or a sum (`most`, `p < len`), and the raw
+ * gather ends in a 2-byte store. Compression 0 (crx_pack) launches only k_zip_scan, which then marks every chunk raw, and the emit.
  * Only __ballot, __shfl, __shfl_up, __shfl_xor, __syncthreads and atomicMax / atomicOr on 32-bit LDS words: the file compiles unmodified on tests/emu/hipemu.
  */
 #pragma once
 
+/* binary32 -> binary16, the rule of include/cray_hip_exr.h, in integer arithmetic: the same bits on the device, on the emulation and in tests/emu/half_check.cpp
+ * (which defines CRX_ZIP_CONVERSION_ONLY and takes this function alone). Round to nearest, ties to even; gradual underflow; |x| < 2^-25 and the tie 2^-25 to +-0;
+ * what rounds to 2^16 or more (|x| >= 65520) to +-infinity; a NaN keeps its top ten mantissa bits, bit 0 set if those are all zero. */
+__host__ __device__ __forceinline__ uint32_t zipHalfBits(uint32_t w) {
+	const uint32_t sign = (w >> 16) & 0x8000u, a = w & 0x7fffffffu;
+	if (a > 0x7f800000u) { const uint32_t m = (a >> 13) & 0x3ffu; return sign | 0x7c00u | m | (m == 0u ? 1u : 0u); }
+	if (a >= 0x477ff000u) return sign | 0x7c00u;          /* infinity, and what rounds to 2^16 or more */
+	if (a >= 0x38800000u) {                               /* a normal half: exponent rebiased by 112, rounded at bit 13 (a carry runs into the exponent) */
+		const uint32_t v = a - 0x38000000u;
+		return sign | ((v + 0xfffu + ((v >> 13) & 1u)) >> 13);
+	}
+	if (a < 0x33000000u) return sign;                     /* below 2^-25 */
+	const uint32_t shift = 126u - (a >> 23), m = (a & 0x7fffffu) | 0x800000u;          /* 14 .. 24: units of 2^-24 */
+	const uint32_t r = m >> shift, rest = m & ((1u << shift) - 1u), tie = 1u << (shift - 1u);
+	return sign | (r + (rest > tie || (rest == tie && (r & 1u)) ? 1u : 0u));
+}
+
+#ifndef CRX_ZIP_CONVERSION_ONLY
 #define CRX_SEG 4096u                 /* bytes of T' per segment (a multiple of 256) */
 #define CRX_SEG_OUT 4640u             /* bytes a segment's output can take: 3 + 9 * CRX_SEG + 7 + 3 bits, padded to a byte, + 4: 4614, rounded up to a multiple of 32 */
 #define CRX_HASH_BITS 11
@@ -31,19 +55,23 @@
 struct ZipChan {
 	const uint32_t *src;          /* [H, W, stride] words */
 	const uint32_t *map;          /* device copy of the map, or null */
-	uint32_t stride, component, mapCount, pad;
+	uint32_t stride, component, mapCount, half;          /* half: stored as binary16 (never with a map) */
 };
 struct ZipArgs { ZipChan ch[CRH_PACK_MAX_CHANNELS]; };
+struct ZipRow { uint32_t off[CRH_PACK_MAX_CHANNELS + 1u]; };          /* where channel c's plane starts in a stored row, in bytes; off[nch] = rowBytes */
 struct ZipGeom {
 	uint32_t nch, width, firstRow, rowCount;          /* rowCount rows from stored row firstRow */
 	uint32_t lpc, nchunks;                            /* lines per chunk, chunks of this call */
-	uint32_t fullBytes;                               /* 4 * nch * width * lpc: the raw bytes of a full chunk, and the pitch of the T' buffer */
+	uint32_t fullBytes;                               /* rowBytes * lpc: the raw bytes of a full chunk */
 	uint32_t segsPerChunk;                            /* ceil(fullBytes / CRX_SEG) */
+	uint32_t rowBytes;                                /* width * the sum of the channels' pixel sizes: 4 * nch * width where all are FLOAT */
+	uint32_t pitch;                                   /* words a chunk in the T' buffer: ceil(fullBytes / 4) */
+	uint32_t allRaw;                                  /* compression 0: k_zip_scan marks every chunk raw, nothing was deflated */
 };
 
 __host__ __device__ __forceinline__ uint32_t zipMin(uint32_t a, uint32_t b) { return a < b ? a : b; }
 /* raw bytes of chunk k of the call (the last one of the image may be short) */
-__host__ __device__ __forceinline__ uint32_t zipChunkBytes(const ZipGeom &G, uint32_t k) { return 4u * G.nch * G.width * zipMin(G.lpc, G.rowCount - k * G.lpc); }
+__host__ __device__ __forceinline__ uint32_t zipChunkBytes(const ZipGeom &G, uint32_t k) { return G.rowBytes * zipMin(G.lpc, G.rowCount - k * G.lpc); }
 
 /* the word a mapped channel stores for the source word w (exr_pack.h's rule: converted only once it is known to lie in [0, mapCount)) */
 __device__ __forceinline__ uint32_t zipMapped(const ZipChan &k, uint32_t w) {
@@ -85,7 +113,58 @@ __global__ __launch_bounds__(256) void k_zip_transform(const ZipArgs A, const Zi
 	}
 	uint32_t out = 0u;
 	for (uint32_t b = 0; b < 4u; ++b) out |= ((wi == 0u && b == 0u ? t[1] : t[b + 1] - t[b] + 128u) & 255u) << (8u * b);
-	T[(size_t)k * (G.fullBytes / 4u) + wi] = out;
+	T[(size_t)k * G.pitch + wi] = out;
+}
+
+/* ---- mixed HALF / FLOAT rows ---- */
+/* the element last fetched: bytes [lo, hi) of the chunk are the little-endian bytes of v; it lies in the plane [planeLo, planeHi) of channel c on stored row y */
+struct ZipHeld { uint32_t lo, hi, v, planeLo, planeHi, c, y; };
+
+/* byte i of chunk k's raw bytes; off: the prefix table in LDS. Consecutive calls mostly stay in one plane: only leaving it costs the division and the search. */
+__device__ __forceinline__ uint32_t zipMixedByte(const ZipArgs &A, const ZipGeom &G, const uint32_t *off, uint32_t k, uint32_t i, ZipHeld &h) {
+	if (i < h.lo || i >= h.hi) {
+		if (i < h.planeLo || i >= h.planeHi) {
+			const uint32_t line = i / G.rowBytes, rest = i - line * G.rowBytes;
+			uint32_t c = 0u, end = G.nch;          /* off[c] <= rest < off[end] */
+			while (end - c > 1u) {
+				const uint32_t mid = (c + end) >> 1;
+				if (off[mid] <= rest) c = mid; else end = mid;
+			}
+			h.c = c; h.y = G.firstRow + k * G.lpc + line;
+			h.planeLo = line * G.rowBytes + off[c]; h.planeHi = line * G.rowBytes + off[c + 1u];
+		}
+		const ZipChan &ch = A.ch[h.c];
+		const uint32_t within = i - h.planeLo, x = ch.half ? within >> 1 : within >> 2;
+		uint32_t w = ch.src[((size_t)h.y * G.width + x) * ch.stride + ch.component];
+		if (ch.map) w = zipMapped(ch, w);
+		if (ch.half) { h.v = zipHalfBits(w); h.lo = h.planeLo + 2u * x; h.hi = h.lo + 2u; }
+		else { h.v = w; h.lo = h.planeLo + 4u * x; h.hi = h.lo + 4u; }
+	}
+	return (h.v >> (8u * (i - h.lo))) & 255u;
+}
+
+/* k_zip_transform for rows with HALF channels: the same four bytes of T' a lane, from up to five elements; the bytes behind n in a chunk's last word are zero */
+__global__ __launch_bounds__(256) void k_zip_transform_mixed(const ZipArgs A, const ZipRow R, const ZipGeom G, uint32_t blocksPerChunk, uint32_t *T) {
+	__shared__ uint32_t sOff[CRH_PACK_MAX_CHANNELS + 1u];
+	if (threadIdx.x <= G.nch) sOff[threadIdx.x] = R.off[threadIdx.x];
+	__syncthreads();
+	const uint32_t k = blockIdx.x / blocksPerChunk, wi = (blockIdx.x - k * blocksPerChunk) * 256u + threadIdx.x;
+	const uint32_t n = zipChunkBytes(G, k);          /* even */
+	if (4u * wi >= n) return;
+	const uint32_t half = n / 2u;
+	ZipHeld h = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
+	uint32_t t[5];
+	for (uint32_t b = 0; b < 5u; ++b) {                /* T[4 wi - 1] .. T[4 wi + 3] */
+		const uint32_t j = 4u * wi + b - 1u;
+		if ((wi == 0u && b == 0u) || j >= n) { t[b] = 0u; continue; }
+		t[b] = zipMixedByte(A, G, sOff, k, j < half ? 2u * j : 2u * (j - half) + 1u, h);
+	}
+	uint32_t out = 0u;
+	for (uint32_t b = 0; b < 4u; ++b) {
+		if (4u * wi + b >= n) break;
+		out |= ((wi == 0u && b == 0u ? t[1] : t[b + 1] - t[b] + 128u) & 255u) << (8u * b);
+	}
+	T[(size_t)k * G.pitch + wi] = out;
 }
 
 /* ---- fixed Huffman codes (RFC 1951, 3.2.6), packed from bit 0: Huffman codes enter most significant bit first, extra bits least significant first ---- */
@@ -145,7 +224,7 @@ __global__ __launch_bounds__(64) void k_zip_deflate(const ZipGeom G, const uint3
 	if (begin >= n) return;          /* (the whole wave: a short last chunk has fewer segments) */
 	const uint32_t len = zipMin(CRX_SEG, n - begin), lane = threadIdx.x;
 	const bool last = begin + len == n;
-	const uint32_t *const src = T + (size_t)k * (G.fullBytes / 4u) + begin / 4u;
+	const uint32_t *const src = T + (size_t)k * G.pitch + begin / 4u;
 	for (uint32_t i = lane; i < CRX_SEG / 4u + 4u; i += 64u) sData[i] = 4u * i < len ? src[i] : 0u;
 	for (uint32_t i = lane; i < (1u << CRX_HASH_BITS); i += 64u) sHash[i] = 0u;
 	for (uint32_t i = lane; i < CRX_SEG_OUT / 4u; i += 64u) sBits[i] = lane == 0u && i == 0u ? (last ? 1u : 0u) | 2u : 0u;          /* BFINAL, BTYPE 01 */
@@ -237,7 +316,7 @@ __global__ __launch_bounds__(256) void k_zip_scan(const ZipGeom G, const uint32_
 	for (uint32_t k = threadIdx.x; k < G.nchunks; k += 256u) {
 		const uint32_t n = zipChunkBytes(G, k), segs = (n + CRX_SEG - 1u) / CRX_SEG;
 		uint32_t a = 1u, b = 0u, off = 0u;          /* (off <= segs * CRX_SEG_OUT < 2^32 for n < 2^31) */
-		for (uint32_t s = 0; s < segs; ++s) {
+		for (uint32_t s = 0; s < segs && !G.allRaw; ++s) {
 			const size_t at = (size_t)k * G.segsPerChunk + s;
 			const uint32_t *const meta = segMeta + 4u * at;
 			segOff[at] = off;
@@ -246,7 +325,7 @@ __global__ __launch_bounds__(256) void k_zip_scan(const ZipGeom G, const uint32_
 			a = (a + meta[1]) % CRX_ADLER;
 		}
 		const uint64_t stream = 2u + (uint64_t)off + 4u;
-		const bool raw = stream >= n;
+		const bool raw = G.allRaw || stream >= n;
 		uint32_t *const info = chunkInfo + 4u * (size_t)k;
 		info[0] = raw ? n : (uint32_t)stream; info[1] = raw ? 1u : 0u; info[2] = b << 16 | a; info[3] = 0u;
 	}
@@ -264,9 +343,10 @@ __global__ __launch_bounds__(256) void k_zip_scan(const ZipGeom G, const uint32_
 
 __device__ __forceinline__ void zipStore4(uint8_t *p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
 
-/* One workgroup per segment: its bytes to their place in the output */
-__global__ __launch_bounds__(256) void k_zip_emit(const ZipArgs A, const ZipGeom G, const uint32_t *segOut, const uint32_t *segMeta, const uint32_t *segOff,
-                                                  const uint32_t *chunkInfo, const uint64_t *chunkPos, uint8_t *out) {
+/* One workgroup per segment: its bytes to their place in the output. MIXED: rows with HALF channels (off: their prefix table in LDS) */
+template <bool MIXED>
+__device__ __forceinline__ void zipEmit(const ZipArgs &A, const ZipGeom &G, const uint32_t *off, const uint32_t *segOut, const uint32_t *segMeta, const uint32_t *segOff,
+                                        const uint32_t *chunkInfo, const uint64_t *chunkPos, uint8_t *out) {
 	const uint32_t k = blockIdx.x / G.segsPerChunk, seg = blockIdx.x - k * G.segsPerChunk;
 	const uint32_t n = zipChunkBytes(G, k), begin = seg * CRX_SEG;
 	if (begin >= n) return;
@@ -281,7 +361,14 @@ __global__ __launch_bounds__(256) void k_zip_emit(const ZipArgs A, const ZipGeom
 			t[0] = (uint8_t)(adler >> 24); t[1] = (uint8_t)(adler >> 16); t[2] = (uint8_t)(adler >> 8); t[3] = (uint8_t)adler;
 		}
 	}
-	if (raw) {
+	if (raw && MIXED) {
+		const uint32_t bytes = zipMin(CRX_SEG, n - begin);          /* even */
+		ZipHeld h = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
+		for (uint32_t w = threadIdx.x; 4u * w < bytes; w += 256u) {
+			uint8_t *const to = chunk + 8u + begin + 4u * w;
+			for (uint32_t b = 0; b < 4u && 4u * w + b < bytes; ++b) to[b] = (uint8_t)zipMixedByte(A, G, off, k, begin + 4u * w + b, h);          /* a last 2-byte store */
+		}
+	} else if (raw) {
 		const uint32_t words = zipMin(CRX_SEG, n - begin) / 4u;
 		for (uint32_t w = threadIdx.x; w < words; w += 256u) zipStore4(chunk + 8u + begin + 4u * w, zipRawWord(A, G, k, begin / 4u + w));
 	} else {
@@ -291,3 +378,17 @@ __global__ __launch_bounds__(256) void k_zip_emit(const ZipArgs A, const ZipGeom
 		for (uint32_t i = threadIdx.x; i < bytes; i += 256u) to[i] = from[i];
 	}
 }
+
+__global__ __launch_bounds__(256) void k_zip_emit(const ZipArgs A, const ZipGeom G, const uint32_t *segOut, const uint32_t *segMeta, const uint32_t *segOff,
+                                                  const uint32_t *chunkInfo, const uint64_t *chunkPos, uint8_t *out) {
+	zipEmit<false>(A, G, nullptr, segOut, segMeta, segOff, chunkInfo, chunkPos, out);
+}
+
+__global__ __launch_bounds__(256) void k_zip_emit_mixed(const ZipArgs A, const ZipRow R, const ZipGeom G, const uint32_t *segOut, const uint32_t *segMeta, const uint32_t *segOff,
+                                                        const uint32_t *chunkInfo, const uint64_t *chunkPos, uint8_t *out) {
+	__shared__ uint32_t sOff[CRH_PACK_MAX_CHANNELS + 1u];
+	if (threadIdx.x <= G.nch) sOff[threadIdx.x] = R.off[threadIdx.x];
+	__syncthreads();
+	zipEmit<true>(A, G, sOff, segOut, segMeta, segOff, chunkInfo, chunkPos, out);
+}
+#endif          /* CRX_ZIP_CONVERSION_ONLY */

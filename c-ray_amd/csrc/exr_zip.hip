@@ -79,43 +79,57 @@ int crx_context_destroy(crx_ctx *c) {
 	return CRH_OK;
 }
 
-int crx_pack_zip(crx_ctx *c, const crh_pack_channel *ch, uint32_t nch, int width, int height, int first_row, int row_count, int lines_per_chunk, void *host_out,
-                 uint64_t *chunk_bytes_host, uint64_t *total_bytes) {
+}  // extern "C"
+
+namespace {
+/* crx_pack_zip (types NULL, allRaw false) and crx_pack. A call without a HALF channel launches k_zip_transform and k_zip_emit, as it always has. */
+int pack(const char *who, crx_ctx *c, const crh_pack_channel *ch, const uint8_t *types, uint32_t nch, int width, int height, int first_row, int row_count, int lines_per_chunk,
+         bool allRaw, void *host_out, uint64_t *chunk_bytes_host, uint64_t *total_bytes) {
 	bool ok = c && ch && host_out && chunk_bytes_host && total_bytes && nch >= 1 && nch <= CRH_PACK_MAX_CHANNELS && width > 0 && height > 0 && first_row >= 0 &&
 	          row_count >= 0 && row_count <= height - first_row && (uint64_t)nch * (uint64_t)width < (1ull << 29) - 2u && (lines_per_chunk == 1 || lines_per_chunk == 16);
-	ok = ok && first_row % lines_per_chunk == 0 && (first_row + row_count == height || (first_row + row_count) % lines_per_chunk == 0) &&
-	     4ull * nch * (uint64_t)width * (uint64_t)lines_per_chunk < (1ull << 31);
+	ok = ok && first_row % lines_per_chunk == 0 && (first_row + row_count == height || (first_row + row_count) % lines_per_chunk == 0);
 	ZipArgs A;
+	ZipRow R;
 	memset(&A, 0, sizeof(A));
+	memset(&R, 0, sizeof(R));
 	size_t mapAt[CRH_PACK_MAX_CHANNELS], mapWords = 0;          /* channels that name the same map share its copy; the first of them in the list (bit i) uploads it */
 	uint64_t first = 0;
+	bool mixed = false;
 	for (uint32_t i = 0; ok && i < nch; ++i) {
 		const crh_pack_channel &k = ch[i];
-		ok = k.dev_src && k.stride >= 1 && k.stride <= 64 && k.component < k.stride && k.map_count <= 65536 && (!k.map_host || k.map_count);
-		A.ch[i] = ZipChan{(const uint32_t *)k.dev_src, k.map_host, k.stride, k.component, k.map_count, 0};
+		const uint32_t type = types ? types[i] : (uint32_t)CRX_PIXEL_FLOAT;
+		ok = k.dev_src && k.stride >= 1 && k.stride <= 64 && k.component < k.stride && k.map_count <= 65536 && (!k.map_host || k.map_count) &&
+		     (type == CRX_PIXEL_FLOAT || (type == CRX_PIXEL_HALF && !k.map_host));
+		A.ch[i] = ZipChan{(const uint32_t *)k.dev_src, k.map_host, k.stride, k.component, k.map_count, type == CRX_PIXEL_HALF ? 1u : 0u};
+		R.off[i + 1u] = R.off[i] + (type == CRX_PIXEL_HALF ? 2u : 4u) * (uint32_t)width;          /* (< 2^31: nch * width < 2^29) */
+		mixed = mixed || type == CRX_PIXEL_HALF;
 		uint32_t j = 0;
 		while (j < i && (ch[j].map_host != k.map_host || ch[j].map_count != k.map_count)) ++j;
 		mapAt[i] = j < i ? mapAt[j] : mapWords;
 		if (j == i && k.map_host) { first |= 1ull << i; mapWords += k.map_count; }
 	}
-	if (!ok) return fail(CRH_ERR_INVALID, "crx_pack_zip: bad argument");
+	ok = ok && (uint64_t)R.off[nch] * (uint64_t)lines_per_chunk < (1ull << 31);
+	if (!ok) return fail(CRH_ERR_INVALID, std::string(who) + ": bad argument");
 	if (row_count == 0) { *total_bytes = 0; return CRH_OK; }
 
 	ZipGeom G;
 	G.nch = nch; G.width = (uint32_t)width; G.firstRow = (uint32_t)first_row; G.rowCount = (uint32_t)row_count; G.lpc = (uint32_t)lines_per_chunk;
 	G.nchunks = (G.rowCount + G.lpc - 1u) / G.lpc;
-	G.fullBytes = 4u * nch * G.width * G.lpc;
+	G.rowBytes = R.off[nch];
+	G.fullBytes = G.rowBytes * G.lpc;
+	G.pitch = (G.fullBytes + 3u) / 4u;
+	G.allRaw = allRaw ? 1u : 0u;
 	G.segsPerChunk = (G.fullBytes + CRX_SEG - 1u) / CRX_SEG;
-	const uint32_t blocksPerChunk = (G.fullBytes / 4u + 255u) / 256u;
+	const uint32_t blocksPerChunk = (G.pitch + 255u) / 256u;
 	const uint64_t segs = (uint64_t)G.nchunks * G.segsPerChunk, blocks = (uint64_t)G.nchunks * blocksPerChunk;
-	if (segs >= (1ull << 31) || blocks >= (1ull << 31)) return fail(CRH_ERR_NOMEM, "crx_pack_zip: too many rows for one call (pass fewer rows at a time)");
-	const size_t rawBytes = 4u * (size_t)nch * (size_t)width * (size_t)row_count, outBytes = 8u * (size_t)G.nchunks + rawBytes;
+	if (segs >= (1ull << 31) || blocks >= (1ull << 31)) return fail(CRH_ERR_NOMEM, std::string(who) + ": too many rows for one call (pass fewer rows at a time)");
+	const size_t rawBytes = (size_t)G.rowBytes * (size_t)row_count, outBytes = 8u * (size_t)G.nchunks + rawBytes;
 	const size_t sizeWords = 2u * (size_t)G.nchunks + 1u;          /* chunkPos */
 
 	HIP_TRY(hipSetDevice(c->device));
 	int rc;
-	if ((rc = c->dT.grow(c->stream, (size_t)G.nchunks * (G.fullBytes / 4u)))) return rc;
-	if ((rc = c->dSegOut.grow(c->stream, (size_t)segs * (CRX_SEG_OUT / 4u)))) return rc;
+	if ((rc = c->dT.grow(c->stream, allRaw ? 1u : (size_t)G.nchunks * G.pitch))) return rc;
+	if ((rc = c->dSegOut.grow(c->stream, allRaw ? 1u : (size_t)segs * (CRX_SEG_OUT / 4u)))) return rc;
 	if ((rc = c->dMeta.grow(c->stream, 5u * (size_t)segs + 4u * (size_t)G.nchunks))) return rc;
 	if ((rc = c->dMaps.grow(c->stream, mapWords ? mapWords : 1u))) return rc;
 	if ((rc = c->dPos.grow(c->stream, sizeWords))) return rc;
@@ -130,16 +144,22 @@ int crx_pack_zip(crx_ctx *c, const crh_pack_channel *ch, uint32_t nch, int width
 		A.ch[i].map = dev;
 	}
 	if ((rc = c->watch.start(c->stream))) return rc;
-	hipLaunchKernelGGL(k_zip_transform, dim3((uint32_t)blocks), dim3(256), 0, c->stream, A, G, blocksPerChunk, c->dT.p);
-	HIP_TRY(hipGetLastError());
+	if (!allRaw) {
+		if (mixed) hipLaunchKernelGGL(k_zip_transform_mixed, dim3((uint32_t)blocks), dim3(256), 0, c->stream, A, R, G, blocksPerChunk, c->dT.p);
+		else hipLaunchKernelGGL(k_zip_transform, dim3((uint32_t)blocks), dim3(256), 0, c->stream, A, G, blocksPerChunk, c->dT.p);
+		HIP_TRY(hipGetLastError());
+	}
 	if ((rc = c->watch.mark(c->stream))) return rc;
-	hipLaunchKernelGGL(k_zip_deflate, dim3((uint32_t)segs), dim3(64), 0, c->stream, G, c->dT.p, c->dSegOut.p, segMeta);
-	HIP_TRY(hipGetLastError());
+	if (!allRaw) {
+		hipLaunchKernelGGL(k_zip_deflate, dim3((uint32_t)segs), dim3(64), 0, c->stream, G, c->dT.p, c->dSegOut.p, segMeta);
+		HIP_TRY(hipGetLastError());
+	}
 	if ((rc = c->watch.mark(c->stream))) return rc;
 	hipLaunchKernelGGL(k_zip_scan, dim3(1), dim3(256), 0, c->stream, G, segMeta, segOff, chunkInfo, c->dPos.p);
 	HIP_TRY(hipGetLastError());
 	if ((rc = c->watch.mark(c->stream))) return rc;
-	hipLaunchKernelGGL(k_zip_emit, dim3((uint32_t)segs), dim3(256), 0, c->stream, A, G, c->dSegOut.p, segMeta, segOff, chunkInfo, c->dPos.p, c->dOut.p);
+	if (mixed) hipLaunchKernelGGL(k_zip_emit_mixed, dim3((uint32_t)segs), dim3(256), 0, c->stream, A, R, G, c->dSegOut.p, segMeta, segOff, chunkInfo, c->dPos.p, c->dOut.p);
+	else hipLaunchKernelGGL(k_zip_emit, dim3((uint32_t)segs), dim3(256), 0, c->stream, A, G, c->dSegOut.p, segMeta, segOff, chunkInfo, c->dPos.p, c->dOut.p);
 	HIP_TRY(hipGetLastError());
 	if ((rc = c->watch.mark(c->stream))) return rc;
 	c->watch.stop();
@@ -149,13 +169,27 @@ int crx_pack_zip(crx_ctx *c, const crh_pack_channel *ch, uint32_t nch, int width
 	HIP_TRY(hipMemcpyAsync(sizes, c->dPos.p, sizeWords * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	const uint64_t total = sizes[2u * (size_t)G.nchunks];
-	if (total > outBytes || total < 8u * (uint64_t)G.nchunks) return fail(CRH_ERR_HIP, "crx_pack_zip: the device reported an impossible size");
+	if (total > outBytes || total < 8u * (uint64_t)G.nchunks) return fail(CRH_ERR_HIP, std::string(who) + ": the device reported an impossible size");
 	memcpy(chunk_bytes_host, sizes + G.nchunks, G.nchunks * sizeof(uint64_t));
 	*total_bytes = total;
 	HIP_TRY(hipMemcpyAsync(c->pinned, c->dOut.p, total, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	memcpy(host_out, c->pinned, total);
 	return CRH_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int crx_pack_zip(crx_ctx *c, const crh_pack_channel *ch, uint32_t nch, int width, int height, int first_row, int row_count, int lines_per_chunk, void *host_out,
+                 uint64_t *chunk_bytes_host, uint64_t *total_bytes) {
+	return pack("crx_pack_zip", c, ch, nullptr, nch, width, height, first_row, row_count, lines_per_chunk, false, host_out, chunk_bytes_host, total_bytes);
+}
+
+int crx_pack(crx_ctx *c, const crh_pack_channel *ch, const uint8_t *pixel_types, uint32_t nch, int width, int height, int first_row, int row_count, int compression,
+             void *host_out, uint64_t *chunk_bytes_host, uint64_t *total_bytes) {
+	if (compression != 0 && compression != 2 && compression != 3) return fail(CRH_ERR_INVALID, "crx_pack: bad argument (compression is 0, 2 or 3)");
+	return pack("crx_pack", c, ch, pixel_types, nch, width, height, first_row, row_count, compression == 3 ? 16 : 1, compression == 0, host_out, chunk_bytes_host, total_bytes);
 }
 
 int crx_pack_zip_phases_ms(crx_ctx *c, float phases_ms[CRX_ZIP_PHASES]) {

@@ -1,11 +1,14 @@
-"""exr.py — the host side of the multi-layer OpenEXR output: a single-part scanline file whose channels are all FLOAT — uncompressed, or ZIP / ZIPS
-compressed from chunks deflated on the device (file_bytes_chunked; Context.write_layers_exr(compression=...), exrzip.py) —, and Cryptomatte's naming of ids.
+"""exr.py — the host side of the multi-layer OpenEXR output: a single-part scanline file whose channels are FLOAT or, where asked for, HALF (`pixel_types`;
+Context.write_layers_exr(half=...)) — uncompressed, or ZIP / ZIPS compressed from chunks deflated on the device (file_bytes_chunked;
+Context.write_layers_exr(compression=...), exrzip.py) —, and Cryptomatte's naming of ids.
 The pixel data comes packed from the device (Context.pack_scanlines: crh_pack_scanlines, include/cray_hip.h); this module writes what goes around it — header, offset table — and knows which channel of which buffer carries which name. c-ray_amd/host/exr_write.c states the same in C
 for the drop-in program; both write the same bytes.
 
 File layout: magic 76 2f 31 01, version 02 00 00 00, attributes in ascending byte order of name (each `name\\0 type\\0 int32 size, value`), one \\0,
 `height` uint64 absolute offsets, then per stored row (row 0 = the top of the image = y 0, lineOrder increasing y) a block of int32 y,
-int32 4 * channels * width and one plane of `width` floats per channel, channels in ascending byte order of name.
+int32 4 * channels * width and one plane of `width` floats per channel, channels in ascending byte order of name. With HALF channels a row is
+`width` 2-byte pixels for each of those and the byte count is width * (the sum of the channels' pixel sizes); the offset table then has one entry per chunk
+(file_bytes_chunked, also for compression 0: a chunk a row).
 """
 import json
 import struct
@@ -92,16 +95,22 @@ def _attr(name, kind, value):
     return raw + b"\0" + kind.encode() + b"\0" + struct.pack("<i", len(value)) + value
 
 
-def header(width, height, channel_names, strings=None, compression=0):
+FLOAT, HALF = 0, 1          # pixel types as crx_pack takes them (include/cray_hip_exr.h); the file's chlist says 2 and 1
+PIXEL_BYTES = {FLOAT: 4, HALF: 2}
+
+
+def header(width, height, channel_names, strings=None, compression=0, pixel_types=None):
     """The bytes before the offset table. channel_names must be in ascending byte order; `strings` are further attributes of type string; `compression` is the
-    value of the attribute of that name: 0 none, 2 ZIPS (a chunk a row), 3 ZIP (a chunk every 16 rows)."""
+    value of the attribute of that name: 0 none, 2 ZIPS (a chunk a row), 3 ZIP (a chunk every 16 rows); `pixel_types`: FLOAT or HALF per channel (None: all FLOAT)."""
     assert compression in (0, 2, 3)
+    types = [FLOAT] * len(channel_names) if pixel_types is None else [int(t) for t in pixel_types]
+    assert len(types) == len(channel_names) and all(t in PIXEL_BYTES for t in types), "one pixel type, FLOAT or HALF, per channel"
     raw = [c.encode("utf-8") for c in channel_names]
     assert raw == sorted(raw) and len(set(raw)) == len(raw), "channels must be unique and in ascending byte order of name"
     chlist = b""
-    for c in raw:
+    for c, t in zip(raw, types):
         assert 0 < len(c) <= MAX_NAME, f"channel name {c!r} is longer than {MAX_NAME} bytes"
-        chlist += c + b"\0" + struct.pack("<iB3xii", 2, 0, 1, 1)          # FLOAT, pLinear 0, xSampling 1, ySampling 1
+        chlist += c + b"\0" + struct.pack("<iB3xii", 1 if t == HALF else 2, 0, 1, 1)          # HALF 1 / FLOAT 2, pLinear 0, xSampling 1, ySampling 1
     chlist += b"\0"
     window = struct.pack("<4i", 0, 0, width - 1, height - 1)
     attrs = {"channels": ("chlist", chlist), "compression": ("compression", bytes([compression])), "dataWindow": ("box2i", window), "displayWindow": ("box2i", window),
@@ -128,14 +137,15 @@ def file_bytes(width, height, channel_names, blocks, strings=None):
 LINES_PER_CHUNK = {0: 1, 2: 1, 3: 16}          # by the compression attribute
 
 
-def file_bytes_chunked(width, height, channel_names, chunk_data, chunk_sizes, strings=None, compression=3):
+def file_bytes_chunked(width, height, channel_names, chunk_data, chunk_sizes, strings=None, compression=3, pixel_types=None):
     """The whole file of compression 2 (ZIPS) or 3 (ZIP): `chunk_data` is the chunks back to back in row order as crx_pack_zip writes them (include/cray_hip_exr.h:
-    int32 y, int32 size, `size` bytes), `chunk_sizes` their byte counts (8 + size). The offset table has one entry per chunk; the chunks follow verbatim."""
-    assert compression in (2, 3)
+    int32 y, int32 size, `size` bytes), `chunk_sizes` their byte counts (8 + size). The offset table has one entry per chunk; the chunks follow verbatim.
+    With `pixel_types` (FLOAT or HALF per channel, the chunks as crx_pack writes them) compression 0 is accepted as well: a raw chunk a row."""
+    assert compression in (2, 3) or (compression == 0 and pixel_types is not None)
     sizes = [int(v) for v in chunk_sizes]
     assert len(sizes) == -(-height // LINES_PER_CHUNK[compression]), "one chunk for every LINES_PER_CHUNK rows"
     assert sum(sizes) == len(chunk_data) and all(v >= 8 for v in sizes), "the chunk sizes do not add up to the chunk data"
-    head = header(width, height, channel_names, strings, compression)
+    head = header(width, height, channel_names, strings, compression, pixel_types)
     at, offsets = len(head) + 8 * len(sizes), []
     for v in sizes:
         offsets.append(at)
@@ -143,14 +153,49 @@ def file_bytes_chunked(width, height, channel_names, chunk_data, chunk_sizes, st
     return head + struct.pack(f"<{len(sizes)}Q", *offsets) + bytes(chunk_data)
 
 
-def pack_host(planes, width, height):
-    """The pixel data from host arrays — planes: [height, width] arrays of 32-bit words in channel order —, for files that never were on a device."""
+def half_bits(words):
+    """The binary16 bits crx_pack stores for 32-bit words read as binary32 (include/cray_hip_exr.h's rule: numpy's astype(float16))."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        return np.ascontiguousarray(words).view(np.float32).astype(np.float16).view(np.uint16)
+
+
+def pack_host(planes, width, height, pixel_types=None):
+    """The pixel data from host arrays — planes: [height, width] arrays of 32-bit words in channel order —, for files that never were on a device. With
+    `pixel_types` the typed form, as crx_pack lays out compression 0: per row int32 y, int32 rowBytes and a plane per channel of 4-byte words or, for HALF,
+    of the words' binary16 conversions; file_bytes_chunked(..., [8 + rowBytes] * height, compression=0, pixel_types=...) takes it."""
+    if pixel_types is not None:
+        assert len(pixel_types) == len(planes)
+        words = [np.ascontiguousarray(p).view(np.uint32).reshape(height, width) for p in planes]
+        typed = [half_bits(p).astype("<u2").view(np.uint8) if t == HALF else p.astype("<u4").view(np.uint8) for p, t in zip(words, pixel_types)]
+        row_bytes = width * sum(PIXEL_BYTES[t] for t in pixel_types)
+        head = np.empty((height, 2), "<u4")
+        head[:, 0], head[:, 1] = np.arange(height), row_bytes
+        return np.concatenate([head.view(np.uint8).reshape(height, 8)] + [t.reshape(height, -1) for t in typed], axis=1).tobytes()
     rows = np.stack([np.ascontiguousarray(p).view(np.uint32).reshape(height, width) for p in planes], axis=1)          # [H, C, W]
     out = np.empty((height, 2 + len(planes) * width), np.uint32)
     out[:, 0] = np.arange(height, dtype=np.uint32)
     out[:, 1] = 4 * len(planes) * width
     out[:, 2:] = rows.reshape(height, -1)
     return out.astype("<u4").tobytes()
+
+
+HALF_DEFAULT = ("R", "G", "B", "albedo.R", "albedo.G", "albedo.B", "normal.X", "normal.Y", "normal.Z", "denoised.R", "denoised.G", "denoised.B")
+
+
+def half_types(names, half):
+    """The pixel type of every channel of `names` for write_layers_exr's `half`: True is HALF_DEFAULT — the colour-like layers; Z, A and the Cryptomatte channels stay
+    FLOAT —, an iterable of channel names exactly those. ValueError for a name that is not in the file or a Cryptomatte channel (an id is a 32-bit word, and a
+    matte's coverages stay beside it). Values above 65504 become infinity in a HALF channel: that is the format."""
+    if isinstance(half, (bool, int)):
+        chosen = set(HALF_DEFAULT) & set(names)
+    else:
+        chosen = {half} if isinstance(half, str) else set(half)
+        for n in sorted(chosen):
+            if n not in names:
+                raise ValueError(f"half: the file has no channel {n!r}")
+            if n.startswith(CRYPTO_LAYERS):
+                raise ValueError(f"half: {n!r} is a Cryptomatte channel and stays FLOAT")
+    return [HALF if n in chosen else FLOAT for n in names]
 
 
 def layer_channels(fb, aov=None, denoised=None, instance_ranked=None, material_ranked=None, instance_map=None, material_map=None):

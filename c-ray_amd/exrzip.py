@@ -1,5 +1,5 @@
 """exrzip.py — thin ctypes binding of libcray_hip_exr.so (include/cray_hip_exr.h), the companion library of output codecs: the pixel data of a ZIP / ZIPS
-compressed scanline OpenEXR file, deflated on the device. Plumbing: the work is in c-ray_amd/csrc/exr_zip.h. The library loads on first use; there is no CPU
+compressed scanline OpenEXR file, deflated on the device, FLOAT or per channel HALF. Plumbing: the work is in c-ray_amd/csrc/exr_zip.h. The library loads on first use; there is no CPU
 fallback: `library()` raises if it has not been built, every call raises `CrhError` on a non-zero return code.
 """
 import ctypes as C
@@ -38,6 +38,7 @@ def library():
         "crx_context_destroy": (C.c_int, [ctx]),
         "crx_last_error": (C.c_char_p, []),
         "crx_pack_zip": (C.c_int, [ctx, C.POINTER(abi.PackChannel), C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+        "crx_pack": (C.c_int, [ctx, C.POINTER(abi.PackChannel), C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
         "crx_pack_zip_time_ms": (C.c_int, [ctx, C.POINTER(C.c_float)]),
         "crx_pack_zip_phases_ms": (C.c_int, [ctx, C.POINTER(C.c_float)]),
         "crx_zip_segment_bytes": (C.c_uint32, []),
@@ -109,6 +110,28 @@ class ZipContext:
         sizes = np.zeros(max(chunks, 1), np.uint64)
         total = C.c_uint64(0)
         _check(self.L.crx_pack_zip(self.h, arr, n, width, height, first_row, rows, lines_per_chunk, out.ctypes.data, sizes.ctypes.data, C.byref(total)), "crx_pack_zip")
+        del keep
+        return out[:total.value].tobytes(), sizes[:chunks if total.value else 0]
+
+    def pack(self, channels, width, height, compression, pixel_types=None, first_row=0, row_count=None):
+        """pack_zip with a pixel type per channel (crx_pack): `compression` is the file's attribute — 0 none (a raw chunk a row), 2 ZIPS, 3 ZIP — or its name in
+        COMPRESSION, `pixel_types` 0 (FLOAT: the word as it is) or 1 (HALF: the word's binary16 conversion, round to nearest even; values above 65504 become infinity) per channel, None
+        for all FLOAT. Returns (the chunks as bytes, the uint64 array of their byte counts)."""
+        compression = COMPRESSION[compression][0] if isinstance(compression, str) else int(compression)
+        arr, keep = pack_channels(channels)
+        n = len(channels)
+        types = None if pixel_types is None else np.ascontiguousarray(pixel_types, dtype=np.uint8)
+        if types is not None and types.shape != (n,):
+            raise ValueError("pixel_types: one entry per channel")
+        rows = height - first_row if row_count is None else row_count
+        lines = 16 if compression == 3 else 1
+        chunks = max(-(-max(rows, 0) // lines), 0)
+        row_bytes = max(width, 0) * (4 * n if types is None else int(np.where(types == 1, 2, 4).sum()))
+        out = np.empty(8 * chunks + row_bytes * max(rows, 0), np.uint8)
+        sizes = np.zeros(max(chunks, 1), np.uint64)
+        total = C.c_uint64(0)
+        _check(self.L.crx_pack(self.h, arr, None if types is None else types.ctypes.data, n, width, height, first_row, rows, compression, out.ctypes.data,
+                               sizes.ctypes.data, C.byref(total)), "crx_pack")
         del keep
         return out[:total.value].tobytes(), sizes[:chunks if total.value else 0]
 

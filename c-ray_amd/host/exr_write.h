@@ -1,5 +1,5 @@
-/* exr_write.h — the host side of the multi-layer OpenEXR output, in C for the drop-in program: a single-part scanline file whose channels are all
- * FLOAT — uncompressed, or ZIP / ZIPS from chunks deflated on the device —, and Cryptomatte's naming of ids. The pixel data comes packed from the library (crh_pack_scanlines, include/cray_hip.h); this file knows which channel of
+/* exr_write.h — the host side of the multi-layer OpenEXR output, in C for the drop-in program: a single-part scanline file whose channels are
+ * FLOAT or, in the typed functions, HALF — uncompressed, or ZIP / ZIPS from chunks deflated on the device —, and Cryptomatte's naming of ids. The pixel data comes packed from the library (crh_pack_scanlines, include/cray_hip.h); this file knows which channel of
  * which buffer carries which name and writes what goes around the data. c-ray_amd/exr.py states the same in Python; both write the same bytes. Not part of the
  * library. */
 #pragma once
@@ -38,3 +38,16 @@ int exr_write_file(const char *path, int width, int height, const char *const *c
  * another compression, a chunk count that does not fit the height, a chunk of less than 8 bytes). Same bytes as exr.file_bytes_chunked. */
 int exr_write_file_chunked(const char *path, int width, int height, const char *const *channel_names, int channel_count, const struct exr_attr *strings,
                            int string_count, int compression, const void *chunk_data, const uint64_t *chunk_sizes, int chunk_count);
+
+/* Pixel types as crx_pack takes them (CRX_PIXEL_FLOAT / CRX_PIXEL_HALF of include/cray_hip_exr.h); the file's channel list says 2 and 1. */
+#define EXR_FLOAT 0
+#define EXR_HALF 1
+
+/* exr_write_file_chunked with a pixel type per channel (NULL: all FLOAT, and then its bytes) and the chunks as crx_pack writes them: compression 0 — a raw chunk a
+ * row, chunk_count = height — is accepted too. 0, or -1 (also: a pixel type that is neither). Same bytes as exr.file_bytes_chunked(..., pixel_types=...). */
+int exr_write_file_chunked_typed(const char *path, int width, int height, const char *const *channel_names, const uint8_t *pixel_types, int channel_count,
+                                 const struct exr_attr *strings, int string_count, int compression, const void *chunk_data, const uint64_t *chunk_sizes, int chunk_count);
+
+/* CRAY_HIP_EXR_HALF=1's default set, as Context.write_layers_exr(half=True) chooses it: pixel_types[c] = EXR_HALF for R G B, albedo.R/G/B, normal.X/Y/Z and
+ * denoised.R/G/B, EXR_FLOAT for everything else (Z, A, the Cryptomatte channels). Returns how many are HALF. */
+int exr_half_types(const char *const *channel_names, int channel_count, uint8_t *pixel_types);

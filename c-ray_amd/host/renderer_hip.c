@@ -48,7 +48,9 @@
  * CRAY_HIP_EXR=1 (user-facing): one multi-layer OpenEXR file <imgFileName>_layers beside the frame — the frame's floats, and whatever CRAY_HIP_AOV and CRAY_HIP_DENOISE
  * produced, unscaled: the buffers stay on GPU 0 until writeLayers below has packed them (crh_pack_scanlines) —; CRAY_HIP_IDS=<n> beside it: GPU 0 also renders n passes
  * of the instance and material ID buffers (crh_render_ids), which go into the file as Cryptomatte layers named after the scene's meshes. The frame, its image and the
- * other side files are those of a run without the two.
+ * other side files are those of a run without the two. CRAY_HIP_EXR_COMPRESSION=zip|zips beside it: the file is ZIP / ZIPS compressed, deflated on the device.
+ * CRAY_HIP_EXR_HALF=1 beside it: the colour layers (R G B, albedo.*, normal.*, denoised.*) are 16-bit HALF channels, Z, A and the Cryptomatte channels stay FLOAT
+ * (crx_pack of libcray_hip_exr.so, for every compression); values above 65504 become infinity in them. Anything else or unset: all FLOAT.
  * No GPU => logr(error, ...) (which exits, src/utils/logging.c:69-73): there is no CPU fallback in this file.
  */
 #include <stdlib.h>
@@ -824,7 +826,8 @@ static void layerNamesFree(struct layerNames *n) {
 /* CRAY_HIP_EXR=1: <imgFilePath><imgFileName>_layers_<imgCount, four digits>.exr — the name the frame's own file would get for <imgFileName>_layers — holds the frame
  * `fb`, the guide buffers `aov` and the denoised frame `denoised` where CRAY_HIP_AOV / CRAY_HIP_DENOISE left them on GPU 0, and with CRAY_HIP_IDS=<n> the ranked ids of
  * min(n, sampleCount) passes of both ID buffers rendered here, as Cryptomatte layers. The channels are packed on the device (crh_pack_scanlines), at most 32 MB a call;
- * with CRAY_HIP_EXR_COMPRESSION=zip|zips beside it they are deflated there as well (crx_pack_zip of libcray_hip_exr.so) and the file is a ZIP / ZIPS one. */
+ * with CRAY_HIP_EXR_COMPRESSION=zip|zips beside it they are deflated there as well (crx_pack_zip of libcray_hip_exr.so) and the file is a ZIP / ZIPS one; with
+ * CRAY_HIP_EXR_HALF=1 the colour layers are HALF (crx_pack and exr_write_file_chunked_typed, whatever the compression). */
 static void writeLayers(struct renderer *r, crh_ctx *ctx, const float *fb, const float *aov, const float *denoised, const struct layerNames *names, int W, int H) {
 	const char *e = getenv("CRAY_HIP_IDS");
 	int n = e ? atoi(e) : 0;
@@ -861,40 +864,48 @@ static void writeLayers(struct renderer *r, crh_ctx *ctx, const float *fb, const
 	if (how && !strcmp(how, "zip")) kind = 3;
 	else if (how && !strcmp(how, "zips")) kind = 2;
 	else if (how && *how && strcmp(how, "none")) logr(warning, "c-ray-hip: CRAY_HIP_EXR_COMPRESSION=%s is not zip, zips or none; the layers file stays uncompressed\n", how);
+	const char *halfEnv = getenv("CRAY_HIP_EXR_HALF");
+	uint8_t types[CRH_PACK_MAX_CHANNELS];
+	const bool half = halfEnv && !strcmp(halfEnv, "1") && exr_half_types(channelNames, count, types) > 0;
+	const bool chunked = kind || half;          /* the companion library packs: crx_pack_zip, or crx_pack where there are HALF channels */
 	const int lines = kind == 3 ? 16 : 1, chunks = (H + lines - 1) / lines;
 	const size_t block = 8u + 4u * (size_t)count * (size_t)W;
-	char *blocks = ok ? malloc(kind ? 8u * (size_t)chunks + (block - 8u) * (size_t)H : block * (size_t)H) : NULL;
-	uint64_t *sizes = kind ? malloc((size_t)chunks * sizeof(*sizes)) : NULL;
+	char *blocks = ok ? malloc(chunked ? 8u * (size_t)chunks + (block - 8u) * (size_t)H : block * (size_t)H) : NULL;
+	uint64_t *sizes = chunked ? malloc((size_t)chunks * sizeof(*sizes)) : NULL;
 	int chunk = (int)(((size_t)32 << 20) / block);
 	if (chunk < 1) chunk = 1;
 	chunk = (chunk + lines - 1) / lines * lines;
-	ok = ok && blocks && (!kind || sizes);
+	ok = ok && blocks && (!chunked || sizes);
 	const char *why = NULL;
-	if (kind && ok) {
+	if (chunked && ok) {
 		crx_ctx *zip = NULL;
 		size_t at = 0;
 		ok = crh_synchronize(ctx) == CRH_OK;          /* the companion's stream is its own: the sources must be complete */
 		if (ok && crx_context_create(0, NULL, &zip) != CRH_OK) { ok = false; why = crx_last_error(); }
 		for (int y = 0; ok && y < H; y += chunk) {
 			uint64_t total = 0;
-			if (crx_pack_zip(zip, channels, (uint32_t)count, W, H, y, H - y < chunk ? H - y : chunk, lines, blocks + at, sizes + y / lines, &total) != CRH_OK) { ok = false; why = crx_last_error(); }
+			const int rows = H - y < chunk ? H - y : chunk;
+			const int rc = half ? crx_pack(zip, channels, types, (uint32_t)count, W, H, y, rows, kind, blocks + at, sizes + y / lines, &total)
+			                    : crx_pack_zip(zip, channels, (uint32_t)count, W, H, y, rows, lines, blocks + at, sizes + y / lines, &total);
+			if (rc != CRH_OK) { ok = false; why = crx_last_error(); }
 			at += (size_t)total;
 		}
 		if (why) logr(warning, "c-ray-hip: %s\n", why);
 		crx_context_destroy(zip);
 	}
-	for (int y = 0; !kind && ok && y < H; y += chunk)
+	for (int y = 0; !chunked && ok && y < H; y += chunk)
 		ok = crh_pack_scanlines(ctx, channels, (uint32_t)count, W, H, y, H - y < chunk ? H - y : chunk, blocks + block * (size_t)y) == CRH_OK;
 	const char *base = r->prefs.imgFileName ? r->prefs.imgFileName : "rendered";
 	const char *dir = r->prefs.imgFilePath ? r->prefs.imgFilePath : "";
 	char *path = malloc(strlen(dir) + strlen(base) + 32);
 	if (ok && path) {
 		sprintf(path, "%s%s_layers_%04d.exr", dir, base, r->prefs.imgCount);
-		const int rc = kind ? exr_write_file_chunked(path, W, H, channelNames, count, strings, stringCount, kind, blocks, sizes, chunks)
-		                    : exr_write_file(path, W, H, channelNames, count, strings, stringCount, blocks);
+		const int rc = half ? exr_write_file_chunked_typed(path, W, H, channelNames, types, count, strings, stringCount, kind, blocks, sizes, chunks)
+		               : kind ? exr_write_file_chunked(path, W, H, channelNames, count, strings, stringCount, kind, blocks, sizes, chunks)
+		                      : exr_write_file(path, W, H, channelNames, count, strings, stringCount, blocks);
 		if (rc == 0) logr(info, "Layers written to %s (%i channels%s).\n", path, count, ids ? ", Cryptomatte ids" : "");
 		else logr(warning, "c-ray-hip: the layers file %s could not be written\n", path);
-	} else logr(warning, "c-ray-hip: the layers file could not be made: %s\n", blocks && path && (!kind || sizes) ? crh_last_error() : "out of memory");
+	} else logr(warning, "c-ray-hip: the layers file could not be made: %s\n", blocks && path && (!chunked || sizes) ? crh_last_error() : "out of memory");
 	free(sizes);
 	free(path); free(blocks);
 	exr_free_attrs(strings, stringCount);

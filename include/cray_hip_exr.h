@@ -1,7 +1,7 @@
 /*
  * cray_hip_exr.h — the C-ABI of libcray_hip_exr.so, the companion library of the output codecs: what leaves the product as a file and needs no scene, no path
  * state and nothing of the render path. Its first and so far only codec: the pixel data of a ZIP- or ZIPS-compressed scanline OpenEXR file, deflated on the device
- * from the buffers libcray_hip.so already makes (c-ray_amd/csrc/exr_zip.h). Plain C, int return codes: 0 (CRH_OK) is ok, the negative CRH_ERR_* values of cray_hip.h
+ * from the buffers libcray_hip.so already makes (c-ray_amd/csrc/exr_zip.h) — all FLOAT (crx_pack_zip), or with a pixel type per channel, FLOAT or HALF (crx_pack). Plain C, int return codes: 0 (CRH_OK) is ok, the negative CRH_ERR_* values of cray_hip.h
  * are reused, crx_last_error() holds the text of the calling thread's last failure. There is NO CPU path: without a HIP device crx_context_create answers
  * CRH_ERR_NO_DEVICE. A context belongs to one device and one stream and is used by one thread at a time.
  *
@@ -53,8 +53,31 @@ const char *crx_last_error(void);
 int crx_pack_zip(crx_ctx *ctx, const crh_pack_channel *channels, uint32_t channel_count, int width, int height, int first_row, int row_count, int lines_per_chunk,
                  void *host_out, uint64_t *chunk_bytes_host, uint64_t *total_bytes);
 
-/* The last complete crx_pack_zip's kernel time between the library's own events (waits for it): the sum of its launches, and per launch in phases_ms —
- * [0] gather + transform, [1] deflate, [2] sizes and offsets, [3] compaction. 0 before the first call. */
+/* crx_pack_zip with a pixel type per channel and the file's compression attribute in place of lines_per_chunk: the pixel data of a scanline OpenEXR file whose
+ * colour-like channels are HALF, uncompressed (0), ZIPS (2) or ZIP (3). pixel_types[i] is the type of channels[i]; NULL means all FLOAT.
+ *
+ * The conversion, part of the interface: binary32 -> binary16, round to nearest, ties to even, in integer arithmetic (c-ray_amd/csrc/exr_zip.h: zipHalfBits), the
+ * bits of numpy's astype(float16): gradual underflow to half subnormals; |x| < 2^-25 and the tie 2^-25 itself go to +-0; results that round to 2^16 or more
+ * (|x| >= 65520) become +-infinity — values above 65504 do not survive a HALF channel, that is the format —; +-infinity stay; a NaN becomes
+ * sign | 0x7c00 | (mantissa >> 13), with bit 0 set if that mantissa field would be 0. HALF on a channel that has a map is refused: an id is a 32-bit word.
+ *
+ * Raw bytes. A stored row is one plane per channel in list order, `width` pixels of that channel's type each (a HALF pixel: 2 bytes little-endian) — the OpenEXR
+ * scanline layout —: rowBytes = width * the sum of the channels' pixel sizes.
+ * Chunks. 1 row a chunk for compression 0 and 2, 16 rows for 3, the image's last chunk may be shorter; n = rowBytes * lines, even but not always a multiple of 4.
+ * Transform, the choice "zlib stream if shorter than n, else raw", the chunk header int32 y, int32 size, the row alignment rules, determinism and the output bound
+ * 8 * chunks + raw bytes (rowBytes * row_count) are crx_pack_zip's with this n. Compression 0 is the chunk form with every chunk raw: int32 y, int32 rowBytes, the
+ * row; nothing is transformed or deflated.
+ * Identities. With pixel_types NULL or all 0 and compression 2 / 3 the bytes and sizes are those of crx_pack_zip with 1 / 16 lines (the same kernels run); with
+ * compression 0 the bytes are those of crh_pack_scanlines.
+ * CRH_ERR_INVALID, nothing written anywhere: everything crx_pack_zip refuses, a compression other than 0, 2, 3, a pixel type other than 0 or 1, HALF on a channel
+ * with a map, a chunk of 2^31 bytes or more (from rowBytes). */
+#define CRX_PIXEL_FLOAT 0          /* the 32-bit word, bit for bit: what crx_pack_zip stores */
+#define CRX_PIXEL_HALF 1           /* the word read as binary32, converted to binary16 by the rule above, 2 bytes little-endian */
+int crx_pack(crx_ctx *ctx, const crh_pack_channel *channels, const uint8_t *pixel_types, uint32_t channel_count, int width, int height, int first_row, int row_count,
+             int compression, void *host_out, uint64_t *chunk_bytes_host, uint64_t *total_bytes);
+
+/* The last complete crx_pack_zip's or crx_pack's kernel time between the library's own events (waits for it): the sum of its launches, and per launch in phases_ms —
+ * [0] gather + transform, [1] deflate, [2] sizes and offsets, [3] compaction (compression 0 launches only the last two; the others read 0). 0 before the first call. */
 #define CRX_ZIP_PHASES 4
 int crx_pack_zip_time_ms(crx_ctx *ctx, float *ms);
 int crx_pack_zip_phases_ms(crx_ctx *ctx, float phases_ms[CRX_ZIP_PHASES]);

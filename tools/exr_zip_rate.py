@@ -3,6 +3,7 @@
 1280 x 720 with all 38 channels — the frame, the guides, a denoised frame and both ranked ID buffers.
 
     python tools/exr_zip_rate.py [--out profiles/exr_zip_rate.log]
+    python tools/exr_zip_rate.py --half [--out profiles/exr_half_rate.log]
 
 One process, behind warm-up rounds, medians of interleaved rounds of
   zip, zips     crx_pack_zip over the whole frame in one call (lines_per_chunk 16 and 1): the kernels per phase by crx_pack_zip_phases_ms (the companion library's
@@ -11,7 +12,12 @@ One process, behind warm-up rounds, medians of interleaved rounds of
   none          the wall time of Context.pack_scanlines on the same buffers and of exr.file_bytes + the file's write.
 Then, once, the yardstick: host zlib, level 1, fixed codes (Z_FIXED), per chunk on the same transformed bytes, raw where not shorter, on one thread.
 Two expectations are marked met or refuted: the compressed call + write is no slower end to end than the uncompressed one, and the device's size is within a few
-percent (5 %) of the yardstick's. Without a GPU nothing is measured and the log says so."""
+percent (5 %) of the yardstick's. Without a GPU nothing is measured and the log says so.
+
+--half adds, interleaved with those in the same rounds, the rows of the file whose colour layers are HALF (Context.write_layers_exr(half=True)'s set, 12 of the 38
+channels): "zip half", "zips half" and "none half" through crx_pack (compression 3, 2 and 0) with the same phases, call and write times and file bytes, the spread
+between the rounds of every kernel sum, and two more expectations: the half call's kernel time is no larger than the all-FLOAT call's by more than that spread,
+and the half file is smaller for every compression (the ratio is recorded)."""
 import os
 import statistics
 import sys
@@ -34,7 +40,7 @@ def zip_forward(raw):
     return p.tobytes()
 
 
-def measure():
+def measure(half=False):
     sys.path.insert(0, REPO)
     sys.path.insert(0, os.path.join(REPO, "tools"))
     from __graft_entry__ import load_package
@@ -61,18 +67,25 @@ def measure():
     n = len(chans)
     ctx.synchronize()
     zctx = exrzip.ZipContext(0)
-    t = {k: {"call": [], "write": [], "phases": []} for k in ("zip", "zips", "none")}
+    kinds = ("zip", "zips", "none") + (("zip half", "zips half", "none half") if half else ())
+    types = exr.half_types(names, True)
+    t = {k: {"call": [], "write": [], "phases": []} for k in kinds}
     size, device = {}, {}          # the files' bytes; the bytes of the device's chunks
     with tempfile.TemporaryDirectory() as tmp:
         for r in range(WARM + ROUNDS):
-            for kind in ("zip", "zips", "none"):
+            for kind in kinds:
                 t0 = time.perf_counter()
                 if kind == "none":
                     blocks = ctx.pack_scanlines([c[1:] for c in chans], W, H)
+                elif kind.endswith("half"):
+                    data, sizes = zctx.pack([c[1:] for c in chans], W, H, exrzip.COMPRESSION[kind.split()[0]][0], types)
                 else:
                     data, sizes = zctx.pack_zip([c[1:] for c in chans], W, H, exrzip.COMPRESSION[kind][1])
                 t1 = time.perf_counter()
-                whole = exr.file_bytes(W, H, names, blocks, strings) if kind == "none" else exr.file_bytes_chunked(W, H, names, data, sizes, strings, exrzip.COMPRESSION[kind][0])
+                if kind == "none":
+                    whole = exr.file_bytes(W, H, names, blocks, strings)
+                else:
+                    whole = exr.file_bytes_chunked(W, H, names, data, sizes, strings, exrzip.COMPRESSION[kind.split()[0]][0], types if kind.endswith("half") else None)
                 with open(os.path.join(tmp, "layers.exr"), "wb") as f:
                     f.write(whole)
                 t2 = time.perf_counter()
@@ -115,18 +128,53 @@ def measure():
         chunks = device[kind]
         lines.append(f"expectation: the device's size ({kind}) is within 5 % of the yardstick's: {chunks / yard[kind]:.4f} at segment {exrzip.segment_bytes()}: "
                      f"{'met' if chunks <= 1.05 * yard[kind] else 'REFUTED'}")
+    if half:
+        lines += half_lines(t, size)
     zctx.close()
     ctx.close()
     return lines
 
 
+def half_lines(t, size):
+    """the rows of --half: the files whose colour layers are HALF beside the all-FLOAT ones of the same rounds"""
+    med = statistics.median
+    lines = [f"half: R G B, albedo.R/G/B, normal.X/Y/Z, denoised.R/G/B stored as HALF (12 of the channels), through crx_pack; the rows above are the all-FLOAT files of the same rounds"]
+    sums = {}
+    for kind in ("zip", "zips", "none"):
+        k = kind + " half"
+        ph = np.median(np.array(t[k]["phases"]), axis=0)
+        sums[k] = np.array(t[k]["phases"]).sum(axis=1)
+        lines.append(f"{k:10s} kernels (crx_pack_zip_phases_ms): " + ", ".join(f"{name} {v:.3f} ms" for name, v in zip(PHASES, ph)) + f"; sum {ph.sum():.3f} ms")
+    for kind in ("zip", "zips"):
+        sums[kind] = np.array(t[kind]["phases"]).sum(axis=1)
+    for k in ("zip", "zips", "zip half", "zips half", "none half"):
+        lines.append(f"{k:10s} kernel sum per round: median {med(sums[k]):.3f} ms, min {sums[k].min():.3f}, max {sums[k].max():.3f} (spread {sums[k].max() - sums[k].min():.3f} ms)")
+    for kind in ("zip", "zips", "none"):
+        k = kind + " half"
+        c, w = med(t[k]["call"]), med(t[k]["write"])
+        lines.append(f"{k:10s} whole call (wall) median {c:9.3f} ms (min {min(t[k]['call']):.3f}, max {max(t[k]['call']):.3f});  file bytes + write median {w:9.3f} ms;  "
+                     f"together {c + w:9.3f} ms;  file {size[k]} bytes = {size[k] / size[kind]:.4f} of the all-FLOAT {kind} file")
+    for kind in ("zip", "zips"):
+        k = kind + " half"
+        spread = max(sums[kind].max() - sums[kind].min(), sums[k].max() - sums[k].min())
+        a, b = med(sums[k]), med(sums[kind])
+        lines.append(f"expectation (a): the half call's kernel time ({kind}) is no larger than the all-FLOAT call's by more than the spread between the rounds: "
+                     f"{a:.3f} ms against {b:.3f} ms, spread {spread:.3f} ms: {'met' if a <= b + spread else 'REFUTED'}")
+    for kind in ("zip", "zips", "none"):
+        k = kind + " half"
+        lines.append(f"expectation (b): the half file ({kind}) is smaller than the all-FLOAT one: {size[k]} against {size[kind]} bytes, ratio {size[k] / size[kind]:.4f}: "
+                     f"{'met' if size[k] < size[kind] else 'REFUTED'}")
+    return lines
+
+
 def main():
     args = sys.argv[1:]
-    out = args[args.index("--out") + 1] if "--out" in args else os.path.join(REPO, "profiles", "exr_zip_rate.log")
+    half = "--half" in args
+    out = args[args.index("--out") + 1] if "--out" in args else os.path.join(REPO, "profiles", "exr_half_rate.log" if half else "exr_zip_rate.log")
     sys.path.insert(0, REPO)
     from __graft_entry__ import load_package
     gpu = load_package().api.device_count() > 0
-    lines = measure() if gpu else ["no HIP device here: nothing is measured"]
+    lines = measure(half) if gpu else ["no HIP device here: nothing is measured"]
     text = "\n".join(lines) + "\n"
     print(text, end="")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
