@@ -5,6 +5,8 @@ Field order and sizes must match the header exactly (tests/test_abi.py checks th
 """
 import ctypes as C
 
+import numpy as np
+
 ABI_VERSION = 5
 AOV_CHANNELS = 8            # CRH_AOV_CHANNELS: albedo r g b, normal x y z, depth, coverage
 ID_SLOTS, ID_WORDS = 6, 16  # CRH_ID_SLOTS, CRH_ID_WORDS: id[0..5], count[0..5], lost, total, two reserved words
@@ -144,6 +146,27 @@ class PackChannel(C.Structure):
     _fields_ = [("dev_src", C.c_void_p), ("stride", C.c_uint32), ("component", C.c_uint32), ("map_host", C.c_void_p), ("map_count", C.c_uint32), ("pad", C.c_uint32)]
 
 PACK_MAX_CHANNELS = 64             # CRH_PACK_MAX_CHANNELS
+
+
+def pack_channels(channels):
+    """(the crh_pack_channel array of a list of (device pointer, stride, component[, map]), the maps' arrays: they must outlive the call that takes the array)"""
+    arr = (PackChannel * max(len(channels), 1))()
+    keep = []
+    for k, ch in zip(arr, channels):
+        src, stride, component = ch[0], ch[1], ch[2]
+        m = ch[3] if len(ch) > 3 else None
+        k.dev_src = src.value if isinstance(src, C.c_void_p) else src
+        k.stride, k.component = stride, component
+        if m is not None:
+            m = np.ascontiguousarray(m, dtype=np.uint32)
+            same = [a for a in keep if a.shape == m.shape and np.array_equal(a, m)]          # (one array per distinct map: the library uploads each once)
+            m = same[0] if same else m
+            if not same:
+                keep.append(m)
+            k.map_host, k.map_count = m.ctypes.data, m.size
+    return arr, keep
+
+
 ADAPTIVE_CELLS_MAX = 1024          # CRH_ADAPTIVE_CELLS_MAX: cells one rectangle may hold
 
 

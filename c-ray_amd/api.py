@@ -428,23 +428,11 @@ class Context:
         component of a float buffer [height, width, stride]; with a map — a uint32 array — the value is an id and the word is map[id], 0 for anything that is not
         an id below len(map)."""
         n = len(channels)
-        arr = (abi.PackChannel * max(n, 1))()
-        keep = []          # the maps' arrays live until the call returns
-        for k, ch in zip(arr, channels):
-            src, stride, component = ch[0], ch[1], ch[2]
-            m = ch[3] if len(ch) > 3 else None
-            k.dev_src = src.value if isinstance(src, C.c_void_p) else src
-            k.stride, k.component = stride, component
-            if m is not None:
-                m = np.ascontiguousarray(m, dtype=np.uint32)
-                same = [a for a in keep if a.shape == m.shape and np.array_equal(a, m)]          # (one array per distinct map: the library uploads each once)
-                m = same[0] if same else m
-                if not same:
-                    keep.append(m)
-                k.map_host, k.map_count = m.ctypes.data, m.size
+        arr, keep = abi.pack_channels(channels)
         rows = height - first_row if row_count is None else row_count
         out = np.empty(max(rows, 0) * (2 + n * width), np.uint32)
         _check(self.L.crh_pack_scanlines(self.h, arr, n, width, height, first_row, rows, out.ctypes.data), "crh_pack_scanlines")
+        del keep          # (the maps' arrays lived until the call returned)
         return out.tobytes()
 
     def pack_time_ms(self):
@@ -464,7 +452,8 @@ class Context:
         half: True stores the colour layers that are present — R G B, albedo.R/G/B, normal.X/Y/Z, denoised.R/G/B — as 16-bit HALF channels, as compositors expect
         them; Z, A and the Cryptomatte channels stay FLOAT. An iterable of channel names stores exactly those as HALF; a name the file does not have, or a
         Cryptomatte channel, raises ValueError. The conversion rounds to nearest even (include/cray_hip_exr.h); values above 65504 become infinity — that is
-        the format, not a fault. With `half` every compression, "none" too, is packed by the companion library (crx_pack); falsy: today's paths and bytes."""
+        the format, not a fault. Only the uncompressed all-FLOAT file is packed by this library alone (crh_pack_scanlines) and can be written where the companion
+        library is not built; every other one by crx_pack."""
         from . import exrzip          # (binds the companion library on first use)
         if compression not in exrzip.COMPRESSION:
             raise ValueError(f"compression {compression!r}: one of {sorted(exrzip.COMPRESSION)}")
@@ -485,30 +474,22 @@ class Context:
                 ranked[k], maps[k] = p, exr.id_map(names)
                 strings.update(exr.crypto_attributes(exr.CRYPTO_LAYERS[k], names))
             chans = exr.layer_channels(fb, aov, denoised, ranked[0], ranked[1], maps[0], maps[1])
-            step = height if not chunk_rows else chunk_rows
-            types = exr.half_types([c[0] for c in chans], half) if half else None
-            if types is not None:
-                kind, lines = exrzip.COMPRESSION[compression]
-                step = -(-step // lines) * lines
-                self.synchronize()          # the companion's stream may be another: its sources must be complete
-                parts = [self._zip_context().pack([c[1:] for c in chans], width, height, kind, types, y, min(step, height - y)) for y in range(0, height, step)]
-            elif compression == "none":
-                blocks = b"".join(self.pack_scanlines([c[1:] for c in chans], width, height, y, min(step, height - y)) for y in range(0, height, step))
+            names, sources = [c[0] for c in chans], [c[1:] for c in chans]
+            kind, lines = exrzip.COMPRESSION[compression]
+            step = -(-(chunk_rows or height) // lines) * lines
+            types = exr.half_types(names, half) if half else None
+            if kind == 0 and types is None:
+                data, sizes = b"".join(self.pack_scanlines(sources, width, height, y, min(step, height - y)) for y in range(0, height, step)), None
             else:
-                kind, lines = exrzip.COMPRESSION[compression]
-                step = -(-step // lines) * lines
                 self.synchronize()          # the companion's stream may be another: its sources must be complete
-                parts = [self._zip_context().pack_zip([c[1:] for c in chans], width, height, lines, y, min(step, height - y)) for y in range(0, height, step)]
+                parts = [self._zip_context().pack(sources, width, height, kind, types, y, min(step, height - y)) for y in range(0, height, step)]
+                data, sizes = b"".join(p[0] for p in parts), np.concatenate([p[1] for p in parts])
         finally:
             for p in scratch:
                 self.L.crh_ids_free(self.h, p)
-        if types is None and compression == "none":
-            data = exr.file_bytes(width, height, [c[0] for c in chans], blocks, strings)
-        else:
-            data = exr.file_bytes_chunked(width, height, [c[0] for c in chans], b"".join(p[0] for p in parts), np.concatenate([p[1] for p in parts]), strings, kind, types)
         with open(path, "wb") as f:
-            f.write(data)
-        return [c[0] for c in chans]
+            f.write(exr.file_bytes(width, height, names, data, sizes, strings, kind, types))
+        return names
 
     # ---- the guided a-trous denoiser (include/cray_hip.h: crh_denoise) ----
     def denoise(self, fb, aov, width, height, out=None, **params):

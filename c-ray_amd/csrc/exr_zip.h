@@ -18,7 +18,8 @@
  *                    shorter than n); then the chunks' positions in the output, their byte counts and the total.
  *   k_zip_emit       one workgroup per segment copies it behind the chunk's 8-byte header and the zlib header — or, in a raw chunk, gathers that stretch of
  *                    raw bytes from the sources; the first writes the headers and the Adler-32 trailer.
- * A call whose channels are all FLOAT runs exactly these. A call with a HALF channel (crx_pack) runs k_zip_transform_mixed and k_zip_emit_mixed in their places:
+ * A call whose channels are all FLOAT runs exactly these. A call with a HALF channel (crx_pack) runs k_zip_transform_mixed and k_zip_emit_mixed in their places —
+ * the MIXED == true instantiations of the bodies (zipTransform, zipEmit) whose MIXED == false instantiations the plain kernels are —:
  * a row is no longer nch * width words but one plane of 2- or 4-byte pixels per channel, so byte i of a chunk is found as line i / rowBytes, the channel whose
  * stretch of the row holds the rest (a binary search in the prefix table of the channels' byte offsets, at most 65 words, in LDS), pixel and byte within the
  * pixel; a lane still makes four consecutive bytes of T' and stores one word. n is even but not always a multiple of 4: the T' pitch is whole words, the two
@@ -96,27 +97,7 @@ __device__ __forceinline__ uint32_t zipRawWord(const ZipArgs &A, const ZipGeom &
 	return w;
 }
 
-/* T': word wi of every chunk (bytes 4 wi .. 4 wi + 3), blocksPerChunk workgroups of 256 lanes a chunk */
-__global__ __launch_bounds__(256) void k_zip_transform(const ZipArgs A, const ZipGeom G, uint32_t blocksPerChunk, uint32_t *T) {
-	const uint32_t k = blockIdx.x / blocksPerChunk, wi = (blockIdx.x - k * blocksPerChunk) * 256u + threadIdx.x;
-	const uint32_t n = zipChunkBytes(G, k);          /* a multiple of 4: (n + 1) / 2 == n / 2 */
-	if (4u * wi >= n) return;
-	const uint32_t half = n / 2u;
-	uint32_t heldAt = 0xffffffffu, held = 0u;          /* the raw word last fetched: consecutive bytes of T come from the same or the next one */
-	uint32_t t[5];
-	for (uint32_t b = 0; b < 5u; ++b) {                /* T[4 wi - 1] .. T[4 wi + 3] */
-		const uint32_t j = 4u * wi + b - 1u;
-		if (wi == 0u && b == 0u) { t[0] = 0u; continue; }
-		const uint32_t i = j < half ? 2u * j : 2u * (j - half) + 1u;
-		if ((i >> 2) != heldAt) { heldAt = i >> 2; held = zipRawWord(A, G, k, heldAt); }
-		t[b] = (held >> (8u * (i & 3u))) & 255u;
-	}
-	uint32_t out = 0u;
-	for (uint32_t b = 0; b < 4u; ++b) out |= ((wi == 0u && b == 0u ? t[1] : t[b + 1] - t[b] + 128u) & 255u) << (8u * b);
-	T[(size_t)k * G.pitch + wi] = out;
-}
-
-/* ---- mixed HALF / FLOAT rows ---- */
+/* ---- mixed HALF / FLOAT rows: what k_zip_transform_mixed and k_zip_emit_mixed read their bytes through ---- */
 /* the element last fetched: bytes [lo, hi) of the chunk are the little-endian bytes of v; it lies in the plane [planeLo, planeHi) of channel c on stored row y */
 struct ZipHeld { uint32_t lo, hi, v, planeLo, planeHi, c, y; };
 
@@ -143,28 +124,45 @@ __device__ __forceinline__ uint32_t zipMixedByte(const ZipArgs &A, const ZipGeom
 	return (h.v >> (8u * (i - h.lo))) & 255u;
 }
 
-/* k_zip_transform for rows with HALF channels: the same four bytes of T' a lane, from up to five elements; the bytes behind n in a chunk's last word are zero */
+/* T': word wi of every chunk (bytes 4 wi .. 4 wi + 3), blocksPerChunk workgroups of 256 lanes a chunk. MIXED: rows with HALF channels (off: their prefix table
+ * in LDS) — the same four bytes of T' a lane, from up to five elements instead of three words; n is even, not always a multiple of 4, and the bytes behind n in a
+ * chunk's last word are zero */
+template <bool MIXED>
+__device__ __forceinline__ void zipTransform(const ZipArgs &A, const ZipGeom &G, const uint32_t *off, uint32_t blocksPerChunk, uint32_t *T) {
+	const uint32_t k = blockIdx.x / blocksPerChunk, wi = (blockIdx.x - k * blocksPerChunk) * 256u + threadIdx.x;
+	const uint32_t n = zipChunkBytes(G, k);          /* !MIXED: a multiple of 4, (n + 1) / 2 == n / 2 */
+	if (4u * wi >= n) return;
+	const uint32_t half = n / 2u;
+	uint32_t heldAt = 0xffffffffu, held = 0u;          /* !MIXED: the raw word last fetched: consecutive bytes of T come from the same or the next one */
+	ZipHeld h = {0u, 0u, 0u, 0u, 0u, 0u, 0u};          /* MIXED: the element last fetched */
+	uint32_t t[5];
+	for (uint32_t b = 0; b < 5u; ++b) {                /* T[4 wi - 1] .. T[4 wi + 3] */
+		const uint32_t j = 4u * wi + b - 1u;
+		if ((wi == 0u && b == 0u) || (MIXED && j >= n)) { t[b] = 0u; continue; }
+		const uint32_t i = j < half ? 2u * j : 2u * (j - half) + 1u;
+		if (MIXED) t[b] = zipMixedByte(A, G, off, k, i, h);
+		else {
+			if ((i >> 2) != heldAt) { heldAt = i >> 2; held = zipRawWord(A, G, k, heldAt); }
+			t[b] = (held >> (8u * (i & 3u))) & 255u;
+		}
+	}
+	uint32_t out = 0u;
+	for (uint32_t b = 0; b < 4u; ++b) {
+		if (MIXED && 4u * wi + b >= n) break;
+		out |= ((wi == 0u && b == 0u ? t[1] : t[b + 1] - t[b] + 128u) & 255u) << (8u * b);
+	}
+	T[(size_t)k * G.pitch + wi] = out;
+}
+
+__global__ __launch_bounds__(256) void k_zip_transform(const ZipArgs A, const ZipGeom G, uint32_t blocksPerChunk, uint32_t *T) {
+	zipTransform<false>(A, G, nullptr, blocksPerChunk, T);
+}
+
 __global__ __launch_bounds__(256) void k_zip_transform_mixed(const ZipArgs A, const ZipRow R, const ZipGeom G, uint32_t blocksPerChunk, uint32_t *T) {
 	__shared__ uint32_t sOff[CRH_PACK_MAX_CHANNELS + 1u];
 	if (threadIdx.x <= G.nch) sOff[threadIdx.x] = R.off[threadIdx.x];
 	__syncthreads();
-	const uint32_t k = blockIdx.x / blocksPerChunk, wi = (blockIdx.x - k * blocksPerChunk) * 256u + threadIdx.x;
-	const uint32_t n = zipChunkBytes(G, k);          /* even */
-	if (4u * wi >= n) return;
-	const uint32_t half = n / 2u;
-	ZipHeld h = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
-	uint32_t t[5];
-	for (uint32_t b = 0; b < 5u; ++b) {                /* T[4 wi - 1] .. T[4 wi + 3] */
-		const uint32_t j = 4u * wi + b - 1u;
-		if ((wi == 0u && b == 0u) || j >= n) { t[b] = 0u; continue; }
-		t[b] = zipMixedByte(A, G, sOff, k, j < half ? 2u * j : 2u * (j - half) + 1u, h);
-	}
-	uint32_t out = 0u;
-	for (uint32_t b = 0; b < 4u; ++b) {
-		if (4u * wi + b >= n) break;
-		out |= ((wi == 0u && b == 0u ? t[1] : t[b + 1] - t[b] + 128u) & 255u) << (8u * b);
-	}
-	T[(size_t)k * G.pitch + wi] = out;
+	zipTransform<true>(A, G, sOff, blocksPerChunk, T);
 }
 
 /* ---- fixed Huffman codes (RFC 1951, 3.2.6), packed from bit 0: Huffman codes enter most significant bit first, extra bits least significant first ---- */

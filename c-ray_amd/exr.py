@@ -1,14 +1,15 @@
 """exr.py — the host side of the multi-layer OpenEXR output: a single-part scanline file whose channels are FLOAT or, where asked for, HALF (`pixel_types`;
-Context.write_layers_exr(half=...)) — uncompressed, or ZIP / ZIPS compressed from chunks deflated on the device (file_bytes_chunked;
-Context.write_layers_exr(compression=...), exrzip.py) —, and Cryptomatte's naming of ids.
-The pixel data comes packed from the device (Context.pack_scanlines: crh_pack_scanlines, include/cray_hip.h); this module writes what goes around it — header, offset table — and knows which channel of which buffer carries which name. c-ray_amd/host/exr_write.c states the same in C
+Context.write_layers_exr(half=...)), uncompressed, or ZIP / ZIPS compressed from chunks deflated on the device (Context.write_layers_exr(compression=...), exrzip.py), and
+Cryptomatte's naming of ids.
+The pixel data comes packed from the device (Context.pack_scanlines: crh_pack_scanlines, include/cray_hip.h; ZipContext.pack: crx_pack, include/cray_hip_exr.h); this
+module writes what goes around it — header, offset table — and knows which channel of which buffer carries which name. c-ray_amd/host/exr_write.c states the same in C
 for the drop-in program; both write the same bytes.
 
-File layout: magic 76 2f 31 01, version 02 00 00 00, attributes in ascending byte order of name (each `name\\0 type\\0 int32 size, value`), one \\0,
-`height` uint64 absolute offsets, then per stored row (row 0 = the top of the image = y 0, lineOrder increasing y) a block of int32 y,
-int32 4 * channels * width and one plane of `width` floats per channel, channels in ascending byte order of name. With HALF channels a row is
-`width` 2-byte pixels for each of those and the byte count is width * (the sum of the channels' pixel sizes); the offset table then has one entry per chunk
-(file_bytes_chunked, also for compression 0: a chunk a row).
+File layout: magic 76 2f 31 01, version 02 00 00 00, attributes in ascending byte order of name (each `name\\0 type\\0 int32 size, value`), one \\0, one uint64 absolute
+offset per chunk, then the chunks in row order (row 0 = the top of the image = y 0, lineOrder increasing y): a chunk is int32 y of its first row, int32 byte count and
+the data of LINES_PER_CHUNK[compression] rows, the last chunk of the image the rows that are left. A row is one plane of `width` pixels per channel, channels in
+ascending byte order of name, 4 bytes a FLOAT pixel and 2 a HALF one. Compression 0: a chunk is a row as it is — crh_pack_scanlines' block; 2 (ZIPS) and 3 (ZIP): the
+rows' bytes transformed and deflated, or as they are where that is not shorter (include/cray_hip_exr.h).
 """
 import json
 import struct
@@ -125,27 +126,20 @@ def header(width, height, channel_names, strings=None, compression=0, pixel_type
     return out + b"\0"
 
 
-def file_bytes(width, height, channel_names, blocks, strings=None):
-    """The whole file: `blocks` is the packed pixel data of all `height` rows, as crh_pack_scanlines lays it out."""
-    block = 8 + 4 * len(channel_names) * width
-    assert len(blocks) == block * height, "the pixel data is not height blocks of 8 + 4 * channels * width bytes"
-    head = header(width, height, channel_names, strings)
-    first = len(head) + 8 * height
-    return head + struct.pack(f"<{height}Q", *[first + block * y for y in range(height)]) + bytes(blocks)
-
-
 LINES_PER_CHUNK = {0: 1, 2: 1, 3: 16}          # by the compression attribute
 
 
-def file_bytes_chunked(width, height, channel_names, chunk_data, chunk_sizes, strings=None, compression=3, pixel_types=None):
-    """The whole file of compression 2 (ZIPS) or 3 (ZIP): `chunk_data` is the chunks back to back in row order as crx_pack_zip writes them (include/cray_hip_exr.h:
-    int32 y, int32 size, `size` bytes), `chunk_sizes` their byte counts (8 + size). The offset table has one entry per chunk; the chunks follow verbatim.
-    With `pixel_types` (FLOAT or HALF per channel, the chunks as crx_pack writes them) compression 0 is accepted as well: a raw chunk a row."""
-    assert compression in (2, 3) or (compression == 0 and pixel_types is not None)
+def file_bytes(width, height, channel_names, chunk_data, chunk_sizes=None, strings=None, compression=0, pixel_types=None):
+    """The whole file: `chunk_data` is the chunks back to back in row order as crx_pack writes them (include/cray_hip_exr.h: int32 y, int32 size, `size` bytes),
+    `chunk_sizes` their byte counts (8 + size). The offset table has one entry per chunk; the chunks follow verbatim. chunk_sizes None, for compression 0 only: every
+    chunk is a row of 8 + rowBytes bytes, which is what Context.pack_scanlines and pack_host return."""
+    head = header(width, height, channel_names, strings, compression, pixel_types)
+    if chunk_sizes is None:
+        assert compression == 0, "only the chunks of an uncompressed file have a size that follows from the header"
+        chunk_sizes = [8 + width * sum(PIXEL_BYTES[int(t)] for t in (pixel_types if pixel_types is not None else [FLOAT] * len(channel_names)))] * height
     sizes = [int(v) for v in chunk_sizes]
     assert len(sizes) == -(-height // LINES_PER_CHUNK[compression]), "one chunk for every LINES_PER_CHUNK rows"
     assert sum(sizes) == len(chunk_data) and all(v >= 8 for v in sizes), "the chunk sizes do not add up to the chunk data"
-    head = header(width, height, channel_names, strings, compression, pixel_types)
     at, offsets = len(head) + 8 * len(sizes), []
     for v in sizes:
         offsets.append(at)
@@ -160,23 +154,16 @@ def half_bits(words):
 
 
 def pack_host(planes, width, height, pixel_types=None):
-    """The pixel data from host arrays — planes: [height, width] arrays of 32-bit words in channel order —, for files that never were on a device. With
-    `pixel_types` the typed form, as crx_pack lays out compression 0: per row int32 y, int32 rowBytes and a plane per channel of 4-byte words or, for HALF,
-    of the words' binary16 conversions; file_bytes_chunked(..., [8 + rowBytes] * height, compression=0, pixel_types=...) takes it."""
-    if pixel_types is not None:
-        assert len(pixel_types) == len(planes)
-        words = [np.ascontiguousarray(p).view(np.uint32).reshape(height, width) for p in planes]
-        typed = [half_bits(p).astype("<u2").view(np.uint8) if t == HALF else p.astype("<u4").view(np.uint8) for p, t in zip(words, pixel_types)]
-        row_bytes = width * sum(PIXEL_BYTES[t] for t in pixel_types)
-        head = np.empty((height, 2), "<u4")
-        head[:, 0], head[:, 1] = np.arange(height), row_bytes
-        return np.concatenate([head.view(np.uint8).reshape(height, 8)] + [t.reshape(height, -1) for t in typed], axis=1).tobytes()
-    rows = np.stack([np.ascontiguousarray(p).view(np.uint32).reshape(height, width) for p in planes], axis=1)          # [H, C, W]
-    out = np.empty((height, 2 + len(planes) * width), np.uint32)
-    out[:, 0] = np.arange(height, dtype=np.uint32)
-    out[:, 1] = 4 * len(planes) * width
-    out[:, 2:] = rows.reshape(height, -1)
-    return out.astype("<u4").tobytes()
+    """The pixel data from host arrays — planes: [height, width] arrays of 32-bit words in channel order —, for files that never were on a device, as crx_pack lays
+    out compression 0: per row int32 y, int32 rowBytes and a plane per channel of 4-byte words or, for HALF, of the words' binary16 conversions. `pixel_types` None:
+    all FLOAT, crh_pack_scanlines' blocks. file_bytes(..., pixel_types=pixel_types) takes it."""
+    types = [FLOAT] * len(planes) if pixel_types is None else pixel_types
+    assert len(types) == len(planes)
+    words = [np.ascontiguousarray(p).view(np.uint32).reshape(height, width) for p in planes]
+    typed = [half_bits(p).astype("<u2").view(np.uint8) if t == HALF else p.astype("<u4").view(np.uint8) for p, t in zip(words, types)]
+    head = np.empty((height, 2), "<u4")
+    head[:, 0], head[:, 1] = np.arange(height), width * sum(PIXEL_BYTES[t] for t in types)
+    return np.concatenate([head.view(np.uint8).reshape(height, 8)] + [t.reshape(height, -1) for t in typed], axis=1).tobytes()
 
 
 HALF_DEFAULT = ("R", "G", "B", "albedo.R", "albedo.G", "albedo.B", "normal.X", "normal.Y", "normal.Z", "denoised.R", "denoised.G", "denoised.B")

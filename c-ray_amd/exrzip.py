@@ -60,26 +60,6 @@ def segment_bytes():
     return int(library().crx_zip_segment_bytes())
 
 
-def pack_channels(channels):
-    """(the crh_pack_channel array of a list of (device pointer, stride, component[, map]), the arrays that must outlive the call)"""
-    n = len(channels)
-    arr = (abi.PackChannel * max(n, 1))()
-    keep = []
-    for k, ch in zip(arr, channels):
-        src, stride, component = ch[0], ch[1], ch[2]
-        m = ch[3] if len(ch) > 3 else None
-        k.dev_src = src.value if isinstance(src, C.c_void_p) else src
-        k.stride, k.component = stride, component
-        if m is not None:
-            m = np.ascontiguousarray(m, dtype=np.uint32)
-            same = [a for a in keep if a.shape == m.shape and np.array_equal(a, m)]          # (one array per distinct map: the library uploads each once)
-            m = same[0] if same else m
-            if not same:
-                keep.append(m)
-            k.map_host, k.map_count = m.ctypes.data, m.size
-    return arr, keep
-
-
 class ZipContext:
     """One crx_ctx: a device, a stream (a raw hipStream_t, or None for one of the library's own) and the scratch of its calls."""
 
@@ -99,41 +79,36 @@ class ZipContext:
         except Exception:
             pass
 
+    def _pack(self, where, call, channels, pixel_bytes, width, lines_per_chunk, rows):
+        """One call of the pack entry named `where` — call(the crh_pack_channel array, output, sizes, total) -> its return code — with the output sized to its bound,
+        8 bytes a chunk + the raw bytes (pixel_bytes: the sum of the channels' pixel sizes): (the chunks as bytes, the uint64 array of their byte counts)."""
+        arr, keep = abi.pack_channels(channels)
+        chunks = max(-(-max(rows, 0) // max(lines_per_chunk, 1)), 0)
+        out = np.empty(8 * chunks + pixel_bytes * max(width, 0) * max(rows, 0), np.uint8)
+        sizes = np.zeros(max(chunks, 1), np.uint64)
+        total = C.c_uint64(0)
+        _check(call(arr, out.ctypes.data, sizes.ctypes.data, C.byref(total)), where)
+        del keep
+        return out[:total.value].tobytes(), sizes[:chunks if total.value else 0]
+
     def pack_zip(self, channels, width, height, lines_per_chunk, first_row=0, row_count=None):
         """(the chunks of stored rows [first_row, first_row + row_count) as bytes — per chunk int32 y, int32 size, the data —, the uint64 array of their byte
         counts). Channels as Context.pack_scanlines takes them; lines_per_chunk 1 (ZIPS) or 16 (ZIP). The sources must be complete."""
-        arr, keep = pack_channels(channels)
-        n = len(channels)
-        rows = height - first_row if row_count is None else row_count
-        chunks = max(-(-max(rows, 0) // max(lines_per_chunk, 1)), 0)
-        out = np.empty(8 * chunks + 4 * n * max(width, 0) * max(rows, 0), np.uint8)
-        sizes = np.zeros(max(chunks, 1), np.uint64)
-        total = C.c_uint64(0)
-        _check(self.L.crx_pack_zip(self.h, arr, n, width, height, first_row, rows, lines_per_chunk, out.ctypes.data, sizes.ctypes.data, C.byref(total)), "crx_pack_zip")
-        del keep
-        return out[:total.value].tobytes(), sizes[:chunks if total.value else 0]
+        n, rows = len(channels), height - first_row if row_count is None else row_count
+        return self._pack("crx_pack_zip", lambda arr, *out: self.L.crx_pack_zip(self.h, arr, n, width, height, first_row, rows, lines_per_chunk, *out),
+                          channels, 4 * n, width, lines_per_chunk, rows)
 
     def pack(self, channels, width, height, compression, pixel_types=None, first_row=0, row_count=None):
         """pack_zip with a pixel type per channel (crx_pack): `compression` is the file's attribute — 0 none (a raw chunk a row), 2 ZIPS, 3 ZIP — or its name in
         COMPRESSION, `pixel_types` 0 (FLOAT: the word as it is) or 1 (HALF: the word's binary16 conversion, round to nearest even; values above 65504 become infinity) per channel, None
         for all FLOAT. Returns (the chunks as bytes, the uint64 array of their byte counts)."""
         compression = COMPRESSION[compression][0] if isinstance(compression, str) else int(compression)
-        arr, keep = pack_channels(channels)
-        n = len(channels)
+        n, rows = len(channels), height - first_row if row_count is None else row_count
         types = None if pixel_types is None else np.ascontiguousarray(pixel_types, dtype=np.uint8)
         if types is not None and types.shape != (n,):
             raise ValueError("pixel_types: one entry per channel")
-        rows = height - first_row if row_count is None else row_count
-        lines = 16 if compression == 3 else 1
-        chunks = max(-(-max(rows, 0) // lines), 0)
-        row_bytes = max(width, 0) * (4 * n if types is None else int(np.where(types == 1, 2, 4).sum()))
-        out = np.empty(8 * chunks + row_bytes * max(rows, 0), np.uint8)
-        sizes = np.zeros(max(chunks, 1), np.uint64)
-        total = C.c_uint64(0)
-        _check(self.L.crx_pack(self.h, arr, None if types is None else types.ctypes.data, n, width, height, first_row, rows, compression, out.ctypes.data,
-                               sizes.ctypes.data, C.byref(total)), "crx_pack")
-        del keep
-        return out[:total.value].tobytes(), sizes[:chunks if total.value else 0]
+        return self._pack("crx_pack", lambda arr, *out: self.L.crx_pack(self.h, arr, None if types is None else types.ctypes.data, n, width, height, first_row, rows, compression, *out),
+                          channels, 4 * n if types is None else int(np.where(types == 1, 2, 4).sum()), width, 16 if compression == 3 else 1, rows)
 
     def time_ms(self):
         """Milliseconds of the most recent pack_zip's kernels, summed (waits for them)."""

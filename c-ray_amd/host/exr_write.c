@@ -1,12 +1,11 @@
 /* exr_write.c — see exr_write.h. The layout, for a reader of this file alone:
  *   magic 76 2f 31 01, version 02 00 00 00 (single part, scanline, short names);
  *   attributes in ascending byte order of name, each `name\0 type\0 int32 size, value`: channels (chlist: per channel name\0, int32 pixelType 2 = FLOAT or 1 = HALF, uint8 pLinear 0,
- *   three zero bytes, int32 xSampling 1, int32 ySampling 1; one \0 ends the list), compression (one byte: 0, or 2 ZIPS / 3 ZIP in a chunked file), dataWindow and displayWindow (box2i 0, 0, W - 1, H - 1),
+ *   three zero bytes, int32 xSampling 1, int32 ySampling 1; one \0 ends the list), compression (one byte: 0, 2 ZIPS or 3 ZIP), dataWindow and displayWindow (box2i 0, 0, W - 1, H - 1),
  *   lineOrder (one byte 0: increasing y, stored row 0 is y 0), pixelAspectRatio (float 1), screenWindowCenter (v2f 0, 0), screenWindowWidth (float 1), the string
  *   attributes (size = length, no terminator); one \0 ends the header;
- *   H uint64 absolute offsets; the packed blocks. A chunked file (exr_write_file_chunked): one offset per chunk of 1 (ZIPS) or 16 (ZIP) rows, the chunks as
- *   crx_pack_zip writes them (include/cray_hip_exr.h: int32 y, int32 size, the data). With HALF channels (exr_write_file_chunked_typed, chunks from crx_pack) also
- *   compression 0: a raw chunk a row.
+ *   one uint64 absolute offset per chunk of 1 (compression 0, ZIPS) or 16 (ZIP) rows; the chunks as crx_pack writes them (include/cray_hip_exr.h: int32 y, int32 size,
+ *   the data). Compression 0: a raw chunk a row, which where all channels are FLOAT is crh_pack_scanlines' block.
  * Little-endian throughout, written byte by byte. */
 #include "exr_write.h"
 
@@ -159,11 +158,13 @@ int exr_layer_channels(const float *fb, const float *aov, const float *denoised,
 struct attr { const char *name, *type; const void *value; size_t size; };
 static int attr_by_name(const void *a, const void *b) { return strcmp(((const struct attr *)a)->name, ((const struct attr *)b)->name); }
 
-/* both files: compression 0 with `height` blocks of one size (sizes NULL), or chunk_count chunks of the sizes given; types: EXR_FLOAT / EXR_HALF per channel, NULL: all FLOAT */
-static int write_file(const char *path, int width, int height, const char *const *channel_names, const uint8_t *types, int channel_count, const struct exr_attr *strings,
-                      int string_count, int compression, const void *blocks, const uint64_t *sizes, int chunk_count) {
-	if (width <= 0 || height <= 0 || channel_count <= 0 || string_count < 0) return -1;
-	for (int c = 0; types && c < channel_count; ++c) if (types[c] != EXR_FLOAT && types[c] != EXR_HALF) return -1;
+int exr_write_file(const char *path, int width, int height, const char *const *channel_names, const uint8_t *pixel_types, int channel_count, const struct exr_attr *strings,
+                   int string_count, int compression, const void *chunk_data, const uint64_t *chunk_sizes, int chunk_count) {
+	if (width <= 0 || height <= 0 || channel_count <= 0 || string_count < 0 || !chunk_data || !chunk_sizes) return -1;
+	if (compression != 0 && compression != 2 && compression != 3) return -1;
+	const int lines = compression == 3 ? 16 : 1;
+	if (chunk_count != (height + lines - 1) / lines) return -1;
+	for (int c = 0; pixel_types && c < channel_count; ++c) if (pixel_types[c] != EXR_FLOAT && pixel_types[c] != EXR_HALF) return -1;
 	const unsigned char kind = (unsigned char)compression;
 	struct bytes chlist = {0}, window = {0}, one = {0}, zero2 = {0}, head = {0};
 	for (int c = 0; c < channel_count; ++c) {
@@ -171,7 +172,7 @@ static int write_file(const char *path, int width, int height, const char *const
 		assert(len >= 1 && len <= EXR_MAX_NAME);
 		if (len < 1 || len > EXR_MAX_NAME || (c && strcmp(channel_names[c - 1], channel_names[c]) >= 0)) { free(chlist.p); return -1; }
 		put(&chlist, channel_names[c], len + 1);
-		put_u32(&chlist, types && types[c] == EXR_HALF ? 1u : 2u);          /* HALF / FLOAT */
+		put_u32(&chlist, pixel_types && pixel_types[c] == EXR_HALF ? 1u : 2u);          /* HALF / FLOAT */
 		put_u32(&chlist, 0u);          /* pLinear 0 and three zero bytes */
 		put_u32(&chlist, 1u); put_u32(&chlist, 1u);
 	}
@@ -202,43 +203,22 @@ static int write_file(const char *path, int width, int height, const char *const
 			put_attr(&head, attrs[k].name, attrs[k].type, attrs[k].value, attrs[k].size);
 		}
 		put(&head, "", 1);
-		const uint64_t block = 8u + 4u * (uint64_t)channel_count * (uint64_t)width;
 		uint64_t at = head.n + 8u * (uint64_t)chunk_count, total = 0;
 		for (int k = 0; k < chunk_count; ++k) {
-			const uint64_t size = sizes ? sizes[k] : block;
-			if (size < 8u) rc = -1;
+			if (chunk_sizes[k] < 8u) rc = -1;
 			put_u64(&head, at + total);
-			total += size;
+			total += chunk_sizes[k];
 		}
 		if (head.failed) rc = -1;
 		FILE *f = rc ? NULL : fopen(path, "wb");
 		if (!f) rc = -1;
 		else {
-			if (fwrite(head.p, 1, head.n, f) != head.n || fwrite(blocks, 1, (size_t)total, f) != (size_t)total) rc = -1;
+			if (fwrite(head.p, 1, head.n, f) != head.n || fwrite(chunk_data, 1, (size_t)total, f) != (size_t)total) rc = -1;
 			if (fclose(f) != 0) rc = -1;
 		}
 	}
 	free(attrs); free(chlist.p); free(window.p); free(one.p); free(zero2.p); free(head.p);
 	return rc;
-}
-
-int exr_write_file(const char *path, int width, int height, const char *const *channel_names, int channel_count, const struct exr_attr *strings, int string_count,
-                   const void *blocks) {
-	return write_file(path, width, height, channel_names, NULL, channel_count, strings, string_count, 0, blocks, NULL, height);
-}
-
-int exr_write_file_chunked(const char *path, int width, int height, const char *const *channel_names, int channel_count, const struct exr_attr *strings,
-                           int string_count, int compression, const void *chunk_data, const uint64_t *chunk_sizes, int chunk_count) {
-	if (compression != 2 && compression != 3) return -1;
-	return exr_write_file_chunked_typed(path, width, height, channel_names, NULL, channel_count, strings, string_count, compression, chunk_data, chunk_sizes, chunk_count);
-}
-
-int exr_write_file_chunked_typed(const char *path, int width, int height, const char *const *channel_names, const uint8_t *pixel_types, int channel_count,
-                                 const struct exr_attr *strings, int string_count, int compression, const void *chunk_data, const uint64_t *chunk_sizes, int chunk_count) {
-	if ((compression != 0 && compression != 2 && compression != 3) || height <= 0 || !chunk_data || !chunk_sizes) return -1;
-	const int lines = compression == 3 ? 16 : 1;
-	if (chunk_count != (height + lines - 1) / lines) return -1;
-	return write_file(path, width, height, channel_names, pixel_types, channel_count, strings, string_count, compression, chunk_data, chunk_sizes, chunk_count);
 }
 
 int exr_half_types(const char *const *channel_names, int channel_count, uint8_t *pixel_types) {

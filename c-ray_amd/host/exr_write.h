@@ -1,5 +1,6 @@
 /* exr_write.h — the host side of the multi-layer OpenEXR output, in C for the drop-in program: a single-part scanline file whose channels are
- * FLOAT or, in the typed functions, HALF — uncompressed, or ZIP / ZIPS from chunks deflated on the device —, and Cryptomatte's naming of ids. The pixel data comes packed from the library (crh_pack_scanlines, include/cray_hip.h); this file knows which channel of
+ * FLOAT or HALF — uncompressed, or ZIP / ZIPS from chunks deflated on the device —, and Cryptomatte's naming of ids. The pixel data comes packed from the libraries
+ * (crh_pack_scanlines, include/cray_hip.h; crx_pack, include/cray_hip_exr.h); this file knows which channel of
  * which buffer carries which name and writes what goes around the data. c-ray_amd/exr.py states the same in Python; both write the same bytes. Not part of the
  * library. */
 #pragma once
@@ -28,25 +29,17 @@ int exr_layer_channels(const float *fb, const float *aov, const float *denoised,
                        const uint32_t *instance_map, uint32_t instance_count, const uint32_t *material_map, uint32_t material_count,
                        crh_pack_channel channels[CRH_PACK_MAX_CHANNELS], const char *names[CRH_PACK_MAX_CHANNELS]);
 
-/* The file: header (channel names in ascending byte order; the fixed attributes and `strings`, sorted here), offset table, and `blocks` — height blocks of
- * 8 + 4 * channel_count * width bytes as crh_pack_scanlines lays them out — verbatim. 0, or -1 (a name too long or out of order, out of memory, the file). */
-int exr_write_file(const char *path, int width, int height, const char *const *channel_names, int channel_count, const struct exr_attr *strings, int string_count,
-                   const void *blocks);
-
-/* The same file with compression 2 (ZIPS: a chunk a row) or 3 (ZIP: a chunk every 16 rows): the offset table has chunk_count = ceil(height / 1 or 16) entries and
- * `chunk_data` — the chunks back to back as crx_pack_zip writes them (include/cray_hip_exr.h), chunk k of chunk_sizes[k] bytes — follows verbatim. 0, or -1 (also:
- * another compression, a chunk count that does not fit the height, a chunk of less than 8 bytes). Same bytes as exr.file_bytes_chunked. */
-int exr_write_file_chunked(const char *path, int width, int height, const char *const *channel_names, int channel_count, const struct exr_attr *strings,
-                           int string_count, int compression, const void *chunk_data, const uint64_t *chunk_sizes, int chunk_count);
-
 /* Pixel types as crx_pack takes them (CRX_PIXEL_FLOAT / CRX_PIXEL_HALF of include/cray_hip_exr.h); the file's channel list says 2 and 1. */
 #define EXR_FLOAT 0
 #define EXR_HALF 1
 
-/* exr_write_file_chunked with a pixel type per channel (NULL: all FLOAT, and then its bytes) and the chunks as crx_pack writes them: compression 0 — a raw chunk a
- * row, chunk_count = height — is accepted too. 0, or -1 (also: a pixel type that is neither). Same bytes as exr.file_bytes_chunked(..., pixel_types=...). */
-int exr_write_file_chunked_typed(const char *path, int width, int height, const char *const *channel_names, const uint8_t *pixel_types, int channel_count,
-                                 const struct exr_attr *strings, int string_count, int compression, const void *chunk_data, const uint64_t *chunk_sizes, int chunk_count);
+/* The file: header (channel names in ascending byte order, a pixel type per channel — pixel_types NULL: all FLOAT —; the fixed attributes and `strings`, sorted
+ * here), offset table, and `chunk_data` — the chunks back to back as crx_pack writes them (include/cray_hip_exr.h), chunk k of chunk_sizes[k] bytes — verbatim.
+ * compression 0 (a raw chunk a row: where all channels are FLOAT, crh_pack_scanlines' blocks of 8 + 4 * channel_count * width bytes), 2 (ZIPS: a chunk a row) or
+ * 3 (ZIP: a chunk every 16 rows); the offset table has chunk_count = ceil(height / 1 or 16) entries. 0, or -1 (a name too long or out of order, a pixel type that
+ * is neither, another compression, a chunk count that does not fit the height, a chunk of less than 8 bytes, out of memory, the file). Same bytes as exr.file_bytes. */
+int exr_write_file(const char *path, int width, int height, const char *const *channel_names, const uint8_t *pixel_types, int channel_count,
+                   const struct exr_attr *strings, int string_count, int compression, const void *chunk_data, const uint64_t *chunk_sizes, int chunk_count);
 
 /* CRAY_HIP_EXR_HALF=1's default set, as Context.write_layers_exr(half=True) chooses it: pixel_types[c] = EXR_HALF for R G B, albedo.R/G/B, normal.X/Y/Z and
  * denoised.R/G/B, EXR_FLOAT for everything else (Z, A, the Cryptomatte channels). Returns how many are HALF. */

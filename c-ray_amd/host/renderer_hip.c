@@ -826,8 +826,8 @@ static void layerNamesFree(struct layerNames *n) {
 /* CRAY_HIP_EXR=1: <imgFilePath><imgFileName>_layers_<imgCount, four digits>.exr — the name the frame's own file would get for <imgFileName>_layers — holds the frame
  * `fb`, the guide buffers `aov` and the denoised frame `denoised` where CRAY_HIP_AOV / CRAY_HIP_DENOISE left them on GPU 0, and with CRAY_HIP_IDS=<n> the ranked ids of
  * min(n, sampleCount) passes of both ID buffers rendered here, as Cryptomatte layers. The channels are packed on the device (crh_pack_scanlines), at most 32 MB a call;
- * with CRAY_HIP_EXR_COMPRESSION=zip|zips beside it they are deflated there as well (crx_pack_zip of libcray_hip_exr.so) and the file is a ZIP / ZIPS one; with
- * CRAY_HIP_EXR_HALF=1 the colour layers are HALF (crx_pack and exr_write_file_chunked_typed, whatever the compression). */
+ * with CRAY_HIP_EXR_COMPRESSION=zip|zips beside it they are deflated there as well (crx_pack of libcray_hip_exr.so) and the file is a ZIP / ZIPS one; with
+ * CRAY_HIP_EXR_HALF=1 the colour layers are HALF (crx_pack too, whatever the compression). */
 static void writeLayers(struct renderer *r, crh_ctx *ctx, const float *fb, const float *aov, const float *denoised, const struct layerNames *names, int W, int H) {
 	const char *e = getenv("CRAY_HIP_IDS");
 	int n = e ? atoi(e) : 0;
@@ -858,7 +858,7 @@ static void writeLayers(struct renderer *r, crh_ctx *ctx, const float *fb, const
 	crh_pack_channel channels[CRH_PACK_MAX_CHANNELS];
 	const char *channelNames[CRH_PACK_MAX_CHANNELS];
 	const int count = exr_layer_channels(fb, aov, denoised, ids ? ranked[0] : NULL, ids ? ranked[1] : NULL, map[0], names->instanceCount, map[1], names->materialCount, channels, channelNames);
-	/* CRAY_HIP_EXR_COMPRESSION=zip|zips: the chunks deflated on the device by the companion library (crx_pack_zip, include/cray_hip_exr.h), 16 rows or one a chunk */
+	/* CRAY_HIP_EXR_COMPRESSION=zip|zips: the chunks deflated on the device by the companion library (crx_pack, include/cray_hip_exr.h), 16 rows or one a chunk */
 	const char *how = getenv("CRAY_HIP_EXR_COMPRESSION");
 	int kind = 0;
 	if (how && !strcmp(how, "zip")) kind = 3;
@@ -867,17 +867,17 @@ static void writeLayers(struct renderer *r, crh_ctx *ctx, const float *fb, const
 	const char *halfEnv = getenv("CRAY_HIP_EXR_HALF");
 	uint8_t types[CRH_PACK_MAX_CHANNELS];
 	const bool half = halfEnv && !strcmp(halfEnv, "1") && exr_half_types(channelNames, count, types) > 0;
-	const bool chunked = kind || half;          /* the companion library packs: crx_pack_zip, or crx_pack where there are HALF channels */
+	const bool companion = kind || half;          /* crx_pack packs; the uncompressed all-FLOAT file needs crh_pack_scanlines alone */
 	const int lines = kind == 3 ? 16 : 1, chunks = (H + lines - 1) / lines;
-	const size_t block = 8u + 4u * (size_t)count * (size_t)W;
-	char *blocks = ok ? malloc(chunked ? 8u * (size_t)chunks + (block - 8u) * (size_t)H : block * (size_t)H) : NULL;
-	uint64_t *sizes = chunked ? malloc((size_t)chunks * sizeof(*sizes)) : NULL;
+	const size_t block = 8u + 4u * (size_t)count * (size_t)W;          /* a FLOAT row behind its header: no row of any file takes more */
+	char *blocks = ok ? malloc(block * (size_t)H) : NULL;
+	uint64_t *sizes = malloc((size_t)chunks * sizeof(*sizes));
 	int chunk = (int)(((size_t)32 << 20) / block);
 	if (chunk < 1) chunk = 1;
 	chunk = (chunk + lines - 1) / lines * lines;
-	ok = ok && blocks && (!chunked || sizes);
+	ok = ok && blocks && sizes;
 	const char *why = NULL;
-	if (chunked && ok) {
+	if (companion && ok) {
 		crx_ctx *zip = NULL;
 		size_t at = 0;
 		ok = crh_synchronize(ctx) == CRH_OK;          /* the companion's stream is its own: the sources must be complete */
@@ -885,27 +885,23 @@ static void writeLayers(struct renderer *r, crh_ctx *ctx, const float *fb, const
 		for (int y = 0; ok && y < H; y += chunk) {
 			uint64_t total = 0;
 			const int rows = H - y < chunk ? H - y : chunk;
-			const int rc = half ? crx_pack(zip, channels, types, (uint32_t)count, W, H, y, rows, kind, blocks + at, sizes + y / lines, &total)
-			                    : crx_pack_zip(zip, channels, (uint32_t)count, W, H, y, rows, lines, blocks + at, sizes + y / lines, &total);
-			if (rc != CRH_OK) { ok = false; why = crx_last_error(); }
+			if (crx_pack(zip, channels, half ? types : NULL, (uint32_t)count, W, H, y, rows, kind, blocks + at, sizes + y / lines, &total) != CRH_OK) { ok = false; why = crx_last_error(); }
 			at += (size_t)total;
 		}
 		if (why) logr(warning, "c-ray-hip: %s\n", why);
 		crx_context_destroy(zip);
 	}
-	for (int y = 0; !chunked && ok && y < H; y += chunk)
+	for (int y = 0; !companion && ok && y < H; y += chunk)
 		ok = crh_pack_scanlines(ctx, channels, (uint32_t)count, W, H, y, H - y < chunk ? H - y : chunk, blocks + block * (size_t)y) == CRH_OK;
+	for (int y = 0; !companion && ok && y < H; ++y) sizes[y] = block;
 	const char *base = r->prefs.imgFileName ? r->prefs.imgFileName : "rendered";
 	const char *dir = r->prefs.imgFilePath ? r->prefs.imgFilePath : "";
 	char *path = malloc(strlen(dir) + strlen(base) + 32);
 	if (ok && path) {
 		sprintf(path, "%s%s_layers_%04d.exr", dir, base, r->prefs.imgCount);
-		const int rc = half ? exr_write_file_chunked_typed(path, W, H, channelNames, types, count, strings, stringCount, kind, blocks, sizes, chunks)
-		               : kind ? exr_write_file_chunked(path, W, H, channelNames, count, strings, stringCount, kind, blocks, sizes, chunks)
-		                      : exr_write_file(path, W, H, channelNames, count, strings, stringCount, blocks);
-		if (rc == 0) logr(info, "Layers written to %s (%i channels%s).\n", path, count, ids ? ", Cryptomatte ids" : "");
+		if (exr_write_file(path, W, H, channelNames, half ? types : NULL, count, strings, stringCount, kind, blocks, sizes, chunks) == 0) logr(info, "Layers written to %s (%i channels%s).\n", path, count, ids ? ", Cryptomatte ids" : "");
 		else logr(warning, "c-ray-hip: the layers file %s could not be written\n", path);
-	} else logr(warning, "c-ray-hip: the layers file could not be made: %s\n", blocks && path && (!chunked || sizes) ? crh_last_error() : "out of memory");
+	} else logr(warning, "c-ray-hip: the layers file could not be made: %s\n", blocks && path && sizes ? crh_last_error() : "out of memory");
 	free(sizes);
 	free(path); free(blocks);
 	exr_free_attrs(strings, stringCount);

@@ -2,7 +2,7 @@
 are FLOAT or HALF — uncompressed, ZIPS or ZIP —, exr.py and exr_write.c write the typed channel list around the chunks, Context.write_layers_exr(half=...) and the
 drop-in program's CRAY_HIP_EXR_HALF=1 choose the colour layers.
 
-The reader below is this file's own (mixed HALF / FLOAT planes, compression 0, 2 and 3) and is anchored by a 3 x 1 file spelled out field by field. CPU tier: the
+The reader (tests/exr_reader.py: mixed HALF / FLOAT planes, compression 0, 2 and 3) is anchored here by a 3 x 1 file spelled out field by field. CPU tier: the
 format, the Python writer, the C writer against it under AddressSanitizer and UBSan, the conversion over all 2^32 words against the CPU's F16C instruction, and this
 file's GPU tests run by a child pytest on the emulation. GPU tier: the identities with crx_pack_zip and pack_scanlines, every chunk inflated against a numpy
 restatement, the conversion on the device, determinism, refusals, a rendered file, the drop-in program."""
@@ -14,100 +14,14 @@ import subprocess
 import numpy as np
 import pytest
 
-from exr_reader import ALL_38, check_crypto_layer, run_dropin
+from exr_reader import (ALL_38, BYTES, F, H, LINES, check_crypto_layer, flat_source, hand_built_2x1, host_chunks, inflate_chunk, read_exr, run_dropin, split_chunks, strip_headers, to_half,
+                        typed_rows, zip_case)
 from firsthit_spec import resolve_expected
 from support import EMU_DIR, REPO, DeviceArray, ctx, dropin_env, dropin_paths, run_gpu_tests_on_emulation  # noqa: F401 (ctx: the fixture)
-from test_exr_zip import flat_source, inflate_chunk, read_exr, strip_headers, zip_case, zip_forward
-
-LINES = {0: 1, 2: 1, 3: 16}
-F, H = 0, 1
-BYTES = {F: 4, H: 2}
 
 # the table of the interface (include/cray_hip_exr.h): binary32 word -> binary16 word
 TABLE = [(0x7F800001, 0x7C01), (0x7F802000, 0x7C01), (0x7FC00000, 0x7E00), (0x477FEFFF, 0x7BFF), (0x477FF000, 0x7C00), (0x33000000, 0x0000), (0x33000001, 0x0001),
          (0x387FC000, 0x03FF), (0x3F801000, 0x3C00), (0x3F803000, 0x3C02)]
-
-
-def to_half(words):
-    """numpy's conversion of 32-bit words read as binary32: the uint16 bits"""
-    with np.errstate(over="ignore", invalid="ignore"):
-        return np.ascontiguousarray(words, np.uint32).view(np.float32).astype(np.float16).view(np.uint16)
-
-
-def typed_rows(words, types):
-    """uint32 [rows, channels, w] -> uint8 [rows, rowBytes]: a plane per channel, 4-byte words or their 2-byte conversions, little-endian"""
-    parts = [(to_half(words[:, c]).astype("<u2") if t == H else words[:, c].astype("<u4")).view(np.uint8).reshape(words.shape[0], -1) for c, t in enumerate(types)]
-    return np.concatenate(parts, axis=1)
-
-
-def split_typed(data, sizes, row_bytes, first, rows, lines):
-    """crx_pack's output -> [(y, data bytes, n)] after checking the layout: chunks back to back in row order, sizes as stated"""
-    out, at = [], 0
-    assert len(sizes) == -(-rows // lines)
-    for k, total in enumerate(int(v) for v in sizes):
-        y, size = struct.unpack_from("<ii", data, at)
-        n = row_bytes * min(lines, rows - k * lines)
-        assert y == first + k * lines and total == 8 + size and 0 < size <= n, (k, y, size, n)
-        out.append((y, data[at + 8:at + 8 + size], n))
-        at += total
-    assert at == len(data)
-    return out
-
-
-# ---- the reader: mixed HALF / FLOAT planes, compression 0, 2 and 3 ------------------------------------------------------------------------
-def read_typed(data):
-    """A single-part scanline OpenEXR file whose channels are HALF or FLOAT, uncompressed, ZIPS or ZIP -> width, height, attrs, names, types {name: H or F},
-    planes {name: uint16 or uint32 [H, W]}, compression, chunks [(y, size, n)]. Every offset is checked against the position of its chunk."""
-    assert data[0:8] == bytes([0x76, 0x2F, 0x31, 0x01, 2, 0, 0, 0])
-    pos, attrs, order = 8, {}, []
-    while data[pos] != 0:
-        end = data.index(b"\0", pos)
-        name = data[pos:end]
-        end2 = data.index(b"\0", end + 1)
-        size, = struct.unpack_from("<i", data, end2 + 1)
-        attrs[name.decode()] = (data[end + 1:end2].decode(), data[end2 + 5:end2 + 5 + size])
-        order.append(name)
-        pos = end2 + 5 + size
-    pos += 1
-    kind_attr, chl = attrs["channels"]
-    assert kind_attr == "chlist" and chl[-1] == 0
-    names, types, c = [], [], 0
-    while chl[c] != 0:
-        end = chl.index(b"\0", c)
-        pixel_type, *rest = struct.unpack_from("<iBBBBii", chl, end + 1)
-        assert pixel_type in (1, 2) and rest == [0, 0, 0, 0, 1, 1], chl[c:end]
-        names.append(chl[c:end].decode())
-        types.append(H if pixel_type == 1 else F)
-        c = end + 17
-    assert c == len(chl) - 1
-    kind = attrs["compression"][1][0]
-    assert attrs["compression"] == ("compression", bytes([kind])) and kind in (0, 2, 3) and attrs["lineOrder"] == ("lineOrder", b"\0")
-    x0, y0, x1, y1 = struct.unpack("<4i", attrs["dataWindow"][1])
-    assert (x0, y0) == (0, 0) and attrs["displayWindow"] == attrs["dataWindow"]
-    w, h, lines = x1 + 1, y1 + 1, LINES[kind]
-    row_bytes = w * sum(BYTES[t] for t in types)
-    count = -(-h // lines)
-    offsets = list(struct.unpack_from(f"<{count}Q", data, pos))
-    pos += 8 * count
-    raw, chunks = b"", []
-    for k in range(count):
-        assert offsets[k] == pos, "every offset is the position of its chunk"
-        y, size = struct.unpack_from("<ii", data, pos)
-        n = row_bytes * min(lines, h - k * lines)
-        assert y == k * lines and 0 < size <= n and (kind != 0 or size == n)
-        raw += inflate_chunk(data[pos + 8:pos + 8 + size], n)
-        chunks.append((y, size, n))
-        pos += 8 + size
-    assert pos == len(data), "nothing behind the last chunk"
-    assert order == sorted(order) and [s.encode() for s in names] == sorted(s.encode() for s in names)
-    rows = np.frombuffer(raw, np.uint8).reshape(h, row_bytes)
-    planes, at = {}, 0
-    for name, t in zip(names, types):
-        planes[name] = np.ascontiguousarray(rows[:, at:at + BYTES[t] * w]).view("<u2" if t == H else "<u4").astype(np.uint16 if t == H else np.uint32)
-        at += BYTES[t] * w
-    assert at == row_bytes
-    return {"width": w, "height": h, "attrs": attrs, "attr_order": order, "names": names, "types": dict(zip(names, types)), "planes": planes, "offsets": offsets,
-            "compression": kind, "chunks": chunks}
 
 
 def hand_built_3x1():
@@ -138,34 +52,21 @@ def hand_built_3x1():
 HAND_PLANES = [np.array([[0x3E800000, 0x80000000, 0x7FC00123]], np.uint32),                       # A as it is
                np.array([[0x3F800000, 0x477FE000, 0xB3800000]], np.uint32),                       # B: 1.0, 65504.0, -2^-24 as binary32
                np.array([[0x7F800000, 0x7FC00000, 0x3EAAAAAB]], np.uint32)]                       # C: inf, NaN, 1 / 3 (rounds to 0x3555)
-
-
-def host_typed_chunks(planes, types, w, h, kind):
-    """crx_pack's chunks made on the host: (data, sizes)"""
-    import zlib
-    rows = typed_rows(np.stack([np.ascontiguousarray(p).view(np.uint32).reshape(h, w) for p in planes], axis=1), types)
-    data, sizes = b"", []
-    for y in range(0, h, LINES[kind]):
-        raw = rows[y:y + LINES[kind]].tobytes()
-        z = zlib.compress(zip_forward(raw), 1) if kind else raw
-        body = z if len(z) < len(raw) else raw
-        data += struct.pack("<ii", y, len(body)) + body
-        sizes.append(8 + len(body))
-    return data, sizes
+FLAT_PLANES = [np.array([[0x3E800000, 0x80000000]], np.uint32), np.array([[0x3FC00000, 0x7FC00123]], np.uint32)]          # exr_reader.hand_built_2x1's B and R
 
 
 # ---- CPU tier: the format ---------------------------------------------------------------------------------------------------------------
 def test_reader_is_anchored_and_exr_py_writes_the_typed_file(pkg):
     exr = pkg.exr
     data = hand_built_3x1()
-    f = read_typed(data)
+    f = read_exr(data)
     assert (f["width"], f["height"], f["names"], f["compression"]) == (3, 1, ["A", "B", "C"], 0) and f["types"] == {"A": F, "B": H, "C": H}
     assert f["planes"]["A"].tolist() == [[0x3E800000, 0x80000000, 0x7FC00123]] and f["planes"]["A"].dtype == np.uint32
     assert f["planes"]["B"].tolist() == [[0x3C00, 0x7BFF, 0x8001]] and f["planes"]["C"].tolist() == [[0x7C00, 0x7E00, 0x3555]] and f["planes"]["C"].dtype == np.uint16
     types = [F, H, H]
     blocks = exr.pack_host(HAND_PLANES, 3, 1, types)
     assert blocks == data[-32:]
-    assert exr.file_bytes_chunked(3, 1, ["A", "B", "C"], blocks, [32], compression=0, pixel_types=types) == data
+    assert exr.file_bytes(3, 1, ["A", "B", "C"], blocks, [32], compression=0, pixel_types=types) == data
     assert exr.header(3, 1, ["A", "B", "C"], pixel_types=types) == data[:-8 - 32]
     # pixel_types=None: today's bytes, from every function
     names, strings = ["A", "B", "C"], {"zzz": "ä"}
@@ -176,10 +77,11 @@ def test_reader_is_anchored_and_exr_py_writes_the_typed_file(pkg):
     rng = np.random.default_rng(5)
     planes = [np.repeat(rng.integers(0x3C000000, 0x40000000, (17, 5), dtype=np.uint32), 8, axis=1) for _ in range(3)]
     for kind in (2, 3):
-        chunks, sizes = host_typed_chunks(planes, [F, F, F], 40, 17, kind)
-        assert exr.file_bytes_chunked(40, 17, names, chunks, sizes, strings, kind, None) == exr.file_bytes_chunked(40, 17, names, chunks, sizes, strings, kind)
-    with pytest.raises(AssertionError):
-        exr.file_bytes_chunked(40, 17, names, chunks, sizes, None, 0)          # compression 0 stays a typed form
+        chunks, sizes = host_chunks(planes, 40, 17, kind, [F, F, F])
+        assert exr.file_bytes(40, 17, names, chunks, sizes, strings, kind, None) == exr.file_bytes(40, 17, names, chunks, sizes, strings, kind)
+    # compression 0 without types is the flat file, whether its chunks' sizes are stated or not
+    flat = exr.pack_host(FLAT_PLANES, 2, 1)
+    assert exr.file_bytes(2, 1, ["B", "R"], flat, [24], None, 0) == exr.file_bytes(2, 1, ["B", "R"], flat) == hand_built_2x1()
     with pytest.raises(AssertionError):
         exr.header(3, 1, names, pixel_types=[F, 2, H])
     with pytest.raises(AssertionError):
@@ -189,16 +91,16 @@ def test_reader_is_anchored_and_exr_py_writes_the_typed_file(pkg):
     for w in (40, 3):
         planes = [np.repeat(rng.integers(0x3C000000, 0x40000000, (17, -(-w // 8)), dtype=np.uint32), 8, axis=1)[:, :w] for _ in range(3)]
         for kind in (0, 2, 3):
-            chunks, sizes = host_typed_chunks(planes, types, w, 17, kind)
-            g = read_typed(exr.file_bytes_chunked(w, 17, names, chunks, sizes, strings, kind, types))
+            chunks, sizes = host_chunks(planes, w, 17, kind, types)
+            g = read_exr(exr.file_bytes(w, 17, names, chunks, sizes, strings, kind, types))
             assert g["compression"] == kind and len(g["chunks"]) == (2 if kind == 3 else 17) and g["types"] == dict(zip(names, types))
             assert w == 3 or kind == 0 or any(size < n for _, size, n in g["chunks"])
             for name, p, t in zip(names, planes, types):
                 assert np.array_equal(g["planes"][name], to_half(p) if t == H else p), (w, kind, name)
             assert g["attrs"]["zzz"] == ("string", "ä".encode())
     # a chunk of n = 2 (mod 4) bytes: 3 FLOAT and 3 HALF pixels
-    chunks, sizes = host_typed_chunks(HAND_PLANES[:2], [F, H], 3, 1, 2)
-    assert sizes == [8 + 18] and read_typed(exr.file_bytes_chunked(3, 1, ["A", "B"], chunks, sizes, None, 2, [F, H]))["planes"]["B"].tolist() == [[0x3C00, 0x7BFF, 0x8001]]
+    chunks, sizes = host_chunks(HAND_PLANES[:2], 3, 1, 2, [F, H])
+    assert sizes == [8 + 18] and read_exr(exr.file_bytes(3, 1, ["A", "B"], chunks, sizes, None, 2, [F, H]))["planes"]["B"].tolist() == [[0x3C00, 0x7BFF, 0x8001]]
     # the names write_layers_exr(half=...) takes
     lay = sorted(ALL_38, key=lambda s: s.encode())
     t = exr.half_types(lay, True)
@@ -221,6 +123,11 @@ int main(int argc, char **argv) {
 	crh_pack_channel channels[CRH_PACK_MAX_CHANNELS];
 	const char *names[CRH_PACK_MAX_CHANNELS];
 	uint8_t types[CRH_PACK_MAX_CHANNELS], bad[CRH_PACK_MAX_CHANNELS];
+	/* the 2 x 1 image B = (0.25, -0.0), R = (1.5, a NaN) as one raw chunk: written to <out>.flat with compression 0 and no types */
+	static const char *flatNames[2] = {"B", "R"};
+	static const uint32_t flat[6] = {0u, 16u, 0x3e800000u, 0x80000000u, 0x3fc00000u, 0x7fc00123u};
+	const uint64_t flatSize = sizeof(flat);
+	char flatPath[4096];
 	struct exr_attr strings[2] = {{"aaa", ""}, {"zzz", "\303\244 \"q\""}};
 	if (argc < 7) return 1;
 	const int n = exr_layer_channels(dummy, dummy, dummy, dummy, dummy, map, 1, map, 1, channels, names);
@@ -235,22 +142,23 @@ int main(int argc, char **argv) {
 	FILE *f = fopen(argv[5], "rb");
 	if (!f || fread(data, 1, total, f) != total) return 3;
 	fclose(f);
-	const int rc = exr_write_file_chunked_typed(argv[1], w, h, names, types, n, strings, 2, kind, data, sizes, count);
-	const int refused = exr_write_file_chunked_typed(argv[1], w, h, names, types, n, strings, 2, kind, data, sizes, count - 1) == 0 ||
-	                    exr_write_file_chunked_typed(argv[1], w, h, names, types, n, strings, 2, 1, data, sizes, count) == 0 ||
-	                    exr_write_file_chunked_typed(argv[1], w, h, names, bad, n, strings, 2, kind, data, sizes, count) == 0 ||
-	                    exr_write_file_chunked(argv[1], w, h, names, n, strings, 2, 0, data, sizes, count) == 0;
+	const int rc = exr_write_file(argv[1], w, h, names, types, n, strings, 2, kind, data, sizes, count);
+	const int refused = exr_write_file(argv[1], w, h, names, types, n, strings, 2, kind, data, sizes, count - 1) == 0 ||
+	                    exr_write_file(argv[1], w, h, names, types, n, strings, 2, 1, data, sizes, count) == 0 ||
+	                    exr_write_file(argv[1], w, h, names, bad, n, strings, 2, kind, data, sizes, count) == 0;
+	snprintf(flatPath, sizeof(flatPath), "%s.flat", argv[1]);
+	const int flatRc = exr_write_file(flatPath, 2, 1, flatNames, NULL, 2, NULL, 0, 0, flat, &flatSize, 1);
 	for (int c = 0; c < n; ++c) printf("%s %d\n", names[c], types[c]);
 	free(sizes); free(data);
-	return rc ? 2 : refused ? 4 : 0;
+	return rc ? 2 : refused ? 4 : flatRc ? 6 : 0;
 }
 """
 
 
 def test_c_typed_writer_writes_the_bytes_of_exr_py(pkg, tmp_path):
-    """exr_write_file_chunked_typed and exr_half_types in a program of their own (AddressSanitizer and UBSan) against exr.file_bytes_chunked(pixel_types=...), byte
-    for byte: every layer's 38 channels with the default half set, compression 0, 2 and 3, host-made chunks, a short last chunk; a wrong chunk count, compression 1,
-    a pixel type 2 and compression 0 through the untyped function are refused."""
+    """exr_write_file and exr_half_types in a program of their own (AddressSanitizer and UBSan) against exr.file_bytes(pixel_types=...), byte
+    for byte: every layer's 38 channels with the default half set, compression 0, 2 and 3, host-made chunks, a short last chunk; a wrong chunk count, compression 1
+    and a pixel type 2 are refused; compression 0 without types writes the flat file, exr.file_bytes' and the hand-built one's bytes."""
     exr = pkg.exr
     host = os.path.join(REPO, "c-ray_amd", "host")
     src, exe = tmp_path / "hc.c", tmp_path / "hc"
@@ -265,16 +173,17 @@ def test_c_typed_writer_writes_the_bytes_of_exr_py(pkg, tmp_path):
     for p in planes:
         p[16:32] = rng.integers(0, 2 ** 32, (16, w), dtype=np.uint32)
     for kind in (0, 2, 3):
-        chunks, sizes = host_typed_chunks(planes, types, w, h, kind)
+        chunks, sizes = host_chunks(planes, w, h, kind, types)
         blob, out = tmp_path / f"chunks{kind}", tmp_path / f"c{kind}.exr"
         blob.write_bytes(chunks)
         r = subprocess.run([str(exe), str(out), str(w), str(h), str(kind), str(blob)] + [str(s) for s in sizes], capture_output=True, text=True, timeout=120)
         assert r.returncode == 0, r.stdout + r.stderr
         assert [line.split() for line in r.stdout.splitlines()] == [[n, str(t)] for n, t in zip(names, types)], "exr_half_types chooses what exr.half_types chooses"
-        want = exr.file_bytes_chunked(w, h, names, chunks, sizes, {"aaa": "", "zzz": "ä \"q\""}, kind, types)
+        want = exr.file_bytes(w, h, names, chunks, sizes, {"aaa": "", "zzz": "ä \"q\""}, kind, types)
         got = out.read_bytes()
         assert got == want
-        f = read_typed(got)
+        assert (tmp_path / f"c{kind}.exr.flat").read_bytes() == exr.file_bytes(2, 1, ["B", "R"], exr.pack_host(FLAT_PLANES, 2, 1)) == hand_built_2x1()
+        f = read_exr(got)
         assert kind == 0 or min(sizes) < max(sizes), "deflated chunks among the others"
         for name, p, t in zip(names, planes, types):
             assert np.array_equal(f["planes"][name], to_half(p) if t == H else p), name
@@ -433,7 +342,7 @@ def test_mixed_round_trip_against_numpy(pkg, ctx, zctx):
         row_bytes = w * sum(BYTES[t] for t in types)
         for kind in (0, 2, 3):
             data, sizes, want = run_pack(pkg, ctx, zctx, case, kind)
-            chunks = split_typed(data, sizes, row_bytes, 0, h, LINES[kind])
+            chunks = split_chunks(data, sizes, row_bytes, 0, h, LINES[kind])
             got = b"".join(inflate_chunk(d, n) for _, d, n in chunks)
             assert len(want) == row_bytes * h and len(got) == len(want), (w, h, kind)
             bad = np.flatnonzero(np.frombuffer(got, np.uint8) != np.frombuffer(want, np.uint8))
@@ -487,7 +396,7 @@ def test_conversion_on_the_device_matches_numpy(pkg, ctx, zctx):
     ctx.synchronize()
     for kind in (0, 3):
         data, sizes = zctx.pack([(dev.ptr, 1, 0)], w, rows, kind, [H])
-        chunks = split_typed(data, sizes, 2 * w, 0, rows, LINES[kind])
+        chunks = split_chunks(data, sizes, 2 * w, 0, rows, LINES[kind])
         got = np.frombuffer(b"".join(inflate_chunk(d, n) for _, d, n in chunks), "<u2").reshape(rows, w)
         bad = np.argwhere(got != want)
         assert bad.size == 0, (kind, len(bad), [(hex(plane[y, x, 0]), hex(got[y, x]), hex(want[y, x])) for y, x in bad[:5]])
@@ -511,7 +420,7 @@ def test_determinism_and_row_ranges(pkg, ctx, zctx):
         assert b"".join(p[0] for p in parts) == whole
         assert np.array_equal(np.concatenate([p[1] for p in parts]), sizes)
         for (data, sz, raw), (f, r) in zip(parts, ranges):
-            assert b"".join(inflate_chunk(d, n) for _, d, n in split_typed(data, sz, row_bytes, f, r, LINES[kind])) == raw
+            assert b"".join(inflate_chunk(d, n) for _, d, n in split_chunks(data, sz, row_bytes, f, r, LINES[kind])) == raw
         run_pack(pkg, ctx, zctx, other, kind)
         assert run_pack(pkg, ctx, zctx, case, kind)[0] == whole
 
@@ -566,7 +475,7 @@ def test_refused_arguments_leave_everything_untouched(pkg, ctx, zctx):
     assert np.array_equal(a.read(ctx), sa) and np.array_equal(b.read(ctx), sb), "a refused call wrote a source"
     assert call() == abi.OK
     row_bytes = w * (2 + 4 + 2)
-    chunks = split_typed(out[:total.value].tobytes(), sizes[:3], row_bytes, 0, h, 16)
+    chunks = split_chunks(out[:total.value].tobytes(), sizes[:3], row_bytes, 0, h, 16)
     words = np.frombuffer(strip_headers(ctx.pack_scanlines([(a.ptr, 3, 1), (b.ptr, 8, 7, m), (a.ptr, 3, 2)], w, h), 3, w), "<u4").reshape(h, 3, w)
     assert b"".join(inflate_chunk(d, n) for _, d, n in chunks) == typed_rows(words, good_types).tobytes()
     assert (out[total.value:] == 0xA5).all() and (sizes[3:] == 0xA5A5A5A5A5A5A5A5).all(), "nothing behind the chunks is written"
@@ -605,7 +514,7 @@ def test_rendered_layers_file_with_half_channels(pkg, ctx, golden_blob, manifest
         path = str(tmp_path / f"half_{compression}.exr")
         assert ctx.write_layers_exr(path, w, h, fb, compression=compression, chunk_rows=chunk_rows, half=True, **kw) == names
         data = open(path, "rb").read()
-        f = read_typed(data)
+        f = read_exr(data)
         assert (f["compression"], f["width"], f["height"], f["names"]) == (kind, w, h, names)
         assert {c for c in names if f["types"][c] == H} == half_set, "R G B, albedo.*, normal.*, denoised.*: HALF; Z, A and the Cryptomatte channels: FLOAT"
         for c in names:
@@ -617,7 +526,7 @@ def test_rendered_layers_file_with_half_channels(pkg, ctx, golden_blob, manifest
         print(f"{compression}: half {len(data)} of {len(plain[compression])} bytes")
     path = str(tmp_path / "z.exr")
     ctx.write_layers_exr(path, w, h, fb, half=("Z",), **kw)
-    f = read_typed(open(path, "rb").read())
+    f = read_exr(open(path, "rb").read())
     assert [c for c in names if f["types"][c] == H] == ["Z"] and np.array_equal(f["planes"]["Z"], to_half(f0["planes"]["Z"])) and np.array_equal(f["planes"]["R"], f0["planes"]["R"])
     for bad in (("nope",), ("CryptoObject00.R",), ("R", "CryptoMaterial01.G")):
         with pytest.raises(ValueError):
@@ -642,7 +551,7 @@ def test_dropin_program_writes_the_half_layers_file(pkg, ctx, manifest, golden_b
     for name, data in plain.items():
         assert name == "refrun_layers_0000.exr" or files[name] == data, f"{name} changed"
     data = files["refrun_layers_0000.exr"]
-    f, f0 = read_typed(data), read_exr(plain["refrun_layers_0000.exr"])
+    f, f0 = read_exr(data), read_exr(plain["refrun_layers_0000.exr"])
     assert f["compression"] == 3 and f0["compression"] == 3 and len(data) < len(plain["refrun_layers_0000.exr"])
     assert sum(t == H for t in f["types"].values()) == 12 and f["types"]["Z"] == F and f["types"]["R"] == H
     for c in f0["names"]:

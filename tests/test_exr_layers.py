@@ -55,7 +55,7 @@ def test_round_trip(w, h, nch, pkg):
     names = sorted((ALL_38[i] for i in rng.permutation(38)[:nch]), key=lambda s: s.encode())
     planes = [rng.integers(0, 2 ** 32, (h, w), dtype=np.uint32) for _ in names]          # any bit pattern: NaNs, infinities, subnormals
     strings = {"cryptomatte/3ae39a5/name": "CryptoObject", "aaa": "", "zzz": "ä \"quoted\""} if nch > 1 else None
-    data = exr.file_bytes(w, h, names, exr.pack_host(planes, w, h), strings)
+    data = exr.file_bytes(w, h, names, exr.pack_host(planes, w, h), strings=strings)
     f = read_exr(data)
     check_structure(f, data)
     assert (f["width"], f["height"], f["names"]) == (w, h, names)
@@ -107,6 +107,7 @@ int main(int argc, char **argv) {
 	static float a, b, c, d, e;
 	const int n = exr_layer_channels(&a, &b, &c, &d, &e, NULL, 0, NULL, 0, ch, names);
 	uint32_t blocks[2][2 + 38 * 3];
+	const uint64_t sizes[2] = {sizeof(blocks[0]), sizeof(blocks[1])};
 	struct exr_attr strings[8];
 	if (argc < 2 || n != 38 || exr_crypto_attrs("CryptoObject", inst, 3, strings) || exr_crypto_attrs("CryptoMaterial", mat, 2, strings + 4)) return 1;
 	for (int y = 0; y < 2; ++y) {
@@ -115,7 +116,7 @@ int main(int argc, char **argv) {
 	}
 	for (int k = 0; k < n; ++k) printf("%s %u %u %d\n", names[k], ch[k].stride, ch[k].component, (int)(ch[k].dev_src == &a ? 0 : ch[k].dev_src == &b ? 1 : ch[k].dev_src == &c ? 2 : ch[k].dev_src == &d ? 3 : 4));
 	printf("hash %08x %08x %08x %08x\n", exr_murmur3_32("", 0, 0), exr_crypto_id(""), exr_crypto_id("hello"), exr_crypto_id("foo"));
-	const int rc = exr_write_file(argv[1], 3, 2, names, n, strings, 8, blocks);
+	const int rc = exr_write_file(argv[1], 3, 2, names, NULL, n, strings, 8, 0, blocks, sizes, 2);
 	exr_free_attrs(strings, 8);
 	return rc ? 2 : 0;
 }
@@ -140,7 +141,7 @@ def test_c_writer_writes_the_bytes_of_exr_py(pkg, tmp_path):
     inst, mat = ["sphere#0", "a \"quoted\\\" mesh\n#1", "mäsh#2"], ["material#0", "material#1"]
     strings = dict(exr.crypto_attributes("CryptoObject", inst), **exr.crypto_attributes("CryptoMaterial", mat))
     planes = [np.array([[0x3F000000 + 4096 * k + 16 * y + x for x in range(3)] for y in range(2)], np.uint32) for k in range(38)]
-    want = exr.file_bytes(3, 2, [c[0] for c in chans], exr.pack_host(planes, 3, 2), strings)
+    want = exr.file_bytes(3, 2, [c[0] for c in chans], exr.pack_host(planes, 3, 2), strings=strings)
     got = out.read_bytes()
     assert got == want
     f = read_exr(got)

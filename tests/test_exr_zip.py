@@ -1,9 +1,9 @@
 """The layers file, ZIP / ZIPS compressed on the device: crx_pack_zip of the companion library libcray_hip_exr.so (include/cray_hip_exr.h, c-ray_amd/csrc/exr_zip.h)
 gathers the channels crh_pack_scanlines gathers, applies OpenEXR's byte split and predictor and deflates every chunk with fixed Huffman codes;
-exr.file_bytes_chunked and exr_write_file_chunked (c-ray_amd/host/exr_write.c) write the file around the chunks.
+exr.file_bytes and exr_write_file (c-ray_amd/host/exr_write.c) write the file around the chunks.
 
-The reader below is this file's own (compression 0, 2 and 3; it inflates with Python's zlib, undoes the predictor and the split and checks the offset table against the
-chunk positions) and is anchored by a 2 x 1 ZIPS file spelled out field by field. CPU tier: the format, the Python writer, the C writer against it, and this file's
+The reader (tests/exr_reader.py: it inflates with Python's zlib, undoes the predictor and the split and checks the offset table against the chunk positions) is
+anchored here by a 2 x 1 ZIPS file spelled out field by field. CPU tier: the format, the Python writer, the C writer against it, and this file's
 GPU tests run by a child pytest on the emulation (tests/emu/Makefile.exr). GPU tier: the inflated chunks bit for bit against Context.pack_scanlines, crafted
 planes, chunked calls, refused arguments, size conditions against host zlib with fixed codes, a rendered file, the drop-in program."""
 import ctypes as C
@@ -15,68 +15,10 @@ import zlib
 import numpy as np
 import pytest
 
-import exr_reader
-from exr_reader import ALL_38, SPECIAL, check_crypto_layer, hand_built_2x1, plant_ids, run_dropin
+from exr_reader import (ALL_38, LINES, check_crypto_layer, flat_source, hand_built_2x1, host_chunks, inflate_chunk, raw_of, read_exr, run_dropin, split_chunks, strip_headers,
+                        zip_case, zip_forward, zip_inverse)
 from firsthit_spec import resolve_expected
 from support import EMU_DIR, REPO, DeviceArray, ctx, dropin_env, dropin_paths, run_gpu_tests_on_emulation  # noqa: F401 (ctx: the fixture)
-
-LINES = {0: 1, 2: 1, 3: 16}
-
-
-# ---- OpenEXR's ZIP transform on the host --------------------------------------------------------------------------------------------------
-def zip_forward(raw):
-    """raw bytes R -> T': even bytes first, then odd ones; then every byte but the first becomes its difference to its predecessor + 128"""
-    r = np.frombuffer(bytes(raw), np.uint8)
-    t = np.concatenate([r[0::2], r[1::2]]).astype(np.int64)
-    p = t.copy()
-    p[1:] = (t[1:] - t[:-1] + 128) & 255
-    return p.astype(np.uint8).tobytes()
-
-
-def zip_inverse(tp):
-    """T' -> R"""
-    p = np.frombuffer(bytes(tp), np.uint8).astype(np.int64)
-    n = p.size
-    t = ((np.cumsum(p) - 128 * np.arange(n)) & 255).astype(np.uint8)
-    r = np.empty(n, np.uint8)
-    r[0::2] = t[:(n + 1) // 2]
-    r[1::2] = t[(n + 1) // 2:]
-    return r.tobytes()
-
-
-def inflate_chunk(data, n):
-    """the raw bytes of a chunk's data (n: its raw size): size == n is raw, anything else a complete zlib stream of T' with nothing behind it"""
-    if len(data) == n:
-        return bytes(data)
-    assert len(data) < n, "a chunk larger than its raw bytes"
-    assert data[0:2] == b"\x78\x01", "zlib header: CM 8, 32 K window, no dictionary"
-    d = zlib.decompressobj()
-    tp = d.decompress(bytes(data))
-    assert d.eof and d.unused_data == b"" and len(tp) == n, "one complete zlib stream of n bytes"
-    return zip_inverse(tp)
-
-
-def split_chunks(data, sizes, nch, w, first, rows, lines):
-    """crx_pack_zip's output -> [(y, data bytes, n)] after checking the layout: chunks back to back in row order, sizes as stated"""
-    out, at = [], 0
-    assert len(sizes) == -(-rows // lines)
-    for k, total in enumerate(int(v) for v in sizes):
-        y, size = struct.unpack_from("<ii", data, at)
-        n = 4 * nch * w * min(lines, rows - k * lines)
-        assert y == first + k * lines and total == 8 + size and 0 < size <= n, (k, y, size, n)
-        out.append((y, data[at + 8:at + 8 + size], n))
-        at += total
-    assert at == len(data)
-    return out
-
-
-def raw_of(chunks):
-    return b"".join(inflate_chunk(d, n) for _, d, n in chunks)
-
-
-def strip_headers(blocks, nch, w):
-    """Context.pack_scanlines' bytes without the 8-byte header of every row"""
-    return np.frombuffer(blocks, np.uint8).reshape(-1, 8 + 4 * nch * w)[:, 8:].tobytes()
 
 
 def yardstick(raw, n_per_chunk):
@@ -89,73 +31,6 @@ def yardstick(raw, n_per_chunk):
         got += 8 + min(len(z), len(r))
         want += 8 + len(r)
     return got, want
-
-
-# ---- the reader: compression 0, 2 and 3 -------------------------------------------------------------------------------------------------
-def read_exr(data):
-    """A single-part scanline OpenEXR file whose channels are all FLOAT, uncompressed, ZIPS or ZIP -> what exr_reader.read_exr returns, and `compression`,
-    `chunks` [(y, size, n)]. Every offset is checked against the position of its chunk."""
-    kind = data[data.index(b"compression\0compression\0") + 28]
-    if kind == 0:
-        f = exr_reader.read_exr(data)
-        f["compression"] = 0
-        return f
-    assert kind in (2, 3)
-    pos, attrs, order = 8, {}, []
-    assert data[0:8] == bytes([0x76, 0x2F, 0x31, 0x01, 2, 0, 0, 0])
-    while data[pos] != 0:
-        end = data.index(b"\0", pos)
-        name = data[pos:end]
-        end2 = data.index(b"\0", end + 1)
-        typ = data[end + 1:end2]
-        size, = struct.unpack_from("<i", data, end2 + 1)
-        attrs[name.decode()] = (typ.decode(), data[end2 + 5:end2 + 5 + size])
-        order.append(name)
-        pos = end2 + 5 + size
-    pos += 1
-    chl, names, c = attrs["channels"][1], [], 0
-    while chl[c] != 0:
-        end = chl.index(b"\0", c)
-        assert struct.unpack_from("<iBBBBii", chl, end + 1) == (2, 0, 0, 0, 0, 1, 1)
-        names.append(chl[c:end].decode())
-        c = end + 17
-    assert attrs["compression"] == ("compression", bytes([kind])) and attrs["lineOrder"] == ("lineOrder", b"\0")
-    x0, y0, x1, y1 = struct.unpack("<4i", attrs["dataWindow"][1])
-    assert (x0, y0) == (0, 0) and attrs["displayWindow"] == attrs["dataWindow"]
-    w, h, lines = x1 + 1, y1 + 1, LINES[kind]
-    count = -(-h // lines)
-    offsets = list(struct.unpack_from(f"<{count}Q", data, pos))
-    pos += 8 * count
-    first = pos
-    planes = np.empty((len(names), h, w), np.uint32)
-    chunks = []
-    for k in range(count):
-        assert offsets[k] == pos, "every offset is the position of its chunk"
-        y, size = struct.unpack_from("<ii", data, pos)
-        rows = min(lines, h - k * lines)
-        n = 4 * len(names) * w * rows
-        assert y == k * lines and 0 < size <= n
-        raw = inflate_chunk(data[pos + 8:pos + 8 + size], n)
-        planes[:, y:y + rows, :] = np.frombuffer(raw, "<u4").reshape(rows, len(names), w).transpose(1, 0, 2)
-        chunks.append((y, size, n))
-        pos += 8 + size
-    assert pos == len(data), "nothing behind the last chunk"
-    assert order == sorted(order) and [s.encode() for s in names] == sorted(s.encode() for s in names)
-    return {"width": w, "height": h, "attrs": attrs, "attr_order": order, "names": names, "planes": dict(zip(names, planes)), "offsets": offsets, "first": first,
-            "end": pos, "compression": kind, "chunks": chunks}
-
-
-def host_chunks(planes, w, h, lines):
-    """chunks made on the host from [h, w] planes in channel order: (data, sizes); a chunk whose stream is not shorter stays raw"""
-    rows = np.stack([np.ascontiguousarray(p).view(np.uint32).reshape(h, w) for p in planes], axis=1)          # [H, C, W]
-    data, sizes = b"", []
-    for y in range(0, h, lines):
-        raw = rows[y:y + lines].astype("<u4").tobytes()
-        z = zlib.compress(zip_forward(raw), 1)          # (level 1: the header is 78 01)
-        body = z if len(z) < len(raw) else raw
-        data += struct.pack("<ii", y, len(body)) + body
-        sizes.append(8 + len(body))
-    return data, sizes
 
 
 # ---- CPU tier: the format ---------------------------------------------------------------------------------------------------------------
@@ -195,27 +70,29 @@ def test_reader_is_anchored_and_exr_py_writes_the_chunked_file(pkg):
     assert (f["width"], f["height"], f["names"], f["compression"]) == (2, 1, ["B", "R"], 2)
     assert f["planes"]["B"].tolist() == [[0x3E800000, 0x80000000]] and f["planes"]["R"].tolist() == [[0x3FC00000, 0x7FC00123]]
     b, r = np.array([[0x3E800000, 0x80000000]], np.uint32), np.array([[0x3FC00000, 0x7FC00123]], np.uint32)
-    chunks, sizes = host_chunks([b, r], 2, 1, 1)
+    chunks, sizes = host_chunks([b, r], 2, 1, 2)
     assert sizes == [24]
-    assert exr.file_bytes_chunked(2, 1, ["B", "R"], chunks, sizes, compression=2) == data
-    # compression 0 keeps its bytes: header() and file_bytes() as before
+    assert exr.file_bytes(2, 1, ["B", "R"], chunks, sizes, compression=2) == data
+    # compression 0 keeps its bytes
     assert exr.file_bytes(2, 1, ["B", "R"], exr.pack_host([b, r], 2, 1)) == hand_built_2x1()
     assert exr.header(2, 1, ["B", "R"]) == exr.header(2, 1, ["B", "R"], compression=0) == hand_built_2x1()[:-8 - 24]
     # a compressible image of two ZIP chunks (17 rows) and of 17 ZIPS chunks: deflated chunks, a short last chunk, strings
     rng = np.random.default_rng(5)
     planes = [np.repeat(rng.integers(0, 2 ** 32, (17, 5), dtype=np.uint32), 8, axis=1) for _ in range(3)]
     for kind in (2, 3):
-        chunks, sizes = host_chunks(planes, 40, 17, LINES[kind])
-        whole = exr.file_bytes_chunked(40, 17, ["A", "B", "C"], chunks, sizes, {"zzz": "ä"}, kind)
+        chunks, sizes = host_chunks(planes, 40, 17, kind)
+        whole = exr.file_bytes(40, 17, ["A", "B", "C"], chunks, sizes, {"zzz": "ä"}, kind)
         g = read_exr(whole)
         assert g["compression"] == kind and len(g["chunks"]) == (17 if kind == 2 else 2) and any(size < n for _, size, n in g["chunks"])
         for name, p in zip("ABC", planes):
             assert np.array_equal(g["planes"][name], p)
         assert g["attrs"]["zzz"] == ("string", "ä".encode())
     with pytest.raises(AssertionError):
-        exr.file_bytes_chunked(40, 17, ["A", "B", "C"], chunks, sizes[:-1], None, 3)          # a chunk short
+        exr.file_bytes(40, 17, ["A", "B", "C"], chunks, sizes[:-1], None, 3)          # a chunk short
+    # compression 0 without types is the flat file: its chunks are the packer's blocks, with their sizes stated or left out
+    assert exr.file_bytes(2, 1, ["B", "R"], exr.pack_host([b, r], 2, 1), [24], compression=0) == hand_built_2x1()
     with pytest.raises(AssertionError):
-        exr.file_bytes_chunked(40, 17, ["A", "B", "C"], chunks, sizes, None, 0)
+        exr.file_bytes(40, 17, ["A", "B", "C"], chunks, None, None, 3)          # only compression 0 says what its chunks' sizes are
 
 
 C_PROGRAM = r"""
@@ -235,9 +112,9 @@ int main(int argc, char **argv) {
 	FILE *f = fopen(argv[5], "rb");
 	if (!f || fread(data, 1, total, f) != total) return 3;
 	fclose(f);
-	const int rc = exr_write_file_chunked(argv[1], w, h, names, 3, strings, 2, kind, data, sizes, count);
-	const int refused = exr_write_file_chunked(argv[1], w, h, names, 3, strings, 2, kind, data, sizes, count - 1) == 0 ||
-	                    exr_write_file_chunked(argv[1], w, h, names, 3, strings, 2, 1, data, sizes, count) == 0;
+	const int rc = exr_write_file(argv[1], w, h, names, NULL, 3, strings, 2, kind, data, sizes, count);
+	const int refused = exr_write_file(argv[1], w, h, names, NULL, 3, strings, 2, kind, data, sizes, count - 1) == 0 ||
+	                    exr_write_file(argv[1], w, h, names, NULL, 3, strings, 2, 1, data, sizes, count) == 0;
 	free(sizes); free(data);
 	return rc ? 2 : refused ? 4 : 0;
 }
@@ -245,7 +122,7 @@ int main(int argc, char **argv) {
 
 
 def test_c_chunked_writer_writes_the_bytes_of_exr_py(pkg, tmp_path):
-    """exr_write_file_chunked in a program of its own (AddressSanitizer and UBSan) against exr.file_bytes_chunked, byte for byte: ZIP and ZIPS, host-made chunks
+    """exr_write_file in a program of its own (AddressSanitizer and UBSan) against exr.file_bytes, byte for byte: ZIP and ZIPS, host-made chunks
     with a raw-fallback chunk (random rows) among deflated ones and a short last chunk; a wrong chunk count and a wrong compression are refused."""
     exr = pkg.exr
     host = os.path.join(REPO, "c-ray_amd", "host")
@@ -259,14 +136,14 @@ def test_c_chunked_writer_writes_the_bytes_of_exr_py(pkg, tmp_path):
     for p in planes:
         p[16:32] = rng.integers(0, 2 ** 32, (16, w), dtype=np.uint32)          # the second ZIP chunk and rows 16 .. 31 do not deflate
     for kind in (2, 3):
-        chunks, sizes = host_chunks(planes, w, h, LINES[kind])
+        chunks, sizes = host_chunks(planes, w, h, kind)
         n = 4 * 3 * w * LINES[kind]
         assert (8 + n) in sizes and min(sizes) < 8 + n // 2 and (kind == 2 or sizes[-1] < 8 + 4 * 3 * w * 3), "a raw chunk, deflated ones, a short last one"
         blob, out = tmp_path / f"chunks{kind}", tmp_path / f"c{kind}.exr"
         blob.write_bytes(chunks)
         r = subprocess.run([str(exe), str(out), str(w), str(h), str(kind), str(blob)] + [str(s) for s in sizes], capture_output=True, text=True, timeout=120)
         assert r.returncode == 0, r.stdout + r.stderr
-        want = exr.file_bytes_chunked(w, h, ["A", "B", "C"], chunks, sizes, {"aaa": "", "zzz": "ä \"q\""}, kind)
+        want = exr.file_bytes(w, h, ["A", "B", "C"], chunks, sizes, {"aaa": "", "zzz": "ä \"q\""}, kind)
         got = out.read_bytes()
         assert got == want
         f = read_exr(got)
@@ -286,35 +163,6 @@ def zctx(pkg, ctx):
 def seg():
     import cray_amd.exrzip as exrzip
     return exrzip.segment_bytes()
-
-
-def flat_source(rng, w, h, stride):
-    """uint32 [h, w, stride] that deflates: per component runs of a few columns of one word — NaNs with payloads, infinities, -0.0, subnormals among them — with
-    a random word every so often"""
-    pick = rng.integers(0, SPECIAL.size, (h, -(-w // 5), stride))
-    a = np.repeat(SPECIAL[pick], 5, axis=1)[:, :w, :].copy()
-    noise = rng.random((h, w, stride)) < 0.03
-    a[noise] = rng.integers(0, 2 ** 32, int(noise.sum()), dtype=np.uint32)
-    return np.ascontiguousarray(a)
-
-
-def zip_case(name):
-    """(w, h, sources {key: uint32 array}, channels [(key, stride, component, map key or None)], maps) — flat and random sources mixed, ids through maps"""
-    rng = np.random.default_rng(sum(name.encode()))
-    maps = {"big": rng.integers(0, 2 ** 32, 65536, dtype=np.uint32), "five": rng.integers(1, 2 ** 32, 5, dtype=np.uint32)}
-    w, h, nch = (int(v) for v in name.split("x"))
-    src = {"f3": flat_source(rng, w, h, 3), "f12": flat_source(rng, w, h, 12), "r8": rng.integers(0, 2 ** 32, (h, w, 8), dtype=np.uint32)}
-    ids = (rng.integers(0, 5, (h, -(-w // 7))).repeat(7, axis=1)[:, :w]).astype(np.float32)          # ids in runs, the edge values of plant_ids in front
-    src["f12"][:, :, 4] = ids.view(np.uint32)
-    edge = np.array([-1.0, 0.0, 4, 5, 2.5, np.nan, 16777216.0, -0.0, 0.5, 4.5, 1e30, np.inf, -np.inf, 1e-45, -2.0, 4294967296.0], np.float32).view(np.uint32)
-    flat = src["f12"][:, :, 4].reshape(-1)
-    flat[:min(16, flat.size)] = edge[:flat.size]
-    src["f12"][:, :, 4] = flat.reshape(h, w)
-    plant_ids(rng, src["r8"], 2, 65536)
-    pool = [("f3", 3, 0, None), ("f12", 12, 4, "five"), ("f12", 12, 1, None), ("r8", 8, 2, "big"), ("f3", 3, 2, None), ("f12", 12, 11, None), ("r8", 8, 7, None),
-            ("f3", 3, 1, None)]
-    chans = [pool[i % len(pool)] if i < len(pool) else ("f12", 12, i % 12, None) for i in range(nch)]
-    return w, h, src, chans, maps
 
 
 def run_zip(pkg, ctx, zctx, case, lines, **rows):
@@ -353,7 +201,7 @@ def test_round_trip_against_the_packer(lines, pkg, ctx, zctx):
         case = zip_case(name)
         w, h, nch = case[0], case[1], len(case[3])
         data, sizes, want = run_zip(pkg, ctx, zctx, case, lines)
-        chunks = split_chunks(data, sizes, nch, w, 0, h, lines)
+        chunks = split_chunks(data, sizes, 4 * nch * w, 0, h, lines)
         got = raw_of(chunks)
         assert got == want, name
         assert int(sizes.sum()) == len(data) and all(8 + len(d) <= 8 + n for _, d, n in chunks)
@@ -413,7 +261,7 @@ def test_crafted_planes(pkg, ctx, zctx):
     dev = DeviceArray(pkg, planes.reshape(h, w, 1), np.uint32)
     ctx.synchronize()
     data, sizes = zctx.pack_zip([(dev.ptr, 1, 0)], w, h, 1)
-    chunks = split_chunks(data, sizes, 1, w, 0, h, 1)
+    chunks = split_chunks(data, sizes, 4 * w, 0, h, 1)
     for k, (y, d, nn) in enumerate(chunks):
         assert inflate_chunk(d, nn) == planes[k].astype("<u4").tobytes(), what[k]
         if len(d) < nn:
@@ -424,7 +272,7 @@ def test_crafted_planes(pkg, ctx, zctx):
     assert size["largest distance"] <= size["no repeat"] - 6, size                                # twelve literals became one match
     # ZIP: the same planes as chunks of 16 rows (the last of 11 - 16 rows): every byte again
     data16, sizes16 = zctx.pack_zip([(dev.ptr, 1, 0)], w, h, 16)
-    assert raw_of(split_chunks(data16, sizes16, 1, w, 0, h, 16)) == planes.astype("<u4").tobytes()
+    assert raw_of(split_chunks(data16, sizes16, 4 * w, 0, h, 16)) == planes.astype("<u4").tobytes()
 
 
 @pytest.mark.gpu
@@ -441,7 +289,7 @@ def test_determinism_and_chunked_calls(pkg, ctx, zctx):
         assert b"".join(p[0] for p in parts) == whole
         assert np.array_equal(np.concatenate([p[1] for p in parts]), sizes)
         for (data, sz, raw), (f, r) in zip(parts, ((0, 16), (16, 32), (48, h - 48))):
-            assert raw_of(split_chunks(data, sz, nch, w, f, r, lines)) == raw
+            assert raw_of(split_chunks(data, sz, 4 * nch * w, f, r, lines)) == raw
         # a call of another shape in between changes nothing
         run_zip(pkg, ctx, zctx, zip_case("3x2x7"), lines)
         assert run_zip(pkg, ctx, zctx, case, lines)[0] == whole
@@ -487,7 +335,7 @@ def test_refused_arguments_leave_everything_untouched(pkg, ctx, zctx):
         assert (out == 0xA5).all() and (sizes == 0xA5A5A5A5A5A5A5A5).all()
         total.value = 0x5A5A5A5A5A5A5A5A
     assert call() == abi.OK
-    chunks = split_chunks(out[:total.value].tobytes(), sizes[:3], 2, w, 0, h, 16)
+    chunks = split_chunks(out[:total.value].tobytes(), sizes[:3], 4 * 2 * w, 0, h, 16)
     want = strip_headers(ctx.pack_scanlines([(a.ptr, 3, 1), (b.ptr, 8, 7, m)], w, h), 2, w)
     assert raw_of(chunks) == want
     assert (out[total.value:] == 0xA5).all() and (sizes[3:] == 0xA5A5A5A5A5A5A5A5).all(), "nothing behind the chunks is written"
@@ -528,7 +376,7 @@ def test_size_conditions(name, pkg, ctx, zctx):
         n = 4 * nch * w * lines
         ygot, ywant = yardstick(raw, n)
         data, sizes = zctx.pack_zip(ch, w, h, lines)
-        chunks = split_chunks(data, sizes, nch, w, 0, h, lines)
+        chunks = split_chunks(data, sizes, 4 * nch * w, 0, h, lines)
         assert raw_of(chunks) == raw
         share, yshare = len(data) / ywant, ygot / ywant
         print(f"{name} lines {lines}: yardstick {yshare:.4f}, device {share:.4f} of {ywant} bytes, segment {seg()}")

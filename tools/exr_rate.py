@@ -72,7 +72,7 @@ def measure():
             t_copy = (copies_ms(COPIES + 1) - copies_ms(1)) / COPIES
             t = time.perf_counter()
             with open(os.path.join(tmp, "layers.exr"), "wb") as f:
-                f.write(exr.file_bytes(W, H, [c[0] for c in chans], blocks, strings))
+                f.write(exr.file_bytes(W, H, [c[0] for c in chans], blocks, strings=strings))
             t_write = (time.perf_counter() - t) * 1e3
             if r >= WARM:
                 pack.append(t_pack); copy.append(t_copy); call.append(t_call); write.append(t_write)

@@ -8,7 +8,7 @@
 One process, behind warm-up rounds, medians of interleaved rounds of
   zip, zips     crx_pack_zip over the whole frame in one call (lines_per_chunk 16 and 1): the kernels per phase by crx_pack_zip_phases_ms (the companion library's
                 events around its four launches), the wall time of the whole call (map upload, kernels, sizes, copy through pinned memory, copy out), and the
-                wall time of exr.file_bytes_chunked + the file's write to a temporary directory;
+                wall time of exr.file_bytes + the file's write to a temporary directory;
   none          the wall time of Context.pack_scanlines on the same buffers and of exr.file_bytes + the file's write.
 Then, once, the yardstick: host zlib, level 1, fixed codes (Z_FIXED), per chunk on the same transformed bytes, raw where not shorter, on one thread.
 Two expectations are marked met or refuted: the compressed call + write is no slower end to end than the uncompressed one, and the device's size is within a few
@@ -83,9 +83,9 @@ def measure(half=False):
                     data, sizes = zctx.pack_zip([c[1:] for c in chans], W, H, exrzip.COMPRESSION[kind][1])
                 t1 = time.perf_counter()
                 if kind == "none":
-                    whole = exr.file_bytes(W, H, names, blocks, strings)
+                    whole = exr.file_bytes(W, H, names, blocks, strings=strings)
                 else:
-                    whole = exr.file_bytes_chunked(W, H, names, data, sizes, strings, exrzip.COMPRESSION[kind.split()[0]][0], types if kind.endswith("half") else None)
+                    whole = exr.file_bytes(W, H, names, data, sizes, strings, exrzip.COMPRESSION[kind.split()[0]][0], types if kind.endswith("half") else None)
                 with open(os.path.join(tmp, "layers.exr"), "wb") as f:
                     f.write(whole)
                 t2 = time.perf_counter()
