@@ -442,7 +442,7 @@ class Context:
         return float(ms.value)
 
     def write_layers_exr(self, path, width, height, fb, aov=None, denoised=None, instance_ids=None, material_ids=None, instance_names=None, material_names=None,
-                         chunk_rows=None, compression="none", half=False):
+                         chunk_rows=None, compression="none", half=False, codes="fixed"):
         """One multi-layer OpenEXR file (scanline, FLOAT channels; HALF ones with `half`) of the frame `fb` and whichever of the others is given: R G B; the guides of
         an AOV buffer as albedo.R/G/B, normal.X/Y/Z, Z and A, unscaled; a denoised frame as denoised.R/G/B; the ID buffers `instance_ids` / `material_ids`
         (render_ids) as the Cryptomatte layers CryptoObject00..02 / CryptoMaterial00..02 with their metadata. instance_names[i] / material_names[i] name id i
@@ -453,10 +453,16 @@ class Context:
         them; Z, A and the Cryptomatte channels stay FLOAT. An iterable of channel names stores exactly those as HALF; a name the file does not have, or a
         Cryptomatte channel, raises ValueError. The conversion rounds to nearest even (include/cray_hip_exr.h); values above 65504 become infinity — that is
         the format, not a fault. Only the uncompressed all-FLOAT file is packed by this library alone (crh_pack_scanlines) and can be written where the companion
-        library is not built; every other one by crx_pack."""
+        library is not built; every other one by crx_pack.
+        codes: "fixed" — the default, the deflate blocks there have always been — or "dynamic": every 4 096-byte segment of a "zip" / "zips" chunk is coded with the
+        cheaper of the fixed Huffman codes and a dynamic code built on the device from its own counts (crx_set_codes: set on the companion context for this call,
+        then put back to what it was). The pixels are the same, the file is never larger; with compression "none" the argument has no effect. Another value
+        raises ValueError."""
         from . import exrzip          # (binds the companion library on first use)
         if compression not in exrzip.COMPRESSION:
             raise ValueError(f"compression {compression!r}: one of {sorted(exrzip.COMPRESSION)}")
+        if codes not in exrzip.CODES:
+            raise ValueError(f"codes {codes!r}: one of {sorted(exrzip.CODES)}")
         ranked, maps, strings, scratch = [None, None], [None, None], {}, []
         try:
             for k, (ids, names, stem) in enumerate(((instance_ids, instance_names, "instance"), (material_ids, material_names, "material"))):
@@ -482,7 +488,13 @@ class Context:
                 data, sizes = b"".join(self.pack_scanlines(sources, width, height, y, min(step, height - y)) for y in range(0, height, step)), None
             else:
                 self.synchronize()          # the companion's stream may be another: its sources must be complete
-                parts = [self._zip_context().pack(sources, width, height, kind, types, y, min(step, height - y)) for y in range(0, height, step)]
+                z = self._zip_context()
+                before = z.codes
+                z.set_codes(codes)
+                try:
+                    parts = [z.pack(sources, width, height, kind, types, y, min(step, height - y)) for y in range(0, height, step)]
+                finally:
+                    z.set_codes(before)
                 data, sizes = b"".join(p[0] for p in parts), np.concatenate([p[1] for p in parts])
         finally:
             for p in scratch:

@@ -28,6 +28,7 @@ struct crx_ctx {
 	void *pinned = nullptr;
 	size_t pinnedBytes = 0;
 	Stopwatch<CRX_ZIP_PHASES> watch;
+	int codes = CRX_CODES_FIXED;                         /* crx_set_codes */
 };
 
 namespace {
@@ -151,7 +152,8 @@ int pack(const char *who, crx_ctx *c, const crh_pack_channel *ch, const uint8_t 
 	}
 	if ((rc = c->watch.mark(c->stream))) return rc;
 	if (!allRaw) {
-		hipLaunchKernelGGL(k_zip_deflate, dim3((uint32_t)segs), dim3(64), 0, c->stream, G, c->dT.p, c->dSegOut.p, segMeta);
+		if (c->codes == CRX_CODES_DYNAMIC) hipLaunchKernelGGL(k_zip_deflate_dynamic, dim3((uint32_t)segs), dim3(64), 0, c->stream, G, c->dT.p, c->dSegOut.p, segMeta);
+		else hipLaunchKernelGGL(k_zip_deflate, dim3((uint32_t)segs), dim3(64), 0, c->stream, G, c->dT.p, c->dSegOut.p, segMeta);
 		HIP_TRY(hipGetLastError());
 	}
 	if ((rc = c->watch.mark(c->stream))) return rc;
@@ -190,6 +192,40 @@ int crx_pack(crx_ctx *c, const crh_pack_channel *ch, const uint8_t *pixel_types,
              void *host_out, uint64_t *chunk_bytes_host, uint64_t *total_bytes) {
 	if (compression != 0 && compression != 2 && compression != 3) return fail(CRH_ERR_INVALID, "crx_pack: bad argument (compression is 0, 2 or 3)");
 	return pack("crx_pack", c, ch, pixel_types, nch, width, height, first_row, row_count, compression == 3 ? 16 : 1, compression == 0, host_out, chunk_bytes_host, total_bytes);
+}
+
+int crx_set_codes(crx_ctx *c, int codes) {
+	if (!c || (codes != CRX_CODES_FIXED && codes != CRX_CODES_DYNAMIC)) return fail(CRH_ERR_INVALID, "crx_set_codes: bad argument (a context, and CRX_CODES_FIXED or CRX_CODES_DYNAMIC)");
+	c->codes = codes;
+	return CRH_OK;
+}
+
+int crx_get_codes(crx_ctx *c, int *codes) {
+	if (!c || !codes) return fail(CRH_ERR_INVALID, "crx_get_codes: NULL argument");
+	*codes = c->codes;
+	return CRH_OK;
+}
+
+int crx_debug_code_lengths(crx_ctx *c, const uint32_t *freq, uint32_t symbols, uint32_t limit, uint32_t count, uint8_t *lengths) {
+	bool ok = c && freq && lengths && symbols >= 1 && symbols <= CRX_MAX_SYMBOLS && (limit == 7 || limit == 15) && symbols <= (1u << limit) && count < (1u << 20);
+	for (uint32_t h = 0; ok && h < count; ++h) {
+		uint64_t sum = 0;
+		for (uint32_t s = 0; s < symbols; ++s) sum += freq[(size_t)h * symbols + s];
+		ok = sum < CRX_FREQ_LIMIT;
+	}
+	if (!ok) return fail(CRH_ERR_INVALID, "crx_debug_code_lengths: bad argument");
+	if (count == 0) return CRH_OK;
+	const size_t n = (size_t)count * symbols;
+	HIP_TRY(hipSetDevice(c->device));
+	int rc;
+	if ((rc = c->dT.grow(c->stream, n))) return rc;
+	if ((rc = c->dOut.grow(c->stream, n))) return rc;
+	HIP_TRY(hipMemcpyAsync(c->dT.p, freq, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	hipLaunchKernelGGL(k_zip_code_lengths, dim3(count), dim3(64), 0, c->stream, c->dT.p, symbols, limit, c->dOut.p);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(lengths, c->dOut.p, n, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	return CRH_OK;
 }
 
 int crx_pack_zip_phases_ms(crx_ctx *c, float phases_ms[CRX_ZIP_PHASES]) {

@@ -13,6 +13,7 @@ from .api import CrhError
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CRX_LIB") or os.path.join(HERE, "_lib", "libcray_hip_exr.so")    # CRX_LIB: another build (dev, the emulation tier)
 COMPRESSION = {"none": (0, 1), "zips": (2, 1), "zip": (3, 16)}          # name -> (the file's compression attribute, lines per chunk)
+CODES = {"fixed": 0, "dynamic": 1}          # name -> CRX_CODES_*
 
 _lib = None
 
@@ -42,6 +43,9 @@ def library():
         "crx_pack_zip_time_ms": (C.c_int, [ctx, C.POINTER(C.c_float)]),
         "crx_pack_zip_phases_ms": (C.c_int, [ctx, C.POINTER(C.c_float)]),
         "crx_zip_segment_bytes": (C.c_uint32, []),
+        "crx_set_codes": (C.c_int, [ctx, C.c_int]),
+        "crx_get_codes": (C.c_int, [ctx, C.POINTER(C.c_int)]),
+        "crx_debug_code_lengths": (C.c_int, [ctx, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -78,6 +82,29 @@ class ZipContext:
             self.close()
         except Exception:
             pass
+
+    def set_codes(self, codes):
+        """Which Huffman codes the deflate blocks of the following calls use (crx_set_codes): "fixed" — the default, the bytes there have always been — or
+        "dynamic": per segment the cheaper of the fixed codes and a dynamic code built on the device from the segment's own counts. Sticky on the context."""
+        if codes not in CODES:
+            raise ValueError(f"codes {codes!r}: one of {sorted(CODES)}")
+        _check(self.L.crx_set_codes(self.h, CODES[codes]), "crx_set_codes")
+
+    @property
+    def codes(self):
+        value = C.c_int(-1)
+        _check(self.L.crx_get_codes(self.h, C.byref(value)), "crx_get_codes")
+        return {v: k for k, v in CODES.items()}[value.value]
+
+    def code_lengths(self, freq, limit):
+        """crx_debug_code_lengths: the deflate kernel's code construction on histograms of the caller's — `freq` [count, symbols] or [symbols] counts, `limit` 7 or
+        15 bits — gives the uint8 array of code lengths, shaped like freq."""
+        f = np.ascontiguousarray(freq, dtype=np.uint32)
+        if f.ndim not in (1, 2) or f.size == 0:
+            raise ValueError("freq: [symbols] or [count, symbols] counts")
+        out = np.zeros(f.shape, np.uint8)
+        _check(self.L.crx_debug_code_lengths(self.h, f.ctypes.data, f.shape[-1], int(limit), f.size // f.shape[-1], out.ctypes.data), "crx_debug_code_lengths")
+        return out
 
     def _pack(self, where, call, channels, pixel_bytes, width, lines_per_chunk, rows):
         """One call of the pack entry named `where` — call(the crh_pack_channel array, output, sizes, total) -> its return code — with the output sized to its bound,

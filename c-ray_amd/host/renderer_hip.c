@@ -51,6 +51,8 @@
  * other side files are those of a run without the two. CRAY_HIP_EXR_COMPRESSION=zip|zips beside it: the file is ZIP / ZIPS compressed, deflated on the device.
  * CRAY_HIP_EXR_HALF=1 beside it: the colour layers (R G B, albedo.*, normal.*, denoised.*) are 16-bit HALF channels, Z, A and the Cryptomatte channels stay FLOAT
  * (crx_pack of libcray_hip_exr.so, for every compression); values above 65504 become infinity in them. Anything else or unset: all FLOAT.
+ * CRAY_HIP_EXR_CODES=dynamic beside CRAY_HIP_EXR_COMPRESSION: every segment of a chunk is deflated with the cheaper of the fixed Huffman codes and a dynamic code
+ * built on the device (crx_set_codes): the same pixels in a smaller file. Anything else or unset: the fixed codes.
  * No GPU => logr(error, ...) (which exits, src/utils/logging.c:69-73): there is no CPU fallback in this file.
  */
 #include <stdlib.h>
@@ -827,7 +829,8 @@ static void layerNamesFree(struct layerNames *n) {
  * `fb`, the guide buffers `aov` and the denoised frame `denoised` where CRAY_HIP_AOV / CRAY_HIP_DENOISE left them on GPU 0, and with CRAY_HIP_IDS=<n> the ranked ids of
  * min(n, sampleCount) passes of both ID buffers rendered here, as Cryptomatte layers. The channels are packed on the device (crh_pack_scanlines), at most 32 MB a call;
  * with CRAY_HIP_EXR_COMPRESSION=zip|zips beside it they are deflated there as well (crx_pack of libcray_hip_exr.so) and the file is a ZIP / ZIPS one; with
- * CRAY_HIP_EXR_HALF=1 the colour layers are HALF (crx_pack too, whatever the compression). */
+ * CRAY_HIP_EXR_HALF=1 the colour layers are HALF (crx_pack too, whatever the compression); with CRAY_HIP_EXR_CODES=dynamic the deflate blocks may use dynamic Huffman
+ * codes (crx_set_codes; anything else or unset: the fixed codes). */
 static void writeLayers(struct renderer *r, crh_ctx *ctx, const float *fb, const float *aov, const float *denoised, const struct layerNames *names, int W, int H) {
 	const char *e = getenv("CRAY_HIP_IDS");
 	int n = e ? atoi(e) : 0;
@@ -882,6 +885,8 @@ static void writeLayers(struct renderer *r, crh_ctx *ctx, const float *fb, const
 		size_t at = 0;
 		ok = crh_synchronize(ctx) == CRH_OK;          /* the companion's stream is its own: the sources must be complete */
 		if (ok && crx_context_create(0, NULL, &zip) != CRH_OK) { ok = false; why = crx_last_error(); }
+		const char *codes = getenv("CRAY_HIP_EXR_CODES");          /* dynamic: per segment the cheaper of the fixed and a dynamic Huffman code */
+		if (ok && codes && !strcmp(codes, "dynamic") && crx_set_codes(zip, CRX_CODES_DYNAMIC) != CRH_OK) { ok = false; why = crx_last_error(); }
 		for (int y = 0; ok && y < H; y += chunk) {
 			uint64_t total = 0;
 			const int rows = H - y < chunk ? H - y : chunk;

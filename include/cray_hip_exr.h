@@ -40,10 +40,10 @@ const char *crx_last_error(void);
  * Transform (OpenEXR's ZIP rule). T[i / 2] = R[i] for even i, T[(n + 1) / 2 + i / 2] = R[i] for odd i; then T'[0] = T[0] and T'[j] = (T[j] - T[j - 1] + 128) mod 256
  * for j >= 1, computed on the un-predicted T.
  * The chunk in host_out: int32 y (its first stored row), int32 size, `size` bytes of data. The data is a zlib stream of T' — header 0x78 0x01, deflate blocks any
- * inflate accepts (fixed Huffman codes, matches within segments of the chunk), Adler-32 of T' big-endian — if that stream is shorter than n; otherwise the n raw
+ * inflate accepts (fixed Huffman codes, or per segment dynamic ones under crx_set_codes below; matches within segments of the chunk), Adler-32 of T' big-endian — if that stream is shorter than n; otherwise the n raw
  * bytes R. size == n means raw. Chunks stand back to back in row order; chunk_bytes_host[k] = 8 + size of chunk k, *total_bytes their sum. host_out must hold
  * 8 * chunks + 4 * channel_count * width * row_count bytes, chunk_bytes_host one entry per chunk; the output is never larger.
- * Determinism. The bytes are a function of the arguments and the sources only — not of scheduling, of the number of CUs, or of earlier calls: two calls give equal
+ * Determinism. The bytes are a function of the arguments, the sources and of the codes setting (crx_set_codes) only — not of scheduling, of the number of CUs, or of earlier calls: two calls give equal
  * bytes, and the chunks of consecutive calls over first_row ranges concatenate to those of one call.
  * CRH_ERR_INVALID: everything crh_pack_scanlines refuses (a NULL context, list, source or output; channel_count outside 1 .. CRH_PACK_MAX_CHANNELS; a size <= 0; rows
  * outside the image; stride outside 1 .. 64; component >= stride; map_count > 65536; a map with count 0), lines_per_chunk not 1 or 16, misaligned rows, a NULL
@@ -84,6 +84,32 @@ int crx_pack_zip_phases_ms(crx_ctx *ctx, float phases_ms[CRX_ZIP_PHASES]);
 
 /* The bytes of T' one deflate segment covers (matches do not cross segments; a chunk of at most this many bytes is one deflate block). */
 uint32_t crx_zip_segment_bytes(void);
+
+/* Which Huffman codes the deflate blocks of crx_pack_zip and of crx_pack with compression 2 / 3 use, all FLOAT or with HALF channels (compression 0 deflates
+ * nothing and ignores it). The setting is sticky on the context and starts as CRX_CODES_FIXED: the fixed codes of RFC 1951, 3.2.6, the bytes every call wrote before
+ * the setting existed. CRX_CODES_DYNAMIC: every segment's block is coded with whichever costs fewer bits — the fixed codes, or a dynamic code (3.2.7) built on the
+ * device from that segment's own literal, length and distance counts, none longer than 15 bits (7 for the code-length code); a tie goes to fixed, and a segment
+ * that chooses fixed has, bit for bit, the bytes it has under CRX_CODES_FIXED. The parse — which matches are taken — is the same under both settings.
+ * A dynamic block is what any inflate accepts: the code-length code is always complete (a second symbol of length 1 where one would do); a segment without a
+ * match sends HDIST = 1 with one distance length of 0; a segment whose matches share one distance symbol sends that symbol with length 1.
+ * Everything else of the contract stands as it is: the chunk form, the zlib header 78 01, the Adler-32 of T', "stream if shorter than n, else raw" (now on the
+ * stream's size under the setting), the output bound, the refusals, the row alignment. A chunk is never larger than under CRX_CODES_FIXED.
+ * Determinism: the bytes are a function of the arguments, the sources and of the codes setting only.
+ * CRH_ERR_INVALID: a NULL context, a value other than the two (the setting stays as it was); crx_get_codes: a NULL context or output. */
+#define CRX_CODES_FIXED 0
+#define CRX_CODES_DYNAMIC 1
+int crx_set_codes(crx_ctx *ctx, int codes);
+int crx_get_codes(crx_ctx *ctx, int *codes);
+
+/* ---- debug ---- */
+/* The code construction of CRX_CODES_DYNAMIC on histograms of the caller's: `count` histograms of `symbols` counts each in freq (host memory), one wave a
+ * histogram through the device function the deflate kernel calls (c-ray_amd/csrc/exr_zip.h: zipCodeLengths); lengths[h * symbols + s] is the code length of symbol
+ * s under histogram h. A count of zero gives length 0; a used symbol 1 .. limit. Two or more used symbols give a complete prefix code (Kraft sum exactly 1), of
+ * Huffman's cost wherever Huffman's tree of least depth stays within the limit. A single used symbol gets length 1 and nothing else gets a length — the one
+ * incomplete code inflate allows (for a code-length code the deflate kernel adds a second symbol itself). No used symbol: all zero.
+ * CRH_ERR_INVALID: a NULL argument, symbols outside 1 .. 288 or above 2^limit, a limit other than 7 or 15, a histogram whose counts sum to 2^23 or more, 2^20
+ * histograms or more. count == 0 is CRH_OK. */
+int crx_debug_code_lengths(crx_ctx *ctx, const uint32_t *freq, uint32_t symbols, uint32_t limit, uint32_t count, uint8_t *lengths);
 
 #ifdef __cplusplus
 }

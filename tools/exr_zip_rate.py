@@ -4,6 +4,7 @@
 
     python tools/exr_zip_rate.py [--out profiles/exr_zip_rate.log]
     python tools/exr_zip_rate.py --half [--out profiles/exr_half_rate.log]
+    python tools/exr_zip_rate.py --half --codes dynamic [--out ...]
 
 One process, behind warm-up rounds, medians of interleaved rounds of
   zip, zips     crx_pack_zip over the whole frame in one call (lines_per_chunk 16 and 1): the kernels per phase by crx_pack_zip_phases_ms (the companion library's
@@ -17,7 +18,12 @@ percent (5 %) of the yardstick's. Without a GPU nothing is measured and the log 
 --half adds, interleaved with those in the same rounds, the rows of the file whose colour layers are HALF (Context.write_layers_exr(half=True)'s set, 12 of the 38
 channels): "zip half", "zips half" and "none half" through crx_pack (compression 3, 2 and 0) with the same phases, call and write times and file bytes, the spread
 between the rounds of every kernel sum, and two more expectations: the half call's kernel time is no larger than the all-FLOAT call's by more than that spread,
-and the half file is smaller for every compression (the ratio is recorded)."""
+and the half file is smaller for every compression (the ratio is recorded).
+
+--codes dynamic adds, interleaved in the same rounds again, the rows of crx_set_codes(CRX_CODES_DYNAMIC): "zip dynamic" and "zips dynamic" (with --half also "zip half
+dynamic" and "zips half dynamic") — phases, call and write times, the file's bytes as a share of raw and of the fixed-codes file, the deflate kernel's time beside the
+fixed kernel's of the same rounds — and a second host yardstick: zlib level 1 with the default strategy (dynamic codes allowed) per chunk on the same T'. The
+expectation "no slower end to end than the uncompressed output" is marked for the dynamic rows too."""
 import os
 import statistics
 import sys
@@ -40,7 +46,7 @@ def zip_forward(raw):
     return p.tobytes()
 
 
-def measure(half=False):
+def measure(half=False, dynamic=False):
     sys.path.insert(0, REPO)
     sys.path.insert(0, os.path.join(REPO, "tools"))
     from __graft_entry__ import load_package
@@ -68,6 +74,8 @@ def measure(half=False):
     ctx.synchronize()
     zctx = exrzip.ZipContext(0)
     kinds = ("zip", "zips", "none") + (("zip half", "zips half", "none half") if half else ())
+    if dynamic:
+        kinds += ("zip dynamic", "zips dynamic") + (("zip half dynamic", "zips half dynamic") if half else ())
     types = exr.half_types(names, True)
     t = {k: {"call": [], "write": [], "phases": []} for k in kinds}
     size, device = {}, {}          # the files' bytes; the bytes of the device's chunks
@@ -77,15 +85,17 @@ def measure(half=False):
                 t0 = time.perf_counter()
                 if kind == "none":
                     blocks = ctx.pack_scanlines([c[1:] for c in chans], W, H)
-                elif kind.endswith("half"):
-                    data, sizes = zctx.pack([c[1:] for c in chans], W, H, exrzip.COMPRESSION[kind.split()[0]][0], types)
+                elif kind != "zip" and kind != "zips":
+                    zctx.set_codes("dynamic" if kind.endswith("dynamic") else "fixed")
+                    data, sizes = zctx.pack([c[1:] for c in chans], W, H, exrzip.COMPRESSION[kind.split()[0]][0], types if "half" in kind else None)
+                    zctx.set_codes("fixed")
                 else:
                     data, sizes = zctx.pack_zip([c[1:] for c in chans], W, H, exrzip.COMPRESSION[kind][1])
                 t1 = time.perf_counter()
                 if kind == "none":
                     whole = exr.file_bytes(W, H, names, blocks, strings=strings)
                 else:
-                    whole = exr.file_bytes(W, H, names, data, sizes, strings, exrzip.COMPRESSION[kind.split()[0]][0], types if kind.endswith("half") else None)
+                    whole = exr.file_bytes(W, H, names, data, sizes, strings, exrzip.COMPRESSION[kind.split()[0]][0], types if "half" in kind else None)
                 with open(os.path.join(tmp, "layers.exr"), "wb") as f:
                     f.write(whole)
                 t2 = time.perf_counter()
@@ -130,6 +140,8 @@ def measure(half=False):
                      f"{'met' if chunks <= 1.05 * yard[kind] else 'REFUTED'}")
     if half:
         lines += half_lines(t, size)
+    if dynamic:
+        lines += dynamic_lines(t, size, device, raw, n, types if half else None, exr, exrzip, none_ms)
     zctx.close()
     ctx.close()
     return lines
@@ -167,14 +179,58 @@ def half_lines(t, size):
     return lines
 
 
+def dynamic_lines(t, size, device, raw, n, types, exr, exrzip, none_ms):
+    """the rows of --codes dynamic beside the fixed-codes rows of the same rounds; types: the HALF set where --half is given"""
+    med = statistics.median
+    lines = ["codes: crx_set_codes(CRX_CODES_DYNAMIC) — per 4 096-byte segment the cheaper of the fixed codes and a dynamic code built on the device; the parse is run twice"]
+    rows = [("zip", None), ("zips", None)] + ([("zip half", types), ("zips half", types)] if types is not None else [])
+    planes = np.frombuffer(raw, "<u4").reshape(H, n, W)
+    for kind, tt in rows:
+        k = kind + " dynamic"
+        ph, ph0 = np.median(np.array(t[k]["phases"]), axis=0), np.median(np.array(t[kind]["phases"]), axis=0)
+        d = np.array(t[k]["phases"])[:, 1]
+        lines.append(f"{k:18s} kernels (crx_pack_zip_phases_ms): " + ", ".join(f"{name} {v:.3f} ms" for name, v in zip(PHASES, ph)) + f"; sum {ph.sum():.3f} ms; "
+                     f"deflate {ph[1]:.3f} ms (min {d.min():.3f}, max {d.max():.3f}) against {ph0[1]:.3f} ms with fixed codes = {ph[1] / ph0[1]:.2f} x")
+    for kind, tt in rows:
+        k = kind + " dynamic"
+        c, w = med(t[k]["call"]), med(t[k]["write"])
+        none = "none half" if tt is not None else "none"
+        lines.append(f"{k:18s} whole call (wall) median {c:9.3f} ms (min {min(t[k]['call']):.3f}, max {max(t[k]['call']):.3f});  file bytes + write median {w:9.3f} ms;  "
+                     f"together {c + w:9.3f} ms;  file {size[k]} bytes = {size[k] / size[none]:.4f} of the uncompressed file, {size[k] / size[kind]:.4f} of the fixed-codes file")
+    for kind, tt in rows:
+        lpc = exrzip.COMPRESSION[kind.split()[0]][1]
+        if tt is None:
+            typed = planes.reshape(H, -1).view(np.uint8)
+        else:
+            typed = np.concatenate([(exr.half_bits(planes[:, c]).astype("<u2") if v else planes[:, c]).view(np.uint8).reshape(H, -1) for c, v in enumerate(tt)], axis=1)
+        t0 = time.perf_counter()
+        got = {zlib.Z_FIXED: 0, zlib.Z_DEFAULT_STRATEGY: 0}
+        for y in range(0, H, lpc):
+            chunk = typed[y:y + lpc].tobytes()
+            tp = zip_forward(chunk)
+            for strategy in got:
+                c = zlib.compressobj(1, zlib.DEFLATED, 15, 8, strategy)
+                got[strategy] += 8 + min(len(c.compress(tp) + c.flush()), len(chunk))
+        yf, yd = got[zlib.Z_FIXED], got[zlib.Z_DEFAULT_STRATEGY]
+        lines.append(f"{kind:10s} yardsticks (host zlib level 1 per chunk on the same T', one thread, {(time.perf_counter() - t0) * 1e3:.0f} ms for both): Z_FIXED {yf} bytes, default strategy "
+                     f"(dynamic codes allowed) {yd} bytes = {yd / yf:.4f} of it; the device's chunks: fixed {device[kind]} = {device[kind] / yf:.4f} of Z_FIXED's, "
+                     f"dynamic {device[kind + ' dynamic']} = {device[kind + ' dynamic'] / yd:.4f} of the default strategy's and {device[kind + ' dynamic'] / device[kind]:.4f} of its own fixed")
+    for kind, tt in rows:
+        k = kind + " dynamic"
+        ms = med(t[k]["call"]) + med(t[k]["write"])
+        lines.append(f"expectation: the compressed output ({k}) is no slower end to end than the uncompressed one: {ms:.1f} ms against {none_ms:.1f} ms: {'met' if ms <= none_ms else 'REFUTED'}")
+    return lines
+
+
 def main():
     args = sys.argv[1:]
     half = "--half" in args
+    dynamic = "--codes" in args and args[args.index("--codes") + 1] == "dynamic"
     out = args[args.index("--out") + 1] if "--out" in args else os.path.join(REPO, "profiles", "exr_half_rate.log" if half else "exr_zip_rate.log")
     sys.path.insert(0, REPO)
     from __graft_entry__ import load_package
     gpu = load_package().api.device_count() > 0
-    lines = measure(half) if gpu else ["no HIP device here: nothing is measured"]
+    lines = measure(half, dynamic) if gpu else ["no HIP device here: nothing is measured"]
     text = "\n".join(lines) + "\n"
     print(text, end="")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
