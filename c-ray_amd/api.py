@@ -140,6 +140,12 @@ def _check(rc, where):
         raise CrhError(rc, where, (library().crh_last_error() or b"").decode(errors="replace"))
 
 
+def _tile_array(tiles):
+    """A list of (x0, y0, x1, y1) as the C entries take it: a crh_tile array, NULL for an empty list (every entry accepts NULL beside a count of 0)."""
+    n = len(tiles)
+    return (abi.Tile * n)(*[abi.Tile(*t) for t in tiles]) if n else None
+
+
 def device_count():
     return library().crh_device_count()
 
@@ -157,7 +163,7 @@ def adaptive_cell_offsets(tiles, cell):
     """crh_adaptive_cell_offsets: the uint32 [n + 1] index of every rectangle's first cell in the cell-granular arrays (the last entry is the total): a rectangle
     of tw x th pixels holds ceil(tw / cell) x ceil(th / cell) cells, rows of cells from its first stored row down, x ascending within a row."""
     n = len(tiles)
-    arr = (abi.Tile * n)(*[abi.Tile(*t) for t in tiles]) if n else None
+    arr = _tile_array(tiles)
     out = np.zeros(n + 1, np.uint32)
     total = library().crh_adaptive_cell_offsets(arr, n, cell, out.ctypes.data)
     if total < 0:
@@ -207,7 +213,7 @@ def plan_units(width, height, samples, tiles, cu_count=256, first_pass=0, pass_c
     """crh_debug_plan_units (no device needed): the work units of one dispatch in hand-out order, as an int32 array [n, 8] of
     x0, y0, x1, y1, block area, taper level, first pass, pass count — and the pass chunk."""
     p = abi.RenderParams(0, 0, 0, 0, width, height, first_pass, samples - first_pass if pass_count is None else pass_count, samples, 1)
-    arr = (abi.Tile * len(tiles))(*[abi.Tile(*t) for t in tiles])
+    arr = _tile_array(tiles)
     n, chunk = C.c_uint64(0), C.c_int32(0)
     _check(library().crh_debug_plan_units(C.byref(p), arr, len(tiles), cu_count, None, 0, C.byref(n), C.byref(chunk)), "crh_debug_plan_units")
     units = np.zeros((n.value, 8), np.int32)
@@ -341,7 +347,7 @@ class Context:
     def render_tiles(self, fb, width, height, samples, bounces, tiles, first_pass=0, pass_count=None):
         p = abi.RenderParams(0, 0, 0, 0, width, height, first_pass,
                              samples - first_pass if pass_count is None else pass_count, samples, bounces)
-        arr = (abi.Tile * len(tiles))(*[abi.Tile(*t) for t in tiles])
+        arr = _tile_array(tiles)
         _check(self.L.crh_render_tiles(self.h, C.byref(p), arr, len(tiles), fb), "crh_render_tiles")
 
     # ---- AOV buffers: albedo, normal, depth, coverage of every camera ray's first hit (include/cray_hip.h: crh_render_aov) ----
@@ -362,7 +368,7 @@ class Context:
         if tiles is None:
             _check(self.L.crh_render_aov(self.h, C.byref(p), None, 0, buf), "crh_render_aov")
         elif len(tiles):          # (an empty list is no work; to the C entry a count of 0 means "the region of params")
-            arr = (abi.Tile * len(tiles))(*[abi.Tile(*t) for t in tiles])
+            arr = _tile_array(tiles)
             _check(self.L.crh_render_aov(self.h, C.byref(p), arr, len(tiles), buf), "crh_render_aov")
 
     def download_aov(self, buf, width, height):
@@ -396,7 +402,7 @@ class Context:
         if tiles is None:
             _check(self.L.crh_render_ids(self.h, C.byref(p), None, 0, instance_ids, material_ids), "crh_render_ids")
         elif len(tiles):          # (an empty list is no work; to the C entry a count of 0 means "the region of params")
-            arr = (abi.Tile * len(tiles))(*[abi.Tile(*t) for t in tiles])
+            arr = _tile_array(tiles)
             _check(self.L.crh_render_ids(self.h, C.byref(p), arr, len(tiles), instance_ids, material_ids), "crh_render_ids")
 
     def download_ids(self, buf, width, height):
@@ -537,7 +543,7 @@ class Context:
         """One step over `tiles` (a list of x0, y0, x1, y1): (errors float32 [n], flags bool [n]); where a tile's flag is set — its error is not <= threshold —
         half := fb over it. Waits for the result. threshold = inf measures only."""
         n = len(tiles)
-        arr = (abi.Tile * n)(*[abi.Tile(*t) for t in tiles]) if n else None
+        arr = _tile_array(tiles)
         errors, flags = np.zeros(n, np.float32), np.zeros(n, np.uint8)
         _check(self.L.crh_adaptive_step(self.h, fb, half, width, height, arr, n, threshold, errors.ctypes.data, flags.ctypes.data), "crh_adaptive_step")
         return errors, flags.astype(bool)
@@ -549,7 +555,7 @@ class Context:
         n = len(tiles)
         p = abi.RenderParams(0, 0, 0, 0, width, height, 0, max_samples if passes is None else passes, max_samples, bounces)
         a = abi.AdaptiveParams(min_passes, threshold)
-        arr = (abi.Tile * n)(*[abi.Tile(*t) for t in tiles]) if n else None
+        arr = _tile_array(tiles)
         count, errors = np.zeros(n, np.int32), np.zeros(n, np.float32)
         _check(self.L.crh_render_adaptive(self.h, C.byref(p), arr, n, C.byref(a), fb, half, count.ctypes.data, errors.ctypes.data), "crh_render_adaptive")
         return count, errors
@@ -561,7 +567,7 @@ class Context:
         live: one truth value per cell (None: all). Waits for the result. threshold = inf measures only."""
         n = len(tiles)
         total = int(adaptive_cell_offsets(tiles, cell)[-1])
-        arr = (abi.Tile * n)(*[abi.Tile(*t) for t in tiles]) if n else None
+        arr = _tile_array(tiles)
         errors, flags = np.zeros(total, np.float32), np.zeros(total, np.uint8)
         mask = None
         if live is not None:
@@ -579,7 +585,7 @@ class Context:
         total = int(adaptive_cell_offsets(tiles, cell)[-1])
         p = abi.RenderParams(0, 0, 0, 0, width, height, 0, max_samples if passes is None else passes, max_samples, bounces)
         a = abi.AdaptiveCellsParams(min_passes, threshold, cell, int(dilate))
-        arr = (abi.Tile * n)(*[abi.Tile(*t) for t in tiles]) if n else None
+        arr = _tile_array(tiles)
         count, errors = np.zeros(total, np.int32), np.zeros(total, np.float32)
         _check(self.L.crh_render_adaptive_cells(self.h, C.byref(p), arr, n, C.byref(a), fb, half, count.ctypes.data, errors.ctypes.data), "crh_render_adaptive_cells")
         return count, errors

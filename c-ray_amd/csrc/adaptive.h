@@ -10,7 +10,8 @@
  * One 256-thread workgroup per tile. Thread t sums the errors of the pixels t, t + 256, ... of the tile's enumeration (stored rows top to bottom, x ascending)
  * in that order; the 256 partials are folded by a binary tree in LDS (strides 128 .. 1, a barrier per level: eight barriers a tile against 36 bytes of traffic a
  * pixel). The additions and their order are the interface; nothing else is. The pixel index advances without a division (256 = q tw + r once per workgroup).
- * No packed-float instructions, no MFMA, no scratch; 1 KB of LDS.
+ * No packed-float instructions, no MFMA, no scratch; 1 KB of LDS. The enumeration, a thread's error sum and the copy are written once for both kernels of this file
+ * (AdWalk, adErrorSum, adCopy), parameterised by the number of threads that share a rectangle.
  */
 #pragma once
 
@@ -38,51 +39,45 @@ __device__ __forceinline__ float adPixelError(const float *fb, const float *half
 	return e < CRH_AD_ERROR_MAX ? e : CRH_AD_ERROR_MAX;          /* NaN and overflow take the second branch */
 }
 
-__global__ __launch_bounds__(CRH_BLOCK) void k_adaptive_step(const AdaptiveArgs A) {
-	__shared__ float s_part[CRH_BLOCK];
-	const uint32_t t = threadIdx.x;
-	const crh_tile T = A.tiles[blockIdx.x];
-	const uint32_t tw = (uint32_t)(T.x1 - T.x0), th = (uint32_t)(T.y1 - T.y0), n = tw * th;          /* (the host refuses empty tiles and tiles of more than 2^30 pixels) */
-	const size_t origin = ((size_t)(A.H - T.y1) * (size_t)A.W + (size_t)T.x0) * 3u;                       /* the tile's first stored row, its first pixel */
-	const size_t pitch = (size_t)A.W * 3u;
-	bool cont = A.advanceAll != 0;
-	if (!A.advanceAll) {
-		const uint32_t q = CRH_BLOCK / tw, r = CRH_BLOCK % tw;
-		uint32_t row = t / tw, x = t % tw;
-		float p = 0.0f;
-#pragma unroll 4
-		for (uint32_t k = t; k < n; k += CRH_BLOCK) {
-			p = p + adPixelError(A.fb, A.half, origin + (size_t)row * pitch + (size_t)x * 3u);
-			row += q; x += r;
-			if (x >= tw) { x -= tw; ++row; }
-		}
-		s_part[t] = p;
-		__syncthreads();
-#pragma unroll
-		for (uint32_t stride = CRH_BLOCK / 2; stride >= 1u; stride >>= 1) {
-			if (t < stride) s_part[t] = s_part[t] + s_part[t + stride];
-			__syncthreads();
-		}
-		const float E = s_part[0] / (float)n;
-		cont = !(E <= A.threshold);
-		if (t == 0) { A.errors[blockIdx.x] = E; A.flags[blockIdx.x] = cont ? 1u : 0u; }
+/* The enumeration both kernels walk: the pixels t, t + STRIDE, ... of a rectangle `w` pixels wide (stored rows top to bottom, x ascending) for thread t of the STRIDE
+ * that share the rectangle — the workgroup's CRH_BLOCK threads for a tile of k_adaptive_step, a wave's 64 lanes for a cell of k_adaptive_cells. The index advances
+ * without a division (STRIDE = q w + r once). */
+template <uint32_t STRIDE> struct AdWalk {
+	uint32_t w, q, r, row, x;
+	__device__ __forceinline__ AdWalk(uint32_t width, uint32_t t) : w(width), q(STRIDE / width), r(STRIDE % width), row(t / width), x(t % width) {}
+	/* the first word of the pixel the walk stands on */
+	__device__ __forceinline__ size_t word(size_t origin, size_t pitch) const { return origin + (size_t)row * pitch + (size_t)x * 3u; }
+	/* on to the thread's next pixel */
+	__device__ __forceinline__ void step() {
+		row += q; x += r;
+		if (x >= w) { x -= w; ++row; }
 	}
-	if (!cont) return;
-	/* half := fb over the tile, raw bits, all three channels: a pixel a thread in the enumeration above, four pixels' loads in flight before their stores (the
-	 * compiler may not move a load across a store to the other buffer itself). A pixel past the end reads the batch's first one again and stores nothing. */
-	const uint32_t *src = (const uint32_t *)A.fb;
-	uint32_t *dst = (uint32_t *)A.half;
-	const uint32_t q = CRH_BLOCK / tw, r = CRH_BLOCK % tw;
-	uint32_t row = t / tw, x = t % tw;
+};
+
+/* thread t's partial sum: the errors of its pixels of the rectangle's n, added in that order */
+template <uint32_t STRIDE>
+__device__ __forceinline__ float adErrorSum(const float *fb, const float *half, size_t origin, size_t pitch, uint32_t w, uint32_t n, uint32_t t) {
+	AdWalk<STRIDE> walk(w, t);
+	float p = 0.0f;
+#pragma unroll 4
+	for (uint32_t k = t; k < n; k += STRIDE, walk.step()) p = p + adPixelError(fb, half, walk.word(origin, pitch));
+	return p;
+}
+
+/* half := fb over the rectangle, raw bits, all three channels: a pixel a thread in the enumeration, four pixels' loads in flight before their stores (the compiler
+ * may not move a load across a store to the other buffer itself). A pixel past the end reads the batch's first one again and stores nothing. */
+template <uint32_t STRIDE>
+__device__ __forceinline__ void adCopy(const uint32_t *src, uint32_t *dst, size_t origin, size_t pitch, uint32_t w, uint32_t n, uint32_t t) {
+	AdWalk<STRIDE> walk(w, t);
 #define CRH_AD_NEXT(at, ok, u) \
-	const bool ok = k + (u) * CRH_BLOCK < n; \
-	const size_t at = ok ? origin + (size_t)row * pitch + (size_t)x * 3u : at0; \
-	row += q; x += r; \
-	if (x >= tw) { x -= tw; ++row; }
+	const bool ok = k + (u) * STRIDE < n; \
+	const size_t at = ok ? walk.word(origin, pitch) : at0; \
+	walk.step();
 #define CRH_AD_LOAD(v, at) const uint32_t v##r = src[at], v##g = src[at + 1], v##b = src[at + 2];
 #define CRH_AD_STORE(v, at) { dst[at] = v##r; dst[at + 1] = v##g; dst[at + 2] = v##b; }
-	for (uint32_t k = t; k < n; k += 4u * CRH_BLOCK) {
-		CRH_AD_NEXT(at0, ok0, 0u)
+	for (uint32_t k = t; k < n; k += 4u * STRIDE) {
+		const size_t at0 = walk.word(origin, pitch);          /* (k < n) */
+		walk.step();
 		CRH_AD_NEXT(at1, ok1, 1u)
 		CRH_AD_NEXT(at2, ok2, 2u)
 		CRH_AD_NEXT(at3, ok3, 3u)
@@ -95,6 +90,31 @@ __global__ __launch_bounds__(CRH_BLOCK) void k_adaptive_step(const AdaptiveArgs 
 #undef CRH_AD_NEXT
 #undef CRH_AD_LOAD
 #undef CRH_AD_STORE
+}
+
+__global__ __launch_bounds__(CRH_BLOCK) void k_adaptive_step(const AdaptiveArgs A) {
+	__shared__ float s_part[CRH_BLOCK];
+	const uint32_t t = threadIdx.x;
+	const crh_tile T = A.tiles[blockIdx.x];
+	const uint32_t tw = (uint32_t)(T.x1 - T.x0), th = (uint32_t)(T.y1 - T.y0), n = tw * th;          /* (the host refuses empty tiles and tiles of more than 2^30 pixels) */
+	const size_t origin = ((size_t)(A.H - T.y1) * (size_t)A.W + (size_t)T.x0) * 3u;                       /* the tile's first stored row, its first pixel */
+	const size_t pitch = (size_t)A.W * 3u;
+	bool cont = A.advanceAll != 0;
+	if (!A.advanceAll) {
+		const float p = adErrorSum<CRH_BLOCK>(A.fb, A.half, origin, pitch, tw, n, t);
+		s_part[t] = p;
+		__syncthreads();
+#pragma unroll
+		for (uint32_t stride = CRH_BLOCK / 2; stride >= 1u; stride >>= 1) {
+			if (t < stride) s_part[t] = s_part[t] + s_part[t + stride];
+			__syncthreads();
+		}
+		const float E = s_part[0] / (float)n;
+		cont = !(E <= A.threshold);
+		if (t == 0) { A.errors[blockIdx.x] = E; A.flags[blockIdx.x] = cont ? 1u : 0u; }
+	}
+	if (!cont) return;
+	adCopy<CRH_BLOCK>((const uint32_t *)A.fb, (uint32_t *)A.half, origin, pitch, tw, n, t);
 }
 
 /* ---- k_adaptive_cells: the same step at cell granularity within each rectangle (crh_adaptive_step_cells, crh_render_adaptive_cells) ----------------------
@@ -130,36 +150,6 @@ struct AdaptiveCellsArgs {
 
 __device__ __forceinline__ uint32_t adMin(uint32_t a, uint32_t b) { return a < b ? a : b; }
 
-/* half := fb over one cell, raw bits, a pixel a lane in the cell's enumeration, four pixels' loads in flight before their stores (as in k_adaptive_step: a pixel
- * past the end reads the batch's first one again and stores nothing). */
-__device__ __forceinline__ void adCopyCell(const uint32_t *src, uint32_t *dst, size_t origin, size_t pitch, uint32_t cw, uint32_t n, uint32_t lane) {
-	const uint32_t q = CRH_AD_WAVE / cw, r = CRH_AD_WAVE % cw;
-	uint32_t row = lane / cw, x = lane % cw;
-#define CRH_ADC_STEP row += q; x += r; if (x >= cw) { x -= cw; ++row; }
-#define CRH_ADC_NEXT(at, ok, u) \
-	const bool ok = k + (u) * CRH_AD_WAVE < n; \
-	const size_t at = ok ? origin + (size_t)row * pitch + (size_t)x * 3u : at0; \
-	CRH_ADC_STEP
-#define CRH_ADC_LOAD(v, at) const uint32_t v##r = src[at], v##g = src[at + 1], v##b = src[at + 2];
-#define CRH_ADC_STORE(v, at) { dst[at] = v##r; dst[at + 1] = v##g; dst[at + 2] = v##b; }
-	for (uint32_t k = lane; k < n; k += 4u * CRH_AD_WAVE) {
-		const size_t at0 = origin + (size_t)row * pitch + (size_t)x * 3u;          /* (k < n) */
-		CRH_ADC_STEP
-		CRH_ADC_NEXT(at1, ok1, 1u)
-		CRH_ADC_NEXT(at2, ok2, 2u)
-		CRH_ADC_NEXT(at3, ok3, 3u)
-		CRH_ADC_LOAD(v0, at0) CRH_ADC_LOAD(v1, at1) CRH_ADC_LOAD(v2, at2) CRH_ADC_LOAD(v3, at3)
-		CRH_ADC_STORE(v0, at0)
-		if (ok1) CRH_ADC_STORE(v1, at1)
-		if (ok2) CRH_ADC_STORE(v2, at2)
-		if (ok3) CRH_ADC_STORE(v3, at3)
-	}
-#undef CRH_ADC_NEXT
-#undef CRH_ADC_STEP
-#undef CRH_ADC_LOAD
-#undef CRH_ADC_STORE
-}
-
 __global__ __launch_bounds__(CRH_BLOCK) void k_adaptive_cells(const AdaptiveCellsArgs A) {
 	__shared__ float s_err[CRH_AD_CELLS_MAX];
 	__shared__ uint8_t s_hot[CRH_AD_CELLS_MAX];          /* bit 0: hot, bit 1: live */
@@ -181,15 +171,7 @@ __global__ __launch_bounds__(CRH_BLOCK) void k_adaptive_cells(const AdaptiveCell
 			if (isLive) {
 				const uint32_t cw = adMin(c, tw - i * c), ch = adMin(c, th - j * c), n = cw * ch;
 				const size_t at = origin + (size_t)(j * c) * pitch + (size_t)(i * c) * 3u;
-				const uint32_t q = CRH_AD_WAVE / cw, r = CRH_AD_WAVE % cw;
-				uint32_t row = lane / cw, x = lane % cw;
-				float p = 0.0f;
-#pragma unroll 4
-				for (uint32_t k = lane; k < n; k += CRH_AD_WAVE) {
-					p = p + adPixelError(A.fb, A.half, at + (size_t)row * pitch + (size_t)x * 3u);
-					row += q; x += r;
-					if (x >= cw) { x -= cw; ++row; }
-				}
+				float p = adErrorSum<CRH_AD_WAVE>(A.fb, A.half, at, pitch, cw, n, lane);
 #pragma unroll
 				for (int stride = (int)CRH_AD_WAVE / 2; stride >= 1; stride >>= 1) p = p + __shfl_xor(p, stride);
 				E = p / (float)n;
@@ -224,7 +206,7 @@ __global__ __launch_bounds__(CRH_BLOCK) void k_adaptive_cells(const AdaptiveCell
 		const bool go = A.advanceAll ? (!A.live || A.live[first + idx] != 0) : s_go[idx] != 0;
 		if (go) {
 			const uint32_t cw = adMin(c, tw - i * c), ch = adMin(c, th - j * c);
-			adCopyCell(src, dst, origin + (size_t)(j * c) * pitch + (size_t)(i * c) * 3u, pitch, cw, cw * ch, lane);
+			adCopy<CRH_AD_WAVE>(src, dst, origin + (size_t)(j * c) * pitch + (size_t)(i * c) * 3u, pitch, cw, cw * ch, lane);
 		}
 		i += CRH_BLOCK / CRH_AD_WAVE;
 		while (i >= cx) { i -= cx; ++j; }

@@ -21,10 +21,10 @@
  * CRH_AOV_STACK frames are open at a time; the scene compiler reports the deepest nesting under a material's root (CompiledScene::max_albedo_depth), and a
  * scene that nests deeper makes crh_render_aov answer CRH_ERR_UNSUPPORTED.
  *
- * Shape. A wave takes `group` = 64 / min(passes, 64) consecutive pixels of a tile (row by row) at a time, for all passes of the dispatch; it pulls units of a few
+ * Shape (firstHitWaves below: k_aov and k_ids share the loop and differ in the sample and its fold). A wave takes `group` = 64 / min(passes, 64) consecutive pixels of a tile (row by row) at a time, for all passes of the dispatch; it pulls units of a few
  * such groups from an atomic counter (one group per pull was measured: 230 000 pulls of ONE counter bounded the 1280 x 720 x 16 dispatch at 2.76 ms whatever the
  * occupancy; the host sizes the units so that a wave gets about eight). Per chunk of up to 64 passes, lane l takes pixel l / chunk, pass l % chunk (pixel-major, like decodeItem: the passes of a pixel sit in neighbouring
- * lanes — coherent rays), walks its ray from start to end (one ray per lane, traverse()'s loop), and leaves its eight floats in LDS; lane p then folds pixel p's
+ * lanes — coherent rays), walks its ray from start to end (one ray per lane, traverse()'s loop: walkToShade), and leaves its eight floats in LDS; lane p then folds pixel p's
  * samples in pass order into the buffer (two 16-byte loads, two 16-byte stores). The chunks of a pixel are folded by the same lane of the same wave one after
  * the other, so the order needs no atomics. A lane owns one 27-word column of LDS: 12 traversal-stack entries + the 15 park slots while it walks (deeper
  * entries: the wave's overflow columns in global memory, as in the render kernels), the albedo frames (8 node words, then 3 colour words per frame: six frames
@@ -55,6 +55,7 @@ struct AovStack {
 	lds_u32 *col;              /* &s_lane[threadIdx.x]: word i of this lane's column at col[i * CRH_BLOCK] (bank = lane mod 32) */
 	glb_u32 *ovf;              /* wave-uniform: the wave's overflow columns */
 	const lds_u32 *inst0;      /* workgroup-uniform: line 0 of the instance records (scenes of <= CRH_INST_LDS0_MAX instances), or null */
+	const lds_u32 *waveCols;   /* the column of lane l of this wave: waveCols + l (what a folding lane reads) */
 	__device__ __forceinline__ InstLine instLine(const DScene &S, int32_t idx, int line) const {
 		if (line == 0 && inst0) {
 			const lds_u32 *p = inst0 + (uint32_t)idx * 16u;
@@ -87,6 +88,17 @@ struct AovStack {
 		return v;
 	}
 };
+/* a lane's stack over the workgroup's LDS arrays — CRH_AOV_LANE_WORDS * CRH_BLOCK words of columns, the instance records' line 0 (stageInstLine0: walk_machine.h) */
+template <size_t NL, size_t NI>
+__device__ __forceinline__ AovStack aovStack(const DScene &S, uint32_t (&s_lane)[NL], uint32_t (&s_inst0)[NI], uint32_t *ovfAll) {
+	const uint32_t wave = (blockIdx.x * CRH_BLOCK + threadIdx.x) >> 6;
+	AovStack stk;
+	stk.col = (lds_u32 *)&s_lane[threadIdx.x];
+	stk.ovf = (glb_u32 *)ovfAll + (size_t)__builtin_amdgcn_readfirstlane(wave) * CRH_OVF_WORDS_PER_WAVE;
+	stk.inst0 = CRH_AOV_INST_LDS ? stageInstLine0(S, s_inst0) : nullptr;
+	stk.waveCols = (const lds_u32 *)&s_lane[threadIdx.x & ~63u];
+	return stk;
+}
 template <bool RARE> struct AovCounters { static constexpr int level = 0; static constexpr bool programs = RARE; static constexpr bool wide = false; };
 
 /* The albedo of a hit (the header comment): frame f of the evaluator is word f of the lane's column (the mix / add node, bit 31 = its a branch is done) and
@@ -142,23 +154,22 @@ struct AovUnits {
 	uint32_t groups;           /* such groups per unit (consecutive ones of a tile) */
 };
 
-/* SAMP: the sampler (0 random, 1 Halton); RARE: node programs or volumes, as in k_pathtrace_roll */
-template <int SAMP, bool RARE>
-__global__ __launch_bounds__(CRH_BLOCK, RARE ? 4 : CRH_AOV_WPS) void k_aov(const DScene Sarg, const crh_render_params P, const AovUnits U, float *aovArg, uint32_t rayFlags, uint32_t *ovfAll) {
-	__shared__ uint32_t s_lane[CRH_AOV_LANE_WORDS * CRH_BLOCK];
-	__shared__ __attribute__((aligned(16))) uint32_t s_inst0[CRH_AOV_INST_LDS ? CRH_INST_LDS0_MAX * 16u : 4u];
-	CRH_EM_POW_TABLES_INIT();
-	const DScene S = globalize(Sarg);
+/* The wave loop of a first-hit kernel (k_aov below; k_ids: idmatte.h) — the header's Shape, written once: the pull of a unit, its tile, the groups, the chunks of up to
+ * 64 passes, the pixel-major lane assignment, the lane's walk, the two fence / lock-step pairs around the fold. What the kernels differ in comes with K:
+ *   K::Rng, seed(rng)       the paths' sampler, and what it holds besides the state beginPath seeds (IdsRng's kind)
+ *   K::rare                 node programs or volumes in the walk, as in k_pathtrace_roll
+ *   K::Sample               what a lane leaves in its column: constructed as a miss, put(stk) writes it
+ *   hit(S, lp, w, stk, cnt, s)   fills it from a finished walk that hit (w.hit.inst >= 0)
+ *   foldLane(lane, npix)    which of the group's npix pixels this lane folds (>= npix: none)
+ *   fold(pixel, col, pc, p0, lane, npix)   the folding lane: its pixel's index in the buffer, the column of the pixel's first sample of this chunk (sample k, word i:
+ *                           col[i * CRH_BLOCK + k]), the chunk's passes p0 .. p0 + pc
+ * stk: the lane's column over the workgroup's LDS (aovStack). */
+template <class K>
+__device__ __forceinline__ void firstHitWaves(const DScene &S, const crh_render_params &P, const AovUnits &U, uint32_t rayFlags, AovStack &stk, const K &kern) {
 	const crh_tile *const tiles = asGlobal(U.tiles);
 	const uint32_t *const start = asGlobal(U.start);
-	f4 *const aov = (f4 *)(__attribute__((address_space(1))) f4 *)aovArg;
 	const uint32_t lane = threadIdx.x & 63u;
-	const uint32_t wave = (blockIdx.x * CRH_BLOCK + threadIdx.x) >> 6;
-	AovStack stk;
-	stk.col = (lds_u32 *)&s_lane[threadIdx.x];
-	stk.ovf = (glb_u32 *)ovfAll + (size_t)__builtin_amdgcn_readfirstlane(wave) * CRH_OVF_WORDS_PER_WAVE;
-	stk.inst0 = CRH_AOV_INST_LDS ? stageInstLine0(S, s_inst0) : nullptr;          /* (walk_machine.h) */
-	const lds_u32 *const waveCols = (const lds_u32 *)&s_lane[threadIdx.x & ~63u];          /* column of lane l of this wave: waveCols + l */
+	const lds_u32 *const waveCols = stk.waveCols;
 	const int passEnd = P.first_pass + P.pass_count;
 	for (;;) {
 		uint32_t u = 0;
@@ -173,59 +184,87 @@ __global__ __launch_bounds__(CRH_BLOCK, RARE ? 4 : CRH_AOV_WPS) void k_aov(const
 		const uint32_t first = ((u - start[lo]) * U.groups + gi) * U.group;                     /* the group's first pixel, counted inside the tile */
 		if (first >= tilePixels) break;
 		const uint32_t npix = min(U.group, tilePixels - first);
-		/* the pixel this lane FOLDS (lane < npix) */
-		const uint32_t fIdx = first + min(lane, npix - 1u);
+		/* the pixel this lane FOLDS (fl < npix) */
+		const uint32_t fl = kern.foldLane(lane, npix);
+		const uint32_t fIdx = first + min(fl, npix - 1u);
 		const int fx = t.x0 + (int)(fIdx % tw), fy = t.y0 + (int)(fIdx / tw);
-		f4 *const out = aov + ((size_t)fx + (size_t)(P.image_height - (fy + 1)) * (size_t)P.image_width) * 2u;
+		const size_t fPixel = (size_t)fx + (size_t)(P.image_height - (fy + 1)) * (size_t)P.image_width;
 		for (int p0 = P.first_pass; p0 < passEnd; p0 += 64) {
 			const uint32_t pc = (uint32_t)min(64, passEnd - p0);
 			const uint32_t pj = lane / pc;                                                      /* pixel-major: the passes of a pixel in neighbouring lanes */
-			float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f, s4 = 0.0f, s5 = 0.0f, s6 = 0.0f, s7 = 0.0f;          /* a miss: eight zeros */
+			typename K::Sample s;
 			if (pj < npix) {
 				const uint32_t idx = first + pj;
 				const int x = t.x0 + (int)(idx % tw), y = t.y0 + (int)(idx / tw), pass = p0 + (int)(lane - pj * pc);
-				AovCounters<RARE> cnt;
-				LanePathT<RngT<SAMP>> lp;
+				AovCounters<K::rare> cnt;
+				LanePathT<typename K::Rng> lp;
 				memset(&lp, 0, sizeof(lp));
+				kern.seed(lp.r.rng);
 				beginPath(S, P, x, y, pass, lp.ro, lp.rd, lp.r, cnt);
 				auto port = lanePort(lp);
 				Walk w;
 				walkBegin(S, w, stk, lp.ro, lp.rd, cnt, port, rayFlags);
-				while (w.phase != PH_SHADE) {          /* traverse() with the path's port */
-					if (w.phase == PH_NODE) stepNodeAny<true>(S, w, stk, cnt, port);
-					else if (w.phase == PH_NODE_SLOW) stepNodeAny<false>(S, w, stk, cnt, port);
-					else if (w.phase == PH_TRI) stepTri(S, w, stk, cnt, port);
-					else stepCtrl(S, w, stk, cnt, port);
-				}
-				if (w.hit.inst >= 0) {
-					const HitInfo h = finishHit<true, RARE>(S, lp.ro, lp.rd, w.hit, stk);
-					const crh_material mat = loadMaterial(S, stk, h.material);
-					ShadeRec rec;
-					rec.dir = lp.rd; rec.point = h.point; rec.normal = h.normal; rec.uv = h.uv; rec.distance = w.hit.t; rec.ior = mat.ior;
-					evalAlbedo(S, mat.bsdf, rec, cnt, stk, s0, s1, s2);
-					if (!(RARE && w.hit.slot == -2)) { s3 = h.normal.x; s4 = h.normal.y; s5 = h.normal.z; }          /* (a scattering event's normal is a placeholder: zeros) */
-					s6 = w.hit.t; s7 = 1.0f;
-				}
+				walkToShade(S, w, stk, cnt, port);
+				if (w.hit.inst >= 0) kern.hit(S, lp, w, stk, cnt, s);
 			}
-			stk.put(0, asU32(s0)); stk.put(1, asU32(s1)); stk.put(2, asU32(s2)); stk.put(3, asU32(s3));
-			stk.put(4, asU32(s4)); stk.put(5, asU32(s5)); stk.put(6, asU32(s6)); stk.put(7, asU32(s7));
+			s.put(stk);
 			__threadfence_block();                 /* the samples of all lanes are visible to the folding lanes */
 			CRH_LOCKSTEP();
-			if (lane < npix) {
-				f4 a = out[0], b = out[1];
-				const lds_u32 *sp = waveCols + lane * pc;
-				float unused = 0.0f;
-				for (uint32_t k = 0; k < pc; ++k) {          /* renderer.c:288-291, channel by channel, in pass order */
-					const int cs = p0 + (int)k + 1;
-					foldSample(a.x, a.y, a.z, asF32(sp[k]), asF32(sp[CRH_BLOCK + k]), asF32(sp[2 * CRH_BLOCK + k]), cs);
-					foldSample(a.w, b.x, b.y, asF32(sp[3 * CRH_BLOCK + k]), asF32(sp[4 * CRH_BLOCK + k]), asF32(sp[5 * CRH_BLOCK + k]), cs);
-					foldSample(b.z, b.w, unused, asF32(sp[6 * CRH_BLOCK + k]), asF32(sp[7 * CRH_BLOCK + k]), 0.0f, cs);
-				}
-				out[0] = a; out[1] = b;
-			}
+			if (fl < npix) kern.fold(fPixel, waveCols + fl * pc, pc, p0, lane, npix);
 			__threadfence_block();                 /* ... and read before the next chunk's walks overwrite them */
 			CRH_LOCKSTEP();
 		}
 		}
 	}
+}
+
+/* k_aov's sample: the eight floats; of a miss, eight zeros */
+struct AovSample {
+	float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f, s4 = 0.0f, s5 = 0.0f, s6 = 0.0f, s7 = 0.0f;
+	__device__ __forceinline__ void put(AovStack &stk) const {
+		stk.put(0, asU32(s0)); stk.put(1, asU32(s1)); stk.put(2, asU32(s2)); stk.put(3, asU32(s3));
+		stk.put(4, asU32(s4)); stk.put(5, asU32(s5)); stk.put(6, asU32(s6)); stk.put(7, asU32(s7));
+	}
+};
+template <int SAMP, bool RARE> struct AovKernel {
+	typedef RngT<SAMP> Rng;
+	typedef AovSample Sample;
+	static constexpr bool rare = RARE;
+	f4 *aov;
+	__device__ __forceinline__ void seed(Rng &) const {}
+	__device__ __forceinline__ uint32_t foldLane(uint32_t lane, uint32_t) const { return lane; }
+	template <class LP, class Cnt>
+	__device__ __forceinline__ void hit(const DScene &S, LP &lp, const Walk &w, AovStack &stk, Cnt &cnt, AovSample &s) const {
+		const HitInfo h = finishHit<true, RARE>(S, lp.ro, lp.rd, w.hit, stk);
+		const crh_material mat = loadMaterial(S, stk, h.material);
+		ShadeRec rec;
+		rec.dir = lp.rd; rec.point = h.point; rec.normal = h.normal; rec.uv = h.uv; rec.distance = w.hit.t; rec.ior = mat.ior;
+		evalAlbedo(S, mat.bsdf, rec, cnt, stk, s.s0, s.s1, s.s2);
+		if (!(RARE && w.hit.slot == -2)) { s.s3 = h.normal.x; s.s4 = h.normal.y; s.s5 = h.normal.z; }          /* (a scattering event's normal is a placeholder: zeros) */
+		s.s6 = w.hit.t; s.s7 = 1.0f;
+	}
+	/* two 16-byte loads, renderer.c:288-291 channel by channel in pass order, two 16-byte stores */
+	__device__ __forceinline__ void fold(size_t pixel, const lds_u32 *sp, uint32_t pc, int p0, uint32_t, uint32_t) const {
+		f4 *const out = aov + pixel * 2u;
+		f4 a = out[0], b = out[1];
+		float unused = 0.0f;
+		for (uint32_t k = 0; k < pc; ++k) {
+			const int cs = p0 + (int)k + 1;
+			foldSample(a.x, a.y, a.z, asF32(sp[k]), asF32(sp[CRH_BLOCK + k]), asF32(sp[2 * CRH_BLOCK + k]), cs);
+			foldSample(a.w, b.x, b.y, asF32(sp[3 * CRH_BLOCK + k]), asF32(sp[4 * CRH_BLOCK + k]), asF32(sp[5 * CRH_BLOCK + k]), cs);
+			foldSample(b.z, b.w, unused, asF32(sp[6 * CRH_BLOCK + k]), asF32(sp[7 * CRH_BLOCK + k]), 0.0f, cs);
+		}
+		out[0] = a; out[1] = b;
+	}
+};
+
+/* SAMP: the sampler (0 random, 1 Halton); RARE: node programs or volumes, as in k_pathtrace_roll */
+template <int SAMP, bool RARE>
+__global__ __launch_bounds__(CRH_BLOCK, RARE ? 4 : CRH_AOV_WPS) void k_aov(const DScene Sarg, const crh_render_params P, const AovUnits U, float *aovArg, uint32_t rayFlags, uint32_t *ovfAll) {
+	__shared__ uint32_t s_lane[CRH_AOV_LANE_WORDS * CRH_BLOCK];
+	__shared__ __attribute__((aligned(16))) uint32_t s_inst0[CRH_AOV_INST_LDS ? CRH_INST_LDS0_MAX * 16u : 4u];
+	CRH_EM_POW_TABLES_INIT();
+	const DScene S = globalize(Sarg);
+	AovStack stk = aovStack(S, s_lane, s_inst0, ovfAll);
+	firstHitWaves(S, P, U, rayFlags, stk, AovKernel<SAMP, RARE>{(f4 *)(__attribute__((address_space(1))) f4 *)aovArg});
 }

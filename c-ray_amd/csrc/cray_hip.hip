@@ -585,6 +585,13 @@ __global__ void k_eval_math(int fn, const float *x, const float *y, uint64_t n, 
 }
 
 /* ---- context ------------------------------------------------------------------------------------ */
+/* What a dispatch of k_aov's work shape keeps beside the render path (aovLaunchBegin / aovLaunchEnd): its work counter, reset behind the kernel; the pinned host buffer
+ * and device twin its tile list and unit starts go through; a lap around the kernel */
+struct SideDispatch {
+	uint32_t *counter = nullptr;
+	StagedBuf tiles;
+	Stopwatch<1> watch;
+};
 struct crh_ctx {
 	int device = 0;
 	void *pinned = nullptr;                  /* page-locked host scratch of the BVH builder (crh_internal_pinned) */
@@ -667,12 +674,9 @@ struct crh_ctx {
 	float lastMs = 0.0f;
 	double totalMs = 0.0;
 	uint64_t launches = 0;
-	/* crh_render_aov (aov.h): state of its own — an AOV dispatch leaves the render path's counters, times and kernel name as they were. The dispatch's tile list and unit
-	 * starts go through one pinned host buffer and its device twin; the work counter is reset behind the kernel */
+	/* crh_render_aov (aov.h): state of its own — an AOV dispatch leaves the render path's counters, times and kernel name as they were */
 	uint32_t aovDepth = 0;                   /* CompiledScene::max_albedo_depth of the resident scene */
-	uint32_t *dAovCounter = nullptr;
-	StagedBuf aovTiles;
-	Stopwatch<1> aovWatch;                   /* around the kernel (crh_aov_kernel_time_ms) */
+	SideDispatch aov;                        /* (the lap: crh_aov_kernel_time_ms) */
 	/* crh_denoise / crh_denoise_variance (denoise.h): three planes of 16-byte records (C ping, C pong, G) — and, for the variance kind, a plane of floats behind
 	 * them — sized lazily for the largest call so far, and a lap for every launch (prepare, the variance prefilter, the iterations) of the most recent denoise of either kind */
 	DevBuf<uint8_t> dDenoise;
@@ -681,11 +685,9 @@ struct crh_ctx {
 	 * so one of each serves), and a lap around the kernel */
 	StagedBuf adaptive;
 	Stopwatch<1> adaptiveWatch;
-	/* crh_render_ids / crh_ids_resolve / crh_ids_matte (idmatte.h): state of its own, as the AOV dispatch's — the tile list's staging buffer, the work counter, and a lap
-	 * around the most recent kernel of the three (crh_ids_kernel_time_ms) */
-	uint32_t *dIdsCounter = nullptr;
-	StagedBuf idsTiles;
-	Stopwatch<1> idsWatch;
+	/* crh_render_ids / crh_ids_resolve / crh_ids_matte (idmatte.h): state of its own, as the AOV dispatch's; the lap is around the most recent kernel of the three
+	 * (crh_ids_kernel_time_ms) */
+	SideDispatch ids;
 	/* crh_pack_scanlines (exr_pack.h): the packed rows and, behind them, the id maps of the call; a lap around its kernel (crh_pack_time_ms) */
 	DevBuf<uint8_t> dPack;
 	Stopwatch<1> packWatch;
@@ -996,8 +998,7 @@ int crh_context_destroy(crh_ctx *c) {
 	c->eventPool.release();
 	drop(c->dCounters); drop(c->dWork);
 	c->dStage.release(); c->dDefer.release(); c->dQueues.release(); c->dOvf.release();
-	drop(c->dAovCounter); c->aovTiles.release(); c->aovWatch.release();
-	drop(c->dIdsCounter); c->idsTiles.release(); c->idsWatch.release();
+	for (SideDispatch *s : {&c->aov, &c->ids}) { drop(s->counter); s->tiles.release(); s->watch.release(); }
 	c->dPack.release(); c->packWatch.release();
 	c->dDenoise.release(); c->denoiseWatch.release();
 	c->adaptive.release(); c->adaptiveWatch.release();
@@ -1921,7 +1922,7 @@ int crh_aov_alloc(crh_ctx *c, int width, int height, float **dev_out) { return p
 int crh_aov_free(crh_ctx *c, float *dev_aov) { return pixelBufFree("crh_aov_free", c, dev_aov); }
 int crh_aov_clear(crh_ctx *c, float *dev_aov, int width, int height) { return pixelBufClear("crh_aov_clear", c, dev_aov, width, height, CRH_AOV_CHANNELS * sizeof(float)); }
 int crh_aov_download(crh_ctx *c, const float *dev_aov, int width, int height, float *host_whc8) {
-	return pixelBufDownload("crh_aov_download", c, dev_aov, width, height, CRH_AOV_CHANNELS * sizeof(float), host_whc8, c ? &c->aovTiles : nullptr);
+	return pixelBufDownload("crh_aov_download", c, dev_aov, width, height, CRH_AOV_CHANNELS * sizeof(float), host_whc8, c ? &c->aov.tiles : nullptr);
 }
 
 /* The work of a crh_render_aov or crh_render_ids dispatch (aov.h: AovUnits) from its checked arguments: the rectangles that hold pixels, the first unit of each, and the
@@ -1964,8 +1965,7 @@ static int planAovUnits(const char *who, const crh_ctx *c, const crh_render_para
 /* What a dispatch of k_aov's work shape does around its launch (crh_render_aov, crh_render_ids), on the caller's own counter, list staging and stopwatch. Before it:
  * the plan, the overflow columns, the counter, the tile list on its way to the device, the stopwatch started; grid == 0: a dispatch with no work. */
 struct AovLaunch { AovUnits U; uint32_t grid = 0; };
-static int aovLaunchBegin(const char *who, crh_ctx *c, const crh_render_params *P, const crh_tile *tiles, uint32_t tile_count, uint32_t *&counter, StagedBuf &ts,
-                          Stopwatch<1> &watch, AovLaunch &L) {
+static int aovLaunchBegin(const char *who, crh_ctx *c, const crh_render_params *P, const crh_tile *tiles, uint32_t tile_count, SideDispatch &D, AovLaunch &L) {
 	AovPlan plan;
 	int rc = planAovUnits(who, c, P, tiles, tile_count, plan);
 	if (rc || plan.total == 0) return rc;
@@ -1973,29 +1973,30 @@ static int aovLaunchBegin(const char *who, crh_ctx *c, const crh_render_params *
 	const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)c->cuCount * CRH_AOV_BLOCKS_PER_CU, (plan.total + CRH_BLOCK / 64 - 1) / (CRH_BLOCK / 64));          /* (as many workgroups as a CU holds: aov.h) */
 	/* the render kernels' overflow columns: the same stream, one dispatch at a time */
 	if ((rc = c->dOvf.grow(c->stream, (size_t)grid * (CRH_BLOCK / 64) * CRH_OVF_WORDS_PER_WAVE))) return rc;
-	if (!counter) {
-		HIP_TRY(hipMalloc((void **)&counter, sizeof(uint32_t)));
-		HIP_TRY(hipMemsetAsync(counter, 0, sizeof(uint32_t), c->stream));
+	if (!D.counter) {
+		HIP_TRY(hipMalloc((void **)&D.counter, sizeof(uint32_t)));
+		HIP_TRY(hipMemsetAsync(D.counter, 0, sizeof(uint32_t), c->stream));
 	}
+	StagedBuf &ts = D.tiles;
 	size_t tileBytes, listBytes;
 	if ((rc = stageTileList(ts, plan.work, plan.start, tileBytes, listBytes))) return rc;          /* (waits until the dispatch before this one has read the list) */
 	HIP_TRY(hipMemcpyAsync(ts.dev, ts.host, listBytes, hipMemcpyHostToDevice, c->stream));
 	L.U.tiles = (const crh_tile *)ts.dev;
 	L.U.start = (const uint32_t *)((const char *)ts.dev + tileBytes);
-	L.U.ntiles = (uint32_t)plan.work.size(); L.U.total = (uint32_t)plan.total; L.U.counter = counter; L.U.group = plan.group; L.U.groups = plan.groups;
-	if ((rc = watch.start(c->stream))) return rc;
+	L.U.ntiles = (uint32_t)plan.work.size(); L.U.total = (uint32_t)plan.total; L.U.counter = D.counter; L.U.group = plan.group; L.U.groups = plan.groups;
+	if ((rc = D.watch.start(c->stream))) return rc;
 	L.grid = grid;
 	return CRH_OK;
 }
 /* ... and behind it: the lap, the counter ready for the next dispatch, the list marked in flight, the launch's error reported under the kernel's name */
-static int aovLaunchEnd(const char *kernel, crh_ctx *c, uint32_t *counter, StagedBuf &ts, Stopwatch<1> &watch) {
+static int aovLaunchEnd(const char *kernel, crh_ctx *c, SideDispatch &D) {
 	const hipError_t e = hipGetLastError();
-	int rc = watch.mark(c->stream);
+	int rc = D.watch.mark(c->stream);
 	if (rc) return rc;
-	HIP_TRY(hipMemsetAsync(counter, 0, sizeof(uint32_t), c->stream));
-	if ((rc = ts.markInFlight(c->stream))) return rc;
+	HIP_TRY(hipMemsetAsync(D.counter, 0, sizeof(uint32_t), c->stream));
+	if ((rc = D.tiles.markInFlight(c->stream))) return rc;
 	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string(kernel) + " launch: " + hipGetErrorString(e));
-	watch.stop();
+	D.watch.stop();
 	return CRH_OK;
 }
 
@@ -2014,13 +2015,13 @@ int crh_render_aov(crh_ctx *c, const crh_render_params *P, const crh_tile *tiles
 	const auto *const kernel = pickRow(kAovRows, 0, c->hasPrograms, c->sampler == CRH_SAMPLER_HALTON ? 1 : 0, 0);
 	if (!kernel) return fail(CRH_ERR_HIP, std::string("k_aov launch: ") + hipGetErrorString(hipErrorInvalidDeviceFunction));
 	AovLaunch L;
-	if ((rc = aovLaunchBegin("crh_render_aov", c, P, tiles, tile_count, c->dAovCounter, c->aovTiles, c->aovWatch, L)) || !L.grid) return rc;
+	if ((rc = aovLaunchBegin("crh_render_aov", c, P, tiles, tile_count, c->aov, L)) || !L.grid) return rc;
 	hipLaunchKernelGGL((kernel->fn), dim3(L.grid), dim3(CRH_BLOCK), 0, c->stream, c->d, *P, L.U, dev_aov, (uint32_t)c->sched.rayFlags, c->dOvf.p);
-	return aovLaunchEnd("k_aov", c, c->dAovCounter, c->aovTiles, c->aovWatch);
+	return aovLaunchEnd("k_aov", c, c->aov);
 }
 
 /* Duration of the most recent crh_render_aov's kernel (HIP events on the context's stream; waits for it); 0 before the first one. */
-int crh_aov_kernel_time_ms(crh_ctx *c, float *last_ms) { return watchTimeMs("crh_aov_kernel_time_ms", c, c ? &c->aovWatch : nullptr, last_ms); }
+int crh_aov_kernel_time_ms(crh_ctx *c, float *last_ms) { return watchTimeMs("crh_aov_kernel_time_ms", c, c ? &c->aov.watch : nullptr, last_ms); }
 
 /* ---- the guided a-trous denoiser (denoise.h) ------------------------------------------------------ */
 void crh_denoise_params_default(crh_denoise_params *p) {
@@ -2158,60 +2159,98 @@ int crh_debug_denoise_launch_ms(crh_ctx *c, float *ms, uint32_t cap) {
 	return c->denoiseWatch.laps;
 }
 
-/* ---- adaptive sampling at tile granularity (adaptive.h: k_adaptive_step) ------------------------------------------------------------------ */
-/* One launch over validated tiles, behind whatever the stream holds; waits for it. advanceAll: half := fb over every tile, nothing measured or reported. */
-static int adLaunch(crh_ctx *c, const float *dev_fb, float *dev_half, int width, int height, const crh_tile *tiles, uint32_t tile_count, float threshold, bool advanceAll,
-                    float *errors_host, uint8_t *continue_host) {
+/* ---- adaptive sampling (adaptive.h): k_adaptive_step at tile granularity, k_adaptive_cells at cell granularity within each rectangle ------------------------ */
+/* What a step works on: the frame and its half-sample frame, validated rectangles, and the units a decision is made for — the rectangles themselves, or (cells) the
+ * cells of their grids: offsets[r] = the index of rectangle r's first cell, units = the total. */
+struct AdFrame {
+	crh_ctx *c;
+	const float *fb;
+	float *half;
+	int W, H;
+	const crh_tile *tiles;
+	uint32_t tile_count;
+	bool cells;
+	const uint32_t *offsets;
+	uint32_t units;
+	int cell, dilate;
+};
+
+/* The launch of a step of either granularity, behind whatever the stream holds; waits for it. fill(A, host, dev) writes the staging block — `bytes`, of which the first
+ * `up` go to the device — and points the kernel's arguments A (the caller has set the rest) into its device twin; [backAt, backAt + back) comes back behind the kernel. */
+extern "C++" {          /* (a template inside this file's extern "C") */
+template <class Args, class Fill>
+static int adRun(crh_ctx *c, const char *name, void (*kernel)(const Args), Args &A, uint32_t grid, size_t bytes, size_t up, size_t backAt, size_t back, Fill fill) {
 	int rc = setDevice(c);
 	if (rc) return rc;
-	const size_t tileBytes = (size_t)tile_count * sizeof(crh_tile), wordBytes = (size_t)tile_count * sizeof(uint32_t);
 	/* the buffer is never marked in flight — a call that succeeds ends with the stream drained —, but one that failed half-way may have left its copy queued:
 	 * the stream is drained before the blocks are given up */
 	StagedBuf &sb = c->adaptive;
-	if (tileBytes + 2 * wordBytes > sb.cap) HIP_TRY(hipStreamSynchronize(c->stream));
-	if ((rc = sb.reserve(tileBytes + 2 * wordBytes))) return rc;
-	memcpy(sb.host, tiles, tileBytes);
-	HIP_TRY(hipMemcpyAsync(sb.dev, sb.host, tileBytes, hipMemcpyHostToDevice, c->stream));
-	AdaptiveArgs A;
-	A.fb = dev_fb; A.half = dev_half;
-	A.tiles = (const crh_tile *)sb.dev;
-	A.errors = (float *)((char *)sb.dev + tileBytes);
-	A.flags = (uint32_t *)((char *)sb.dev + tileBytes + wordBytes);
-	A.W = width; A.H = height; A.threshold = threshold; A.advanceAll = advanceAll ? 1 : 0;
+	if (bytes > sb.cap) HIP_TRY(hipStreamSynchronize(c->stream));
+	if ((rc = sb.reserve(bytes))) return rc;
+	fill(A, (char *)sb.host, (char *)sb.dev);
+	HIP_TRY(hipMemcpyAsync(sb.dev, sb.host, up, hipMemcpyHostToDevice, c->stream));
 	if ((rc = c->adaptiveWatch.start(c->stream))) return rc;
-	hipLaunchKernelGGL(k_adaptive_step, dim3(tile_count), dim3(CRH_BLOCK), 0, c->stream, A);
+	hipLaunchKernelGGL(kernel, dim3(grid), dim3(CRH_BLOCK), 0, c->stream, A);
 	const hipError_t e = hipGetLastError();
 	if ((rc = c->adaptiveWatch.mark(c->stream))) return rc;
-	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string("k_adaptive_step launch: ") + hipGetErrorString(e));
-	if (!advanceAll) HIP_TRY(hipMemcpyAsync((char *)sb.host + tileBytes, (char *)sb.dev + tileBytes, 2 * wordBytes, hipMemcpyDeviceToHost, c->stream));
+	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string(name) + " launch: " + hipGetErrorString(e));
+	if (back) HIP_TRY(hipMemcpyAsync((char *)sb.host + backAt, (char *)sb.dev + backAt, back, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	c->adaptiveWatch.stop();
-	if ((rc = c->adaptiveWatch.read())) return rc;
-	if (!advanceAll) {
-		const float *err = (const float *)((const char *)sb.host + tileBytes);
-		const uint32_t *flag = (const uint32_t *)((const char *)sb.host + tileBytes + wordBytes);
-		if (errors_host) memcpy(errors_host, err, wordBytes);
-		if (continue_host) for (uint32_t i = 0; i < tile_count; ++i) continue_host[i] = flag[i] ? 1 : 0;
+	return c->adaptiveWatch.read();
+}
+}
+
+/* One k_adaptive_step launch over the live rectangles (live_host NULL: all of them), compacted in list order; what it reports is indexed like the rectangles.
+ * advanceAll: half := fb over every one of them, nothing measured or reported. The staging block: the list, then per launched rectangle the errors and the flags. */
+static int adLaunch(const AdFrame &F, float threshold, bool advanceAll, const uint8_t *live_host, float *errors_host, uint8_t *continue_host) {
+	uint32_t count = 0;
+	for (uint32_t i = 0; i < F.tile_count; ++i) count += !live_host || live_host[i];
+	if (!count) return CRH_OK;
+	const size_t tileBytes = (size_t)count * sizeof(crh_tile), wordBytes = (size_t)count * sizeof(uint32_t);
+	AdaptiveArgs A;
+	A.fb = F.fb; A.half = F.half; A.W = F.W; A.H = F.H; A.threshold = threshold; A.advanceAll = advanceAll ? 1 : 0;
+	const int rc = adRun(F.c, "k_adaptive_step", k_adaptive_step, A, count, tileBytes + 2 * wordBytes, tileBytes, tileBytes, advanceAll ? 0 : 2 * wordBytes, [&](AdaptiveArgs &A, char *host, char *dev) {
+		crh_tile *list = (crh_tile *)host;
+		for (uint32_t i = 0; i < F.tile_count; ++i) if (!live_host || live_host[i]) *list++ = F.tiles[i];
+		A.tiles = (const crh_tile *)dev;
+		A.errors = (float *)(dev + tileBytes);
+		A.flags = (uint32_t *)(dev + tileBytes + wordBytes);
+	});
+	if (rc || advanceAll) return rc;
+	const float *err = (const float *)((const char *)F.c->adaptive.host + tileBytes);
+	const uint32_t *flag = (const uint32_t *)(err + count);
+	for (uint32_t i = 0, j = 0; i < F.tile_count; ++i) {
+		if (live_host && !live_host[i]) continue;
+		if (errors_host) errors_host[i] = err[j];
+		if (continue_host) continue_host[i] = flag[j] ? 1 : 0;
+		++j;
 	}
 	return CRH_OK;
 }
 
+/* A step's own argument rules, whatever its granularity (dilate: the cell step's; 0 at tile granularity). */
+static int adStepCheck(const char *who, const crh_ctx *c, const float *dev_fb, const float *dev_half, int width, int height, const crh_tile *tiles, uint32_t tile_count,
+                       float threshold, int dilate) {
+	if (!c || !dev_fb || !dev_half || (!tiles && tile_count)) return fail(CRH_ERR_INVALID, std::string(who) + ": NULL argument");
+	if (width <= 0 || height <= 0) return fail(CRH_ERR_INVALID, std::string(who) + ": bad size");
+	if (std::isnan(threshold) || std::signbit(threshold)) return fail(CRH_ERR_INVALID, std::string(who) + ": the threshold is NaN or negative");
+	if (dev_half == dev_fb) return fail(CRH_ERR_INVALID, std::string(who) + ": the half-sample frame is the frame");
+	if (dilate != 0 && dilate != 1) return fail(CRH_ERR_INVALID, std::string(who) + ": dilate must be 0 or 1");
+	return checkRects(who, tiles, tile_count, width, height, true);
+}
+
 int crh_adaptive_step(crh_ctx *c, const float *dev_fb, float *dev_half, int width, int height, const crh_tile *tiles, uint32_t tile_count, float threshold,
                       float *errors_host, uint8_t *continue_host) {
-	if (!c || !dev_fb || !dev_half || (!tiles && tile_count)) return fail(CRH_ERR_INVALID, "crh_adaptive_step: NULL argument");
-	if (width <= 0 || height <= 0) return fail(CRH_ERR_INVALID, "crh_adaptive_step: bad size");
-	if (std::isnan(threshold) || std::signbit(threshold)) return fail(CRH_ERR_INVALID, "crh_adaptive_step: the threshold is NaN or negative");
-	if ((const float *)dev_half == dev_fb) return fail(CRH_ERR_INVALID, "crh_adaptive_step: the half-sample frame is the frame");
-	const int rc = checkRects("crh_adaptive_step", tiles, tile_count, width, height, true);
+	const int rc = adStepCheck("crh_adaptive_step", c, dev_fb, dev_half, width, height, tiles, tile_count, threshold, 0);
 	if (rc) return rc;
-	if (tile_count == 0) return CRH_OK;
-	return adLaunch(c, dev_fb, dev_half, width, height, tiles, tile_count, threshold, false, errors_host, continue_host);
+	return adLaunch(AdFrame{c, dev_fb, dev_half, width, height, tiles, tile_count, false, nullptr, tile_count, 0, 0}, threshold, false, nullptr, errors_host, continue_host);
 }
 
 /* The kernel of the most recent step of either granularity (those of the two loops included), between two events of the library's own; 0 before the first one. */
 int crh_adaptive_time_ms(crh_ctx *c, float *last_ms) {
 	if (!c || !last_ms) return fail(CRH_ERR_INVALID, "crh_adaptive_time_ms: NULL argument");
-	*last_ms = c->adaptiveWatch.sum;          /* (adLaunch has read its lap) */
+	*last_ms = c->adaptiveWatch.sum;          /* (adRun has read its lap) */
 	return CRH_OK;
 }
 
@@ -2220,64 +2259,6 @@ void crh_adaptive_params_default(crh_adaptive_params *p) {
 	p->min_passes = 16; p->threshold = 0.05f;
 }
 
-/* The loop: min_passes everywhere, then every tile doubles its pass count until its error is at most the threshold or the cap is reached. */
-int crh_render_adaptive(crh_ctx *c, const crh_render_params *P, const crh_tile *tiles, uint32_t tile_count, const crh_adaptive_params *A, float *dev_fb, float *dev_half,
-                        int32_t *passes_host, float *errors_host) {
-	if (!c || !P || !A || !dev_fb || !dev_half || (!tiles && tile_count)) return fail(CRH_ERR_INVALID, "crh_render_adaptive: NULL argument");
-	if (!c->haveScene) return fail(CRH_ERR_INVALID, "crh_render_adaptive: no scene uploaded");
-	if (P->image_width <= 0 || P->image_height <= 0 || P->first_pass != 0 || P->pass_count <= 0 || P->max_passes < P->pass_count)
-		return fail(CRH_ERR_INVALID, "crh_render_adaptive: bad render parameters (first_pass must be 0, pass_count is the cap and must not exceed max_passes)");
-	const int m = A->min_passes, cap = P->pass_count;
-	if (m < 2 || (m & 1)) return fail(CRH_ERR_INVALID, "crh_render_adaptive: min_passes must be even and at least 2");
-	{
-		int64_t n = m;
-		while (n < cap) n *= 2;
-		if (n != cap) return fail(CRH_ERR_INVALID, "crh_render_adaptive: the cap (pass_count) must be min_passes times a power of two");
-	}
-	if (std::isnan(A->threshold) || std::signbit(A->threshold)) return fail(CRH_ERR_INVALID, "crh_render_adaptive: the threshold is NaN or negative");
-	if (dev_half == dev_fb) return fail(CRH_ERR_INVALID, "crh_render_adaptive: the half-sample frame is the frame");
-	const int W = P->image_width, H = P->image_height;
-	int rc = checkRects("crh_render_adaptive", tiles, tile_count, W, H, true);
-	if (rc) return rc;
-	if (tile_count == 0) return CRH_OK;
-	crh_render_params p = *P;
-	auto render = [&](const std::vector<crh_tile> &list, int first, int count) {
-		p.first_pass = first; p.pass_count = count;
-		return crh_render_tiles(c, &p, list.data(), (uint32_t)list.size(), dev_fb);
-	};
-	std::vector<crh_tile> live(tiles, tiles + tile_count);
-	std::vector<uint32_t> index(tile_count);          /* live[j] is tiles[index[j]] */
-	for (uint32_t i = 0; i < tile_count; ++i) index[i] = i;
-	if ((rc = render(live, 0, m / 2))) return rc;
-	if ((rc = adLaunch(c, dev_fb, dev_half, W, H, live.data(), tile_count, 0.0f, true, nullptr, nullptr))) return rc;
-	if ((rc = render(live, m / 2, m - m / 2))) return rc;
-	std::vector<float> err;
-	std::vector<uint8_t> go;
-	for (int n = m; !live.empty(); n *= 2) {
-		const uint32_t count = (uint32_t)live.size();
-		const bool last = n == cap;          /* measure only: nothing is left to render, so no half-sample frame moves */
-		err.resize(count); go.resize(count);
-		if ((rc = adLaunch(c, dev_fb, dev_half, W, H, live.data(), count, last ? __builtin_inff() : A->threshold, false, err.data(), go.data()))) return rc;
-		if (!last && A->threshold == 0.0f) {
-			/* threshold 0 asks for the uniform frame: a tile whose error is exactly 0 — the same colour in every pass so far, which is not the colour the
-			 * running mean of more passes rounds to — goes on like the others, so its half-sample frame moves too */
-			std::vector<crh_tile> still;
-			for (uint32_t j = 0; j < count; ++j) if (!go[j]) { still.push_back(live[j]); go[j] = 1; }
-			if (!still.empty() && (rc = adLaunch(c, dev_fb, dev_half, W, H, still.data(), (uint32_t)still.size(), 0.0f, true, nullptr, nullptr))) return rc;
-		}
-		uint32_t kept = 0;
-		for (uint32_t j = 0; j < count; ++j) {
-			if (errors_host) errors_host[index[j]] = err[j];
-			if (go[j] && !last) { live[kept] = live[j]; index[kept] = index[j]; ++kept; }
-			else if (passes_host) passes_host[index[j]] = n;
-		}
-		live.resize(kept); index.resize(kept);
-		if (kept && (rc = render(live, n, n))) return rc;
-	}
-	return CRH_OK;
-}
-
-/* ---- adaptive sampling at cell granularity within each rectangle (adaptive.h: k_adaptive_cells) -------------------------------------------------- */
 /* The cell grid of validated rectangles: offsets[r] = the index of rectangle r's first cell, offsets[tile_count] = the total. */
 static int adCellGrid(const char *who, const crh_tile *tiles, uint32_t tile_count, int cell, std::vector<uint32_t> *offsets, int64_t *total) {
 	if (!tiles && tile_count) return fail(CRH_ERR_INVALID, std::string(who) + ": NULL argument");
@@ -2308,71 +2289,50 @@ int64_t crh_adaptive_cell_offsets(const crh_tile *tiles, uint32_t tile_count, in
 	return total;
 }
 
-/* One launch over validated rectangles and their cell grid (offsets, total), behind whatever the stream holds; waits for it. Only the rectangles that hold a
- * live cell get a workgroup. advanceAll: half := fb over every live cell, nothing measured or reported. */
-static int adCellsLaunch(crh_ctx *c, const float *dev_fb, float *dev_half, int width, int height, const crh_tile *tiles, uint32_t tile_count, const uint32_t *offsets,
-                         uint32_t total, int cell, float threshold, int dilate, bool advanceAll, const uint8_t *live_host, float *errors_host, uint8_t *continue_host) {
+/* One k_adaptive_cells launch over the rectangles that hold a live cell (live_host NULL: every cell is live), with the mask; a cell no workgroup reports on comes
+ * back 0. advanceAll: half := fb over every live cell, nothing measured or reported. The staging block: the launched rectangles, their first cells, then per cell
+ * the errors, the flags and the live mask (zeros go up with the list). */
+static int adCellsLaunch(const AdFrame &F, float threshold, bool advanceAll, const uint8_t *live_host, float *errors_host, uint8_t *continue_host) {
+	const uint32_t total = F.units;
 	if (!advanceAll) {
 		if (errors_host) memset(errors_host, 0, (size_t)total * sizeof(float));
 		if (continue_host) memset(continue_host, 0, total);
 	}
 	std::vector<uint32_t> work;          /* the rectangles that hold a live cell */
-	for (uint32_t r = 0; r < tile_count; ++r) {
+	for (uint32_t r = 0; r < F.tile_count; ++r) {
 		bool any = !live_host;
-		for (uint32_t k = offsets[r]; !any && k < offsets[r + 1]; ++k) any = live_host[k] != 0;
+		for (uint32_t k = F.offsets[r]; !any && k < F.offsets[r + 1]; ++k) any = live_host[k] != 0;
 		if (any) work.push_back(r);
 	}
 	if (work.empty()) return CRH_OK;
-	int rc = setDevice(c);
-	if (rc) return rc;
-	/* the staging block: the launched rectangles, their first cells, then per cell the errors, the flags and the live mask (zeros go up with the list, so a
-	 * cell no workgroup reports on comes back 0) */
 	const size_t groups = work.size(), tileBytes = groups * sizeof(crh_tile), offBytes = groups * sizeof(uint32_t), errBytes = (size_t)total * sizeof(float);
 	const size_t errAt = tileBytes + offBytes, flagAt = errAt + errBytes, liveAt = flagAt + total, bytes = liveAt + (live_host ? total : 0);
-	StagedBuf &sb = c->adaptive;
-	if (bytes > sb.cap) HIP_TRY(hipStreamSynchronize(c->stream));          /* (as in adLaunch: a call that failed half-way may have left its copy queued) */
-	if ((rc = sb.reserve(bytes))) return rc;
-	char *const host = (char *)sb.host, *const dev = (char *)sb.dev;
-	for (size_t g = 0; g < groups; ++g) {
-		((crh_tile *)host)[g] = tiles[work[g]];
-		((uint32_t *)(host + tileBytes))[g] = offsets[work[g]];
-	}
-	memset(host + errAt, 0, errBytes + total);
-	if (live_host) memcpy(host + liveAt, live_host, total);
-	HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, c->stream));
 	AdaptiveCellsArgs A;
-	A.fb = dev_fb; A.half = dev_half;
-	A.tiles = (const crh_tile *)dev;
-	A.offsets = (const uint32_t *)(dev + tileBytes);
-	A.errors = (float *)(dev + errAt);
-	A.flags = (uint8_t *)(dev + flagAt);
-	A.live = live_host ? (const uint8_t *)(dev + liveAt) : nullptr;
-	A.W = width; A.H = height; A.cell = cell; A.threshold = threshold; A.dilate = dilate; A.advanceAll = advanceAll ? 1 : 0;
-	if ((rc = c->adaptiveWatch.start(c->stream))) return rc;
-	hipLaunchKernelGGL(k_adaptive_cells, dim3((uint32_t)groups), dim3(CRH_BLOCK), 0, c->stream, A);
-	const hipError_t e = hipGetLastError();
-	if ((rc = c->adaptiveWatch.mark(c->stream))) return rc;
-	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string("k_adaptive_cells launch: ") + hipGetErrorString(e));
-	if (!advanceAll) HIP_TRY(hipMemcpyAsync(host + errAt, dev + errAt, errBytes + total, hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	c->adaptiveWatch.stop();
-	if ((rc = c->adaptiveWatch.read())) return rc;
-	if (!advanceAll) {
-		if (errors_host) memcpy(errors_host, host + errAt, errBytes);
-		if (continue_host) for (uint32_t k = 0; k < total; ++k) continue_host[k] = host[flagAt + k] ? 1 : 0;
-	}
+	A.fb = F.fb; A.half = F.half; A.W = F.W; A.H = F.H; A.cell = F.cell; A.threshold = threshold; A.dilate = F.dilate; A.advanceAll = advanceAll ? 1 : 0;
+	const int rc = adRun(F.c, "k_adaptive_cells", k_adaptive_cells, A, (uint32_t)groups, bytes, bytes, errAt, advanceAll ? 0 : errBytes + total, [&](AdaptiveCellsArgs &A, char *host, char *dev) {
+		for (size_t g = 0; g < groups; ++g) {
+			((crh_tile *)host)[g] = F.tiles[work[g]];
+			((uint32_t *)(host + tileBytes))[g] = F.offsets[work[g]];
+		}
+		memset(host + errAt, 0, errBytes + total);
+		if (live_host) memcpy(host + liveAt, live_host, total);
+		A.tiles = (const crh_tile *)dev;
+		A.offsets = (const uint32_t *)(dev + tileBytes);
+		A.errors = (float *)(dev + errAt);
+		A.flags = (uint8_t *)(dev + flagAt);
+		A.live = live_host ? (const uint8_t *)(dev + liveAt) : nullptr;
+	});
+	if (rc || advanceAll) return rc;
+	const char *host = (const char *)F.c->adaptive.host;
+	if (errors_host) memcpy(errors_host, host + errAt, errBytes);
+	if (continue_host) for (uint32_t k = 0; k < total; ++k) continue_host[k] = host[flagAt + k] ? 1 : 0;
 	return CRH_OK;
 }
 
-/* The step's own argument rules (crh_adaptive_step's, then the cell grid's). */
-static int adCellsCheck(const char *who, crh_ctx *c, const float *dev_fb, const float *dev_half, int width, int height, const crh_tile *tiles, uint32_t tile_count, int cell,
+/* The cell step's own argument rules: the step's, then the cell grid's. */
+static int adCellsCheck(const char *who, const crh_ctx *c, const float *dev_fb, const float *dev_half, int width, int height, const crh_tile *tiles, uint32_t tile_count, int cell,
                         float threshold, int dilate, std::vector<uint32_t> *offsets, int64_t *total) {
-	if (!c || !dev_fb || !dev_half || (!tiles && tile_count)) return fail(CRH_ERR_INVALID, std::string(who) + ": NULL argument");
-	if (width <= 0 || height <= 0) return fail(CRH_ERR_INVALID, std::string(who) + ": bad size");
-	if (std::isnan(threshold) || std::signbit(threshold)) return fail(CRH_ERR_INVALID, std::string(who) + ": the threshold is NaN or negative");
-	if (dev_half == dev_fb) return fail(CRH_ERR_INVALID, std::string(who) + ": the half-sample frame is the frame");
-	if (dilate != 0 && dilate != 1) return fail(CRH_ERR_INVALID, std::string(who) + ": dilate must be 0 or 1");
-	const int rc = checkRects(who, tiles, tile_count, width, height, true);
+	const int rc = adStepCheck(who, c, dev_fb, dev_half, width, height, tiles, tile_count, threshold, dilate);
 	if (rc) return rc;
 	return adCellGrid(who, tiles, tile_count, cell, offsets, total);
 }
@@ -2384,8 +2344,8 @@ int crh_adaptive_step_cells(crh_ctx *c, const float *dev_fb, float *dev_half, in
 	const int rc = adCellsCheck("crh_adaptive_step_cells", c, dev_fb, dev_half, width, height, tiles, tile_count, cell, threshold, dilate, &offsets, &total);
 	if (rc) return rc;
 	if (tile_count == 0) return CRH_OK;
-	return adCellsLaunch(c, dev_fb, dev_half, width, height, tiles, tile_count, offsets.data(), (uint32_t)total, cell, threshold, dilate, false, live_host, errors_host,
-	                     continue_host);
+	return adCellsLaunch(AdFrame{c, dev_fb, dev_half, width, height, tiles, tile_count, true, offsets.data(), (uint32_t)total, cell, dilate}, threshold, false, live_host,
+	                     errors_host, continue_host);
 }
 
 void crh_adaptive_cells_params_default(crh_adaptive_cells_params *p) {
@@ -2393,54 +2353,75 @@ void crh_adaptive_cells_params_default(crh_adaptive_cells_params *p) {
 	p->min_passes = 16; p->threshold = 0.05f; p->cell = 16; p->dilate = 1;
 }
 
-/* The loop with the cell as the unit: min_passes everywhere, then every cell doubles its pass count until it no longer goes on or the cap is reached. */
-int crh_render_adaptive_cells(crh_ctx *c, const crh_render_params *P, const crh_tile *tiles, uint32_t tile_count, const crh_adaptive_cells_params *A, float *dev_fb,
-                              float *dev_half, int32_t *passes_host, float *errors_host) {
-	const char *who = "crh_render_adaptive_cells";
-	if (!c || !P || !A || !dev_fb || !dev_half || (!tiles && tile_count)) return fail(CRH_ERR_INVALID, "crh_render_adaptive_cells: NULL argument");
-	if (!c->haveScene) return fail(CRH_ERR_INVALID, "crh_render_adaptive_cells: no scene uploaded");
+/* The rectangles the live units ask the renderer for: the live rectangles in list order, or (cells) the live cells' pixels as maximal horizontal runs of live cells
+ * within one cell row of a rectangle — few, wide rectangles for the renderer. */
+static void adLiveRects(const AdFrame &F, const uint8_t *live, std::vector<crh_tile> &list) {
+	list.clear();
+	for (uint32_t r = 0; r < F.tile_count; ++r) {
+		const crh_tile &t = F.tiles[r];
+		if (!F.cells) { if (live[r]) list.push_back(t); continue; }
+		const int cell = F.cell, cx = (t.x1 - t.x0 + cell - 1) / cell, cy = (t.y1 - t.y0 + cell - 1) / cell;
+		for (int j = 0; j < cy; ++j) {
+			/* stored rows (H - y1) + j cell ..: in tile coordinates (y from the bottom) the cell row spans y1 - (j + 1) cell .. y1 - j cell, cut at y0 */
+			const int top = t.y1 - j * cell, bottom = std::max(t.y0, top - cell);
+			for (int i = 0; i < cx; ++i) {
+				if (!live[F.offsets[r] + (uint32_t)(j * cx + i)]) continue;
+				int e = i + 1;
+				while (e < cx && live[F.offsets[r] + (uint32_t)(j * cx + e)]) ++e;
+				list.push_back(crh_tile{t.x0 + i * cell, bottom, std::min(t.x1, t.x0 + e * cell), top});
+				i = e;
+			}
+		}
+	}
+}
+
+/* The loop of either granularity: min_passes everywhere, then every live unit — a rectangle, or (cells) a cell — doubles its pass count until it no longer goes on
+ * or the cap is reached. A granularity brings two things: how a step is issued (adLaunch, adCellsLaunch) and adLiveRects. */
+static int adLoop(const char *who, bool cells, crh_ctx *c, const crh_render_params *P, const crh_tile *tiles, uint32_t tile_count, const crh_adaptive_cells_params *A,
+                  float *dev_fb, float *dev_half, int32_t *passes_host, float *errors_host) {
+	if (!c || !P || !A || !dev_fb || !dev_half || (!tiles && tile_count)) return fail(CRH_ERR_INVALID, std::string(who) + ": NULL argument");
+	if (!c->haveScene) return fail(CRH_ERR_INVALID, std::string(who) + ": no scene uploaded");
 	if (P->image_width <= 0 || P->image_height <= 0 || P->first_pass != 0 || P->pass_count <= 0 || P->max_passes < P->pass_count)
-		return fail(CRH_ERR_INVALID, "crh_render_adaptive_cells: bad render parameters (first_pass must be 0, pass_count is the cap and must not exceed max_passes)");
+		return fail(CRH_ERR_INVALID, std::string(who) + ": bad render parameters (first_pass must be 0, pass_count is the cap and must not exceed max_passes)");
 	const int m = A->min_passes, cap = P->pass_count;
-	if (m < 2 || (m & 1)) return fail(CRH_ERR_INVALID, "crh_render_adaptive_cells: min_passes must be even and at least 2");
+	if (m < 2 || (m & 1)) return fail(CRH_ERR_INVALID, std::string(who) + ": min_passes must be even and at least 2");
 	{
 		int64_t n = m;
 		while (n < cap) n *= 2;
-		if (n != cap) return fail(CRH_ERR_INVALID, "crh_render_adaptive_cells: the cap (pass_count) must be min_passes times a power of two");
+		if (n != cap) return fail(CRH_ERR_INVALID, std::string(who) + ": the cap (pass_count) must be min_passes times a power of two");
 	}
-	const int W = P->image_width, H = P->image_height, cell = A->cell;
+	AdFrame F{c, dev_fb, dev_half, P->image_width, P->image_height, tiles, tile_count, cells, nullptr, tile_count, A->cell, A->dilate};
 	std::vector<uint32_t> offsets;
-	int64_t total64 = 0;
-	int rc = adCellsCheck(who, c, dev_fb, dev_half, W, H, tiles, tile_count, cell, A->threshold, A->dilate, &offsets, &total64);
+	int64_t total = tile_count;
+	int rc = cells ? adCellsCheck(who, c, dev_fb, dev_half, F.W, F.H, tiles, tile_count, A->cell, A->threshold, A->dilate, &offsets, &total)
+	               : adStepCheck(who, c, dev_fb, dev_half, F.W, F.H, tiles, tile_count, A->threshold, 0);
 	if (rc) return rc;
 	if (tile_count == 0) return CRH_OK;
-	const uint32_t total = (uint32_t)total64;
+	F.offsets = offsets.data(); F.units = (uint32_t)total;
 	crh_render_params p = *P;
-	auto render = [&](const std::vector<crh_tile> &list, int first, int count) {
+	std::vector<crh_tile> list(tiles, tiles + tile_count);
+	auto render = [&](int first, int count) {
 		p.first_pass = first; p.pass_count = count;
 		return crh_render_tiles(c, &p, list.data(), (uint32_t)list.size(), dev_fb);
 	};
-	auto step = [&](float threshold, bool advanceAll, const uint8_t *live, float *err, uint8_t *go) {
-		return adCellsLaunch(c, dev_fb, dev_half, W, H, tiles, tile_count, offsets.data(), total, cell, threshold, A->dilate, advanceAll, live, err, go);
-	};
-	std::vector<crh_tile> list(tiles, tiles + tile_count);
-	if ((rc = render(list, 0, m / 2))) return rc;
-	if ((rc = step(0.0f, true, nullptr, nullptr, nullptr))) return rc;
-	if ((rc = render(list, m / 2, m - m / 2))) return rc;
-	std::vector<uint8_t> live(total, 1), go(total), still(total);
-	std::vector<float> err(total);
+	auto step = cells ? adCellsLaunch : adLaunch;
+	if ((rc = render(0, m / 2))) return rc;
+	if ((rc = step(F, 0.0f, true, nullptr, nullptr, nullptr))) return rc;
+	if ((rc = render(m / 2, m - m / 2))) return rc;
+	std::vector<uint8_t> live(F.units, 1), go(F.units), still(F.units);
+	std::vector<float> err(F.units);
 	for (int n = m;; n *= 2) {
 		const bool last = n == cap;          /* measure only: nothing is left to render, so no half-sample frame moves */
-		if ((rc = step(last ? __builtin_inff() : A->threshold, false, live.data(), err.data(), go.data()))) return rc;
+		if ((rc = step(F, last ? __builtin_inff() : A->threshold, false, live.data(), err.data(), go.data()))) return rc;
 		if (!last && A->threshold == 0.0f) {
-			/* threshold 0 asks for the uniform frame (crh_render_adaptive's rule and reason): a live cell that does not go on — its error is exactly 0 and no
-			 * neighbour kept it — goes on like the others, so its half-sample frame moves too */
+			/* threshold 0 asks for the uniform frame: a live unit that does not go on — its error is exactly 0 (the same colour in every pass so far, which is not the
+			 * colour the running mean of more passes rounds to) and, for a cell, no neighbour kept it — goes on like the others, so its half-sample frame moves too */
 			bool any = false;
-			for (uint32_t k = 0; k < total; ++k) { still[k] = live[k] && !go[k]; any = any || still[k]; go[k] = live[k]; }
-			if (any && (rc = step(0.0f, true, still.data(), nullptr, nullptr))) return rc;
+			for (uint32_t k = 0; k < F.units; ++k) { still[k] = live[k] && !go[k]; any = any || still[k]; go[k] = live[k]; }
+			if (any && (rc = step(F, 0.0f, true, still.data(), nullptr, nullptr))) return rc;
 		}
 		bool any = false;
-		for (uint32_t k = 0; k < total; ++k) {
+		for (uint32_t k = 0; k < F.units; ++k) {
 			if (!live[k]) continue;
 			if (errors_host) errors_host[k] = err[k];
 			if (go[k] && !last) { any = true; continue; }
@@ -2448,26 +2429,22 @@ int crh_render_adaptive_cells(crh_ctx *c, const crh_render_params *P, const crh_
 			if (passes_host) passes_host[k] = n;
 		}
 		if (!any) break;
-		/* the live cells' pixels as maximal horizontal runs of live cells within one cell row of a rectangle: few, wide rectangles for the renderer */
-		list.clear();
-		for (uint32_t r = 0; r < tile_count; ++r) {
-			const crh_tile &t = tiles[r];
-			const int cx = (t.x1 - t.x0 + cell - 1) / cell, cy = (t.y1 - t.y0 + cell - 1) / cell;
-			for (int j = 0; j < cy; ++j) {
-				/* stored rows (H - y1) + j cell ..: in tile coordinates (y from the bottom) the cell row spans y1 - (j + 1) cell .. y1 - j cell, cut at y0 */
-				const int top = t.y1 - j * cell, bottom = std::max(t.y0, top - cell);
-				for (int i = 0; i < cx; ++i) {
-					if (!live[offsets[r] + (uint32_t)(j * cx + i)]) continue;
-					int e = i + 1;
-					while (e < cx && live[offsets[r] + (uint32_t)(j * cx + e)]) ++e;
-					list.push_back(crh_tile{t.x0 + i * cell, bottom, std::min(t.x1, t.x0 + e * cell), top});
-					i = e;
-				}
-			}
-		}
-		if ((rc = render(list, n, n))) return rc;
+		adLiveRects(F, live.data(), list);
+		if ((rc = render(n, n))) return rc;
 	}
 	return CRH_OK;
+}
+
+int crh_render_adaptive(crh_ctx *c, const crh_render_params *P, const crh_tile *tiles, uint32_t tile_count, const crh_adaptive_params *A, float *dev_fb, float *dev_half,
+                        int32_t *passes_host, float *errors_host) {
+	crh_adaptive_cells_params a{};
+	if (A) { a.min_passes = A->min_passes; a.threshold = A->threshold; }
+	return adLoop("crh_render_adaptive", false, c, P, tiles, tile_count, A ? &a : nullptr, dev_fb, dev_half, passes_host, errors_host);
+}
+
+int crh_render_adaptive_cells(crh_ctx *c, const crh_render_params *P, const crh_tile *tiles, uint32_t tile_count, const crh_adaptive_cells_params *A, float *dev_fb,
+                              float *dev_half, int32_t *passes_host, float *errors_host) {
+	return adLoop("crh_render_adaptive_cells", true, c, P, tiles, tile_count, A, dev_fb, dev_half, passes_host, errors_host);
 }
 
 /* ---- ID mattes: ranked instance and material coverage per pixel (idmatte.h) ------------------------------------------------------------------------------- */
@@ -2475,7 +2452,7 @@ int crh_ids_alloc(crh_ctx *c, int width, int height, uint32_t **dev_out) { retur
 int crh_ids_free(crh_ctx *c, uint32_t *dev_ids) { return pixelBufFree("crh_ids_free", c, dev_ids); }
 int crh_ids_clear(crh_ctx *c, uint32_t *dev_ids, int width, int height) { return pixelBufClear("crh_ids_clear", c, dev_ids, width, height, CRH_ID_WORDS * sizeof(uint32_t)); }
 int crh_ids_download(crh_ctx *c, const uint32_t *dev_ids, int width, int height, uint32_t *host_hw16) {
-	return pixelBufDownload("crh_ids_download", c, dev_ids, width, height, CRH_ID_WORDS * sizeof(uint32_t), host_hw16, c ? &c->idsTiles : nullptr);
+	return pixelBufDownload("crh_ids_download", c, dev_ids, width, height, CRH_ID_WORDS * sizeof(uint32_t), host_hw16, c ? &c->ids.tiles : nullptr);
 }
 
 int crh_render_ids(crh_ctx *c, const crh_render_params *P, const crh_tile *tiles, uint32_t tile_count, uint32_t *dev_instance_ids, uint32_t *dev_material_ids) {
@@ -2487,14 +2464,14 @@ int crh_render_ids(crh_ctx *c, const crh_render_params *P, const crh_tile *tiles
 	rc = checkRects("crh_render_ids", tiles, tile_count, P->image_width, P->image_height, false);
 	if (rc) return rc;
 	AovLaunch L;          /* k_ids has k_aov's work shape: the same units, the same grid */
-	if ((rc = aovLaunchBegin("crh_render_ids", c, P, tiles, tile_count, c->dIdsCounter, c->idsTiles, c->idsWatch, L)) || !L.grid) return rc;
+	if ((rc = aovLaunchBegin("crh_render_ids", c, P, tiles, tile_count, c->ids, L)) || !L.grid) return rc;
 	hipLaunchKernelGGL(k_ids, dim3(L.grid), dim3(CRH_BLOCK), 0, c->stream, c->d, *P, L.U, dev_instance_ids, dev_material_ids, c->sampler == CRH_SAMPLER_HALTON ? 1u : 0u,
 	                   (uint32_t)c->sched.rayFlags, c->dOvf.p);
-	return aovLaunchEnd("k_ids", c, c->dIdsCounter, c->idsTiles, c->idsWatch);
+	return aovLaunchEnd("k_ids", c, c->ids);
 }
 
 /* Duration of the most recent ID kernel — the dispatch's, the ranking's or the matte's (HIP events on the context's stream; waits for it); 0 before the first one. */
-int crh_ids_kernel_time_ms(crh_ctx *c, float *last_ms) { return watchTimeMs("crh_ids_kernel_time_ms", c, c ? &c->idsWatch : nullptr, last_ms); }
+int crh_ids_kernel_time_ms(crh_ctx *c, float *last_ms) { return watchTimeMs("crh_ids_kernel_time_ms", c, c ? &c->ids.watch : nullptr, last_ms); }
 
 /* What the two consumers share: one lane per pixel over the whole buffer, timed. The check and the stopwatch started ... */
 static int idsConsumeBegin(const char *who, crh_ctx *c, const uint32_t *dev_ids, int width, int height, const void *dev_out, uint64_t &pixels, dim3 &grid) {
@@ -2503,15 +2480,15 @@ static int idsConsumeBegin(const char *who, crh_ctx *c, const uint32_t *dev_ids,
 	if (rc) return rc;
 	pixels = (uint64_t)width * (uint64_t)height;
 	grid = dim3((uint32_t)((pixels + CRH_BLOCK - 1) / CRH_BLOCK));
-	return c->idsWatch.start(c->stream);
+	return c->ids.watch.start(c->stream);
 }
 /* ... and, behind the launch, the lap */
 static int idsConsumeEnd(const char *who, crh_ctx *c) {
 	const hipError_t e = hipGetLastError();
-	const int rc = c->idsWatch.mark(c->stream);
+	const int rc = c->ids.watch.mark(c->stream);
 	if (rc) return rc;
 	if (e != hipSuccess) return fail(CRH_ERR_HIP, std::string(who) + " launch: " + hipGetErrorString(e));
-	c->idsWatch.stop();
+	c->ids.watch.stop();
 	return CRH_OK;
 }
 

@@ -9,7 +9,7 @@
  * HitInfo::material, what crh_trace_rays reports as crh_hit.inst and crh_hit.material — or CRH_IDS_MISS twice. idFold below is the fold rule, word for word the header's:
  * nothing but integer compares, selects and adds, so every word of the buffer is predictable, and consecutive pass ranges compose bit for bit.
  *
- * Shape. k_aov's, and for its reason: a wave pulls units of pixel groups from one counter; per chunk of up to 64 passes lane l walks pixel l / chunk, pass l % chunk and
+ * Shape. k_aov's, and for its reason — the loop itself is k_aov's, firstHitWaves in aov.h; IdsKernel below is what k_ids brings to it: a wave pulls units of pixel groups from one counter; per chunk of up to 64 passes lane l walks pixel l / chunk, pass l % chunk and
  * leaves its two words in words 0 and 1 of its LDS column (AovStack: the walk's entries are dead by then); lane p then folds pixel p's samples in pass order. The chunks
  * of a pixel are folded by the same lane of the same wave one after the other, and a pixel belongs to one group of one unit: no atomics. The folding lane holds ONE
  * record — 14 words — in named registers (three 16-byte accesses and one of 8 bytes each way: the reserved words are neither read nor written). A group of up to 32
@@ -105,6 +105,38 @@ __device__ __forceinline__ float getDimension(IdsRng &r) {
 	return v;
 }
 
+/* k_ids' sample: the two ids; of a miss, CRH_IDS_MISS twice */
+struct IdsSample {
+	uint32_t inst = CRH_IDS_MISS, mat = CRH_IDS_MISS;
+	__device__ __forceinline__ void put(AovStack &stk) const { stk.put(0, inst); stk.put(1, mat); }
+};
+/* what k_ids brings to the wave loop (aov.h: firstHitWaves); either buffer may be null */
+struct IdsKernel {
+	typedef IdsRng Rng;
+	typedef IdsSample Sample;
+	static constexpr bool rare = true;
+	uint32_t *idsInst, *idsMat;
+	uint32_t halton;
+	__device__ __forceinline__ void seed(IdsRng &r) const { r.halton = halton; }
+	/* a group of up to 32 pixels (two passes or more) is folded by both halves of the wave at once — lane p the instance record of pixel p, lane 32 + p its material
+	 * record —, a larger one by lane p for both buffers, one after the other */
+	__device__ __forceinline__ uint32_t foldLane(uint32_t lane, uint32_t npix) const { return npix <= 32u ? (lane & 31u) : lane; }
+	/* a surface, or a scattering event inside a volume: the instance's index in the scene description and the record's material */
+	template <class LP, class Cnt>
+	__device__ __forceinline__ void hit(const DScene &S, LP &lp, const Walk &w, AovStack &stk, Cnt &, IdsSample &s) const {
+		s.inst = S.instances[w.hit.inst].orig;
+		s.mat = finishHit<true, true>(S, lp.ro, lp.rd, w.hit, stk).material;
+	}
+	__device__ __forceinline__ void fold(size_t pixel, const lds_u32 *col, uint32_t pc, int, uint32_t lane, uint32_t npix) const {
+		const bool halves = npix <= 32u;
+		uint32_t b = halves ? lane >> 5 : 0u;                 /* 0: the instance buffer and word 0 of the columns, 1: the material buffer and word 1 */
+		for (const uint32_t bEnd = halves ? b + 1u : 2u; b < bEnd; ++b) {          /* (one record live at a time) */
+			uint32_t *const buf = b ? idsMat : idsInst;
+			if (buf) idFoldPixel(buf + pixel * (size_t)CRH_ID_WORDS, col + b * CRH_BLOCK, pc);
+		}
+	}
+};
+
 /* halton: the sampler (CRH_SAMPLER_HALTON). idsInst / idsMat: the two buffers, either may be null (crh_render_ids). The walk is the rare-features one (volumes) for
  * every scene. */
 __global__ __launch_bounds__(CRH_BLOCK, CRH_IDS_WPS) void k_ids(const DScene Sarg, const crh_render_params P, const AovUnits U, uint32_t *idsInstArg, uint32_t *idsMatArg,
@@ -112,79 +144,8 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_IDS_WPS) void k_ids(const DScene Sar
 	__shared__ uint32_t s_lane[CRH_AOV_LANE_WORDS * CRH_BLOCK];
 	__shared__ __attribute__((aligned(16))) uint32_t s_inst0[CRH_AOV_INST_LDS ? CRH_INST_LDS0_MAX * 16u : 4u];
 	const DScene S = globalize(Sarg);
-	const crh_tile *const tiles = asGlobal(U.tiles);
-	const uint32_t *const start = asGlobal(U.start);
-	uint32_t *const idsInst = (uint32_t *)(__attribute__((address_space(1))) uint32_t *)idsInstArg;
-	uint32_t *const idsMat = (uint32_t *)(__attribute__((address_space(1))) uint32_t *)idsMatArg;
-	const uint32_t lane = threadIdx.x & 63u;
-	const uint32_t wave = (blockIdx.x * CRH_BLOCK + threadIdx.x) >> 6;
-	AovStack stk;
-	stk.col = (lds_u32 *)&s_lane[threadIdx.x];
-	stk.ovf = (glb_u32 *)ovfAll + (size_t)__builtin_amdgcn_readfirstlane(wave) * CRH_OVF_WORDS_PER_WAVE;
-	stk.inst0 = CRH_AOV_INST_LDS ? stageInstLine0(S, s_inst0) : nullptr;          /* (walk_machine.h) */
-	const lds_u32 *const waveCols = (const lds_u32 *)&s_lane[threadIdx.x & ~63u];          /* column of lane l of this wave: waveCols + l */
-	const int passEnd = P.first_pass + P.pass_count;
-	for (;;) {
-		uint32_t u = 0;
-		if (lane == 0) u = atomicAdd((uint32_t *)(__attribute__((address_space(1))) uint32_t *)U.counter, 1u);
-		u = __builtin_amdgcn_readfirstlane(u);
-		if (u >= U.total) break;
-		uint32_t lo = 0, hi = U.ntiles;          /* (wave-uniform) the tile of unit u */
-		while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (start[mid] <= u) lo = mid; else hi = mid; }
-		const crh_tile t = tiles[lo];
-		const uint32_t tw = (uint32_t)(t.x1 - t.x0), tilePixels = tw * (uint32_t)(t.y1 - t.y0);
-		for (uint32_t gi = 0; gi < U.groups; ++gi) {
-		const uint32_t first = ((u - start[lo]) * U.groups + gi) * U.group;                     /* the group's first pixel, counted inside the tile */
-		if (first >= tilePixels) break;
-		const uint32_t npix = min(U.group, tilePixels - first);
-		/* the pixel this lane FOLDS, and into which buffer: a group of up to 32 pixels (two passes or more) is folded by both halves of the wave at once — lane p the
-		 * instance record of pixel p, lane 32 + p its material record —, a larger one by lane p for both buffers, one after the other */
-		const bool halves = npix <= 32u;
-		const uint32_t fl = halves ? (lane & 31u) : lane;
-		const uint32_t fIdx = first + min(fl, npix - 1u);
-		const int fx = t.x0 + (int)(fIdx % tw), fy = t.y0 + (int)(fIdx / tw);
-		const size_t fWord = ((size_t)fx + (size_t)(P.image_height - (fy + 1)) * (size_t)P.image_width) * (size_t)CRH_ID_WORDS;
-		for (int p0 = P.first_pass; p0 < passEnd; p0 += 64) {
-			const uint32_t pc = (uint32_t)min(64, passEnd - p0);
-			const uint32_t pj = lane / pc;                                                      /* pixel-major: the passes of a pixel in neighbouring lanes */
-			uint32_t sInst = CRH_IDS_MISS, sMat = CRH_IDS_MISS;
-			if (pj < npix) {
-				const uint32_t idx = first + pj;
-				const int x = t.x0 + (int)(idx % tw), y = t.y0 + (int)(idx / tw), pass = p0 + (int)(lane - pj * pc);
-				AovCounters<true> cnt;
-				LanePathT<IdsRng> lp;
-				memset(&lp, 0, sizeof(lp));
-				lp.r.rng.halton = halton;
-				beginPath(S, P, x, y, pass, lp.ro, lp.rd, lp.r, cnt);
-				auto port = lanePort(lp);
-				Walk w;
-				walkBegin(S, w, stk, lp.ro, lp.rd, cnt, port, rayFlags);
-				while (w.phase != PH_SHADE) {          /* traverse() with the path's port */
-					if (w.phase == PH_NODE) stepNodeAny<true>(S, w, stk, cnt, port);
-					else if (w.phase == PH_NODE_SLOW) stepNodeAny<false>(S, w, stk, cnt, port);
-					else if (w.phase == PH_TRI) stepTri(S, w, stk, cnt, port);
-					else stepCtrl(S, w, stk, cnt, port);
-				}
-				if (w.hit.inst >= 0) {          /* a surface, or a scattering event inside a volume: the instance's index in the scene description and the record's material */
-					sInst = S.instances[w.hit.inst].orig;
-					sMat = finishHit<true, true>(S, lp.ro, lp.rd, w.hit, stk).material;
-				}
-			}
-			stk.put(0, sInst); stk.put(1, sMat);
-			__threadfence_block();                 /* the samples of all lanes are visible to the folding lanes */
-			CRH_LOCKSTEP();
-			if (fl < npix) {
-				uint32_t b = halves ? lane >> 5 : 0u;                 /* 0: the instance buffer and word 0 of the columns, 1: the material buffer and word 1 */
-				for (const uint32_t bEnd = halves ? b + 1u : 2u; b < bEnd; ++b) {          /* (one record live at a time) */
-					uint32_t *const buf = b ? idsMat : idsInst;
-					if (buf) idFoldPixel(buf + fWord, waveCols + fl * pc + b * CRH_BLOCK, pc);
-				}
-			}
-			__threadfence_block();                 /* ... and read before the next chunk's walks overwrite them */
-			CRH_LOCKSTEP();
-		}
-		}
-	}
+	AovStack stk = aovStack(S, s_lane, s_inst0, ovfAll);
+	firstHitWaves(S, P, U, rayFlags, stk, IdsKernel{(uint32_t *)(__attribute__((address_space(1))) uint32_t *)idsInstArg, (uint32_t *)(__attribute__((address_space(1))) uint32_t *)idsMatArg, halton});
 }
 
 /* ---- the consumers: one pixel per lane, no scene --------------------------------------------------------------------------------------------------------------- */

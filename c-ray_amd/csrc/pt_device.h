@@ -1300,18 +1300,24 @@ CRH_DEV void stepCtrl(const DScene &S, Walk &w, Stack &stk, Cnt &cnt, Port &port
 	walkAdvance(S, w, stk, cnt, port);
 }
 
-/* The whole walk for one lane (k_trace_rays, host emulation): run steps until the walk hands over to shading. */
-template <class Stack, class Cnt>
-CRH_DEV void traverse(const DScene &S, Stack &stk, const v3 rayO, const v3 rayD, TravHit &hit, Cnt &cnt, uint32_t rayFlags = 0u) {
-	Walk w;
-	NullPort port;                    /* caller rays have no path: scenes with volumes are refused before this runs */
-	walkBegin(S, w, stk, rayO, rayD, cnt, port, rayFlags);
+/* One lane's walk from walkBegin to the end: run steps until the walk hands over to shading (traverse below; the first-hit kernels, with a path's port). */
+template <class Stack, class Cnt, class Port>
+CRH_DEV void walkToShade(const DScene &S, Walk &w, Stack &stk, Cnt &cnt, Port &port) {
 	while (w.phase != PH_SHADE) {
 		if (w.phase == PH_NODE) stepNodeAny<true>(S, w, stk, cnt, port);
 		else if (w.phase == PH_NODE_SLOW) stepNodeAny<false>(S, w, stk, cnt, port);
 		else if (w.phase == PH_TRI) stepTri(S, w, stk, cnt, port);
 		else stepCtrl(S, w, stk, cnt, port);
 	}
+}
+
+/* The whole walk for one lane (k_trace_rays, host emulation). */
+template <class Stack, class Cnt>
+CRH_DEV void traverse(const DScene &S, Stack &stk, const v3 rayO, const v3 rayD, TravHit &hit, Cnt &cnt, uint32_t rayFlags = 0u) {
+	Walk w;
+	NullPort port;                    /* caller rays have no path: scenes with volumes are refused before this runs */
+	walkBegin(S, w, stk, rayO, rayD, cnt, port, rayFlags);
+	walkToShade(S, w, stk, cnt, port);
 	hit = w.hit;
 }
 
