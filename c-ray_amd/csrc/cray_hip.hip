@@ -84,6 +84,40 @@ using namespace crh;
 #ifndef CRH_LOCKSTEP
 #define CRH_LOCKSTEP() do { } while (0)
 #endif
+/* Round 10 (profiles/r10_step_costs.log): the same steps with the same lanes, each step cheaper — with all three switches at 0 the kernels' machine code is the parent's, but for
+ * the offsets of the kernel arguments behind DScene, which is one pointer longer. Each was measured alone and combined (cfg2, interleaved bench.py runs, full builds): the merged
+ * advance alone +0.8...1.1 %; the other two nothing alone or paired with it, all three +1.3...1.5 % — kept together.
+ *   CRH_MERGED_ADVANCE    1: the node run of k_pathtrace_roll tests its node lanes and its triangle lanes under their masks (pt_device.h: stepNodeTest, stepTriTest) and
+ *                         calls walkAdvance once for both, instead of once behind each step
+ *   CRH_WAVE_SCOPE_FENCE  1: the per-wave steps of k_pathtrace_roll end in a wavefront-scope fence (CRH_WAVE_FENCE below)
+ *   CRH_STEP_ARGS         1: the SHADE and MISS steps of k_pathtrace_roll, and its staging of the shade tables, read the shading tables' addresses and counts from the
+ *                         scene's record in memory (shadeScene below) instead of from kernel arguments */
+#ifndef CRH_MERGED_ADVANCE
+#define CRH_MERGED_ADVANCE 1
+#endif
+#ifndef CRH_STEP_ARGS
+#define CRH_STEP_ARGS 1
+#endif
+/* CRH_WAVE_FENCE(): the end of a step of k_pathtrace_roll that one wave runs on data only that wave touches — its LDS words (wq, ids, hits), its path table,
+ * its sample slabs and overflow columns (all indexed by readfirstlane(wave)), the chunks of the unit it owns. What one lane wrote another lane of the SAME wave
+ * reads in a later step, and wavefront scope orders exactly that:
+ *   - a wave's LDS operations execute in program order;
+ *   - a wave's vector memory instructions reach the L1 in program order, and a load behind a store to the same address returns the stored value;
+ *   - the AMDGPU backend's memory model therefore emits no wait for a wavefront-scope fence: it is a compiler barrier. (__threadfence_block(), which stood here,
+ *     is `s_waitcnt lgkmcnt(0)` on gfx950 — the waves of a workgroup share an L1, so workgroup scope asks for no vmcnt wait either: what goes is a wait for the
+ *     wave's own LDS stores at eight sites, not an L2 acknowledgement. Measured: nothing alone, +0.5 % together with CRH_STEP_ARGS on top of CRH_MERGED_ADVANCE.)
+ * CRH_WAVE_SCOPE_FENCE=0 gives the workgroup-scope fence back (the parent's machine code, tools/kernel_same_code.py).
+ * What stays at workgroup scope, because a BLOCK shares it: s_cls (pathtrace_roll.h), the shade tables (CRH_STAGE_SHADE_TABLES), the instance tables
+ * (CRH_STAGE_INSTANCE_TABLES) and powf's tables (CRH_EM_POW_TABLES_INIT), each written by all threads in front of its __syncthreads(); and every fence of
+ * pathtrace_alt.h, whose workgroup form shares the path table and the fill levels between waves. */
+#ifndef CRH_WAVE_SCOPE_FENCE
+#define CRH_WAVE_SCOPE_FENCE 1
+#endif
+#if CRH_WAVE_SCOPE_FENCE
+#define CRH_WAVE_FENCE() __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront")
+#else
+#define CRH_WAVE_FENCE() __threadfence_block()
+#endif
 
 /* ---- error plumbing ---------------------------------------------------------------------------- */
 static thread_local std::string t_err;
@@ -239,6 +273,22 @@ __device__ __forceinline__ DScene globalize(const DScene &S) {
 	G.textures = asGlobal(S.textures); G.texels = asGlobal(S.texels);
 	G.camera = (const crh_camera *)(const __attribute__((address_space(4))) crh_camera *)S.camera;          /* constant address space: uniform scalar loads */
 	return G;
+}
+/* The scene as a SHADE or MISS step of k_pathtrace_roll sees it (round 10, CRH_STEP_ARGS): the shading tables' addresses and counts come from the scene's record in
+ * memory (DShadeArgs, constant address space: scalar loads where the step runs), so that the kernel's own copy of them — 22 words of kernel argument — is dead and no
+ * scalar register holds, or spills, one of them across the walk steps. The values are the arguments' own. */
+__device__ __forceinline__ DScene shadeScene(const DScene &S) {
+#if CRH_STEP_ARGS
+	const __attribute__((address_space(4))) DShadeArgs *a = (const __attribute__((address_space(4))) DShadeArgs *)S.shadeArgs;
+	DScene G = S;
+	G.shade = asGlobal(a->shade); G.materials = asGlobal(a->materials); G.bsdfs = asGlobal(a->bsdfs); G.consts = asGlobal(a->consts); G.images = asGlobal(a->images);
+	G.prog = asGlobal(a->prog); G.textures = asGlobal(a->textures); G.texels = asGlobal(a->texels);
+	G.background = a->background; G.image_count = a->image_count; G.texture_count = a->texture_count;
+	G.material_count = a->material_count; G.bsdf_count = a->bsdf_count; G.const_count = a->const_count;
+	return G;
+#else
+	return S;
+#endif
 }
 
 __device__ __forceinline__ uint32_t waveSum(uint32_t v) {
@@ -423,22 +473,24 @@ __device__ __forceinline__ uint32_t laneRank(unsigned long long m) {
 
 /* The workgroup's copies of the hot records (k_pathtrace and k_pathtrace_roll; `S` and `stk` of the calling kernel) */
 #if CRH_SHADE_LDS
-#define CRH_STAGE_SHADE_TABLES() \
+#define CRH_STAGE_SHADE_TABLES() CRH_STAGE_SHADE_TABLES_OF(S)
+#define CRH_STAGE_SHADE_TABLES_OF(SCENE) \
 	__shared__ __attribute__((aligned(16))) uint32_t s_shade[CRH_SHADE_LDS_BYTES / 4u]; \
 	stk.shadeTab = nullptr; \
-	if (S.material_count <= CRH_SHADE_LDS_MATERIALS && S.bsdf_count <= CRH_SHADE_LDS_BSDFS && S.const_count <= CRH_SHADE_LDS_CONSTS && \
-		S.image_count <= CRH_SHADE_LDS_IMAGES && S.texture_count <= CRH_SHADE_LDS_IMAGES) { \
+	if ((SCENE).material_count <= CRH_SHADE_LDS_MATERIALS && (SCENE).bsdf_count <= CRH_SHADE_LDS_BSDFS && (SCENE).const_count <= CRH_SHADE_LDS_CONSTS && \
+		(SCENE).image_count <= CRH_SHADE_LDS_IMAGES && (SCENE).texture_count <= CRH_SHADE_LDS_IMAGES) { \
 		const uint32_t texBase = CRH_SHADE_LDS_MATERIALS * 8u + CRH_SHADE_LDS_BSDFS * 4u + CRH_SHADE_LDS_CONSTS * 4u; \
-		for (uint32_t i = threadIdx.x; i < S.texture_count * 8u; i += CRH_BLOCK) s_shade[texBase + i] = ((const uint32_t *)S.textures)[i]; \
-		for (uint32_t i = threadIdx.x; i < S.image_count * 2u; i += CRH_BLOCK) s_shade[texBase + CRH_SHADE_LDS_IMAGES * 8u + i] = ((const uint32_t *)S.images)[i]; \
-		for (uint32_t i = threadIdx.x; i < S.material_count * 8u; i += CRH_BLOCK) s_shade[i] = ((const uint32_t *)S.materials)[i]; \
-		for (uint32_t i = threadIdx.x; i < S.bsdf_count * 4u; i += CRH_BLOCK) s_shade[CRH_SHADE_LDS_MATERIALS * 8u + i] = ((const uint32_t *)S.bsdfs)[i]; \
-		for (uint32_t i = threadIdx.x; i < S.const_count * 4u; i += CRH_BLOCK) s_shade[CRH_SHADE_LDS_MATERIALS * 8u + CRH_SHADE_LDS_BSDFS * 4u + i] = ((const uint32_t *)S.consts)[i]; \
+		for (uint32_t i = threadIdx.x; i < (SCENE).texture_count * 8u; i += CRH_BLOCK) s_shade[texBase + i] = ((const uint32_t *)(SCENE).textures)[i]; \
+		for (uint32_t i = threadIdx.x; i < (SCENE).image_count * 2u; i += CRH_BLOCK) s_shade[texBase + CRH_SHADE_LDS_IMAGES * 8u + i] = ((const uint32_t *)(SCENE).images)[i]; \
+		for (uint32_t i = threadIdx.x; i < (SCENE).material_count * 8u; i += CRH_BLOCK) s_shade[i] = ((const uint32_t *)(SCENE).materials)[i]; \
+		for (uint32_t i = threadIdx.x; i < (SCENE).bsdf_count * 4u; i += CRH_BLOCK) s_shade[CRH_SHADE_LDS_MATERIALS * 8u + i] = ((const uint32_t *)(SCENE).bsdfs)[i]; \
+		for (uint32_t i = threadIdx.x; i < (SCENE).const_count * 4u; i += CRH_BLOCK) s_shade[CRH_SHADE_LDS_MATERIALS * 8u + CRH_SHADE_LDS_BSDFS * 4u + i] = ((const uint32_t *)(SCENE).consts)[i]; \
 		__syncthreads(); \
 		stk.shadeTab = (const lds_u32 *)s_shade; \
 	}
 #else
 #define CRH_STAGE_SHADE_TABLES() do { } while (0)
+#define CRH_STAGE_SHADE_TABLES_OF(SCENE) do { } while (0)
 #endif
 #if CRH_INST_LDS_BYTES > 0
 #define CRH_STAGE_INSTANCE_TABLES() \
@@ -659,6 +711,7 @@ struct crh_ctx {
 	bool hasPrograms = true;     /* the compiled scene contains node programs -> kernel variant with runProgram() */
 	bool hasVolumes = false;     /* walks draw from the path's sampler: crh_trace_rays (caller rays, no path) refuses such scenes */
 	DScene d;                              /* device pointers */
+	DShadeArgs *dNoShadeArgs = nullptr;    /* an all-zero shade-args record: what DScene::shadeArgs names while no scene is resident (the kernel preload of a context without one) */
 	int walk = CRH_WALK_BINARY;            /* CRH_OPT_WALK: what the NEXT upload prepares and the render kernel walks */
 	bool haveWide = false;                 /* the resident scene has a wide copy of its BVHs (behind the triangles, in the nodes' allocation) */
 	uint32_t wideTlasRoot = 0;             /* ... whose top-level root is this reference (scenes with more than one top-level node) */
@@ -715,6 +768,7 @@ static void freeScene(crh_ctx *c) {
 	for (void *p : c->sceneAllocs) (void)hipFree(p);
 	c->sceneAllocs.clear();
 	c->haveScene = false;
+	c->d = DScene{};          /* (nothing names the freed arrays: a kernel preload without a scene sees empty tables) */
 }
 
 static int resolveTimes(crh_ctx *c, bool wait) {
@@ -840,6 +894,7 @@ static hipError_t launchPathtrace(crh_ctx *c, uint32_t grid, const crh_render_pa
 		const bool wide = wideWalk(c);
 		DScene d = c->d;
 		if (wide && d.tlas_node_count > 1u) d.tlas_root = c->wideTlasRoot;
+		if (!d.shadeArgs) d.shadeArgs = c->dNoShadeArgs;          /* (no scene yet: the kernel reads the record's counts whatever the work queue holds) */
 		if (const auto *r = pickRow(kRollRows, level, c->hasPrograms, samp, wide ? 1 : 0)) {
 			name = r->name;
 			hipLaunchKernelGGL((r->fn), dim3(grid), dim3(CRH_BLOCK), 0, c->stream, d, *P, Q, dev_fb, c->dCounters, c->dStage.p, chunk, c->dWaveStats, c->sched, c->dQueues.p, c->dOvf.p, c->dErr);
@@ -951,6 +1006,8 @@ int crh_context_create(int device, void *stream, crh_ctx **out) {
 	if (e == hipSuccess) e = hipMemset(c->dCounters, 0, CRH_COUNTER_BYTES(c->cuCount));
 	if (e == hipSuccess) e = hipMalloc((void **)&c->dWork, CRH_WORK_SLOTS * sizeof(uint32_t));
 	if (e == hipSuccess) e = hipMemset(c->dWork, 0, CRH_WORK_SLOTS * sizeof(uint32_t));      /* a work counter is zero whenever a dispatch takes it: crh_render_tiles resets it BEHIND the kernel */
+	if (e == hipSuccess) e = hipMalloc((void **)&c->dNoShadeArgs, sizeof(DShadeArgs));
+	if (e == hipSuccess) e = hipMemset(c->dNoShadeArgs, 0, sizeof(DShadeArgs));
 	if (e == hipSuccess) e = hipHostMalloc((void **)&c->hErr, sizeof(unsigned int), hipHostMallocDefault);
 	if (e == hipSuccess) { *c->hErr = 0u; e = hipHostGetDevicePointer((void **)&c->dErr, c->hErr, 0); }
 	if (e != hipSuccess) {
@@ -996,7 +1053,7 @@ int crh_context_destroy(crh_ctx *c) {
 	for (const TimedPair &t : c->pendingTimes) c->eventPool.give(t);
 	c->pendingTimes.clear();
 	c->eventPool.release();
-	drop(c->dCounters); drop(c->dWork);
+	drop(c->dCounters); drop(c->dWork); drop(c->dNoShadeArgs);
 	c->dStage.release(); c->dDefer.release(); c->dQueues.release(); c->dOvf.release();
 	for (SideDispatch *s : {&c->aov, &c->ids}) { drop(s->counter); s->tiles.release(); s->watch.release(); }
 	c->dPack.release(); c->packWatch.release();
@@ -1179,6 +1236,12 @@ static int uploadCompiled(crh_ctx *c, const CompiledScene &cs, const int32_t *pr
 	d.tlas_root = cs.tlas_root; d.tlas_node_count = cs.tlas_node_count; d.tlas_prim_base = cs.tlas_prim_base; d.shade_classes = cs.shade_classes; d.instance_count = (uint32_t)cs.instances.size();
 	d.background = cs.background;
 	{ const crh_camera *cam = nullptr; rc = upload(c, &cs.camera, 1, &cam); if (rc) { freeScene(c); return rc; } d.camera = cam; }
+	{
+		const DShadeArgs sa{d.shade, d.materials, d.bsdfs, d.consts, d.images, d.prog, d.textures, d.texels, d.background, d.image_count, d.texture_count, d.material_count, d.bsdf_count, d.const_count};
+		const DShadeArgs *dev = nullptr;
+		rc = upload(c, &sa, 1, &dev); if (rc) { freeScene(c); return rc; }
+		d.shadeArgs = dev;
+	}
 	c->d = d;
 	c->haveWide = !cs.wide.empty(); c->wideTlasRoot = cs.wide_tlas_root;
 	if (cs.want_wide && !c->haveWide && !cs.wide_refused.empty())          /* (not only under CRH_TRACE_UPLOAD — the frame would silently be the binary walk's) */

@@ -76,7 +76,8 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 	LdsStack stk;
 	stk.lds = (lds_u32 *)&s_stack[threadIdx.x];
 	stk.parkp = (lds_u32 *)&s_park[threadIdx.x];
-	CRH_STAGE_SHADE_TABLES();
+	const DScene Sstage = shadeScene(S);          /* (the counts are tested and the tables copied once, here: the record's words are dead behind it) */
+	CRH_STAGE_SHADE_TABLES_OF(Sstage);
 	CRH_STAGE_INSTANCE_TABLES();
 	CountersT<LEVEL, PROG, WIDE> cnt;
 	memset(&cnt, 0, sizeof(cnt));
@@ -94,6 +95,7 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 	const int passEnd = P.first_pass + P.pass_count;
 	const uint32_t trisOff = (uint32_t)((const char *)S.tris - (const char *)S.nodes);          /* (one allocation: crh_scene_upload) */
 	constexpr bool LEANTAB = CRH_PATH_LEAN && !PROG;
+	constexpr bool MERGED_ADVANCE = CRH_MERGED_ADVANCE != 0;
 	/* round 8 (PathTab::loadRec4 / storeRec4; the lean instantiations only): SHADE, GEN and MISS move a path's 64-B record quad-cooperatively, and a finished miss leaves no hit part */
 	constexpr bool COOP_LOAD = LEANTAB && CRH_REC_COOP_LOAD == 1, COOP_LOAD_MISS = LEANTAB && CRH_REC_COOP_LOAD >= 1 /* (2: ST_MISS alone) */, COOP_STORE = LEANTAB && CRH_REC_COOP_STORE, MISS_SKIP_HIT = LEANTAB && CRH_MISS_SKIP_HIT;
 	const PathTab<LEANTAB> tab{(f4 *)(queues + (size_t)__builtin_amdgcn_readfirstlane(wave) * CRH_WAVE_QUEUE_FLOATS)};          /* (the path's words: PathTab) */
@@ -160,7 +162,7 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 		refreshJobWords();
 	}
 	for (uint32_t i = lane; i < CRH_PATHS; i += 64u) ids[i] = (uint8_t)i;              /* all slots free */
-	__threadfence_block();
+	CRH_WAVE_FENCE();
 	Walk w;
 	memset(&w, 0, sizeof(w));
 	w.phase = PH_IDLE;
@@ -228,7 +230,7 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 		if constexpr (LEVEL >= 2) dumpCount += (uint32_t)take;
 		hq += (int)__popcll(hm); mq += (int)__popcll(mm); rq -= take;
 		if (lane == 0) { wq[RQ_HITS] = hq; wq[RQ_MISSES] = mq; wq[RQ_RAYS] = rq; }
-		__threadfence_block();
+		CRH_WAVE_FENCE();
 	};
 	uint32_t guard = (uint32_t)K.roundLimit;
 	for (;;) {
@@ -328,9 +330,16 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 						if (WIDE && isN) { q6 = *(const f4 *)(rec + 96); q7 = *(const f4 *)(rec + 112); }
 					}
 					if constexpr (WIDE) { if (isN) stepWideLoaded<true>(S, w, stk, cnt, port, q0, q1, q2, q3, q4, q5, q6, q7); }
-					else
+					else if constexpr (MERGED_ADVANCE) {
+						/* one advance site for both kinds of lane (round 10): the tests run under their masks, then every lane that took either step advances — the BLAS-leave
+						 * block and the pop once per iteration instead of once behind each step. walkAdvance reads only the lane's own walk, so a lane ends the iteration
+						 * in the state the unsplit steps leave it in, and the control check below sees the phases it always saw */
+						if (isN) stepNodeTest<true>(w, stk, cnt, q0, q1, q2, q3);
+						if (isT) stepTriTest(w, cnt, q0, q1, q2, q3, q4, q5);
+						if (isN || isT) walkAdvance(S, w, stk, cnt, port);
+					} else
 					if (isN) stepNodeLoaded<true>(S, w, stk, cnt, port, q0, q1, q2, q3);
-					if (isT) stepTriLoaded(S, w, stk, cnt, port, q0, q1, q2, q3, q4, q5);
+					if constexpr (WIDE || !MERGED_ADVANCE) { if (isT) stepTriLoaded(S, w, stk, cnt, port, q0, q1, q2, q3, q4, q5); }
 					if ((int)__popcll(__ballot(w.phase == PH_CTRL)) >= K.ctrlInRun) {
 #ifdef CRH_CENSUS
 						if constexpr (LEVEL >= 2) { const uint32_t n2 = (uint32_t)__popcll(__ballot(w.phase == PH_CTRL)); if (lane == 0) { CRH_WCTR(28, 1); CRH_WCTR(29, n2); } }
@@ -432,7 +441,7 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 #endif
 					refreshJobWords();
 				}
-				__threadfence_block();
+				CRH_WAVE_FENCE();
 				break;
 			}
 			case ST_GEN: {
@@ -473,7 +482,7 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 					j[SJ_NEXT] = (int)(genNext + 64u); j[SJ_OUT] = j[SJ_OUT] + n;
 					refreshJobWords();
 				}
-				__threadfence_block();
+				CRH_WAVE_FENCE();
 				break;
 			}
 			case ST_MISS: {
@@ -497,7 +506,7 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 					mySlot = (int)(item >> CRH_ROLL_SLOT_SHIFT);
 					TravHit h;
 					h.t = MISS_SKIP_HIT ? 0.0f : tab.hit(id)->x; h.u = h.v = 0.0f; h.slot = -1; h.inst = -1;          /* (ShadeRec::distance of a miss: read by node programs only) */
-					(void)shadeCore(S, P, ro, rd, h, r, cnt, stk);
+					(void)shadeCore(shadeScene(S), P, ro, rd, h, r, cnt, stk);
 					float *so = sampleSlot(mySlot, item & CRH_ROLL_ITEM_MASK); so[0] = r.fr; so[1] = r.fg; so[2] = r.fb;
 					ids[CRH_IDS_FREE_END - 1u - (uint32_t)freeQ - lane] = (uint8_t)id;
 				}
@@ -510,21 +519,21 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 					for (int s = 0; s < NS; ++s) if (fin[s]) wq[RQ_SLOT0 + s * SJ_WORDS + SJ_OUT] = wq[RQ_SLOT0 + s * SJ_WORDS + SJ_OUT] - fin[s];
 					refreshJobWords();
 				}
-				__threadfence_block();
+				CRH_WAVE_FENCE();
 				break;
 			}
 			case ST_FOLD: {          /* the older job is complete: its samples go into the frame in pass order; its slot is free again */
 				const int o = wq[RQ_HEAD], open = wq[RQ_OPEN];
 				const BlockJob J = loadJob(o);
-				__threadfence_block();                 /* the staged samples of all lanes are visible to the folding lanes */
+				CRH_WAVE_FENCE();                 /* the staged samples of all lanes are visible to the folding lanes */
 				const float *slab = myStage + (size_t)o * slabFloats;
 				if (!jobDeferred(o)) {          /* (a pass segment's samples are folded behind the kernel) */
 					for (uint32_t pix = lane; pix < (uint32_t)(J.bw * J.bh); pix += 64u) foldBlockPixel(P, J, pix, slab, fb);
 				}
-				__threadfence_block();                 /* ... and read before a later job overwrites them */
+				CRH_WAVE_FENCE();                 /* ... and read before a later job overwrites them */
 				CRH_LOCKSTEP();          /* every lane has read the ring's words */
 				if (lane == 0) { wq[RQ_HEAD] = (o + 1) % NS; wq[RQ_OPEN] = open - 1; refreshJobWords(); }
-				__threadfence_block();
+				CRH_WAVE_FENCE();
 				break;
 			}
 			default: {   /* ST_SHADE */
@@ -609,7 +618,7 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 					h.t = q4.x; h.u = q4.y; h.v = q4.z;
 					h.slot = (int32_t)asU32(q4.w); h.inst = (int32_t)asU32(*tab.inst(id));
 					__builtin_assume(h.inst >= 0);
-					cont = shadeCore(S, P, ro, rd, h, r, cnt, stk);
+					cont = shadeCore(shadeScene(S), P, ro, rd, h, r, cnt, stk);
 					done = !cont;
 					if constexpr (COOP_STORE) packPathRay(q0, q1, q2, q3, ro, rd, r, item);          /* (of an ending path too: words nobody stores, and no select) */
 					else if (cont) putPathRay(q, ro, rd, r, item);
@@ -633,7 +642,7 @@ __global__ __launch_bounds__(CRH_BLOCK, CRH_WPS_OVERRIDE) void k_pathtrace_roll(
 					for (int s = 0; s < NS; ++s) if (fin[s]) wq[RQ_SLOT0 + s * SJ_WORDS + SJ_OUT] = wq[RQ_SLOT0 + s * SJ_WORDS + SJ_OUT] - fin[s];
 					if (nd) refreshJobWords();
 				}
-				__threadfence_block();
+				CRH_WAVE_FENCE();
 				break;
 			}
 		}

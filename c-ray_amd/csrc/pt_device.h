@@ -142,6 +142,20 @@ struct DScene {
 	uint32_t tlas_first;        /* device index of the first TLAS node after the root (the TLAS nodes tlas_first .. tlas_first + tlas_node_count - 2 are contiguous) */
 	const crh_camera *camera;   /* (a record in memory rather than 26 words of kernel argument: only path generation reads it — scalar loads when a GEN step runs instead of scalar
 	                             * registers that live, and spill, across the whole machine) */
+	const struct DShadeArgs *shadeArgs;          /* (round 10: what only shading reads, once more, as a record in memory: the rolling kernel's SHADE and MISS steps take it from there) */
+};
+/* The shading tables of a DScene, as crh_scene_upload leaves them in device memory (DScene::shadeArgs): 22 words that k_pathtrace_roll reads with scalar loads where a SHADE
+ * or MISS step runs (cray_hip.hip: shadeScene) instead of keeping them in scalar registers across the walk steps. The fields are DScene's own, value for value. */
+struct DShadeArgs {
+	const DShadeTri *shade;
+	const crh_material *materials;
+	const DBsdf *bsdfs;
+	const f4 *consts;
+	const DImage *images;
+	const DOp *prog;
+	const DTexture *textures;
+	const f4 *texels;
+	uint32_t background, image_count, texture_count, material_count, bsdf_count, const_count;
 };
 
 /* Counter levels: 0 none, 1 rays + paths only (timed runs), 2 everything (parity / roofline runs).
@@ -1106,8 +1120,10 @@ CRH_DEV void walkBegin(const DScene &S, Walk &w, Stack &stk, const v3 o, const v
 /* NODE: bvh.c:391-436 */
 /* FAST = true serves PH_NODE lanes (regular rays: no degenerate-slab code in the step at all), FAST = false PH_NODE_SLOW lanes */
 /* (the child pair arrives as four 16-byte quarters: stepNode loads them itself; k_pathtrace fetches the pairs of a whole wave quad-cooperatively and calls this) */
-template <bool FAST = true, class Stack, class Cnt, class Port>
-CRH_DEV void stepNodeLoaded(const DScene &S, Walk &w, Stack &stk, Cnt &cnt, Port &port, const f4 l0, const f4 l1, const f4 r0, const f4 r1) {
+/* (stepNodeTest is the step without its closing walkAdvance: the rolling kernel's node run tests its node lanes and its triangle lanes under their masks and advances
+ * both kinds at ONE site — pathtrace_roll.h, CRH_MERGED_ADVANCE; everyone else calls stepNodeLoaded) */
+template <bool FAST = true, class Stack, class Cnt>
+CRH_DEV void stepNodeTest(Walk &w, Stack &stk, Cnt &cnt, const f4 l0, const f4 l1, const f4 r0, const f4 r1) {
 	float tL, tR;
 	CRH_COUNT(cnt, node_tests, 2);
 	const bool hitL = intersectNode<FAST>(l0, l1, w.k, w.hit.t, tL);
@@ -1126,6 +1142,10 @@ CRH_DEV void stepNodeLoaded(const DScene &S, Walk &w, Stack &stk, Cnt &cnt, Port
 	const bool swap = tL > tR;
 	if (inL && inR) stk.push(w.sp++, swap ? fl : fr);
 	w.node = (inL && inR) ? (swap ? fr : fl) : (inL ? fl : (inR ? fr : CRH_NONE));
+}
+template <bool FAST = true, class Stack, class Cnt, class Port>
+CRH_DEV void stepNodeLoaded(const DScene &S, Walk &w, Stack &stk, Cnt &cnt, Port &port, const f4 l0, const f4 l1, const f4 r0, const f4 r1) {
+	stepNodeTest<FAST>(w, stk, cnt, l0, l1, r0, r1);
 	walkAdvance(S, w, stk, cnt, port);
 }
 template <bool FAST = true, class Stack, class Cnt, class Port>
@@ -1203,8 +1223,9 @@ CRH_DEV void testTriangle(const f4 q0, const f4 q1, const f4 q2, uint32_t slot, 
  * first's hit distance: poly.c:17-36 via bvh.c:449-458); both records are requested before either is used. */
 /* (the records arrive loaded: stepTri fetches them itself; the rolling kernel's node run requests them together with the node pairs of the lanes that keep descending
  * and calls this — fused walk steps, pathtrace_roll.h) */
-template <class Stack, class Cnt, class Port>
-CRH_DEV void stepTriLoaded(const DScene &S, Walk &w, Stack &stk, Cnt &cnt, Port &port, const f4 a0, const f4 a1, const f4 a2, const f4 b0, const f4 b1, const f4 b2) {
+/* (stepTriTest: the step without its closing walkAdvance, as stepNodeTest) */
+template <class Cnt>
+CRH_DEV void stepTriTest(Walk &w, Cnt &cnt, const f4 a0, const f4 a1, const f4 a2, const f4 b0, const f4 b1, const f4 b2) {
 	const uint32_t slot = w.pA;
 	const bool two = slot + 1u < w.pAe;
 	const uint32_t slot2 = two ? slot + 1u : slot;
@@ -1212,6 +1233,10 @@ CRH_DEV void stepTriLoaded(const DScene &S, Walk &w, Stack &stk, Cnt &cnt, Port 
 	if (w.pA == w.pAe) { w.pA = w.pB; w.pAe = w.pBe; w.pB = w.pBe = 0; }
 	testTriangle(a0, a1, a2, slot, w, cnt);
 	if (two) testTriangle(b0, b1, b2, slot2, w, cnt);
+}
+template <class Stack, class Cnt, class Port>
+CRH_DEV void stepTriLoaded(const DScene &S, Walk &w, Stack &stk, Cnt &cnt, Port &port, const f4 a0, const f4 a1, const f4 a2, const f4 b0, const f4 b1, const f4 b2) {
+	stepTriTest(w, cnt, a0, a1, a2, b0, b1, b2);
 	walkAdvance(S, w, stk, cnt, port);
 }
 template <class Stack, class Cnt, class Port>
