@@ -509,6 +509,29 @@ class Context:
             f.write(exr.file_bytes(width, height, names, data, sizes, strings, kind, types))
         return names
 
+    def write_png(self, path, width, height, fb, filter="adaptive", codes="dynamic", text=None):
+        """The 8-bit picture of the device frame `fb` — any frame of that shape, a denoised one for example — as a PNG file: the bytes of to_srgb8, filtered,
+        deflated and check-summed on the device by the companion library (exrzip.py, crx_png_pack: loaded on first use). filter: "adaptive" (per row the PNG filter
+        with the least sum of min(v, 256 - v)) or "none", "sub", "up", "average", "paeth" on every row. codes: "dynamic" — the default here: per 4 096-byte segment
+        the cheaper of the fixed Huffman codes and a dynamic code — or "fixed"; set on the companion context for this call, then put back. text: tEXt chunks, a
+        mapping or (key, value) pairs, Latin-1, keys of 1 .. 79 bytes. Returns the file's byte count. An unknown filter or codes name raises ValueError."""
+        from . import exrzip          # (binds the companion library on first use)
+        if filter not in exrzip.PNG_FILTERS:
+            raise ValueError(f"filter {filter!r}: one of {sorted(exrzip.PNG_FILTERS)}")
+        if codes not in exrzip.CODES:
+            raise ValueError(f"codes {codes!r}: one of {sorted(exrzip.CODES)}")
+        self.synchronize()          # the companion's stream may be another: the frame must be complete
+        z = self._zip_context()
+        before = z.codes
+        z.set_codes(codes)
+        try:
+            data = z.png(fb, width, height, filter, text or ())
+        finally:
+            z.set_codes(before)
+        with open(path, "wb") as f:
+            f.write(data)
+        return len(data)
+
     # ---- the guided a-trous denoiser (include/cray_hip.h: crh_denoise) ----
     def denoise(self, fb, aov, width, height, out=None, **params):
         """Filter the float RGB frame `fb` guided by the AOV buffer `aov` into `out` (None: in place). Device pointers, the context's or the caller's;

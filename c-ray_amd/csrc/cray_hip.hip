@@ -606,8 +606,7 @@ __global__ __launch_bounds__(256) void k_fold_deferred(const crh_render_params P
 __global__ void k_to_srgb8(const float *fb, size_t n, uint8_t *out) {
 	CRH_EM_POW_TABLES_INIT();
 	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-		const float v = linearToSRGB(fb[i]);
-		out[i] = (unsigned char)rmin(v * 255.0f, 255.0f);
+		out[i] = linearToSRGB8(fb[i]);          /* srgb8.h */
 	}
 }
 

@@ -1,5 +1,6 @@
 /*
- * exr_zip.hip — libcray_hip_exr.so: the C-ABI of include/cray_hip_exr.h around the kernels of exr_zip.h. A translation unit of its own: it shares no state with
+ * exr_zip.hip — libcray_hip_exr.so: the C-ABI of include/cray_hip_exr.h around the kernels of exr_zip.h (the layers file's chunks) and of png_pack.h (the 8-bit
+ * frame as a PNG, which shares exr_zip.h's deflate and, through srgb8.h, the product's float-to-byte rule). A translation unit of its own: it shares no state with
  * libcray_hip.so and includes of it only what is plain HIP runtime bookkeeping (ctx_buffers.h: DevBuf, Stopwatch) and the channel descriptor (cray_hip.h).
  */
 #include <hip/hip_runtime.h>
@@ -17,6 +18,7 @@ int fail(int code, const std::string &what) { g_error = what; return code; }
 #define HIP_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(CRH_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(e_)); } while (0)
 #include "ctx_buffers.h"
 #include "exr_zip.h"
+#include "png_pack.h"
 
 struct crx_ctx {
 	int device = 0;
@@ -28,6 +30,9 @@ struct crx_ctx {
 	void *pinned = nullptr;
 	size_t pinnedBytes = 0;
 	Stopwatch<CRX_ZIP_PHASES> watch;
+	DevBuf<uint32_t> dImg;                               /* crx_png_pack: the 8-bit image, in words */
+	DevBuf<uint8_t> dTypes;                              /* ... and every row's filter type */
+	Stopwatch<CRX_PNG_PHASES> pngWatch;
 	int codes = CRX_CODES_FIXED;                         /* crx_set_codes */
 };
 
@@ -75,6 +80,7 @@ int crx_context_destroy(crx_ctx *c) {
 	c->dT.release(); c->dSegOut.release(); c->dMeta.release(); c->dMaps.release(); c->dPos.release(); c->dOut.release();
 	if (c->pinned) (void)hipHostFree(c->pinned);
 	c->watch.release();
+	c->dImg.release(); c->dTypes.release(); c->pngWatch.release();
 	if (c->ownStream) (void)hipStreamDestroy(c->stream);
 	delete c;
 	return CRH_OK;
@@ -243,6 +249,155 @@ int crx_pack_zip_time_ms(crx_ctx *c, float *ms) {
 	const int rc = crx_pack_zip_phases_ms(c, phases);
 	if (rc) return rc;
 	*ms = c->watch.sum;
+	return CRH_OK;
+}
+
+}  // extern "C"
+
+/* ---- the PNG codec (png_pack.h) ---- */
+namespace {
+void pngPut4(std::string &s, uint32_t v) { const char b[4] = {(char)(v >> 24), (char)(v >> 16), (char)(v >> 8), (char)v}; s.append(b, 4); }
+/* a chunk: length, type, data, the CRC-32 of type and data (pngCrcByte: the device's own step, conditioned here) */
+void pngChunk(std::string &s, const char *type, const std::string &data) {
+	pngPut4(s, (uint32_t)data.size());
+	const size_t at = s.size();
+	s.append(type, 4);
+	s += data;
+	uint32_t r = 0xffffffffu;
+	for (size_t i = at; i < s.size(); ++i) r = pngCrcByte(r, (uint8_t)s[i]);
+	pngPut4(s, ~r);
+}
+/* what the arguments make of the file: n bytes of filtered data, and — with `head` — everything up to and including the zlib header, the IDAT's length left 0.
+ * False: an argument crx_png_bound and crx_png_pack refuse. */
+bool pngLayout(int width, int height, const crx_png_text *text, uint32_t text_count, uint64_t *n, uint64_t *headBytes, std::string *head) {
+	if (width <= 0 || height <= 0 || (text_count && !text)) return false;
+	*n = (3u * (uint64_t)width + 1u) * (uint64_t)height;
+	if (*n >= (1ull << 31)) return false;
+	uint64_t bytes = 8u + 25u;
+	for (uint32_t i = 0; i < text_count; ++i) {
+		if (!text[i].key || !text[i].value) return false;
+		const size_t k = strlen(text[i].key), v = strlen(text[i].value);
+		if (k < 1 || k > 79 || v >= (1ull << 31) - 80u) return false;
+		bytes += 12u + k + 1u + v;
+	}
+	*headBytes = bytes + 8u + 2u;
+	if (*headBytes >= (1ull << 31)) return false;
+	if (!head) return true;
+	head->assign("\x89PNG\r\n\x1a\n", 8);
+	std::string ihdr;
+	pngPut4(ihdr, (uint32_t)width); pngPut4(ihdr, (uint32_t)height);
+	ihdr.append("\x08\x02\x00\x00\x00", 5);          /* 8 bits a sample, colour type 2 (RGB), deflate, the five filters, no interlace */
+	pngChunk(*head, "IHDR", ihdr);
+	for (uint32_t i = 0; i < text_count; ++i) pngChunk(*head, "tEXt", std::string(text[i].key) + '\0' + text[i].value);
+	pngPut4(*head, 0u);
+	head->append("IDAT\x78\x01", 6);
+	return head->size() == *headBytes;
+}
+uint64_t pngBound(uint64_t n, uint64_t headBytes) { return headBytes + (n + CRX_SEG - 1u) / CRX_SEG * CRX_SEG_OUT + CRX_PNG_FIXED_TAIL; }
+}  // namespace
+
+extern "C" {
+
+int crx_png_bound(int width, int height, const crx_png_text *text, uint32_t text_count, uint64_t *bytes) {
+	uint64_t n = 0, headBytes = 0;
+	if (!bytes || !pngLayout(width, height, text, text_count, &n, &headBytes, nullptr)) return fail(CRH_ERR_INVALID, "crx_png_bound: bad argument");
+	*bytes = pngBound(n, headBytes);
+	return CRH_OK;
+}
+
+int crx_png_pack(crx_ctx *c, const float *dev_fb, int width, int height, int filter, const crx_png_text *text, uint32_t text_count, void *host_out, uint64_t capacity,
+                 uint64_t *total_bytes) {
+	uint64_t n64 = 0, headBytes = 0;
+	std::string head;
+	if (!c || !dev_fb || !host_out || !total_bytes || filter < CRX_PNG_FILTER_ADAPTIVE || filter > 4 || !pngLayout(width, height, text, text_count, &n64, &headBytes, &head) ||
+	    capacity < pngBound(n64, headBytes))
+		return fail(CRH_ERR_INVALID, "crx_png_pack: bad argument (a context, a frame, an output of crx_png_bound bytes; a filter -1 .. 4; tEXt keys of 1 .. 79 bytes)");
+	const uint32_t n = (uint32_t)n64, rowBytes = 3u * (uint32_t)width, count = rowBytes * (uint32_t)height, at = (uint32_t)headBytes - 10u;
+	const uint32_t segs = (n + CRX_SEG - 1u) / CRX_SEG, words = (n + 3u) / 4u, imgWords = (count + 3u) / 4u;
+	const size_t bound = (size_t)pngBound(n64, headBytes);
+	ZipGeom G;          /* one chunk of n bytes */
+	memset(&G, 0, sizeof(G));
+	G.nch = 1u; G.width = n; G.rowCount = 1u; G.lpc = 1u; G.nchunks = 1u; G.fullBytes = n; G.rowBytes = n; G.segsPerChunk = segs; G.pitch = words;
+
+	HIP_TRY(hipSetDevice(c->device));
+	int rc;
+	if ((rc = c->dImg.grow(c->stream, imgWords))) return rc;
+	if ((rc = c->dTypes.grow(c->stream, (size_t)height))) return rc;
+	if ((rc = c->dT.grow(c->stream, words))) return rc;
+	if ((rc = c->dSegOut.grow(c->stream, (size_t)segs * (CRX_SEG_OUT / 4u)))) return rc;
+	if ((rc = c->dMeta.grow(c->stream, 7u * (size_t)segs + 4u))) return rc;
+	if ((rc = c->dOut.grow(c->stream, bound))) return rc;
+	if ((rc = growPinned(c, bound))) return rc;
+	uint32_t *const segMeta = c->dMeta.p, *const segOff = segMeta + 4u * (size_t)segs, *const crcMeta = segOff + segs, *const info = crcMeta + 2u * (size_t)segs;
+	const uint8_t *const img = (const uint8_t *)c->dImg.p;
+
+	memcpy(c->pinned, head.data(), head.size());
+	HIP_TRY(hipMemcpyAsync(c->dOut.p, c->pinned, head.size(), hipMemcpyHostToDevice, c->stream));
+	if ((rc = c->pngWatch.start(c->stream))) return rc;
+	hipLaunchKernelGGL(k_png_convert, dim3((imgWords + 255u) / 256u), dim3(256), 0, c->stream, dev_fb, count, c->dImg.p);
+	HIP_TRY(hipGetLastError());
+	if ((rc = c->pngWatch.mark(c->stream))) return rc;
+	hipLaunchKernelGGL(k_png_choose, dim3(((uint32_t)height + 3u) / 4u), dim3(256), 0, c->stream, img, rowBytes, (uint32_t)height, filter, c->dTypes.p);
+	HIP_TRY(hipGetLastError());
+	hipLaunchKernelGGL(k_png_filter, dim3((words + 255u) / 256u), dim3(256), 0, c->stream, img, c->dTypes.p, rowBytes, n, c->dT.p);
+	HIP_TRY(hipGetLastError());
+	if ((rc = c->pngWatch.mark(c->stream))) return rc;
+	if (c->codes == CRX_CODES_DYNAMIC) hipLaunchKernelGGL(k_zip_deflate_dynamic, dim3(segs), dim3(64), 0, c->stream, G, c->dT.p, c->dSegOut.p, segMeta);
+	else hipLaunchKernelGGL(k_zip_deflate, dim3(segs), dim3(64), 0, c->stream, G, c->dT.p, c->dSegOut.p, segMeta);
+	HIP_TRY(hipGetLastError());
+	if ((rc = c->pngWatch.mark(c->stream))) return rc;
+	hipLaunchKernelGGL(k_png_crc, dim3(segs), dim3(64), 0, c->stream, (const uint8_t *)c->dSegOut.p, CRX_SEG_OUT, segMeta, (uint64_t)0, crcMeta);
+	HIP_TRY(hipGetLastError());
+	hipLaunchKernelGGL(k_png_scan, dim3(1), dim3(256), 0, c->stream, segMeta, crcMeta, segs, n, segOff, info);
+	HIP_TRY(hipGetLastError());
+	if ((rc = c->pngWatch.mark(c->stream))) return rc;
+	hipLaunchKernelGGL(k_png_emit, dim3(segs), dim3(256), 0, c->stream, c->dSegOut.p, segMeta, segOff, info, c->dOut.p, at);
+	HIP_TRY(hipGetLastError());
+	if ((rc = c->pngWatch.mark(c->stream))) return rc;
+	c->pngWatch.stop();
+
+	/* the size first: it says how many bytes to fetch */
+	uint32_t *const got = (uint32_t *)c->pinned;
+	HIP_TRY(hipMemcpyAsync(got, info, 4u * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	const uint64_t total = headBytes + got[0] + CRX_PNG_FIXED_TAIL;
+	if (total > bound) return fail(CRH_ERR_HIP, "crx_png_pack: the device reported an impossible size");
+	HIP_TRY(hipMemcpyAsync(c->pinned, c->dOut.p, total, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	memcpy(host_out, c->pinned, total);
+	*total_bytes = total;
+	return CRH_OK;
+}
+
+int crx_png_phases_ms(crx_ctx *c, float phases_ms[CRX_PNG_PHASES]) {
+	if (!c || !phases_ms) return fail(CRH_ERR_INVALID, "crx_png_phases_ms: NULL argument");
+	HIP_TRY(hipSetDevice(c->device));
+	const int rc = c->pngWatch.read();
+	if (rc) return rc;
+	for (int i = 0; i < CRX_PNG_PHASES; ++i) phases_ms[i] = i < c->pngWatch.laps ? c->pngWatch.ms[i] : 0.0f;
+	return CRH_OK;
+}
+
+int crx_debug_crc32(crx_ctx *c, const void *host_bytes, uint64_t n, uint32_t piece_bytes, uint32_t *crc) {
+	if (!c || !crc || !piece_bytes || (n && !host_bytes) || n >= (1ull << 32) || (n + piece_bytes - 1u) / piece_bytes >= (1ull << 28))
+		return fail(CRH_ERR_INVALID, "crx_debug_crc32: bad argument (below 2^32 bytes in fewer than 2^28 pieces of at least one byte)");
+	const uint32_t pieces = (uint32_t)((n + piece_bytes - 1u) / piece_bytes);
+	HIP_TRY(hipSetDevice(c->device));
+	int rc;
+	if ((rc = c->dT.grow(c->stream, (size_t)(n + 3u) / 4u + 1u))) return rc;
+	if ((rc = c->dMeta.grow(c->stream, 2u * (size_t)pieces + 4u))) return rc;
+	uint32_t *const crcMeta = c->dMeta.p, *const info = crcMeta + 2u * (size_t)pieces;
+	if (n) HIP_TRY(hipMemcpyAsync(c->dT.p, host_bytes, n, hipMemcpyHostToDevice, c->stream));
+	if (pieces) {
+		hipLaunchKernelGGL(k_png_crc, dim3(pieces), dim3(64), 0, c->stream, (const uint8_t *)c->dT.p, piece_bytes, (const uint32_t *)nullptr, n, crcMeta);
+		HIP_TRY(hipGetLastError());
+	}
+	hipLaunchKernelGGL(k_png_scan, dim3(1), dim3(256), 0, c->stream, (const uint32_t *)nullptr, crcMeta, pieces, 0u, (uint32_t *)nullptr, info);
+	HIP_TRY(hipGetLastError());
+	uint32_t got[4];
+	HIP_TRY(hipMemcpyAsync(got, info, sizeof(got), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	*crc = got[2];
 	return CRH_OK;
 }
 

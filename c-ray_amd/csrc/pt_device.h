@@ -19,6 +19,7 @@
 #include <utility>
 #include "cray_hip.h"
 #include "exact_math.h"     /* sinf, cosf, tanf, powf, logf, log10f, atan2f, acosf, asinf with the host libm's bits (namespace crh::em) */
+#include "srgb8.h"          /* linearToSRGB and linearToSRGB8: a frame's float -> the byte of the 8-bit picture */
 
 #if defined(__HIPCC__)
 #define CRH_DEV __device__ __forceinline__
@@ -229,10 +230,7 @@ CRH_DEV rgba cmul(rgba a, rgba b) { return rgba{a.r * b.r, a.g * b.g, a.b * b.b,
 CRH_DEV rgba cadd(rgba a, rgba b) { return rgba{a.r + b.r, a.g + b.g, a.b + b.b, a.a + b.a}; }
 CRH_DEV rgba ccoef(float c, rgba a) { return rgba{a.r * c, a.g * c, a.b * c, a.a * c}; }
 CRH_DEV rgba cmix(rgba c1, rgba c2, float k) { return cadd(ccoef(1.0f - k, c1), ccoef(k, c2)); }   /* color.h:46 */
-CRH_DEV float linearToSRGB(float c) {                                                               /* color.h:51 */
-	if (c <= 0.0031308f) return 12.92f * c;
-	return (1.055f * em::powf_(c, 0.4166666667f)) - 0.055f;
-}
+/* (linearToSRGB, color.h:51, and the byte it becomes: srgb8.h, shared with the companion library's PNG codec) */
 CRH_DEV float SRGBToLinear(float c) {                                                               /* color.h:59 */
 	if (c <= 0.04045f) return c / 12.92f;
 	return em::powf_(((c + 0.055f) / 1.055f), 2.4f);

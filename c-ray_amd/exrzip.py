@@ -1,5 +1,6 @@
 """exrzip.py — thin ctypes binding of libcray_hip_exr.so (include/cray_hip_exr.h), the companion library of output codecs: the pixel data of a ZIP / ZIPS
-compressed scanline OpenEXR file, deflated on the device, FLOAT or per channel HALF. Plumbing: the work is in c-ray_amd/csrc/exr_zip.h. The library loads on first use; there is no CPU
+compressed scanline OpenEXR file, deflated on the device, FLOAT or per channel HALF, and the 8-bit frame as a complete PNG file (ZipContext.png). Plumbing: the work
+is in c-ray_amd/csrc/exr_zip.h and png_pack.h. The library loads on first use; there is no CPU
 fallback: `library()` raises if it has not been built, every call raises `CrhError` on a non-zero return code.
 """
 import ctypes as C
@@ -14,6 +15,23 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CRX_LIB") or os.path.join(HERE, "_lib", "libcray_hip_exr.so")    # CRX_LIB: another build (dev, the emulation tier)
 COMPRESSION = {"none": (0, 1), "zips": (2, 1), "zip": (3, 16)}          # name -> (the file's compression attribute, lines per chunk)
 CODES = {"fixed": 0, "dynamic": 1}          # name -> CRX_CODES_*
+PNG_FILTERS = {"adaptive": -1, "none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4}          # name -> crx_png_pack's filter
+PNG_PHASES = ("convert", "filter", "deflate", "crc + scan", "emit")
+
+
+class PngText(C.Structure):
+    """crx_png_text: a tEXt chunk"""
+    _fields_ = [("key", C.c_char_p), ("value", C.c_char_p)]
+
+
+def png_texts(text):
+    """(the crx_png_text array or None, its count) of `text`: a mapping or an iterable of (key, value), str (stored as Latin-1) or bytes."""
+    pairs = list(text.items()) if hasattr(text, "items") else list(text or ())
+    raw = [tuple(s if isinstance(s, bytes) else str(s).encode("latin-1") for s in kv) for kv in pairs]
+    if any(len(kv) != 2 or b"\0" in kv[0] or b"\0" in kv[1] for kv in raw):
+        raise ValueError("text: (key, value) pairs without NUL bytes")
+    arr = (PngText * len(raw))(*[PngText(k, v) for k, v in raw]) if raw else None
+    return arr, len(raw)
 
 _lib = None
 
@@ -46,6 +64,10 @@ def library():
         "crx_set_codes": (C.c_int, [ctx, C.c_int]),
         "crx_get_codes": (C.c_int, [ctx, C.POINTER(C.c_int)]),
         "crx_debug_code_lengths": (C.c_int, [ctx, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+        "crx_png_bound": (C.c_int, [C.c_int, C.c_int, C.POINTER(PngText), C.c_uint32, C.POINTER(C.c_uint64)]),
+        "crx_png_pack": (C.c_int, [ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(PngText), C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+        "crx_png_phases_ms": (C.c_int, [ctx, C.POINTER(C.c_float)]),
+        "crx_debug_crc32": (C.c_int, [ctx, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -136,6 +158,34 @@ class ZipContext:
             raise ValueError("pixel_types: one entry per channel")
         return self._pack("crx_pack", lambda arr, *out: self.L.crx_pack(self.h, arr, None if types is None else types.ctypes.data, n, width, height, first_row, rows, compression, *out),
                           channels, 4 * n if types is None else int(np.where(types == 1, 2, 4).sum()), width, 16 if compression == 3 else 1, rows)
+
+    def png(self, fb, width, height, filter="adaptive", text=()):
+        """crx_png_pack: the bytes of a complete PNG file of the device frame `fb` ([height, width, 3] floats, complete) — 8-bit sRGB, the bytes of
+        Context.to_srgb8, filtered and deflated on the device under the context's codes setting. filter: a name of PNG_FILTERS ("adaptive": per row the type with
+        the least sum of min(v, 256 - v)) or its number -1 .. 4; text: tEXt chunks, a mapping or (key, value) pairs, Latin-1, keys of 1 .. 79 bytes."""
+        if isinstance(filter, str):
+            if filter not in PNG_FILTERS:
+                raise ValueError(f"filter {filter!r}: one of {sorted(PNG_FILTERS)}")
+            filter = PNG_FILTERS[filter]
+        arr, count = png_texts(text)
+        bound, total = C.c_uint64(0), C.c_uint64(0)
+        _check(self.L.crx_png_bound(width, height, arr, count, C.byref(bound)), "crx_png_bound")
+        out = np.empty(bound.value, np.uint8)
+        _check(self.L.crx_png_pack(self.h, fb, width, height, int(filter), arr, count, out.ctypes.data, bound.value, C.byref(total)), "crx_png_pack")
+        return out[:total.value].tobytes()
+
+    def png_phases_ms(self):
+        """Milliseconds per phase of the most recent png(): convert, filter, deflate, crc + scan, emit (PNG_PHASES; waits for it)."""
+        ms = (C.c_float * len(PNG_PHASES))()
+        _check(self.L.crx_png_phases_ms(self.h, ms), "crx_png_phases_ms")
+        return [float(v) for v in ms]
+
+    def crc32(self, data, piece_bytes):
+        """crx_debug_crc32: the CRC-32 of `data` taken on the device in pieces of piece_bytes and combined there — zlib.crc32(data), whatever the pieces."""
+        data = bytes(data)
+        crc = C.c_uint32(0)
+        _check(self.L.crx_debug_crc32(self.h, data if data else None, len(data), int(piece_bytes), C.byref(crc)), "crx_debug_crc32")
+        return int(crc.value)
 
     def time_ms(self):
         """Milliseconds of the most recent pack_zip's kernels, summed (waits for them)."""

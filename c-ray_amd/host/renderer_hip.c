@@ -53,6 +53,8 @@
  * (crx_pack of libcray_hip_exr.so, for every compression); values above 65504 become infinity in them. Anything else or unset: all FLOAT.
  * CRAY_HIP_EXR_CODES=dynamic beside CRAY_HIP_EXR_COMPRESSION: every segment of a chunk is deflated with the cheaper of the fixed Huffman codes and a dynamic code
  * built on the device (crx_set_codes): the same pixels in a smaller file. Anything else or unset: the fixed codes.
+ * CRAY_HIP_PNG=1 (user-facing): the frame on GPU 0 also as <imgFileName>_gpu_<count>.png, encoded on the device (writeGpuPng below: crx_png_pack), with tEXt chunks for the
+ * sample and bounce counts, next to the frame's own file, which writeImage writes as ever. Dynamic codes unless CRAY_HIP_EXR_CODES=fixed. Unset: nothing of it runs.
  * No GPU => logr(error, ...) (which exits, src/utils/logging.c:69-73): there is no CPU fallback in this file.
  */
 #include <stdlib.h>
@@ -917,6 +919,45 @@ static void writeLayers(struct renderer *r, crh_ctx *ctx, const float *fb, const
 	}
 }
 
+/* CRAY_HIP_PNG=1: <imgFilePath><imgFileName>_gpu_<imgCount, four digits>.png — the frame on GPU 0 as a PNG converted, filtered, deflated and check-summed there
+ * (crx_png_pack of libcray_hip_exr.so), with the tEXt chunks "C-ray Samples" and "C-ray Bounces". Written next to the frame's own file, not in its place: the
+ * reference's writeImage runs untouched. CRAY_HIP_EXR_CODES=fixed applies; otherwise the codes are dynamic. Unset: nothing is allocated or written. */
+static void writeGpuPng(struct renderer *r, crh_ctx *ctx, const float *fb, int W, int H) {
+	struct timeval t;
+	startTimer(&t);
+	char samples[32], bounces[32];
+	snprintf(samples, sizeof(samples), "%i", r->prefs.sampleCount);
+	snprintf(bounces, sizeof(bounces), "%i", r->prefs.bounces);
+	const crx_png_text text[2] = {{"C-ray Samples", samples}, {"C-ray Bounces", bounces}};
+	const char *base = r->prefs.imgFileName ? r->prefs.imgFileName : "rendered";
+	const char *dir = r->prefs.imgFilePath ? r->prefs.imgFilePath : "";
+	const char *codes = getenv("CRAY_HIP_EXR_CODES");
+	const char *why = NULL;
+	uint64_t bound = 0, total = 0;
+	crx_ctx *png = NULL;
+	char *path = malloc(strlen(dir) + strlen(base) + 32);
+	void *file = NULL;
+	bool ok = path && crx_png_bound(W, H, text, 2, &bound) == CRH_OK && (file = malloc((size_t)bound)) != NULL;
+	if (ok && crh_synchronize(ctx) != CRH_OK) { ok = false; why = crh_last_error(); }          /* the companion's stream is its own: the frame must be complete */
+	if (ok && crx_context_create(0, NULL, &png) != CRH_OK) { ok = false; why = crx_last_error(); }
+	if (ok && crx_set_codes(png, codes && !strcmp(codes, "fixed") ? CRX_CODES_FIXED : CRX_CODES_DYNAMIC) != CRH_OK) { ok = false; why = crx_last_error(); }
+	if (ok && crx_png_pack(png, fb, W, H, CRX_PNG_FILTER_ADAPTIVE, text, 2, file, bound, &total) != CRH_OK) { ok = false; why = crx_last_error(); }
+	float phases[CRX_PNG_PHASES] = {0};
+	if (ok) (void)crx_png_phases_ms(png, phases);
+	crx_context_destroy(png);
+	if (ok) {
+		sprintf(path, "%s%s_gpu_%04d.png", dir, base, r->prefs.imgCount);
+		FILE *f = fopen(path, "wb");
+		ok = f && fwrite(file, 1, (size_t)total, f) == (size_t)total;
+		if (f && fclose(f) != 0) ok = false;
+		if (ok) logr(info, "GPU PNG written to %s: %llu bytes, encoded in %.2f ms (kernels %.2f ms).\n", path, (unsigned long long)total, getUs(t) / 1000.0,
+			(double)(phases[0] + phases[1] + phases[2] + phases[3] + phases[4]));
+		else logr(warning, "c-ray-hip: the GPU PNG %s could not be written\n", path);
+	} else logr(warning, "c-ray-hip: the GPU PNG could not be made: %s\n", why ? why : "out of memory");
+	free(file);
+	free(path);
+}
+
 struct texture *renderFrame(struct renderer *r) {
 	const int W = (int)r->prefs.imageWidth, H = (int)r->prefs.imageHeight;
 	struct timeval frame;
@@ -987,6 +1028,7 @@ struct texture *renderFrame(struct renderer *r) {
 	int frc = crh_flatten_world(r, &scene);
 	const long flattenUs = getUs(phase);
 	const bool layers = getenv("CRAY_HIP_EXR") && atoi(getenv("CRAY_HIP_EXR")) > 0;
+	const bool gpuPng = getenv("CRAY_HIP_PNG") && atoi(getenv("CRAY_HIP_PNG")) > 0;
 	struct layerNames layerNames;
 	memset(&layerNames, 0, sizeof(layerNames));
 	if (layers && frc == CRH_OK) layerNamesCollect(r, &scene, &layerNames);
@@ -1116,7 +1158,11 @@ struct texture *renderFrame(struct renderer *r) {
 		}
 		writeDenoised(r, workers[0].ctx, workers[0].fb, halfAt ? workers[0].half : NULL, halfAt, W, H, layers ? &keptDenoised : NULL);
 		if (layers) writeLayers(r, workers[0].ctx, workers[0].fb, keptAov, keptDenoised, &layerNames, W, H);
-	} else if (layers) logr(warning, "c-ray-hip: CRAY_HIP_EXR needs the frame on GPU 0; no layers file\n");
+		if (gpuPng) writeGpuPng(r, workers[0].ctx, workers[0].fb, W, H);
+	} else {
+		if (layers) logr(warning, "c-ray-hip: CRAY_HIP_EXR needs the frame on GPU 0; no layers file\n");
+		if (gpuPng) logr(warning, "c-ray-hip: CRAY_HIP_PNG needs the frame on GPU 0; no GPU PNG\n");
+	}
 	if (keptAov) crh_aov_free(workers[0].ctx, keptAov);
 	if (keptDenoised) crh_framebuffer_free(workers[0].ctx, keptDenoised);
 	layerNamesFree(&layerNames);

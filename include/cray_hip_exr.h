@@ -1,6 +1,6 @@
 /*
  * cray_hip_exr.h — the C-ABI of libcray_hip_exr.so, the companion library of the output codecs: what leaves the product as a file and needs no scene, no path
- * state and nothing of the render path. Its first and so far only codec: the pixel data of a ZIP- or ZIPS-compressed scanline OpenEXR file, deflated on the device
+ * state and nothing of the render path. Its second codec is the 8-bit frame as a PNG file (crx_png_pack, below). Its first: the pixel data of a ZIP- or ZIPS-compressed scanline OpenEXR file, deflated on the device
  * from the buffers libcray_hip.so already makes (c-ray_amd/csrc/exr_zip.h) — all FLOAT (crx_pack_zip), or with a pixel type per channel, FLOAT or HALF (crx_pack). Plain C, int return codes: 0 (CRH_OK) is ok, the negative CRH_ERR_* values of cray_hip.h
  * are reused, crx_last_error() holds the text of the calling thread's last failure. There is NO CPU path: without a HIP device crx_context_create answers
  * CRH_ERR_NO_DEVICE. A context belongs to one device and one stream and is used by one thread at a time.
@@ -101,6 +101,37 @@ uint32_t crx_zip_segment_bytes(void);
 int crx_set_codes(crx_ctx *ctx, int codes);
 int crx_get_codes(crx_ctx *ctx, int *codes);
 
+/* ---- the second codec: the 8-bit frame as a PNG file, filtered and deflated on the device (c-ray_amd/csrc/png_pack.h) ----
+ * host_out receives a complete PNG file: the signature; IHDR (8 bits a sample, colour type 2, no interlace); the caller's tEXt chunks, in order; one IDAT; IEND.
+ * Every chunk's CRC-32 is in place: no caller needs a CRC or a zlib of its own.
+ *
+ * Pixels. dev_fb is a frame buffer [H, W, 3] of floats on the context's device, complete (after work of another context or stream: synchronise that first); stored
+ * row 0 is the PNG's first row. Byte i of the image is the byte crh_framebuffer_to_srgb8 gives for float i: linearToSRGB, then (unsigned char)min(v * 255, 255) —
+ * one statement, c-ray_amd/csrc/srgb8.h, compiled into both libraries. The contract covers finite inputs >= 0, values above 1 included: what a frame holds.
+ * Filtered data F. Per row one filter-type byte, then 3 W bytes filtered with bpp = 3 by the PNG specification's rules — 0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth —;
+ * bytes left of the row and the row above the first row count as 0, arithmetic is mod 256. n = (3 W + 1) H.
+ * Adaptive choice (CRX_PNG_FILTER_ADAPTIVE), part of the interface: a row takes the type whose filtered bytes v have the least sum of min(v, 256 - v); ties go to
+ * the lowest type number. A fixed `filter` 0 .. 4 uses that type on every row, the first included.
+ * IDAT data. A zlib stream of F: header 78 01, deflate blocks any inflate accepts, the big-endian Adler-32 of F. The blocks are crx_pack's segment coder's:
+ * segments of crx_zip_segment_bytes() bytes of F, matches never cross a segment; under the context's crx_set_codes setting the fixed codes, or per segment the
+ * cheaper of fixed and dynamic.
+ * Bound. crx_png_bound gives the worst case for these arguments: the fixed parts and the tEXt chunks, and 4640 bytes for every segment — what a segment without a
+ * single match takes under the fixed codes, whose literals from 144 up have 9 bits: there is no stored-block fallback, so noise may come out larger than n, by about
+ * an eighth at the most. crx_png_pack refuses a smaller `capacity` and writes nothing; *total_bytes is the file's size, never above the bound.
+ * Determinism. The bytes are a function of the arguments, the pixels and the codes setting only.
+ * CRH_ERR_INVALID, nothing written anywhere: a NULL context, frame, output or total_bytes (crx_png_bound: a NULL bytes); width or height <= 0, or n >= 2^31; a filter
+ * outside -1 .. 4; a NULL text list with a non-zero count; a key that is empty, longer than 79 bytes or NULL, or a NULL value; a capacity below the bound.
+ * The call launches behind whatever is queued on the context's stream, copies the size and then the file through the context's pinned scratch and waits. */
+#define CRX_PNG_FILTER_ADAPTIVE (-1)          /* 0 .. 4: that PNG filter type on every row */
+typedef struct { const char *key, *value; } crx_png_text;          /* a tEXt chunk: Latin-1, key 1 .. 79 bytes */
+int crx_png_bound(int width, int height, const crx_png_text *text, uint32_t text_count, uint64_t *bytes);
+int crx_png_pack(crx_ctx *ctx, const float *dev_fb, int width, int height, int filter, const crx_png_text *text, uint32_t text_count, void *host_out, uint64_t capacity,
+                 uint64_t *total_bytes);
+/* The last complete crx_png_pack's kernel time per phase (waits for it): [0] convert, [1] filter (choice and word build), [2] deflate, [3] crc + scan, [4] emit.
+ * 0 before the first call. */
+#define CRX_PNG_PHASES 5
+int crx_png_phases_ms(crx_ctx *ctx, float phases_ms[CRX_PNG_PHASES]);
+
 /* ---- debug ---- */
 /* The code construction of CRX_CODES_DYNAMIC on histograms of the caller's: `count` histograms of `symbols` counts each in freq (host memory), one wave a
  * histogram through the device function the deflate kernel calls (c-ray_amd/csrc/exr_zip.h: zipCodeLengths); lengths[h * symbols + s] is the code length of symbol
@@ -110,6 +141,11 @@ int crx_get_codes(crx_ctx *ctx, int *codes);
  * CRH_ERR_INVALID: a NULL argument, symbols outside 1 .. 288 or above 2^limit, a limit other than 7 or 15, a histogram whose counts sum to 2^23 or more, 2^20
  * histograms or more. count == 0 is CRH_OK. */
 int crx_debug_code_lengths(crx_ctx *ctx, const uint32_t *freq, uint32_t symbols, uint32_t limit, uint32_t count, uint8_t *lengths);
+/* The CRC-32 of crx_png_pack's IDAT on bytes of the caller's: n bytes of host memory in pieces of piece_bytes, the last one shorter; one wave a piece takes its
+ * register (zero initial value), one workgroup combines the pieces' (register, x^(8 length) mod P) pairs by the scan crx_png_pack runs over its segments, the
+ * conditioning applied once at the ends. *crc is what zlib's crc32 gives for the bytes, whatever the pieces; n == 0 gives 0.
+ * CRH_ERR_INVALID: a NULL context or crc, NULL bytes with n > 0, piece_bytes == 0, n >= 2^32, 2^28 pieces or more. */
+int crx_debug_crc32(crx_ctx *ctx, const void *host_bytes, uint64_t n, uint32_t piece_bytes, uint32_t *crc);
 
 #ifdef __cplusplus
 }
