@@ -509,23 +509,41 @@ class Context:
             f.write(exr.file_bytes(width, height, names, data, sizes, strings, kind, types))
         return names
 
-    def write_png(self, path, width, height, fb, filter="adaptive", codes="dynamic", text=None):
+    def write_png(self, path, width, height, fb, filter="adaptive", codes="dynamic", text=None, exposure=1.0, tonemap="clamp", white=4.0, dither=False,
+                  auto_permille=500, auto_target=0.18):
         """The 8-bit picture of the device frame `fb` — any frame of that shape, a denoised one for example — as a PNG file: the bytes of to_srgb8, filtered,
         deflated and check-summed on the device by the companion library (exrzip.py, crx_png_pack: loaded on first use). filter: "adaptive" (per row the PNG filter
         with the least sum of min(v, 256 - v)) or "none", "sub", "up", "average", "paeth" on every row. codes: "dynamic" — the default here: per 4 096-byte segment
         the cheaper of the fixed Huffman codes and a dynamic code — or "fixed"; set on the companion context for this call, then put back. text: tEXt chunks, a
-        mapping or (key, value) pairs, Latin-1, keys of 1 .. 79 bytes. Returns the file's byte count. An unknown filter or codes name raises ValueError."""
+        mapping or (key, value) pairs, Latin-1, keys of 1 .. 79 bytes. Returns the file's byte count. An unknown filter, codes or tonemap name raises ValueError.
+        The display transform (crx_png_pack_display, include/cray_hip_exr.h), between the float and the byte: exposure — a factor, or "auto": the one
+        ZipContext.auto_exposure measures on the device, which takes the auto_permille / 1000 quantile of the luminances to auto_target —; tonemap, a name of
+        exrzip.CURVES ("clamp", "reinhard", "aces", "hable") with its white point; dither, the ordered 8 x 8 one. The defaults are the identity: the file of a call
+        without them, byte for byte. Otherwise one more tEXt chunk, "C-ray Display", behind `text` says what was done, the exposure printed with %.9g."""
         from . import exrzip          # (binds the companion library on first use)
         if filter not in exrzip.PNG_FILTERS:
             raise ValueError(f"filter {filter!r}: one of {sorted(exrzip.PNG_FILTERS)}")
         if codes not in exrzip.CODES:
             raise ValueError(f"codes {codes!r}: one of {sorted(exrzip.CODES)}")
+        if tonemap not in exrzip.CURVES:
+            raise ValueError(f"tonemap {tonemap!r}: one of {sorted(exrzip.CURVES)}")
+        auto = isinstance(exposure, str)
+        if auto and exposure != "auto":
+            raise ValueError(f'exposure {exposure!r}: a number or "auto"')
         self.synchronize()          # the companion's stream may be another: the frame must be complete
         z = self._zip_context()
+        if auto:
+            exposure = z.auto_exposure(fb, width, height, auto_permille, auto_target)[0]
+        exposure = float(np.float32(exposure))
+        display, texts = None, list(text.items()) if hasattr(text, "items") else list(text or ())
+        if exposure != 1.0 or tonemap != "clamp" or dither:
+            display = dict(exposure=exposure, curve=tonemap, white=white, dither=1 if dither else 0)
+            how = f" (auto {int(auto_permille)}/1000 of {float(auto_target):.9g})" if auto else ""
+            texts.append(("C-ray Display", f"exposure={exposure:.9g}{how} curve={tonemap} white={float(white):.9g} dither={display['dither']}"))
         before = z.codes
         z.set_codes(codes)
         try:
-            data = z.png(fb, width, height, filter, text or ())
+            data = z.png(fb, width, height, filter, texts, display)
         finally:
             z.set_codes(before)
         with open(path, "wb") as f:

@@ -1,6 +1,7 @@
 /*
  * exr_zip.hip — libcray_hip_exr.so: the C-ABI of include/cray_hip_exr.h around the kernels of exr_zip.h (the layers file's chunks) and of png_pack.h (the 8-bit
- * frame as a PNG, which shares exr_zip.h's deflate and, through srgb8.h, the product's float-to-byte rule). A translation unit of its own: it shares no state with
+ * frame as a PNG, which shares exr_zip.h's deflate and, through srgb8.h, the product's float-to-byte rule; png_display.h beside it: the display transform and the
+ * automatic exposure). A translation unit of its own: it shares no state with
  * libcray_hip.so and includes of it only what is plain HIP runtime bookkeeping (ctx_buffers.h: DevBuf, Stopwatch) and the channel descriptor (cray_hip.h).
  */
 #include <hip/hip_runtime.h>
@@ -33,6 +34,8 @@ struct crx_ctx {
 	DevBuf<uint32_t> dImg;                               /* crx_png_pack: the 8-bit image, in words */
 	DevBuf<uint8_t> dTypes;                              /* ... and every row's filter type */
 	Stopwatch<CRX_PNG_PHASES> pngWatch;
+	DevBuf<uint32_t> dHist;                              /* crx_auto_exposure: the CRX_HIST_BINS bins, then k_png_pick's four result words */
+	Stopwatch<1> autoWatch;
 	int codes = CRX_CODES_FIXED;                         /* crx_set_codes */
 };
 
@@ -81,6 +84,7 @@ int crx_context_destroy(crx_ctx *c) {
 	if (c->pinned) (void)hipHostFree(c->pinned);
 	c->watch.release();
 	c->dImg.release(); c->dTypes.release(); c->pngWatch.release();
+	c->dHist.release(); c->autoWatch.release();
 	if (c->ownStream) (void)hipStreamDestroy(c->stream);
 	delete c;
 	return CRH_OK;
@@ -305,13 +309,24 @@ int crx_png_bound(int width, int height, const crx_png_text *text, uint32_t text
 	return CRH_OK;
 }
 
-int crx_png_pack(crx_ctx *c, const float *dev_fb, int width, int height, int filter, const crx_png_text *text, uint32_t text_count, void *host_out, uint64_t capacity,
-                 uint64_t *total_bytes) {
+}  // extern "C"
+
+namespace {
+bool displayValid(const crx_display &d) {
+	return d.curve >= CRX_CURVE_CLAMP && d.curve <= CRX_CURVE_HABLE && d.exposure >= CRX_EXPOSURE_MIN && d.exposure <= CRX_EXPOSURE_MAX && d.white >= CRX_WHITE_MIN &&
+	       d.white <= CRX_WHITE_MAX && (d.dither == 0 || d.dither == 1);          /* (a NaN fails every comparison) */
+}
+bool displayIdentity(const crx_display &d) { return d.exposure == 1.0f && d.curve == CRX_CURVE_CLAMP && d.dither == 0; }
+
+/* crx_png_pack (display NULL) and crx_png_pack_display: one body, the convert launch apart. The identity launches k_png_convert, as crx_png_pack always has. */
+int pngPack(const char *who, crx_ctx *c, const float *dev_fb, int width, int height, const crx_display *display, int filter, const crx_png_text *text, uint32_t text_count,
+            void *host_out, uint64_t capacity, uint64_t *total_bytes) {
 	uint64_t n64 = 0, headBytes = 0;
 	std::string head;
-	if (!c || !dev_fb || !host_out || !total_bytes || filter < CRX_PNG_FILTER_ADAPTIVE || filter > 4 || !pngLayout(width, height, text, text_count, &n64, &headBytes, &head) ||
-	    capacity < pngBound(n64, headBytes))
-		return fail(CRH_ERR_INVALID, "crx_png_pack: bad argument (a context, a frame, an output of crx_png_bound bytes; a filter -1 .. 4; tEXt keys of 1 .. 79 bytes)");
+	if (!c || !dev_fb || !host_out || !total_bytes || filter < CRX_PNG_FILTER_ADAPTIVE || filter > 4 || (display && !displayValid(*display)) ||
+	    !pngLayout(width, height, text, text_count, &n64, &headBytes, &head) || capacity < pngBound(n64, headBytes))
+		return fail(CRH_ERR_INVALID, std::string(who) + ": bad argument (a context, a frame, an output of crx_png_bound bytes; a filter -1 .. 4; tEXt keys of 1 .. 79 bytes; "
+		                                                "a display with a curve 0 .. 3, an exposure in [2^-40, 2^40], a white in [2^-10, 2^10], a dither 0 or 1)");
 	const uint32_t n = (uint32_t)n64, rowBytes = 3u * (uint32_t)width, count = rowBytes * (uint32_t)height, at = (uint32_t)headBytes - 10u;
 	const uint32_t segs = (n + CRX_SEG - 1u) / CRX_SEG, words = (n + 3u) / 4u, imgWords = (count + 3u) / 4u;
 	const size_t bound = (size_t)pngBound(n64, headBytes);
@@ -334,7 +349,18 @@ int crx_png_pack(crx_ctx *c, const float *dev_fb, int width, int height, int fil
 	memcpy(c->pinned, head.data(), head.size());
 	HIP_TRY(hipMemcpyAsync(c->dOut.p, c->pinned, head.size(), hipMemcpyHostToDevice, c->stream));
 	if ((rc = c->pngWatch.start(c->stream))) return rc;
-	hipLaunchKernelGGL(k_png_convert, dim3((imgWords + 255u) / 256u), dim3(256), 0, c->stream, dev_fb, count, c->dImg.p);
+	const dim3 convertGrid((imgWords + 255u) / 256u);
+	if (!display || displayIdentity(*display)) hipLaunchKernelGGL(k_png_convert, convertGrid, dim3(256), 0, c->stream, dev_fb, count, c->dImg.p);
+	else {
+		const PngDisplay d = {display->exposure, display->white * display->white, pngHable(2.0f * display->white), display->dither};
+		const uint32_t w = (uint32_t)width;
+		switch (display->curve) {
+		case CRX_CURVE_CLAMP: hipLaunchKernelGGL(k_png_convert_display<CRX_CURVE_CLAMP>, convertGrid, dim3(256), 0, c->stream, dev_fb, count, w, d, c->dImg.p); break;
+		case CRX_CURVE_REINHARD: hipLaunchKernelGGL(k_png_convert_display<CRX_CURVE_REINHARD>, convertGrid, dim3(256), 0, c->stream, dev_fb, count, w, d, c->dImg.p); break;
+		case CRX_CURVE_ACES: hipLaunchKernelGGL(k_png_convert_display<CRX_CURVE_ACES>, convertGrid, dim3(256), 0, c->stream, dev_fb, count, w, d, c->dImg.p); break;
+		default: hipLaunchKernelGGL(k_png_convert_display<CRX_CURVE_HABLE>, convertGrid, dim3(256), 0, c->stream, dev_fb, count, w, d, c->dImg.p); break;
+		}
+	}
 	HIP_TRY(hipGetLastError());
 	if ((rc = c->pngWatch.mark(c->stream))) return rc;
 	hipLaunchKernelGGL(k_png_choose, dim3(((uint32_t)height + 3u) / 4u), dim3(256), 0, c->stream, img, rowBytes, (uint32_t)height, filter, c->dTypes.p);
@@ -366,6 +392,63 @@ int crx_png_pack(crx_ctx *c, const float *dev_fb, int width, int height, int fil
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	memcpy(host_out, c->pinned, total);
 	*total_bytes = total;
+	return CRH_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int crx_png_pack(crx_ctx *c, const float *dev_fb, int width, int height, int filter, const crx_png_text *text, uint32_t text_count, void *host_out, uint64_t capacity,
+                 uint64_t *total_bytes) {
+	return pngPack("crx_png_pack", c, dev_fb, width, height, nullptr, filter, text, text_count, host_out, capacity, total_bytes);
+}
+
+void crx_display_default(crx_display *d) {
+	if (!d) return;
+	d->exposure = 1.0f; d->curve = CRX_CURVE_CLAMP; d->white = 4.0f; d->dither = 0;
+}
+
+int crx_png_pack_display(crx_ctx *c, const float *dev_fb, int width, int height, const crx_display *display, int filter, const crx_png_text *text, uint32_t text_count,
+                         void *host_out, uint64_t capacity, uint64_t *total_bytes) {
+	return pngPack("crx_png_pack_display", c, dev_fb, width, height, display, filter, text, text_count, host_out, capacity, total_bytes);
+}
+
+int crx_auto_exposure(crx_ctx *c, const float *dev_fb, int width, int height, uint32_t permille, float target, float *exposure, float *key, uint64_t *counted) {
+	uint64_t n = 0, headBytes = 0;
+	if (!c || !dev_fb || !exposure || !key || !counted || !pngLayout(width, height, nullptr, 0u, &n, &headBytes, nullptr) || permille < 1u || permille > 1000u ||
+	    !(target > 0.0f) || !(target < __builtin_inff()))
+		return fail(CRH_ERR_INVALID, "crx_auto_exposure: bad argument (a context, a frame crx_png_pack takes, outputs; permille 1 .. 1000; a finite target > 0)");
+	const uint32_t pixels = (uint32_t)width * (uint32_t)height;
+	/* a workgroup a thousand pixels — four a lane — up to four workgroups a CU of the largest part: from one workgroup for 1 x 1 to a grid-stride pass */
+	const uint32_t blocks = zipMin((pixels + 1023u) / 1024u, 1024u);
+	HIP_TRY(hipSetDevice(c->device));
+	int rc;
+	if ((rc = c->dHist.grow(c->stream, CRX_HIST_BINS + 4u))) return rc;
+	if ((rc = growPinned(c, 4u * sizeof(uint32_t)))) return rc;
+	uint32_t *const result = c->dHist.p + CRX_HIST_BINS;
+	HIP_TRY(hipMemsetAsync(c->dHist.p, 0, CRX_HIST_BINS * sizeof(uint32_t), c->stream));
+	if ((rc = c->autoWatch.start(c->stream))) return rc;
+	hipLaunchKernelGGL(k_png_histogram, dim3(blocks), dim3(256), 0, c->stream, dev_fb, pixels, c->dHist.p);
+	HIP_TRY(hipGetLastError());
+	hipLaunchKernelGGL(k_png_pick, dim3(1), dim3(256), 0, c->stream, (const uint32_t *)c->dHist.p, permille, target, result);
+	HIP_TRY(hipGetLastError());
+	if ((rc = c->autoWatch.mark(c->stream))) return rc;
+	c->autoWatch.stop();
+	uint32_t *const got = (uint32_t *)c->pinned;
+	HIP_TRY(hipMemcpyAsync(got, result, 4u * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	memcpy(exposure, &got[0], sizeof(float));
+	memcpy(key, &got[1], sizeof(float));
+	*counted = got[2];
+	return CRH_OK;
+}
+
+int crx_auto_exposure_time_ms(crx_ctx *c, float *ms) {
+	if (!c || !ms) return fail(CRH_ERR_INVALID, "crx_auto_exposure_time_ms: NULL argument");
+	HIP_TRY(hipSetDevice(c->device));
+	const int rc = c->autoWatch.read();
+	if (rc) return rc;
+	*ms = c->autoWatch.sum;
 	return CRH_OK;
 }
 

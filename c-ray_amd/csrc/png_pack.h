@@ -4,6 +4,7 @@
  *
  * Seven launches on one stream, ordered by launch order alone, in the five phases crx_png_phases_ms reports:
  *   convert   k_png_convert   floats -> the 8-bit image on the device, once (srgb8.h: THE conversion, the bytes of crh_framebuffer_to_srgb8); a lane makes one word.
+ *                             crx_png_pack_display with a transform that is not the identity launches png_display.h's k_png_convert_display in its place.
  *   filter    k_png_choose    one wave per row: the five filters' sums of min(v, 256 - v) by wave reductions, the least wins, ties to the lowest type; a fixed
  *                             filter is written as it is. Every row's type in one launch.
  *             k_png_filter    F — per row the type byte, then the 3 W filtered bytes — as whole words, the way k_zip_transform builds T': a lane makes four
@@ -73,6 +74,9 @@ __global__ __launch_bounds__(256) void k_png_convert(const float *fb, uint32_t c
 	for (uint32_t b = 0; b < 4u && 4u * wi + b < count; ++b) out |= (uint32_t)crh::linearToSRGB8(fb[4u * (size_t)wi + b]) << (8u * b);
 	img[wi] = out;
 }
+
+/* crx_png_pack_display's convert (in k_png_convert's place when a display transform is asked for) and crx_auto_exposure's two kernels */
+#include "png_display.h"
 
 /* ---- filter ---- */
 /* the PNG specification's predictors for bpp = 3: a is the byte three to the left, b the byte above, c the one above a; bytes off the image count as 0 */

@@ -1,6 +1,7 @@
 """exrzip.py — thin ctypes binding of libcray_hip_exr.so (include/cray_hip_exr.h), the companion library of output codecs: the pixel data of a ZIP / ZIPS
-compressed scanline OpenEXR file, deflated on the device, FLOAT or per channel HALF, and the 8-bit frame as a complete PNG file (ZipContext.png). Plumbing: the work
-is in c-ray_amd/csrc/exr_zip.h and png_pack.h. The library loads on first use; there is no CPU
+compressed scanline OpenEXR file, deflated on the device, FLOAT or per channel HALF, and the 8-bit frame as a complete PNG file (ZipContext.png), optionally through a display
+transform (display=: exposure, tone curve, dither) at an exposure the device measures (ZipContext.auto_exposure). Plumbing: the work
+is in c-ray_amd/csrc/exr_zip.h, png_pack.h and png_display.h. The library loads on first use; there is no CPU
 fallback: `library()` raises if it has not been built, every call raises `CrhError` on a non-zero return code.
 """
 import ctypes as C
@@ -17,11 +18,35 @@ COMPRESSION = {"none": (0, 1), "zips": (2, 1), "zip": (3, 16)}          # name -
 CODES = {"fixed": 0, "dynamic": 1}          # name -> CRX_CODES_*
 PNG_FILTERS = {"adaptive": -1, "none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4}          # name -> crx_png_pack's filter
 PNG_PHASES = ("convert", "filter", "deflate", "crc + scan", "emit")
+CURVES = {"clamp": 0, "reinhard": 1, "aces": 2, "hable": 3}          # name -> CRX_CURVE_*
 
 
 class PngText(C.Structure):
     """crx_png_text: a tEXt chunk"""
     _fields_ = [("key", C.c_char_p), ("value", C.c_char_p)]
+
+
+class Display(C.Structure):
+    """crx_display: the display transform of crx_png_pack_display"""
+    _fields_ = [("exposure", C.c_float), ("curve", C.c_int), ("white", C.c_float), ("dither", C.c_int)]
+
+
+def display_of(display):
+    """The crx_display of `display`: a Display, None (the default: 1, clamp, 4, no dither) or a mapping with any of exposure, curve (a name of CURVES or its number),
+    white, dither. An unknown curve name or key raises ValueError; whether the values are in range is the library's to say."""
+    if isinstance(display, Display):
+        return display
+    d = Display()
+    library().crx_display_default(C.byref(d))
+    for key, value in dict(display or {}).items():
+        if key not in ("exposure", "curve", "white", "dither"):
+            raise ValueError(f"display: unknown key {key!r}")
+        if key == "curve" and isinstance(value, str):
+            if value not in CURVES:
+                raise ValueError(f"curve {value!r}: one of {sorted(CURVES)}")
+            value = CURVES[value]
+        setattr(d, key, int(value) if key in ("curve", "dither") else float(value))
+    return d
 
 
 def png_texts(text):
@@ -67,6 +92,11 @@ def library():
         "crx_png_bound": (C.c_int, [C.c_int, C.c_int, C.POINTER(PngText), C.c_uint32, C.POINTER(C.c_uint64)]),
         "crx_png_pack": (C.c_int, [ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(PngText), C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
         "crx_png_phases_ms": (C.c_int, [ctx, C.POINTER(C.c_float)]),
+        "crx_display_default": (None, [C.POINTER(Display)]),
+        "crx_png_pack_display": (C.c_int, [ctx, C.c_void_p, C.c_int, C.c_int, C.POINTER(Display), C.c_int, C.POINTER(PngText), C.c_uint32, C.c_void_p, C.c_uint64,
+                                           C.POINTER(C.c_uint64)]),
+        "crx_auto_exposure": (C.c_int, [ctx, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),
+        "crx_auto_exposure_time_ms": (C.c_int, [ctx, C.POINTER(C.c_float)]),
         "crx_debug_crc32": (C.c_int, [ctx, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32)]),
     }
     for name, (res, args) in sig.items():
@@ -159,10 +189,12 @@ class ZipContext:
         return self._pack("crx_pack", lambda arr, *out: self.L.crx_pack(self.h, arr, None if types is None else types.ctypes.data, n, width, height, first_row, rows, compression, *out),
                           channels, 4 * n if types is None else int(np.where(types == 1, 2, 4).sum()), width, 16 if compression == 3 else 1, rows)
 
-    def png(self, fb, width, height, filter="adaptive", text=()):
+    def png(self, fb, width, height, filter="adaptive", text=(), display=None):
         """crx_png_pack: the bytes of a complete PNG file of the device frame `fb` ([height, width, 3] floats, complete) — 8-bit sRGB, the bytes of
         Context.to_srgb8, filtered and deflated on the device under the context's codes setting. filter: a name of PNG_FILTERS ("adaptive": per row the type with
-        the least sum of min(v, 256 - v)) or its number -1 .. 4; text: tEXt chunks, a mapping or (key, value) pairs, Latin-1, keys of 1 .. 79 bytes."""
+        the least sum of min(v, 256 - v)) or its number -1 .. 4; text: tEXt chunks, a mapping or (key, value) pairs, Latin-1, keys of 1 .. 79 bytes. display: None —
+        crx_png_pack, as ever — or what display_of takes: exposure, a tone curve of CURVES, its white point and the ordered dither between the float and the
+        byte (crx_png_pack_display; the default display gives crx_png_pack's bytes)."""
         if isinstance(filter, str):
             if filter not in PNG_FILTERS:
                 raise ValueError(f"filter {filter!r}: one of {sorted(PNG_FILTERS)}")
@@ -171,8 +203,27 @@ class ZipContext:
         bound, total = C.c_uint64(0), C.c_uint64(0)
         _check(self.L.crx_png_bound(width, height, arr, count, C.byref(bound)), "crx_png_bound")
         out = np.empty(bound.value, np.uint8)
-        _check(self.L.crx_png_pack(self.h, fb, width, height, int(filter), arr, count, out.ctypes.data, bound.value, C.byref(total)), "crx_png_pack")
+        if display is None:
+            _check(self.L.crx_png_pack(self.h, fb, width, height, int(filter), arr, count, out.ctypes.data, bound.value, C.byref(total)), "crx_png_pack")
+        else:
+            d = display_of(display)
+            _check(self.L.crx_png_pack_display(self.h, fb, width, height, C.byref(d), int(filter), arr, count, out.ctypes.data, bound.value, C.byref(total)),
+                   "crx_png_pack_display")
         return out[:total.value].tobytes()
+
+    def auto_exposure(self, fb, width, height, permille=500, target=0.18):
+        """crx_auto_exposure: (exposure, key, counted) of the device frame `fb` — the exposure, as np.float32, that takes the bin midpoint `key` of the
+        permille / 1000 quantile of the pixels' luminances to `target`, limited to [2^-40, 2^40]; `counted` pixels have a finite luminance > 0. No such pixel:
+        (1, 0, 0). A function of the pixels and the arguments only."""
+        exposure, key, counted = C.c_float(0.0), C.c_float(0.0), C.c_uint64(0)
+        _check(self.L.crx_auto_exposure(self.h, fb, width, height, int(permille), float(target), C.byref(exposure), C.byref(key), C.byref(counted)), "crx_auto_exposure")
+        return np.float32(exposure.value), np.float32(key.value), int(counted.value)
+
+    def auto_exposure_time_ms(self):
+        """Milliseconds of the most recent auto_exposure's two kernels (waits for them)."""
+        ms = C.c_float(0.0)
+        _check(self.L.crx_auto_exposure_time_ms(self.h, C.byref(ms)), "crx_auto_exposure_time_ms")
+        return float(ms.value)
 
     def png_phases_ms(self):
         """Milliseconds per phase of the most recent png(): convert, filter, deflate, crc + scan, emit (PNG_PHASES; waits for it)."""

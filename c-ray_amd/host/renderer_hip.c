@@ -55,6 +55,9 @@
  * built on the device (crx_set_codes): the same pixels in a smaller file. Anything else or unset: the fixed codes.
  * CRAY_HIP_PNG=1 (user-facing): the frame on GPU 0 also as <imgFileName>_gpu_<count>.png, encoded on the device (writeGpuPng below: crx_png_pack), with tEXt chunks for the
  * sample and bounce counts, next to the frame's own file, which writeImage writes as ever. Dynamic codes unless CRAY_HIP_EXR_CODES=fixed. Unset: nothing of it runs.
+ * CRAY_HIP_PNG_EXPOSURE=<float>|auto, CRAY_HIP_PNG_TONEMAP=clamp|reinhard|aces|hable, CRAY_HIP_PNG_WHITE=<float>, CRAY_HIP_PNG_DITHER=1 beside it: the display
+ * transform of that file (crx_png_pack_display; auto: crx_auto_exposure takes the median luminance to 0.18), named in a third tEXt chunk "C-ray Display" and in the log.
+ * None set: the file of CRAY_HIP_PNG=1 alone, byte for byte. A bad value: a warning, and the file without a transform.
  * No GPU => logr(error, ...) (which exits, src/utils/logging.c:69-73): there is no CPU fallback in this file.
  */
 #include <stdlib.h>
@@ -921,14 +924,47 @@ static void writeLayers(struct renderer *r, crh_ctx *ctx, const float *fb, const
 
 /* CRAY_HIP_PNG=1: <imgFilePath><imgFileName>_gpu_<imgCount, four digits>.png — the frame on GPU 0 as a PNG converted, filtered, deflated and check-summed there
  * (crx_png_pack of libcray_hip_exr.so), with the tEXt chunks "C-ray Samples" and "C-ray Bounces". Written next to the frame's own file, not in its place: the
- * reference's writeImage runs untouched. CRAY_HIP_EXR_CODES=fixed applies; otherwise the codes are dynamic. Unset: nothing is allocated or written. */
+ * reference's writeImage runs untouched. CRAY_HIP_EXR_CODES=fixed applies; otherwise the codes are dynamic. Unset: nothing is allocated or written.
+ * CRAY_HIP_PNG_EXPOSURE / _TONEMAP / _WHITE / _DITHER: the display transform (crx_png_pack_display) and, where it is not the identity, the chunk "C-ray Display". */
 static void writeGpuPng(struct renderer *r, crh_ctx *ctx, const float *fb, int W, int H) {
 	struct timeval t;
 	startTimer(&t);
 	char samples[32], bounces[32];
 	snprintf(samples, sizeof(samples), "%i", r->prefs.sampleCount);
 	snprintf(bounces, sizeof(bounces), "%i", r->prefs.bounces);
-	const crx_png_text text[2] = {{"C-ray Samples", samples}, {"C-ray Bounces", bounces}};
+	char shown[192];
+	crx_png_text text[3] = {{"C-ray Samples", samples}, {"C-ray Bounces", bounces}, {"C-ray Display", shown}};
+	uint32_t texts = 2;
+	/* the display transform: any of the four variables asks for it; a bad value in one of them: a warning and the file without a transform */
+	static const char *const curveNames[4] = {"clamp", "reinhard", "aces", "hable"};
+	const char *envExposure = getenv("CRAY_HIP_PNG_EXPOSURE"), *envCurve = getenv("CRAY_HIP_PNG_TONEMAP"), *envWhite = getenv("CRAY_HIP_PNG_WHITE"),
+	           *envDither = getenv("CRAY_HIP_PNG_DITHER");
+	crx_display display;
+	crx_display_default(&display);
+	const bool autoExposure = envExposure && !strcmp(envExposure, "auto");
+	bool transform = envExposure || envCurve || envWhite || envDither, good = true;
+	char *end = NULL;
+	if (envExposure && !autoExposure) {
+		display.exposure = strtof(envExposure, &end);
+		good = good && end != envExposure && !*end && display.exposure >= 0x1p-40f && display.exposure <= 0x1p40f;
+	}
+	if (envCurve) {
+		display.curve = -1;
+		for (int i = 0; i < 4; ++i) if (!strcmp(envCurve, curveNames[i])) display.curve = i;
+		good = good && display.curve >= 0;
+	}
+	if (envWhite) {
+		display.white = strtof(envWhite, &end);
+		good = good && end != envWhite && !*end && display.white >= 0x1p-10f && display.white <= 0x1p10f;
+	}
+	if (envDither) {
+		display.dither = !strcmp(envDither, "1");
+		good = good && (display.dither || !strcmp(envDither, "0"));
+	}
+	if (transform && !good) {
+		logr(warning, "c-ray-hip: a bad value among CRAY_HIP_PNG_EXPOSURE / _TONEMAP / _WHITE / _DITHER; the GPU PNG is written without a display transform\n");
+		transform = false;
+	}
 	const char *base = r->prefs.imgFileName ? r->prefs.imgFileName : "rendered";
 	const char *dir = r->prefs.imgFilePath ? r->prefs.imgFilePath : "";
 	const char *codes = getenv("CRAY_HIP_EXR_CODES");
@@ -937,11 +973,23 @@ static void writeGpuPng(struct renderer *r, crh_ctx *ctx, const float *fb, int W
 	crx_ctx *png = NULL;
 	char *path = malloc(strlen(dir) + strlen(base) + 32);
 	void *file = NULL;
-	bool ok = path && crx_png_bound(W, H, text, 2, &bound) == CRH_OK && (file = malloc((size_t)bound)) != NULL;
+	bool ok = path != NULL;
 	if (ok && crh_synchronize(ctx) != CRH_OK) { ok = false; why = crh_last_error(); }          /* the companion's stream is its own: the frame must be complete */
 	if (ok && crx_context_create(0, NULL, &png) != CRH_OK) { ok = false; why = crx_last_error(); }
 	if (ok && crx_set_codes(png, codes && !strcmp(codes, "fixed") ? CRX_CODES_FIXED : CRX_CODES_DYNAMIC) != CRH_OK) { ok = false; why = crx_last_error(); }
-	if (ok && crx_png_pack(png, fb, W, H, CRX_PNG_FILTER_ADAPTIVE, text, 2, file, bound, &total) != CRH_OK) { ok = false; why = crx_last_error(); }
+	if (ok && transform && autoExposure) {          /* the exposure that takes the median luminance to 0.18, measured on the device */
+		float key = 0.0f;
+		uint64_t counted = 0;
+		if (crx_auto_exposure(png, fb, W, H, 500u, 0.18f, &display.exposure, &key, &counted) != CRH_OK) { ok = false; why = crx_last_error(); }
+	}
+	if (ok && transform && (display.exposure != 1.0f || display.curve != CRX_CURVE_CLAMP || display.dither)) {
+		snprintf(shown, sizeof(shown), "exposure=%.9g%s curve=%s white=%.9g dither=%d", (double)display.exposure, autoExposure ? " (auto 500/1000 of 0.18)" : "",
+			curveNames[display.curve], (double)display.white, display.dither);
+		texts = 3;
+		logr(info, "GPU PNG display transform: %s\n", shown);
+	}
+	if (ok && !(crx_png_bound(W, H, text, texts, &bound) == CRH_OK && (file = malloc((size_t)bound)) != NULL)) { ok = false; why = "out of memory"; }
+	if (ok && crx_png_pack_display(png, fb, W, H, transform ? &display : NULL, CRX_PNG_FILTER_ADAPTIVE, text, texts, file, bound, &total) != CRH_OK) { ok = false; why = crx_last_error(); }
 	float phases[CRX_PNG_PHASES] = {0};
 	if (ok) (void)crx_png_phases_ms(png, phases);
 	crx_context_destroy(png);

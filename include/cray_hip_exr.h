@@ -1,6 +1,7 @@
 /*
  * cray_hip_exr.h — the C-ABI of libcray_hip_exr.so, the companion library of the output codecs: what leaves the product as a file and needs no scene, no path
- * state and nothing of the render path. Its second codec is the 8-bit frame as a PNG file (crx_png_pack, below). Its first: the pixel data of a ZIP- or ZIPS-compressed scanline OpenEXR file, deflated on the device
+ * state and nothing of the render path. Its second codec is the 8-bit frame as a PNG file (crx_png_pack, below), optionally through a display transform — exposure, a tone curve, a dither
+ * (crx_png_pack_display) — at an exposure the device can measure from the frame (crx_auto_exposure). Its first: the pixel data of a ZIP- or ZIPS-compressed scanline OpenEXR file, deflated on the device
  * from the buffers libcray_hip.so already makes (c-ray_amd/csrc/exr_zip.h) — all FLOAT (crx_pack_zip), or with a pixel type per channel, FLOAT or HALF (crx_pack). Plain C, int return codes: 0 (CRH_OK) is ok, the negative CRH_ERR_* values of cray_hip.h
  * are reused, crx_last_error() holds the text of the calling thread's last failure. There is NO CPU path: without a HIP device crx_context_create answers
  * CRH_ERR_NO_DEVICE. A context belongs to one device and one stream and is used by one thread at a time.
@@ -131,6 +132,65 @@ int crx_png_pack(crx_ctx *ctx, const float *dev_fb, int width, int height, int f
  * 0 before the first call. */
 #define CRX_PNG_PHASES 5
 int crx_png_phases_ms(crx_ctx *ctx, float phases_ms[CRX_PNG_PHASES]);
+
+/* ---- the display transform of the PNG: exposure, a tone curve, an ordered dither (c-ray_amd/csrc/png_display.h) ----
+ * crx_png_pack_display is crx_png_pack with an optional transform between the frame's float and the sRGB byte. Everything else of crx_png_pack's contract carries
+ * over word for word: the file's form, the filters and the adaptive choice, the IDAT data and the codes setting, crx_png_bound (unchanged), determinism (the bytes are
+ * a function of the arguments, the pixels and the codes setting only), tEXt, the copy out. crx_png_phases_ms reports the transform under [0] convert.
+ *
+ * Per component c of the frame (finite, >= 0, as for crx_png_pack), in float32 arithmetic, in this order of operations, nothing contracted into a fused multiply-add:
+ *   x = exposure * c
+ *   for every curve but CLAMP: x = x < 1048576.0f ? x : 1048576.0f          (2^20: past it every curve's byte is 255)
+ *   CRX_CURVE_CLAMP     y = x                                                (no limit: linearToSRGB8 saturates)
+ *   CRX_CURVE_REINHARD  y = (x * (1 + x / (white * white))) / (1 + x)        (extended Reinhard: `white` maps to 1)
+ *   CRX_CURVE_ACES      y = (x * (2.51f * x + 0.03f)) / (x * (2.43f * x + 0.59f) + 0.14f)          (the Narkowicz fit)
+ *   CRX_CURVE_HABLE     h(v) = (v * (0.15f * v + 0.05f) + 0.004f) / (v * (0.15f * v + 0.5f) + 0.06f) - 0.02f / 0.3f;  y = h(2 * x) / h(2 * white)
+ *   t = linearToSRGB(y) * 255.0f                                             (c-ray_amd/csrc/srgb8.h, unchanged)
+ * white * white and h(2 * white) are computed once, on the host, by the same float32 statements. No curve gives a NaN, an infinity or a negative value for
+ * parameters in range and x <= 2^20. The curves are not strictly monotone in float32: they step down by an ulp or two here and there.
+ * The byte. dither == 0: (unsigned char)(t < 255 ? t : 255), crx_png_pack's rule. dither == 1, ordered, 8 x 8:
+ *   t' = t + ((float)B(col & 7, row & 7) - 31.5f) / 64.0f;   byte = t' < 0 ? 0 : t' < 255 ? (unsigned char)t' : 255
+ * with `row` the stored row, the same offset for the three components of a pixel, and B the Bayer index matrix built bit by bit: for i = 0, 1, 2, bit
+ * 2 (2 - i) + 1 of B(x, y) is bit i of x ^ y and bit 2 (2 - i) is bit i of y. B(x, y), one row per y:
+ *    0 32  8 40  2 34 10 42
+ *   48 16 56 24 50 18 58 26
+ *   12 44  4 36 14 46  6 38
+ *   60 28 52 20 62 30 54 22
+ *    3 35 11 43  1 33  9 41
+ *   51 19 59 27 49 17 57 25
+ *   15 47  7 39 13 45  5 37
+ *   63 31 55 23 61 29 53 21
+ * The offset is centred: its mean is 0, so the mean byte of a flat t is t - 0.5, the truncating rule's own; t = 100.25 gives 48 pixels of 100 and 16 of 99 in every
+ * 8 x 8 block.
+ * Ranges: exposure in [2^-40, 2^40], white in [2^-10, 2^10], both finite; curve one of the four; dither 0 or 1.
+ * Identity: with display NULL, or exposure == 1, CRX_CURVE_CLAMP and dither == 0 (whatever `white`), the file is byte for byte crx_png_pack's.
+ * CRH_ERR_INVALID, nothing written anywhere and the frame never written: everything crx_png_pack refuses; a curve outside 0 .. 3; an exposure or a white outside its
+ * range, or a NaN; a dither other than 0 or 1. */
+#define CRX_CURVE_CLAMP 0
+#define CRX_CURVE_REINHARD 1
+#define CRX_CURVE_ACES 2
+#define CRX_CURVE_HABLE 3
+typedef struct { float exposure; int curve; float white; int dither; } crx_display;
+void crx_display_default(crx_display *d);          /* 1, CRX_CURVE_CLAMP, 4, 0; a NULL d: nothing */
+int crx_png_pack_display(crx_ctx *ctx, const float *dev_fb, int width, int height, const crx_display *display /* NULL: the default */, int filter,
+                         const crx_png_text *text, uint32_t text_count, void *host_out, uint64_t capacity, uint64_t *total_bytes);
+
+/* An exposure measured from the frame on the device: the one that takes the `permille` / 1000 quantile of the pixels' luminances to `target`.
+ *   Luminance per pixel: L = ((0.2126f * r) + (0.7152f * g)) + (0.0722f * b), in float32, in that order.
+ *   A pixel counts iff L is finite and > 0. Its bin is bits(L) >> 19 — sign 0, the 8 exponent bits, 4 mantissa bits: sixteen bins an octave, 4 096 bins of uint32,
+ *   the largest one in use 4079.
+ *   *counted = N, the number of pixels that count. The rank r = (N * permille + 999) / 1000 in 64-bit integers; the key bin k is the smallest bin whose cumulative
+ *   count is >= r; *key is the float with the bits (k << 19) | (1 << 18), the bin's midpoint (0.18 lies in bin 1991, whose key is 0.18359375).
+ *   *exposure = target / key, one float32 division, then limited to [2^-40, 2^40]. N == 0: *exposure = 1, *key = 0.
+ * A percentile, not the log-average: it needs no transcendental function, so it restates bit for bit, and fireflies do not move it.
+ * Determinism. Integer counts do not depend on the order they are added in: the result is a function of the pixels and the arguments only — not of scheduling, of
+ * the number of CUs, or of earlier calls.
+ * CRH_ERR_INVALID, nothing written anywhere: a NULL context, frame, exposure, key or counted; width or height <= 0, or a frame crx_png_pack refuses for its size;
+ * permille 0 or above 1000; a target that is a NaN, <= 0 or infinite.
+ * The call launches behind whatever is queued on the context's stream and waits; the frame must be complete (as for crx_png_pack). crx_auto_exposure_time_ms: the
+ * last complete call's kernel time between the library's own events (waits for it), 0 before the first. */
+int crx_auto_exposure(crx_ctx *ctx, const float *dev_fb, int width, int height, uint32_t permille, float target, float *exposure, float *key, uint64_t *counted);
+int crx_auto_exposure_time_ms(crx_ctx *ctx, float *ms);
 
 /* ---- debug ---- */
 /* The code construction of CRX_CODES_DYNAMIC on histograms of the caller's: `count` histograms of `symbols` counts each in freq (host memory), one wave a
