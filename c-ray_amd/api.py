@@ -575,6 +575,15 @@ class Context:
             setattr(p, k, v)
         _check(self.L.crh_denoise_variance(self.h, C.byref(p), fb, half, aov, fb if out is None else out), "crh_denoise_variance")
 
+    def despeckle(self, fb, width, height, also=(), **params):
+        """The firefly filter in front of a denoiser (include/cray_hip_exr.h: crx_despeckle): every pixel of `fb` brighter than factor * (the rank-th largest
+        luminance among its neighbours within radius) + floor is scaled down to that limit, NaN and infinite pixels become 0. CHANGES `fb` IN PLACE — it removes
+        energy: copy_framebuffer first to keep the original, and filter the copy — and scales every frame of `also` (the half-sample buffer of denoise_variance)
+        by the same per-pixel plane. params: radius, rank, factor, floor (2, 4, 4, 2^-6 otherwise); an unknown name raises TypeError. Waits for this context's
+        stream, runs on the companion library's context and waits for it. Returns the stats: clamped, bad, max_clamped, min_scale."""
+        self.synchronize()
+        return self._zip_context().despeckle(fb, width, height, (fb,) + tuple(also), **params)
+
     def copy_framebuffer(self, src, dst, width, height):
         """dst = src on the device, in stream order (crh_framebuffer_copy)."""
         _check(self.L.crh_framebuffer_copy(self.h, src, dst, width, height), "crh_framebuffer_copy")

@@ -30,7 +30,7 @@ OUT_DIR = os.path.join(HERE, "_lib")
 LIB = os.path.join(OUT_DIR, "libcray_hip.so")
 EXR_LIB = os.path.join(OUT_DIR, "libcray_hip_exr.so")
 EXR_SOURCES = [os.path.join(CSRC, "exr_zip.hip")]
-EXR_DEPS = EXR_SOURCES + [os.path.join(CSRC, "exr_zip.h"), os.path.join(CSRC, "png_pack.h"), os.path.join(CSRC, "png_display.h"), os.path.join(CSRC, "srgb8.h"), os.path.join(CSRC, "exact_math.h"),
+EXR_DEPS = EXR_SOURCES + [os.path.join(CSRC, "exr_zip.h"), os.path.join(CSRC, "png_pack.h"), os.path.join(CSRC, "png_display.h"), os.path.join(CSRC, "despeckle.h"), os.path.join(CSRC, "srgb8.h"), os.path.join(CSRC, "exact_math.h"),
                           os.path.join(CSRC, "ctx_buffers.h"), os.path.join(REPO, "include", "cray_hip_exr.h"), os.path.join(REPO, "include", "cray_hip.h")]
 
 SOURCES = [os.path.join(CSRC, "cray_hip.hip"), os.path.join(CSRC, "bvh_build.hip")]

@@ -1,7 +1,7 @@
 /*
  * exr_zip.hip — libcray_hip_exr.so: the C-ABI of include/cray_hip_exr.h around the kernels of exr_zip.h (the layers file's chunks) and of png_pack.h (the 8-bit
  * frame as a PNG, which shares exr_zip.h's deflate and, through srgb8.h, the product's float-to-byte rule; png_display.h beside it: the display transform and the
- * automatic exposure). A translation unit of its own: it shares no state with
+ * automatic exposure; despeckle.h: the firefly filter, which is no codec but needs no scene either). A translation unit of its own: it shares no state with
  * libcray_hip.so and includes of it only what is plain HIP runtime bookkeeping (ctx_buffers.h: DevBuf, Stopwatch) and the channel descriptor (cray_hip.h).
  */
 #include <hip/hip_runtime.h>
@@ -20,6 +20,7 @@ int fail(int code, const std::string &what) { g_error = what; return code; }
 #include "ctx_buffers.h"
 #include "exr_zip.h"
 #include "png_pack.h"
+#include "despeckle.h"
 
 struct crx_ctx {
 	int device = 0;
@@ -36,6 +37,9 @@ struct crx_ctx {
 	Stopwatch<CRX_PNG_PHASES> pngWatch;
 	DevBuf<uint32_t> dHist;                              /* crx_auto_exposure: the CRX_HIST_BINS bins, then k_png_pick's four result words */
 	Stopwatch<1> autoWatch;
+	DevBuf<uint32_t> dScale;                             /* crx_despeckle: the scale plane, rounded up to four floats, then the four stats words */
+	int scaleWidth = 0, scaleHeight = 0;                 /* ... of the last complete call; 0 before it */
+	Stopwatch<2> despeckleWatch;
 	int codes = CRX_CODES_FIXED;                         /* crx_set_codes */
 };
 
@@ -85,6 +89,7 @@ int crx_context_destroy(crx_ctx *c) {
 	c->watch.release();
 	c->dImg.release(); c->dTypes.release(); c->pngWatch.release();
 	c->dHist.release(); c->autoWatch.release();
+	c->dScale.release(); c->despeckleWatch.release();
 	if (c->ownStream) (void)hipStreamDestroy(c->stream);
 	delete c;
 	return CRH_OK;
@@ -449,6 +454,75 @@ int crx_auto_exposure_time_ms(crx_ctx *c, float *ms) {
 	const int rc = c->autoWatch.read();
 	if (rc) return rc;
 	*ms = c->autoWatch.sum;
+	return CRH_OK;
+}
+
+void crx_despeckle_default(crx_despeckle_params *p) {
+	if (!p) return;
+	p->radius = 2; p->rank = 4; p->factor = 4.0f; p->floor = 0x1p-6f;
+}
+
+int crx_despeckle(crx_ctx *c, const crx_despeckle_params *params, const float *dev_guide, int width, int height, float *const *dev_frames, uint32_t frame_count,
+                  crx_despeckle_stats *stats) {
+	crx_despeckle_params p;
+	crx_despeckle_default(&p);
+	if (params) p = *params;
+	uint64_t n = 0, headBytes = 0;
+	bool ok = c && dev_guide && pngLayout(width, height, nullptr, 0u, &n, &headBytes, nullptr) && (p.radius == 1 || p.radius == 2) && p.rank >= 1 &&
+	          p.rank <= (2 * p.radius + 1) * (2 * p.radius + 1) - 1 && p.factor >= 1.0f && p.factor <= CRX_DESPECKLE_FACTOR_MAX && p.floor >= 0.0f &&
+	          p.floor <= CRX_DESPECKLE_FLOOR_MAX && frame_count <= CRX_DESPECKLE_MAX_FRAMES && (dev_frames || !frame_count);          /* (a NaN fails every comparison) */
+	for (uint32_t i = 0; ok && i < frame_count; ++i) ok = dev_frames[i] != nullptr;
+	if (!ok)
+		return fail(CRH_ERR_INVALID, "crx_despeckle: bad argument (a context, a guide frame crx_png_pack takes; radius 1 or 2, rank 1 .. (2 radius + 1)^2 - 1, a factor in "
+		                             "[1, 2^20], a floor in [0, 2^20]; at most 8 frames, none NULL)");
+	const uint32_t pixels = (uint32_t)width * (uint32_t)height, planeWords = (pixels + 3u) / 4u * 4u;
+	const uint32_t tilesX = ((uint32_t)width + DS_TILE_W - 1u) / DS_TILE_W, tilesY = ((uint32_t)height + DS_TILE_H - 1u) / DS_TILE_H;          /* (tilesX * tilesY <= pixels < 2^30) */
+	const DsParams P = {p.factor, p.floor, (uint32_t)p.rank};
+	HIP_TRY(hipSetDevice(c->device));
+	int rc;
+	c->scaleWidth = c->scaleHeight = 0;
+	if ((rc = c->dScale.grow(c->stream, (size_t)planeWords + 4u))) return rc;
+	if ((rc = growPinned(c, 8u * sizeof(uint32_t)))) return rc;
+	float *const plane = (float *)c->dScale.p;
+	uint32_t *const devStats = c->dScale.p + planeWords, *const init = (uint32_t *)c->pinned, *const got = init + 4;
+	init[0] = 0u; init[1] = 0u; init[2] = 0u; init[3] = 0x3f800000u;          /* no clamped pixel: max_clamped 0, min_scale 1 */
+	HIP_TRY(hipMemcpyAsync(devStats, init, 4u * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	if ((rc = c->despeckleWatch.start(c->stream))) return rc;
+	if (p.radius == 1) hipLaunchKernelGGL(k_despeckle_measure<1>, dim3(tilesX * tilesY), dim3(256), 0, c->stream, dev_guide, (uint32_t)width, (uint32_t)height, tilesX, P, plane, devStats);
+	else hipLaunchKernelGGL(k_despeckle_measure<2>, dim3(tilesX * tilesY), dim3(256), 0, c->stream, dev_guide, (uint32_t)width, (uint32_t)height, tilesX, P, plane, devStats);
+	HIP_TRY(hipGetLastError());
+	if ((rc = c->despeckleWatch.mark(c->stream))) return rc;
+	for (uint32_t i = 0; i < frame_count; ++i) {          /* in stream order behind the measure launch: the guide may be among the frames */
+		hipLaunchKernelGGL(k_despeckle_apply, dim3((pixels + 1023u) / 1024u), dim3(256), 0, c->stream, (const float *)plane, pixels, dev_frames[i]);
+		HIP_TRY(hipGetLastError());
+	}
+	if ((rc = c->despeckleWatch.mark(c->stream))) return rc;
+	c->despeckleWatch.stop();
+	HIP_TRY(hipMemcpyAsync(got, devStats, 4u * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	c->scaleWidth = width; c->scaleHeight = height;
+	if (stats) {
+		stats->clamped = got[0]; stats->bad = got[1];
+		memcpy(&stats->max_clamped, &got[2], sizeof(float));
+		memcpy(&stats->min_scale, &got[3], sizeof(float));
+	}
+	return CRH_OK;
+}
+
+int crx_despeckle_scale(crx_ctx *c, float *host_scale) {
+	if (!c || !host_scale || c->scaleWidth <= 0) return fail(CRH_ERR_INVALID, "crx_despeckle_scale: bad argument (a context with a complete crx_despeckle behind it, an output)");
+	HIP_TRY(hipSetDevice(c->device));
+	HIP_TRY(hipMemcpyAsync(host_scale, c->dScale.p, (size_t)c->scaleWidth * (size_t)c->scaleHeight * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	return CRH_OK;
+}
+
+int crx_despeckle_time_ms(crx_ctx *c, float ms[2]) {
+	if (!c || !ms) return fail(CRH_ERR_INVALID, "crx_despeckle_time_ms: NULL argument");
+	HIP_TRY(hipSetDevice(c->device));
+	const int rc = c->despeckleWatch.read();
+	if (rc) return rc;
+	for (int i = 0; i < 2; ++i) ms[i] = i < c->despeckleWatch.laps ? c->despeckleWatch.ms[i] : 0.0f;
 	return CRH_OK;
 }
 

@@ -1,7 +1,8 @@
 """exrzip.py — thin ctypes binding of libcray_hip_exr.so (include/cray_hip_exr.h), the companion library of output codecs: the pixel data of a ZIP / ZIPS
 compressed scanline OpenEXR file, deflated on the device, FLOAT or per channel HALF, and the 8-bit frame as a complete PNG file (ZipContext.png), optionally through a display
-transform (display=: exposure, tone curve, dither) at an exposure the device measures (ZipContext.auto_exposure). Plumbing: the work
-is in c-ray_amd/csrc/exr_zip.h, png_pack.h and png_display.h. The library loads on first use; there is no CPU
+transform (display=: exposure, tone curve, dither) at an exposure the device measures (ZipContext.auto_exposure); and, no codec but at home here because it needs
+no scene, the firefly filter in front of the denoisers (ZipContext.despeckle). Plumbing: the work
+is in c-ray_amd/csrc/exr_zip.h, png_pack.h, png_display.h and despeckle.h. The library loads on first use; there is no CPU
 fallback: `library()` raises if it has not been built, every call raises `CrhError` on a non-zero return code.
 """
 import ctypes as C
@@ -29,6 +30,16 @@ class PngText(C.Structure):
 class Display(C.Structure):
     """crx_display: the display transform of crx_png_pack_display"""
     _fields_ = [("exposure", C.c_float), ("curve", C.c_int), ("white", C.c_float), ("dither", C.c_int)]
+
+
+class DespeckleParams(C.Structure):
+    """crx_despeckle_params: the firefly filter's rule"""
+    _fields_ = [("radius", C.c_int), ("rank", C.c_int), ("factor", C.c_float), ("floor", C.c_float)]
+
+
+class DespeckleStats(C.Structure):
+    """crx_despeckle_stats"""
+    _fields_ = [("clamped", C.c_uint64), ("bad", C.c_uint64), ("max_clamped", C.c_float), ("min_scale", C.c_float)]
 
 
 def display_of(display):
@@ -98,6 +109,10 @@ def library():
         "crx_auto_exposure": (C.c_int, [ctx, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),
         "crx_auto_exposure_time_ms": (C.c_int, [ctx, C.POINTER(C.c_float)]),
         "crx_debug_crc32": (C.c_int, [ctx, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32)]),
+        "crx_despeckle_default": (None, [C.POINTER(DespeckleParams)]),
+        "crx_despeckle": (C.c_int, [ctx, C.POINTER(DespeckleParams), C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(DespeckleStats)]),
+        "crx_despeckle_scale": (C.c_int, [ctx, C.c_void_p]),
+        "crx_despeckle_time_ms": (C.c_int, [ctx, C.POINTER(C.c_float)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -224,6 +239,40 @@ class ZipContext:
         ms = C.c_float(0.0)
         _check(self.L.crx_auto_exposure_time_ms(self.h, C.byref(ms)), "crx_auto_exposure_time_ms")
         return float(ms.value)
+
+    def despeckle(self, guide, width, height, frames=(), **params):
+        """crx_despeckle: the firefly filter. Measures from the device frame `guide` ([height, width, 3] floats, complete) the plane of scales that takes every
+        pixel brighter than factor * (the rank-th largest luminance of its neighbours within radius) + floor down to that limit, and multiplies every device frame
+        of `frames` (at most 8; `guide` may be among them) by it IN PLACE; without frames it only measures. params: radius, rank, factor, floor
+        (crx_despeckle_default otherwise: 2, 4, 4, 2^-6); an unknown name raises TypeError. Returns the stats: clamped and bad pixel counts, max_clamped (the
+        largest luminance clamped, 0 if none) and min_scale (the smallest scale of a clamped pixel, 1 if none), the floats as np.float32. Waits."""
+        p = DespeckleParams()
+        self.L.crx_despeckle_default(C.byref(p))
+        for k, v in params.items():
+            if k not in ("radius", "rank", "factor", "floor"):
+                raise TypeError(f"despeckle() got an unexpected parameter {k!r}")
+            setattr(p, k, int(v) if k in ("radius", "rank") else float(v))
+        frames = list(frames)
+        arr = (C.c_void_p * max(len(frames), 1))(*frames)
+        stats = DespeckleStats()
+        _check(self.L.crx_despeckle(self.h, C.byref(p), guide, width, height, arr if frames else None, len(frames), C.byref(stats)), "crx_despeckle")
+        self._despeckled = (int(width), int(height))
+        return dict(clamped=int(stats.clamped), bad=int(stats.bad), max_clamped=np.float32(stats.max_clamped), min_scale=np.float32(stats.min_scale))
+
+    def despeckle_scale(self, width, height):
+        """crx_despeckle_scale: the plane of scales of the last despeckle() on this context, float32 [height, width] — its own size, anything else raises
+        ValueError: 1 where the pixel stayed, 0 where it was bad, the factor below 1 where it was clamped."""
+        if getattr(self, "_despeckled", None) != (int(width), int(height)):
+            raise ValueError(f"despeckle_scale({width}, {height}): the last despeckle() on this context was {getattr(self, '_despeckled', None)}")
+        out = np.empty((height, width), np.float32)
+        _check(self.L.crx_despeckle_scale(self.h, out.ctypes.data), "crx_despeckle_scale")
+        return out
+
+    def despeckle_time_ms(self):
+        """Milliseconds of the most recent despeckle(): (the measure kernel, the apply kernels summed over the frames); waits for them."""
+        ms = (C.c_float * 2)()
+        _check(self.L.crx_despeckle_time_ms(self.h, ms), "crx_despeckle_time_ms")
+        return float(ms[0]), float(ms[1])
 
     def png_phases_ms(self):
         """Milliseconds per phase of the most recent png(): convert, filter, deflate, crc + scan, emit (PNG_PHASES; waits for it)."""

@@ -39,6 +39,10 @@
  * dumps its floats. The frame, its image and the returned texture are untouched. CRAY_HIP_DENOISE_VARIANCE=1 beside it: the filter is crh_denoise_variance — every GPU
  * thread ends a dispatch exactly at pass sampleCount / 2 and keeps a copy of its frame buffer there (crh_framebuffer_copy), the copies are assembled on GPU 0 like
  * the frame; consecutive pass ranges compose bit for bit, so the frame is the one of a run without the variable.
+ * CRAY_HIP_DESPECKLE=<factor> beside CRAY_HIP_DENOISE (user-facing; CRAY_HIP_DESPECKLE_RANK, _RADIUS, _FLOOR beside it): the denoiser reads a despeckled copy of the
+ * frame — and of the half-sample frame, under the same plane — in which fireflies are scaled down to a rank of their neighbourhood (crx_despeckle of
+ * libcray_hip_exr.so; despeckledCopies below). The frame, its image, the returned texture, R G B of the layers file and the GPU PNG stay as they are. Without
+ * CRAY_HIP_DENOISE: a warning and no effect. A bad value: a warning and the plain denoise. Unset: nothing of it runs.
  * CRAY_HIP_ADAPTIVE=<threshold> (user-facing; CRAY_HIP_ADAPTIVE_MIN=<m>, default 16): adaptive sampling at tile granularity — every GPU thread hands its rectangles
  * (one GPU: the scene's tileWidth x tileHeight grid; several: its strips cut every tileWidth columns) to crh_render_adaptive, which gives every rectangle m passes
  * and doubles that until its error is at most the threshold or sampleCount is reached; a sampleCount that is not m 2^r: a warning and the uniform frame.
@@ -752,6 +756,61 @@ static void writeAovs(struct renderer *r, crh_ctx *ctx, int W, int H, float **ke
  * crh_denoise_variance (CRAY_HIP_DENOISE_VARIANCE=1) — into a second buffer with guides rendered here — CRAY_HIP_AOV's n passes if that
  * is set, min(16, sampleCount) otherwise —, written as <imgFileName>_denoised beside the frame (8-bit exactly as the frame's: crh_framebuffer_to_srgb8, then the
  * reference's newImageFile / writeImage); CRH_DUMP_DENOISED_F32=<path> dumps the [H, W, 3] floats. Unset: nothing is allocated, nothing is written. */
+/* CRAY_HIP_DESPECKLE=<factor> beside CRAY_HIP_DENOISE (CRAY_HIP_DESPECKLE_RANK / _RADIUS / _FLOOR beside it; crx_despeckle's defaults otherwise): the denoiser's
+ * input becomes a despeckled COPY of the frame — fireflies scaled down to factor * a rank of their neighbourhood + floor (include/cray_hip_exr.h) —, and with
+ * `half` a copy of the half-sample frame under the same plane. The copies are the caller's to free (crh_framebuffer_free). The frame and `half` are only read.
+ * False — unset, a bad value (a warning), or a failure (a warning) —: no copy is left behind and the denoiser takes the frame as it is. */
+static bool despeckledCopies(crh_ctx *ctx, const float *fb, const float *half, int W, int H, float **fbCopy, float **halfCopy) {
+	const char *envFactor = getenv("CRAY_HIP_DESPECKLE"), *envRank = getenv("CRAY_HIP_DESPECKLE_RANK"), *envRadius = getenv("CRAY_HIP_DESPECKLE_RADIUS"),
+	           *envFloor = getenv("CRAY_HIP_DESPECKLE_FLOOR");
+	if (!envFactor) return false;
+	crx_despeckle_params p;
+	crx_despeckle_default(&p);
+	char *end = NULL;
+	p.factor = strtof(envFactor, &end);
+	bool good = end != envFactor && !*end && p.factor >= 1.0f && p.factor <= 0x1p20f;
+	if (envRadius) {
+		const long v = strtol(envRadius, &end, 10);
+		good = good && end != envRadius && !*end && (v == 1 || v == 2);
+		p.radius = (int)v;
+	}
+	if (envRank) {
+		const long v = strtol(envRank, &end, 10);
+		good = good && end != envRank && !*end && v >= 1 && v <= (2 * p.radius + 1) * (2 * p.radius + 1) - 1;
+		p.rank = (int)v;
+	}
+	if (envFloor) {
+		p.floor = strtof(envFloor, &end);
+		good = good && end != envFloor && !*end && p.floor >= 0.0f && p.floor <= 0x1p20f;
+	}
+	if (!good) {
+		logr(warning, "c-ray-hip: a bad value among CRAY_HIP_DESPECKLE / _RANK / _RADIUS / _FLOOR; the frame is denoised as it is\n");
+		return false;
+	}
+	const char *why = NULL;
+	crx_ctx *zip = NULL;
+	crx_despeckle_stats stats;
+	float ms[2] = {0.0f, 0.0f};
+	bool ok = crh_framebuffer_alloc(ctx, W, H, fbCopy) == CRH_OK && crh_framebuffer_copy(ctx, fb, *fbCopy, W, H) == CRH_OK &&
+		(!half || (crh_framebuffer_alloc(ctx, W, H, halfCopy) == CRH_OK && crh_framebuffer_copy(ctx, half, *halfCopy, W, H) == CRH_OK)) &&
+		crh_synchronize(ctx) == CRH_OK;          /* the companion's stream is its own: the copies must be complete */
+	if (!ok) why = crh_last_error();
+	if (ok && crx_context_create(0, NULL, &zip) != CRH_OK) { ok = false; why = crx_last_error(); }
+	float *frames[2] = {*fbCopy, *halfCopy};
+	if (ok && (crx_despeckle(zip, &p, *fbCopy, W, H, frames, half ? 2u : 1u, &stats) != CRH_OK || crx_despeckle_time_ms(zip, ms) != CRH_OK)) { ok = false; why = crx_last_error(); }
+	crx_context_destroy(zip);
+	if (ok) {
+		logr(info, "Despeckled the denoiser's input (radius %i, rank %i, factor %g, floor %g): %llu pixels clamped, %llu bad, brightest %g, %.3f ms.\n", p.radius, p.rank,
+			(double)p.factor, (double)p.floor, (unsigned long long)stats.clamped, (unsigned long long)stats.bad, (double)stats.max_clamped, (double)(ms[0] + ms[1]));
+		return true;
+	}
+	logr(warning, "c-ray-hip: the frame could not be despeckled (%s); it is denoised as it is\n", why ? why : "unknown");
+	if (*fbCopy) crh_framebuffer_free(ctx, *fbCopy);
+	if (*halfCopy) crh_framebuffer_free(ctx, *halfCopy);
+	*fbCopy = *halfCopy = NULL;
+	return false;
+}
+
 /* `keep` (CRAY_HIP_EXR): where the denoised device buffer goes instead of being freed — it is the caller's then. */
 static void writeDenoised(struct renderer *r, crh_ctx *ctx, const float *fb, const float *half, int halfPasses, int W, int H, float **keep) {
 	const char *e = getenv("CRAY_HIP_DENOISE");
@@ -777,11 +836,18 @@ static void writeDenoised(struct renderer *r, crh_ctx *ctx, const float *fb, con
 	crh_denoise_variance_params_default(&dv, halfPasses, r->prefs.sampleCount);
 	dv.width = W; dv.height = H; dv.iterations = iterations;
 	float ms = 0.0f;
+	float *cleanFb = NULL, *cleanHalf = NULL;          /* CRAY_HIP_DESPECKLE: the filter reads despeckled copies; the frame stays as it is */
+	if (host && despeckledCopies(ctx, fb, half, W, H, &cleanFb, &cleanHalf)) {
+		fb = cleanFb;
+		if (half) half = cleanHalf;
+	}
 	const bool ok = host && crh_aov_alloc(ctx, W, H, &aov) == CRH_OK && crh_framebuffer_alloc(ctx, W, H, &out) == CRH_OK && crh_render_aov(ctx, &p, NULL, 0, aov) == CRH_OK
 		&& (half ? crh_denoise_variance(ctx, &dv, fb, half, aov, out) : crh_denoise(ctx, &d, fb, aov, out)) == CRH_OK && crh_denoise_time_ms(ctx, &ms) == CRH_OK && crh_framebuffer_to_srgb8(ctx, out, W, H, t->data.byte_p) == CRH_OK
 		&& crh_framebuffer_download(ctx, out, W, H, host) == CRH_OK;
 	if (!ok) logr(warning, "c-ray-hip: the frame could not be denoised: %s\n", host ? crh_last_error() : "out of memory");
 	if (aov) crh_aov_free(ctx, aov);
+	if (cleanFb) crh_framebuffer_free(ctx, cleanFb);
+	if (cleanHalf) crh_framebuffer_free(ctx, cleanHalf);
 	if (out && ok && keep) *keep = out;
 	else if (out) crh_framebuffer_free(ctx, out);
 	const char *base = r->prefs.imgFileName ? r->prefs.imgFileName : "rendered";
@@ -1215,6 +1281,8 @@ struct texture *renderFrame(struct renderer *r) {
 	if (keptDenoised) crh_framebuffer_free(workers[0].ctx, keptDenoised);
 	layerNamesFree(&layerNames);
 	if (!layers && getenv("CRAY_HIP_IDS") && atoi(getenv("CRAY_HIP_IDS")) > 0) logr(warning, "c-ray-hip: CRAY_HIP_IDS has no output without CRAY_HIP_EXR=1\n");
+	if (getenv("CRAY_HIP_DESPECKLE") && !(getenv("CRAY_HIP_DENOISE") && atoi(getenv("CRAY_HIP_DENOISE")) > 0))
+		logr(warning, "c-ray-hip: CRAY_HIP_DESPECKLE filters the denoiser's input and has no effect without CRAY_HIP_DENOISE\n");
 
 	for (int g = 0; g < gpus; ++g) {
 		if (workers[g].ctx && workers[g].fb) crh_framebuffer_free(workers[g].ctx, workers[g].fb);

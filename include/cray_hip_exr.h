@@ -1,7 +1,8 @@
 /*
  * cray_hip_exr.h — the C-ABI of libcray_hip_exr.so, the companion library of the output codecs: what leaves the product as a file and needs no scene, no path
  * state and nothing of the render path. Its second codec is the 8-bit frame as a PNG file (crx_png_pack, below), optionally through a display transform — exposure, a tone curve, a dither
- * (crx_png_pack_display) — at an exposure the device can measure from the frame (crx_auto_exposure). Its first: the pixel data of a ZIP- or ZIPS-compressed scanline OpenEXR file, deflated on the device
+ * (crx_png_pack_display) — at an exposure the device can measure from the frame (crx_auto_exposure). Beside the codecs, because it needs no scene either: the firefly
+ * filter in front of the denoisers (crx_despeckle). Its first: the pixel data of a ZIP- or ZIPS-compressed scanline OpenEXR file, deflated on the device
  * from the buffers libcray_hip.so already makes (c-ray_amd/csrc/exr_zip.h) — all FLOAT (crx_pack_zip), or with a pixel type per channel, FLOAT or HALF (crx_pack). Plain C, int return codes: 0 (CRH_OK) is ok, the negative CRH_ERR_* values of cray_hip.h
  * are reused, crx_last_error() holds the text of the calling thread's last failure. There is NO CPU path: without a HIP device crx_context_create answers
  * CRH_ERR_NO_DEVICE. A context belongs to one device and one stream and is used by one thread at a time.
@@ -191,6 +192,52 @@ int crx_png_pack_display(crx_ctx *ctx, const float *dev_fb, int width, int heigh
  * last complete call's kernel time between the library's own events (waits for it), 0 before the first. */
 int crx_auto_exposure(crx_ctx *ctx, const float *dev_fb, int width, int height, uint32_t permille, float target, float *exposure, float *key, uint64_t *counted);
 int crx_auto_exposure_time_ms(crx_ctx *ctx, float *ms);
+
+/* ---- the firefly filter: clamp outlier pixels to a rank of their neighbourhood (c-ray_amd/csrc/despeckle.h) ----
+ * A path tracer's frame holds a few pixels many times brighter than everything around them. They agree with none of their neighbours, so an edge-aware filter
+ * (crh_denoise) keeps them. crx_despeckle measures, per pixel of a guide frame, a scale s in [0, 1] that takes such a pixel down to a limit derived from its
+ * neighbours, and multiplies up to 8 frames of the same shape by that one plane, in place. It removes energy: it is opt-in everywhere and is for a filter's input,
+ * never for the frame's own file.
+ *
+ * The rule, part of the interface. All arithmetic is float32, correctly rounded * + / and comparisons in this order, nothing contracted into a fused multiply-add.
+ * For every pixel p of dev_guide [H, W, 3]:
+ *   1. luminance      L = ((0.2126f * r) + (0.7152f * g)) + (0.0722f * b)
+ *   2. bad            p is bad iff any of r, g, b is a NaN or infinite, or L is
+ *   3. guarded        g(p) = L if p is not bad and L > 0, otherwise 0
+ *   4. neighbours     the pixels q != p with |dx| <= radius and |dy| <= radius that lie inside the image; m of them (bad ones count, with g = 0)
+ *   5. effective rank k = min(rank, m)
+ *   6. reference      m == 0 (a 1 x 1 image): p is never clamped. Otherwise R = the k-th largest of the g(q), counted with multiplicity (ties need no rule)
+ *   7. limit          T = (factor * R) + floor                      (two roundings)
+ *   8. clamp          p is clamped iff it is not bad and g(p) > T
+ *   9. scale          bad: s(p) = 0;  clamped: s(p) = T / g(p) (one division; below 1, and 0 where T is 0);  otherwise s(p) = 1
+ *  10. apply          to every frame: each component becomes c * s(p), one multiplication. Where s(p) == 0 all three components become +0.0f (not c * 0, which
+ *                     keeps a sign and turns an infinity into a NaN). Where s(p) == 1 the words stay bit for bit as they are.
+ * x -> (factor * x) + floor is monotone in float32, so p is clamped iff fewer than k neighbours have (factor * g(q)) + floor >= g(p): the kernel decides that way
+ * and selects R only for a clamped pixel. The statement above stays the contract (tests/despeckle_spec.py restates it in NumPy, bit for bit).
+ * What the rule does and does not do. A clamped pixel keeps its colour ratios (one factor for r, g and b). One plane scales several buffers: the half-sample
+ * buffer of crh_denoise_variance is the mean of a prefix of the same passes, a per-pixel factor commutes with those means, so scaling the frame and its half by the
+ * same s keeps the variance estimate meaningful. rank trades robustness for detail: rank 1 is "no brighter than the brightest neighbour times factor, plus floor";
+ * a higher rank tolerates clumps of rank - 1 fireflies, and DIMS A REAL HIGHLIGHT that has fewer than `rank` comparably bright neighbours — a 2 x 2 star on black
+ * under the defaults has 3 bright neighbours a pixel, fewer than rank 4, and comes out at `floor`. Lower the rank or raise the floor for such frames.
+ * Parameters: radius 1 or 2; rank 1 .. (2 radius + 1)^2 - 1; factor finite in [1, 2^20]; floor finite in [0, 2^20]. crx_despeckle_default: 2, 4, 4, 2^-6.
+ * Stats (stats may be NULL): clamped and bad pixels; max_clamped, the largest g(p) of a clamped pixel, 0 if none; min_scale, the smallest s of a clamped pixel, 1 if
+ * none.
+ * Frames. dev_frames lists frame_count <= 8 device frames [H, W, 3]; frame_count == 0 measures only. The measure launch completes in stream order before any apply
+ * launch: dev_guide may itself be among dev_frames (the usual case: the frame is its own guide). A frame listed twice is scaled twice.
+ * The plane is scratch of the context, grown on demand; crx_despeckle_scale copies the last complete call's plane [H, W] to host_scale (W * H floats of that call).
+ * Determinism. The plane, the frames and the stats are a function of the arguments and the pixels only: the counts are integers, the two float stats a max and a min.
+ * CRH_ERR_INVALID, nothing written anywhere: a NULL context or guide; width or height <= 0, or a frame crx_png_pack refuses for its size; a parameter outside its
+ * range, or a NaN; frame_count > 8; a NULL list with a non-zero count, or a NULL entry; crx_despeckle_scale: a NULL argument, or no complete call before it.
+ * The call launches behind whatever is queued on the context's stream and waits; the guide and the frames must be complete (as for crx_png_pack).
+ * crx_despeckle_time_ms: the last complete call's kernel time between the library's own events (waits for it): [0] measure, [1] apply, summed over the frames;
+ * 0 before the first. */
+typedef struct { int radius; int rank; float factor; float floor; } crx_despeckle_params;
+typedef struct { uint64_t clamped, bad; float max_clamped, min_scale; } crx_despeckle_stats;
+void crx_despeckle_default(crx_despeckle_params *p);          /* 2, 4, 4, 2^-6; a NULL p: nothing */
+int crx_despeckle(crx_ctx *ctx, const crx_despeckle_params *params /* NULL: the default */, const float *dev_guide, int width, int height, float *const *dev_frames,
+                  uint32_t frame_count, crx_despeckle_stats *stats);
+int crx_despeckle_scale(crx_ctx *ctx, float *host_scale);
+int crx_despeckle_time_ms(crx_ctx *ctx, float ms[2]);
 
 /* ---- debug ---- */
 /* The code construction of CRX_CODES_DYNAMIC on histograms of the caller's: `count` histograms of `symbols` counts each in freq (host memory), one wave a
